@@ -2,8 +2,17 @@
 """bench.py -- audio samples/sec demodulated on MI355X (whole job), 48 kHz f32.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1200|rtty|12000|same]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, the untimed preheat
+and W warm-up passes, the K timed passes, the outputs of the last timed pass (--dump-outputs),
+and one JSON line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+and the configuration.  `--full` adds everything else below: the cold and serial launches
+(`cold_ms_per_step`, `roofline`, `value_serial`), the checks of every output set, of the payloads
+and of the whole batch against the oracle, the CPU baselines, `h2d_inclusive`, `legacy_dropin`,
+`small_batch` and, without --config, the other BASELINE entries under "configs".
 
 Default workload = BASELINE.json configs[1] (the one the metric is quoted on):
 per GPU a batch of 1024 independent synthetic streams x 10 s (480000 samples) of
@@ -26,16 +35,16 @@ the next step).  Streams shard across ranks with no data-path collective.
 the job's total fixed (8 x the per-GPU batch: 65536 streams for --config 12000,
 the size BASELINE.json states) and divides it over the ranks.
 
-Timing: first of all K launches are timed COLD (`cold_ms_per_step`: what a
-25-launch job sees right after host-side set-up); then the kernel is launched untimed for 0.3 s
+Timing: with --full, first of all K launches are timed COLD (`cold_ms_per_step`:
+what a 25-launch job sees right after host-side set-up); then the kernel is launched untimed for 0.3 s
 (`--preheat-ms`: the first launches after set-up run at idle clocks, and the driver's K = 20 is
-7-11 ms of GPU work); then K launches SERIALLY on one stream, one event pair around them
+7-11 ms of GPU work); then, with --full, K launches SERIALLY on one stream, one event pair around them
 (`roofline.*`, `value_serial`); then the W warm-up and the K timed passes go through the library's
 pipeline (mifsk_pipeline_*, `--pipeline` P: pass i on lane i mod P -- a context, a HIP stream and
 an output set of the library's own -- so that it fills the CUs the late streams of pass i - 1
 leave idle), bracketed by barrier + synchronize as the contract says (`value`, `ms_per_step`).
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+Prints ONE JSON line on rank 0, with --full also
   roofline     : HBM-read roofline of the demod kernel, measured live with
                  events on the launch stream (serial launches, see above)
   value_serial : samples / roofline.kernel_ms_avg -- one batch at a time, no overlap
@@ -275,6 +284,32 @@ def hbm_traffic(name):
     return None
 
 
+DUMP_LIMIT = 64 << 20			# --dump-outputs: bytes written at most
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the output set the last timed pass handed its caller (torch views `out`
+    of the library's set: per stream `nframes`, `nbytes`, `status` and the decoded `bytes`, those
+    past a stream's nbytes zeroed) as float32 DIR/<name>.npy.  Where the bytes would not fit
+    DUMP_LIMIT, the rows written are a fixed, seeded sample of the streams; `streams.npy` holds
+    the rows' stream indices either way."""
+    os.makedirs(path, exist_ok=True)
+    nbytes = out["nbytes"].cpu().numpy().astype(np.int64)
+    ns = len(nbytes)
+    cols = int(nbytes.max()) if ns else 0
+    rows = np.arange(ns)
+    fit = (DUMP_LIMIT - 3 * 4 * ns - 4096) // (4 * cols + 4)		# (4096: the .npy headers)
+    if fit < ns:
+        rows = np.sort(np.random.default_rng(0).choice(ns, size=fit, replace=False))
+    b = out["bytes"][:, :cols].cpu().numpy()[rows]
+    b[np.arange(cols)[None, :] >= nbytes[rows][:, None]] = 0
+    arrays = {"nframes": out["nframes"].cpu().numpy(), "nbytes": nbytes, "status": out["status"].cpu().numpy(),
+              "bytes": b, "streams": rows}
+    for key, a in arrays.items():
+        np.save(os.path.join(path, key + ".npy"), np.asarray(a, dtype=np.float32))
+    return {key: list(a.shape) for key, a in arrays.items()}
+
+
 class RankFailed(RuntimeError):
     """some rank (maybe not this one) failed in a phase every rank has now left"""
 
@@ -303,7 +338,7 @@ def get_pipeline(M, torch, depth):
     return _PIPES[depth]
 
 
-def run_workload(name, args, M, torch, dist, ctx, rank, world, steps, warmup, cpu_leg, oracle_leg=True):
+def run_workload(name, args, M, torch, dist, ctx, rank, world, steps, warmup, cpu_leg, oracle_leg=True, dump_dir=None):
     """One BASELINE entry on this rank's shard: synthesize the batch on the device (or host for
     configs[1]), W untimed + K timed passes bracketed by barrier + synchronize, kernel time by
     events on the launch stream.  Returns the JSON line as a dict on rank 0, None elsewhere.
@@ -363,7 +398,7 @@ def run_workload(name, args, M, torch, dist, ctx, rank, world, steps, warmup, cp
     agree(torch, dist, setup_err, "%s: first launch" % name)
     return timed_workload(name, args, M, torch, dist, ctx, pipe, rank, world, steps, warmup, cpu_leg, oracle_leg,
                           cfg, mode, entry, samples, lens, bufs, kw, payloads, lo, nstreams, nsamp, stride,
-                          frames_cap, total_streams, total_samples_local)
+                          frames_cap, total_streams, total_samples_local, dump_dir)
 
 
 def make_batch(name, M, torch, ctx, cfg, rank, lo, nstreams, nsamp, stride, amplitude, payloads):
@@ -458,7 +493,7 @@ def work_counters(name, M, torch, ctx, cfg, samples, lens, kw):
 
 def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps, warmup, cpu_leg, oracle_leg,
                    cfg, mode, entry, samples, lens, bufs, kw, payloads, lo, nstreams, nsamp, stride,
-                   frames_cap, total_streams, total_samples_local):
+                   frames_cap, total_streams, total_samples_local, dump_dir=None):
     pipe = pipeline.depth			# lanes in effect (asked for: pipeline.depth_requested)
     nbuf = pipe					# pass t writes the library's set t % depth
     pending = [None] * nbuf
@@ -513,7 +548,7 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
     # COLD: K serial launches as the first thing after set-up (the state a short job finds the
     # device in: the first launches after idling run at idle clocks), by the host's clock
     cold_ms = None
-    if failure[0] is None:
+    if args.full and failure[0] is None:
         try:
             torch.cuda.synchronize()
             tc = time.perf_counter()
@@ -547,14 +582,15 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
     # warm-up passes (untimed by the contract) -- the figure the rocprofv3 summary under profiles/
     # is compared with -- and the K timed passes below are timed by the contract's clock alone.
     serial_evs = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    try:
-        serial_evs[0].record()			# (torch's current stream, where ctx launches by default)
-        for i in range(steps):
-            M.demod_batch(ctx, cfg, samples, out=bufs[0], **kw)
-        serial_evs[1].record()
-        torch.cuda.synchronize()
-    except Exception as e:			# noqa: BLE001
-        failure[0] = failure[0] or e
+    if args.full:
+        try:
+            serial_evs[0].record()			# (torch's current stream, where ctx launches by default)
+            for i in range(steps):
+                M.demod_batch(ctx, cfg, samples, out=bufs[0], **kw)
+            serial_evs[1].record()
+            torch.cuda.synchronize()
+        except Exception as e:			# noqa: BLE001
+            failure[0] = failure[0] or e
 
     for i in range(warmup):
         step(i)
@@ -579,9 +615,10 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
     # per rank is how long its launches and its waits for the gather took)
     agree(torch, dist, failure[0], "%s: timed loop" % name)
 
-    kernel_ms = [serial_evs[0].elapsed_time(serial_evs[1]) / max(1, steps)] * steps
+    if dump_dir and rank == 0:
+        # (rank 0's shard at N > 1)
+        dump_outputs(dump_dir, pipeline.result(pipeline.next_ticket() - 1))
     total_samples = total_samples_local
-    per_rank = None
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -589,6 +626,42 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
         t = torch.tensor([total_samples_local], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         total_samples = float(t.item())
+
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "audio samples/sec demodulated (whole node), %s-baud 48 kHz f32"
+                      % {"1200": "1200", "1200noise": "1200", "rtty": "45.45", "12000": "12000", "same": "520.83"}[name],
+            "value": total_samples * steps / dt, "unit": "samples/s", "n_gpus": world, "steps": steps,
+            "warmup": warmup, "ms_per_step": dt / steps * 1e3,
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": "%s; %d streams x %d samples per GPU (BASELINE.json)"
+                                   % (entry, nstreams, nsamp),
+                       "streams_per_gpu": nstreams, "samples_per_stream": nsamp,
+                       "total_streams": total_streams,
+                       "input_dtype": "f32", "accumulate_dtype": "f64",
+                       "sharding": ("independent streams per rank, decoded bytes gathered to "
+                                    "rank 0 over RCCL") if world > 1 else "single GPU"},
+            "device": ctx.device_name,
+            "pipeline": {"passes_in_flight": pipe, "asked_for": pipeline.depth_requested,
+                         "hw_queues": pipeline.hw_queues, "through": "mifsk_pipeline_* (C ABI)",
+                         "ms_per_pass": dt / steps * 1e3,
+                         "hbm_frac_of_the_timed_passes": total_samples_local * 4.0 * steps / dt / HBM_PEAK},
+            "preheat": {"untimed_launches_before_warmup": preheat["launches"], "ms": preheat["ms"],
+                        "why": "the first launches after host-side set-up run at idle clocks"},
+        }
+        if world > 1 or args.gather_self:
+            line["gather_through"] = "mifsk_gather_* (C ABI)" if args.native_gather else "torch.distributed (ByteGatherer)"
+    if not args.full:
+        del samples, bufs
+        torch.cuda.empty_cache()
+        return line
+
+    # ---- --full: everything besides the headline ------------------------------------------------
+    kernel_ms = [serial_evs[0].elapsed_time(serial_evs[1]) / max(1, steps)] * steps
+    per_rank = None
+    if dist is not None:
         # root against peers: if the efficiency at N > 1 is short, this says whether the root
         # (which also receives N - 1 shards per step) is the slow rank, and by how much
         mine = torch.tensor([float(np.mean(kernel_ms)), float(np.max(kernel_ms)), wait_s[0] / max(1, steps) * 1e3],
@@ -693,26 +766,11 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
         gather_self_ok = bool(np.array_equal(rn.cpu().numpy(), last["nbytes"])
                               and np.array_equal(rb.cpu().numpy(), last["bytes"][:, :rb.shape[1]]))
 
-    line = None
     if rank == 0:
-        value = total_samples * steps / dt
         kavg = float(np.mean(kernel_ms)) * 1e-3
         achieved = total_samples_local * 4.0 / kavg
         launch = M.demod_plan(ctx, cfg, nstreams, engine=args.engine, nsamples=stride)	# what the library launches
-        line = {
-            "metric": "audio samples/sec demodulated (whole node), %s-baud 48 kHz f32"
-                      % {"1200": "1200", "1200noise": "1200", "rtty": "45.45", "12000": "12000", "same": "520.83"}[name],
-            "value": value, "unit": "samples/s", "n_gpus": world, "steps": steps,
-            "warmup": warmup, "ms_per_step": dt / steps * 1e3,
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "%s; %d streams x %d samples per GPU (BASELINE.json)"
-                                   % (entry, nstreams, nsamp),
-                       "streams_per_gpu": nstreams, "samples_per_stream": nsamp,
-                       "total_streams": total_streams,
-                       "input_dtype": "f32", "accumulate_dtype": "f64",
-                       "sharding": ("independent streams per rank, decoded bytes gathered to "
-                                    "rank 0 over RCCL") if world > 1 else "single GPU"},
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": hbm_traffic(name),
                          "kernel": launch["kernel"], "launch": launch,
@@ -720,22 +778,16 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
                          "events": "one pair around K launches on one stream, between the preheat and the warm-up passes",
                          "algorithmic_bytes_per_launch": total_samples_local * 4.0},
             "payload_roundtrip_ok_streams": "%d/%d" % (ok_streams, judged),
-            "device": ctx.device_name,
             # (one batch at a time per GPU: the job's samples over the slowest rank's kernel time)
             "value_serial": total_samples / (max(per_rank["kernel_ms_avg"]) * 1e-3 if per_rank else kavg),
             "cold_ms_per_step": cold_ms,
-            "pipeline": {"passes_in_flight": pipe, "asked_for": pipeline.depth_requested,
-                         "hw_queues": pipeline.hw_queues, "through": "mifsk_pipeline_* (C ABI)",
-                         "ms_per_pass": dt / steps * 1e3,
-                         "hbm_frac_of_the_timed_passes": total_samples_local * 4.0 * steps / dt / HBM_PEAK,
-                         "output_sets_equal_to_serial_launch": "%d/%d" % (sets_equal, nbuf),
-                         "note": "pass i runs on lane i mod P of the library's pipeline (a context, a HIP stream "
-                                 "and an output set each; one resident batch): it fills the CUs the late streams "
-                                 "of pass i - 1 leave idle; roofline.* and value_serial are the kernel launched "
-                                 "serially on one stream"},
-            "preheat": {"untimed_launches_before_warmup": preheat["launches"], "ms": preheat["ms"],
-                        "why": "the first launches after host-side set-up run at idle clocks"},
-        }
+        })
+        line["pipeline"].update({
+            "output_sets_equal_to_serial_launch": "%d/%d" % (sets_equal, nbuf),
+            "note": "pass i runs on lane i mod P of the library's pipeline (a context, a HIP stream "
+                    "and an output set each; one resident batch): it fills the CUs the late streams "
+                    "of pass i - 1 leave idle; roofline.* and value_serial are the kernel launched "
+                    "serially on one stream"})
         if by_condition is not None:
             line["payload_by_condition"] = by_condition
         if oracle is not None:
@@ -746,8 +798,6 @@ def timed_workload(name, args, M, torch, dist, ctx, pipeline, rank, world, steps
             line["payload_roundtrip_ok_streams_gathered_from_peers"] = "%d/%d" % (peers_ok, peers_judged)
         if gather_self_ok is not None:
             line["gather_self_ok"] = gather_self_ok
-        if world > 1 or args.gather_self:
-            line["gather_through"] = "mifsk_gather_* (C ABI)" if args.native_gather else "torch.distributed (ByteGatherer)"
         if per_rank is not None:
             line["per_rank"] = per_rank
             line["ranks"] = {"world_size": int(dist.get_world_size()), "backend": str(dist.get_backend())}
@@ -913,14 +963,19 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default=None, choices=sorted(WORKLOADS),
-                    help="one BASELINE entry only (default: configs[1] as the line, the others "
-                         "with a few steps each under its \"configs\" key)")
+                    help="one BASELINE entry only (default: configs[1] as the line; with --full the others "
+                         "too, with a few steps each under its \"configs\" key)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU (default: the config's)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline (see the docstring); "
+                         "a plain run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true",
-                    help="skip the CPU legs (the timed baselines and the whole-batch oracle verdict)")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the H2D-inclusive leg")
-    ap.add_argument("--no-extra", action="store_true", help="configs[1] only: skip configs[2..4]")
+                    help="--full: skip the CPU legs (the timed baselines and the whole-batch oracle verdict)")
+    ap.add_argument("--no-h2d", action="store_true", help="--full: skip the H2D-inclusive leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: configs[1] only, skip configs[2..4]")
     ap.add_argument("--pipeline", type=int, default=0,
                     help="passes in flight: pass i is launched on stream i mod P (1 = one stream; "
                          "0 = the workload's own default, 3 or 4)")
@@ -935,6 +990,8 @@ def main():
     ap.add_argument("--engine", default=None, choices=["wave", "workgroup"],
                     help="force a receive-loop engine (default: the library chooses)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(respawn_under_torchrun(args))
@@ -998,9 +1055,10 @@ def main():
     ctx = M.Context(local_rank)
 
     name = args.config or "1200"
+    cpu = args.full and not args.no_cpu
     line = run_workload(name, args, M, torch, dist, ctx, rank, world, args.steps, args.warmup,
-                        cpu_leg=not args.no_cpu, oracle_leg=not args.no_cpu)
-    if args.config is None and not args.no_extra:
+                        cpu_leg=cpu, oracle_leg=cpu, dump_dir=args.dump_outputs)
+    if args.full and args.config is None and not args.no_extra:
         # the other BASELINE entries at their stated per-GPU sizes, the same K and W (with passes in
         # flight a handful of passes would mostly measure the pipeline filling and draining), device
         # generator; CPU leg: the reference program on 64 streams of each (its stdout against the
@@ -1009,8 +1067,8 @@ def main():
         for other in ("1200noise", "12000", "same", "rtty"):	# (shortest kernels first, the 12 ms one last)
             try:
                 sub = run_workload(other, args, M, torch, dist, ctx, rank, world,
-                                   args.steps, args.warmup, cpu_leg=False if args.no_cpu else "ref",
-                                   oracle_leg=not args.no_cpu)
+                                   args.steps, args.warmup, cpu_leg="ref" if cpu else False,
+                                   oracle_leg=cpu)
             except RankFailed as e:
                 # (raised on EVERY rank by agree(): nobody is left inside a collective)
                 sub = {"error": repr(e)} if rank == 0 else None

@@ -60,7 +60,7 @@ def test_bench_line_for_every_config_small():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for cfg, streams in (("1200", 64), ("12000", 128), ("same", 64), ("rtty", 32)):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfg, "--streams",
-                            str(streams), "--steps", "2", "--warmup", "1"], stdout=subprocess.PIPE,
+                            str(streams), "--steps", "2", "--warmup", "1", "--full"], stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, timeout=600, cwd=root)
         assert r.returncode == 0, r.stderr.decode()[-3000:]
         line = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -85,7 +85,7 @@ def test_bench_step_structure_of_n_gt_1_on_one_gpu_with_the_gather_sent_to_itsel
     # (the last one with the gather behind the C ABI: mifsk_gather_*, bench.py --native-gather)
     for cfg, streams, extra in (("1200", 512, []), ("12000", 1024, []), ("1200", 512, ["--native-gather"])):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", cfg, "--streams", str(streams),
-                            "--steps", "8", "--warmup", "2", "--gather-self", "--no-cpu", "--no-h2d",
+                            "--steps", "8", "--warmup", "2", "--gather-self", "--full", "--no-cpu", "--no-h2d",
                             "--preheat-ms", "50"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                            timeout=600, cwd=root, env=env)
         assert r.returncode == 0, r.stderr.decode()[-3000:]

@@ -1,18 +1,23 @@
 """Live comparison of the restatement with the reference built from its own
-sources (oracle/_ref) on the reference's OWN test inputs (tests/*.test in
-/root/reference).  Runs only where both exist, i.e. in the build container;
+sources (oracle/_ref) on the reference's OWN test inputs (its tests/testdata-*
+payloads, stored as tests/golden/refdata.npz).  Runs where oracle/_ref was built;
 the committed goldens (test_oracle_golden.py) cover the same ground elsewhere."""
 import os
 
 import numpy as np
 import pytest
 
+import _golden as G
 import _oracle as O
 
-REF_TESTS = "/root/reference/tests"
-pytestmark = pytest.mark.skipif(
-    not (O.have_ref() and os.path.isdir(REF_TESTS)),
-    reason="needs oracle/_ref and /root/reference/tests (build container only)")
+pytestmark = pytest.mark.skipif(not O.have_ref(), reason="needs oracle/_ref (the reference built from its sources)")
+REFDATA = np.load(os.path.join(G.GOLDEN_DIR, "refdata.npz"))
+
+
+def ref_payload(name):
+    """the reference's test input file `name` (e.g. testdata-ascii.txt), as bytes"""
+    return REFDATA[name.replace("-", "_").replace(".", "_")].tobytes()
+
 
 P24 = "--samplerate 24000 -M 1200 -S 2400"
 K24 = dict(sample_rate=24000, mark_f=1200, space_f=2400)
@@ -57,7 +62,7 @@ CASES = [
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_restatement_equals_reference_program(case, tmp_path):
     name, payload_file, tx, rx, kw, perfect = case
-    payload = open(os.path.join(REF_TESTS, payload_file), "rb").read()
+    payload = ref_payload(payload_file)
     wav = str(tmp_path / "x.wav")
     O.ref_tx(payload, tx.split(), wav)
     out, err = O.ref_rx(wav, rx.split())
@@ -80,7 +85,7 @@ def test_restatement_equals_reference_program(case, tmp_path):
 def test_dc_offset_sweep_tests_40_41(tmp_path):
     """--Xrxnoise adds a DC offset of -factor to every sample (rand()/RAND_MAX is
     an integer division, src/simpleaudio-sndfile.c:64-70); tests 40/41 sweep it."""
-    payload = open(os.path.join(REF_TESTS, "testdata-ascii.txt"), "rb").read()
+    payload = ref_payload("testdata-ascii.txt")
     for flags, kw in (("1200", dict(baudmode="1200")),
                       ("1200 " + P24, dict(baudmode="1200", **K24))):
         wav = str(tmp_path / "n.wav")

@@ -5,7 +5,7 @@ set -u
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/envsweep; mkdir -p $O
 for v in ${VALUES}; do
-  env MIFSK_EXPERIMENT=1 ${VAR}=$v timeout -s KILL 300 python bench.py --config ${CONFIG:-same} --no-cpu --no-h2d ${BENCH_ARGS:-} > $O/$v.json 2> $O/$v.err
+  env MIFSK_EXPERIMENT=1 ${VAR}=$v timeout -s KILL 300 python bench.py --config ${CONFIG:-same} --full --no-cpu --no-h2d ${BENCH_ARGS:-} > $O/$v.json 2> $O/$v.err
   python - $O/$v.json $v <<'PY'
 import json,sys
 l=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

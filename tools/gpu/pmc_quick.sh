@@ -3,7 +3,7 @@ set -u
 C=${1:-rtty}
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/pmcq_$C; mkdir -p $O
-B="python bench.py --config $C --no-cpu --steps 3 --warmup 1"
+B="python bench.py --config $C --full --no-cpu --steps 3 --warmup 1"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O -o fetch -- $B > $O/fetch.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum --output-format csv -d $O -o tcc -- $B > $O/tcc.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCP_TCC_READ_REQ_sum --output-format csv -d $O -o ea -- $B > $O/ea.log 2>&1

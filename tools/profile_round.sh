@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 for C in $CONFIGS; do
   OUT=gpurun_out/profile_${TAG}_$C
   mkdir -p $OUT
-  B="python bench.py --config $C --no-cpu --no-h2d"
+  B="python bench.py --config $C --full --no-cpu --no-h2d"
   # 1. per-kernel time: the kernel launched serially on one stream -- what roofline.kernel_ms_avg
   #    is (bench.py takes it from K serial launches right after the timed passes) ...
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o stats -- \
@@ -31,6 +31,6 @@ for C in $CONFIGS; do
   timeout 300 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \
       --output-format csv -d $OUT -o clk -- $B --steps 4 --warmup 1 --preheat-ms 0 --pipeline 1 > $OUT/pmc_clk.log 2>&1
   # 4. the un-profiled bench line (with the CPU legs)
-  timeout 900 python bench.py --config $C > $OUT/bench.json 2> $OUT/bench.err
+  timeout 900 python bench.py --config $C --full > $OUT/bench.json 2> $OUT/bench.err
   tail -c 600 $OUT/bench.json; echo
 done
