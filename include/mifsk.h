@@ -591,6 +591,78 @@ int mifsk_demod_slab_ring( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mif
 	mifsk_stream_state *d_state, const uint64_t *d_origin, float *d_ring, int final,
 	void *stream );
 
+/* ---- one long recording across the whole chip (DESIGN.md "cutting a stream in time") --- */
+
+/* Every entry point above gets its parallelism from having many streams: one stream's loop
+ * runs on one wavefront.  mifsk_demod_long decodes ONE long recording (an hour of SDR audio,
+ * a day of SAME monitoring) on the whole chip, bit for bit what one mifsk_demod_batch call
+ * over it gives.  The recording is cut into K chunks starting at s_k = k * chunk; every chunk
+ * but the first is first run for `warmup` samples from a zeroed state (pass A, a guess at the
+ * loop's state there), then every chunk runs from its guess to `warmup` samples into the next
+ * chunk (pass B).  A chunk is accepted when the state its guess paused in equals, in every
+ * CONTROL field (the header comment of minimodem_amd/csrc/mifsk_timesplit.hip), the state the
+ * chunk before paused in at the same sample; a rejected chunk is run again from that state.
+ * Re-runs go in rounds: every chunk whose starting state disagrees with its predecessor's
+ * current pause (settled or not) is run again in one batch, and the consistent prefix is
+ * settled -- so the rounds follow the longest chain of rejections, not their number.  The
+ * result is always exact.
+ *
+ * chunk: samples between chunk starts, a multiple of lcm(samplebuf_size / 2, 4) (0: the
+ * library's choice: the chip's worth of chunks); warmup: >= 2 * samplebuf_size (0: the
+ * library's choice, 10 s of audio); chunks: how many chunks the library's choice aims at (0:
+ * as many as the engine keeps resident, 4 per compute unit).  flags: MIFSK_IO_ENGINE_* as for
+ * mifsk_demod_batch; MIFSK_IO_RING_EXACT is -ENOTSUP (the reference's stale cells matter only
+ * at the end of the stream); MIFSK_TIME_SPLIT_REJECT_ALL (tests) rejects every guess, so that
+ * every chunk goes through the re-run path.  With the library's choices a recording shorter
+ * than 4 * warmup is one chunk: the single call. */
+typedef struct mifsk_time_split {
+    uint64_t	chunk;
+    uint64_t	warmup;
+    uint32_t	chunks;
+    uint32_t	flags;
+} mifsk_time_split;
+
+#define MIFSK_TIME_SPLIT_REJECT_ALL	0x10000u
+
+typedef struct mifsk_time_split_stats {
+    uint64_t	nsamples;
+    uint64_t	chunk;			/* L: samples between chunk starts       */
+    uint64_t	warmup;			/* W                                     */
+    uint64_t	lattice;		/* lcm(samplebuf_size / 2, 4)            */
+    uint64_t	samples_speculative;	/* pass A and the warm-up overlaps       */
+    uint64_t	samples_rerun;		/* loop samples of the re-runs           */
+    uint32_t	nchunks;		/* K (1: the single call)                */
+    uint32_t	accepted;		/* guesses accepted (of K - 1)           */
+    uint32_t	rerun;			/* chunks run again                      */
+    uint32_t	rounds;			/* serial rounds of re-runs              */
+} mifsk_time_split_stats;
+
+/* The planner (host only): what mifsk_demod_long would do with `nsamples` samples -- nchunks,
+ * chunk, warmup, lattice and samples_speculative (the rest 0).  Without a device the library's
+ * choice of chunk aims at 1024 chunks (fewer where their warm-up overlap would pass 4 GiB).
+ * -EINVAL: a chunk off the lattice, a warmup below 2 * samplebuf_size, unknown or contradictory
+ * flags, rows of 2^31 samples or more, a single chunk of 2^32 samples or more;
+ * -ENOTSUP: MIFSK_IO_RING_EXACT. */
+int mifsk_time_split_plan_get( const mifsk_rx_config *cfg, uint64_t nsamples,
+	const mifsk_time_split *params, mifsk_time_split_stats *out );
+
+/* Decode d_samples[0 .. nsamples) (16-byte aligned; nothing beyond nsamples is read) as one
+ * stream.  The outputs go to io_out's output fields exactly as mifsk_demod_batch writes those of
+ * a batch of one stream (size them with mifsk_max_frames / mifsk_max_episodes of nsamples); its
+ * input fields, d_counters and flags are ignored.  params may be NULL (the library's choices),
+ * stats too.  Synchronous: verification reads the chunks' states back, so the call waits for
+ * `stream` before it returns.  Device memory: the chunks' rows are a copy of the recording laid
+ * out apart, K * (chunk + warmup) floats -- about (1 + warmup / chunk) times the recording; the
+ * library's choice of chunk keeps the extra (K - 1) * warmup floats within 4 GiB -- plus the
+ * rows' output arrays (about 32 bytes per possible frame), allocated on `stream` and freed before
+ * the return.  Length: a row (chunk + warmup) must stay below 2^31 samples, so the longest
+ * recording is about 2^31 times the chunk count (at 1024 chunks about 2 * 10^12 samples, 500
+ * days at 48 kHz); -EINVAL beyond.  A recording the planner leaves in one chunk must be shorter
+ * than 2^32 samples. */
+int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
+	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,
+	mifsk_time_split_stats *stats, void *stream );
+
 /* ---- streams fed in pieces from host memory ---------------------------------- */
 
 /* mifsk_demod_slab with the bookkeeping done (reference: the loop that reads its stream half a

@@ -254,6 +254,90 @@ def demod_plan(ctx, cfg, nstreams, ring_exact=False, engine=None, nsamples=None)
     return d
 
 
+def _time_split_params(chunk, warmup, chunks, engine, reject_all):
+    p = _lib.TimeSplit()
+    p.chunk = int(chunk or 0)
+    p.warmup = int(warmup or 0)
+    p.chunks = int(chunks or 0)
+    p.flags = (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
+        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0) | \
+        (_lib.TIME_SPLIT_REJECT_ALL if reject_all else 0)
+    return p
+
+
+def time_split_plan(cfg, nsamples, chunk=None, warmup=None, chunks=None, engine=None):
+    """mifsk_time_split_plan_get: how demod_long would cut `nsamples` samples (host only)."""
+    st = _lib.TimeSplitStats()
+    rc = _lib.load().mifsk_time_split_plan_get(C.byref(cfg), int(nsamples),
+                                               C.byref(_time_split_params(chunk, warmup, chunks, engine, False)),
+                                               C.byref(st))
+    if rc != 0:
+        raise ValueError("mifsk_time_split_plan_get failed: %d" % rc)
+    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+
+def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("bytes", "episodes"),
+               frames_cap=None, episodes_cap=None, engine=None, reject_all=False, stream=None):
+    """mifsk_demod_long: ONE long recording decoded across the whole chip by cutting it in
+    time (DESIGN.md "cutting a stream in time"), bit for bit what demod_batch gives for it.
+
+    samples: a 1-D torch.float32 CUDA tensor (16-byte aligned).  chunk / warmup / chunks: the
+    planner's parameters (None: the library's choice).  reject_all: every speculative chunk is
+    re-run (tests).  Returns demod_batch's dict for a batch of one stream plus "stats" (the
+    planner's figures and what verification accepted); synchronous."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 1
+    assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
+    n = int(samples.shape[0])
+    if frames_cap is None:
+        frames_cap = max_frames(cfg, n)
+    if episodes_cap is None:
+        episodes_cap = max_episodes(cfg, n)
+    dev = samples.device
+    with _on(torch, stream):
+        out = {"nframes": torch.zeros(1, dtype=torch.int32, device=dev),
+               "status": torch.zeros(1, dtype=torch.int32, device=dev)}
+        if "bytes" in want:
+            out["bytes"] = torch.zeros((1, frames_cap), dtype=torch.uint8, device=dev)
+            out["nbytes"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        if "bits" in want:
+            out["bits"] = torch.zeros((1, frames_cap), dtype=torch.int64, device=dev)
+        if "frames" in want:
+            out["frames"] = torch.zeros((1, frames_cap, FRAME_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
+            out["carrier_band"] = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        if "episodes" in want:
+            out["episodes"] = torch.zeros((1, episodes_cap, EPISODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            out["nepisodes"] = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def ptr(name):
+        t = out.get(name)
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    io = _lib.DemodIO()
+    io.nstreams = 1
+    io.d_bytes = ptr("bytes")
+    io.d_nbytes = ptr("nbytes")
+    io.d_bits = ptr("bits")
+    io.d_frames = ptr("frames")
+    io.d_nframes = ptr("nframes")
+    io.frames_cap = frames_cap
+    io.d_episodes = ptr("episodes")
+    io.d_nepisodes = ptr("nepisodes")
+    io.episodes_cap = episodes_cap
+    io.d_status = ptr("status")
+    io.d_carrier_band = ptr("carrier_band")
+    st = _lib.TimeSplitStats()
+    rc = lib.mifsk_demod_long(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), n,
+                              C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
+                              C.byref(io), C.byref(st), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_demod_long failed: %d" % rc)
+    out["stats"] = {k: int(getattr(st, k)) for k, _ in st._fields_}
+    return out
+
+
 def results_to_host(out):
     """Copy a demod_batch() result to numpy (synchronises)."""
     res = {}

@@ -215,6 +215,20 @@ class FileResult(C.Structure):
                 ("episodes", C.c_void_p)]
 
 
+class TimeSplit(C.Structure):
+    _fields_ = [("chunk", C.c_uint64), ("warmup", C.c_uint64), ("chunks", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class TimeSplitStats(C.Structure):
+    _fields_ = [("nsamples", C.c_uint64), ("chunk", C.c_uint64), ("warmup", C.c_uint64),
+                ("lattice", C.c_uint64), ("samples_speculative", C.c_uint64),
+                ("samples_rerun", C.c_uint64), ("nchunks", C.c_uint32), ("accepted", C.c_uint32),
+                ("rerun", C.c_uint32), ("rounds", C.c_uint32)]
+
+
+TIME_SPLIT_REJECT_ALL = 0x10000
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
 assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
 
@@ -243,7 +257,7 @@ EXPORTS = [
     "mifsk_gather_unique_id", "mifsk_gather_create", "mifsk_gather_destroy", "mifsk_gather_info_get",
     "mifsk_gather_start", "mifsk_gather_received",
     "mifsk_session_create", "mifsk_session_destroy", "mifsk_session_feed", "mifsk_session_get",
-    "mifsk_session_pending",
+    "mifsk_session_pending", "mifsk_time_split_plan_get", "mifsk_demod_long",
 ]
 
 _lib = None
@@ -414,5 +428,12 @@ def load():
     lib.mifsk_session_pending.argtypes = [C.c_void_p, C.c_int]
     lib.mifsk_selftest_sqrt.restype = C.c_int
     lib.mifsk_selftest_sqrt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.mifsk_time_split_plan_get.restype = C.c_int
+    lib.mifsk_time_split_plan_get.argtypes = [C.POINTER(RxConfig), C.c_uint64, C.POINTER(TimeSplit),
+                                              C.POINTER(TimeSplitStats)]
+    lib.mifsk_demod_long.restype = C.c_int
+    lib.mifsk_demod_long.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_uint64,
+                                     C.POINTER(TimeSplit), C.POINTER(DemodIO), C.POINTER(TimeSplitStats),
+                                     C.c_void_p]
     _lib = lib
     return lib

@@ -500,6 +500,8 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_stream_state);
     MIFSK_SIZEOF(mifsk_wav_info);
     MIFSK_SIZEOF(mifsk_file_result);
+    MIFSK_SIZEOF(mifsk_time_split);
+    MIFSK_SIZEOF(mifsk_time_split_stats);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;
