@@ -26,444 +26,7 @@
 #define M_PI 3.14159265358979323846
 #endif
 
-namespace mifsk {
 
-// The shared-segment plan of one zig-zag scan (SegPlan in mifsk_device.h): cut the span
-// the scan's windows cover at every window edge, drop pieces no window covers (bit
-// offsets are rounded, consecutive windows may leave a sample between them), split the
-// longest pieces until the lanes of ceil(n / 64) passes are full, hand the pieces to
-// the passes longest first.
-// candidates of one zig-zag scan in scan order (fsk.c:477-484), appended to `out`
-static void zigzag_candidates( std::vector<unsigned> &out, unsigned first, unsigned mx, unsigned step )
-{
-    if ( (int)first >= (int)mx || step == 0 )
-	return;
-    const unsigned U = ( mx - first - 1 ) / step + 1;
-    const unsigned D = U - 1 < first / step ? U - 1 : first / step;
-    for ( unsigned i = 0; i < U + D; i++ ) {
-	if ( i == 0 ) out.push_back(first);
-	else if ( i <= 2 * D ) out.push_back(( i & 1u ) ? first + ( ( i + 1 ) / 2 ) * step : first - ( ( i + 1 ) / 2 ) * step);
-	else out.push_back(first + ( i - D ) * step);
-    }
-}
-
-// `cand`: the candidates whose windows the plan covers, window w = candidate w / n_bits, bit w % n_bits
-static void plan_segments( SegPlan &sp, const mifsk_rx_config &c, const std::vector<unsigned> &cand )
-{
-    std::memset(&sp, 0, sizeof(sp));
-    const unsigned nb = c.expect_n_bits, B = c.bit_nsamples;
-    const unsigned J = (unsigned)cand.size();
-    if ( J == 0 || nb == 0 || J * nb > (unsigned)SEGW_MAX )
-	return;
-    auto at = [&]( unsigned i ) -> unsigned { return cand[i]; };
-    std::vector<unsigned> wstart(J * nb);
-    std::vector<unsigned> cuts;
-    for ( unsigned j = 0; j < J; j++ )
-	for ( unsigned k = 0; k < nb; k++ ) {
-	    const unsigned a = at(j) + c.bit_offset[k];
-	    wstart[j * nb + k] = a;
-	    cuts.push_back(a);
-	    cuts.push_back(a + B);
-	}
-    std::sort(cuts.begin(), cuts.end());
-    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-    struct Seg { unsigned rel, len; };
-    std::vector<Seg> segs;
-    for ( size_t i = 0; i + 1 < cuts.size(); i++ ) {
-	const unsigned lo = cuts[i], hi = cuts[i + 1];
-	bool covered = false;
-	for ( unsigned a : wstart )
-	    covered = covered || ( a <= lo && hi <= a + B );
-	if ( covered )
-	    segs.push_back(Seg{lo, hi - lo});
-    }
-    if ( segs.empty() || segs.size() > (size_t)SEG_MAX )
-	return;
-    // Balance.  Every piece may be cut further; the parts go to (at most two) passes of 64 lanes,
-    // longest first.  What a pass costs is decided by its longest part: whole groups of 16 samples
-    // (a group of the sums: ~86 instructions, ~118 where some lane's part ends inside it and the
-    // samples are masked) in whole tile steps of 32 (stage, read back, fetch: ~60).  Two ways of
-    // cutting are tried and the cheapest plan is taken:
-    //  * equal parts: with a target length T piece i gets ceil(len_i / T) parts (all T);
-    //  * caps (round 6): pass 0 takes parts of at most A0 samples, pass 1 of at most A1 <= A0, and
-    //    a piece is cut UNEQUALLY into n0 parts for the one and n1 for the other -- which (n0, n1)
-    //    per piece is a small dynamic program over the 64 lanes of each pass.  RTTY's carrier-held
-    //    plan (pieces of 165, 110, 66, 55, 44 samples) went from 83 + 82 | 110 whole -- 7 + 6 groups
-    //    in 4 + 3 steps -- to 101 + 64 | 110 whole: 7 + 4 groups in 4 + 2 steps.
-    {
-	const std::vector<Seg> pieces = segs;
-	// (the assembly: ~16 instructions per segment of the longest window, once per 64 windows --
-	// per 32 where two lanes share a window, Wave::seg_correlate)
-	const unsigned asm_units = J * nb <= 32u ? 1u : 2u * ( ( J * nb + 63u ) / 64u );
-	auto cost_of = [&]( const std::vector<std::vector<unsigned>> &parts ) -> unsigned {
-	    std::vector<unsigned> lens, at;
-	    for ( size_t i = 0; i < parts.size(); i++ ) {
-		unsigned a = pieces[i].rel;
-		for ( unsigned l : parts[i] ) {
-		    lens.push_back(l);
-		    at.push_back(a);
-		    a += l;
-		}
-	    }
-	    if ( lens.empty() || lens.size() > (size_t)SEG_MAX )
-		return 0xFFFFFFFFu;
-	    unsigned cmax = 0;
-	    for ( unsigned a : wstart ) {
-		unsigned n = 0;
-		for ( size_t i = 0; i < lens.size(); i++ )
-		    n += ( at[i] >= a && at[i] + lens[i] <= a + B ) ? 1u : 0u;
-		cmax = std::max(cmax, n);
-	    }
-	    std::sort(lens.begin(), lens.end(), [](unsigned x, unsigned y) { return x > y; });
-	    unsigned cost = 8u * cmax * asm_units;
-	    for ( size_t p0 = 0; p0 < lens.size(); p0 += 64 ) {
-		const size_t p1 = std::min(lens.size(), p0 + 64);
-		const unsigned lmax = lens[p0], lmin = lens[p1 - 1];
-		const unsigned g = ( lmax + 15 ) / 16, st = ( g + 1 ) / 2, full = lmin / 16;
-		cost += 86u * g + 60u * st + 32u * ( g - std::min(g, full) );
-	    }
-	    return cost;
-	};
-	unsigned best_cost = 0xFFFFFFFFu;
-	std::vector<std::vector<unsigned>> best;		// the parts of every piece, in position order
-	// equal parts
-	{
-	    std::vector<unsigned> cand;
-	    for ( const Seg &s : pieces )
-		for ( unsigned k = 1; k <= 16u && s.len / k >= 16u; k++ )
-		    cand.push_back(( s.len + k - 1 ) / k);
-	    std::sort(cand.begin(), cand.end());
-	    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-	    for ( unsigned T : cand ) {
-		std::vector<std::vector<unsigned>> parts;
-		size_t nparts = 0;
-		for ( const Seg &s : pieces ) {
-		    const unsigned k = ( s.len + T - 1 ) / T;
-		    parts.emplace_back();
-		    for ( unsigned q = 0; q < k; q++ )
-			parts.back().push_back(s.len / k + ( q < s.len % k ? 1u : 0u ));
-		    nparts += k;
-		}
-		if ( nparts > (size_t)SEG_MAX )
-		    continue;
-		const unsigned c = cost_of(parts);
-		if ( c < best_cost ) {
-		    best_cost = c;
-		    best = parts;
-		}
-	    }
-	}
-	// caps
-	{
-	    unsigned lnat = 0, ltot = 0;
-	    for ( const Seg &s : pieces ) {
-		lnat = std::max(lnat, s.len);
-		ltot += s.len;
-	    }
-	    const unsigned amax = ( lnat + 15u ) & ~15u;
-	    constexpr unsigned INF = 0xFFFFu;
-	    std::vector<uint16_t> choice(pieces.size() * 65u);
-	    std::vector<unsigned> dp(65), nx(65);
-	    std::vector<std::vector<unsigned>> parts(pieces.size());
-	    // (caps in whole groups; for very long windows in coarser steps: at most 32 values)
-	    const unsigned astep = std::max(16u, ( amax / 32u + 15u ) & ~15u);
-	    for ( unsigned A0 = astep; A0 <= amax + astep - 1u; A0 += astep )
-		for ( unsigned A1 = astep; A1 <= A0; A1 += astep ) {
-		    if ( 64u * ( A0 + A1 ) < ltot )
-			continue;			// (the lanes of two passes cannot hold the span)
-		    // (a plan whose longest parts are a whole group below its caps is found under the
-		    // smaller caps: these caps cost at least their own groups and steps)
-		    if ( 86u * ( A0 / 16u + A1 / 16u ) + 60u * ( ( A0 + 16u ) / 32u + ( A1 + 16u ) / 32u ) >= best_cost )
-			continue;
-		    // dp[j]: fewest pass-1 parts with j pass-0 parts over the pieces so far
-		    std::fill(dp.begin(), dp.end(), INF);
-		    dp[0] = 0;
-		    for ( size_t i = 0; i < pieces.size(); i++ ) {
-			const unsigned L = pieces[i].len;
-			std::fill(nx.begin(), nx.end(), INF);
-			for ( unsigned j = 0; j <= 64; j++ ) {
-			    if ( dp[j] == INF )
-				continue;
-			    for ( unsigned n0 = 0; n0 <= ( L + A0 - 1 ) / A0 && j + n0 <= 64; n0++ ) {
-				const unsigned rest = L > n0 * A0 ? L - n0 * A0 : 0u;
-				const unsigned n1 = ( rest + A1 - 1 ) / A1;
-				if ( n0 + n1 == 0 || n0 + n1 > L )
-				    continue;
-				if ( dp[j] + n1 < nx[j + n0] ) {
-				    nx[j + n0] = dp[j] + n1;
-				    choice[i * 65u + j + n0] = (uint16_t)n0;
-				}
-			    }
-			}
-			dp.swap(nx);
-		    }
-		    unsigned jbest = 65;
-		    for ( unsigned j = 0; j <= 64; j++ )
-			if ( dp[j] <= 64 && ( jbest == 65 || dp[j] + j < dp[jbest] + jbest ) )
-			    jbest = j;
-		    if ( jbest == 65 )
-			continue;
-		    // walk back: n0 of every piece; its n1 follows
-		    unsigned j = jbest;
-		    for ( size_t i = pieces.size(); i-- > 0; ) {
-			const unsigned L = pieces[i].len, n0 = choice[i * 65u + j];
-			const unsigned rest = L > n0 * A0 ? L - n0 * A0 : 0u;
-			const unsigned n1 = ( rest + A1 - 1 ) / A1;
-			// pass 1's parts as long as they may be, pass 0's share the rest equally
-			unsigned t1 = n1 ? std::min(n1 * A1, L - n0) : 0u;
-			if ( n0 == 0 )
-			    t1 = L;
-			const unsigned t0 = L - t1;
-			parts[i].clear();
-			for ( unsigned q = 0; q < n0; q++ )
-			    parts[i].push_back(t0 / n0 + ( q < t0 % n0 ? 1u : 0u ));
-			for ( unsigned q = 0; q < n1; q++ )
-			    parts[i].push_back(t1 / n1 + ( q < t1 % n1 ? 1u : 0u ));
-			j -= n0;
-		    }
-		    bool sound = true;
-		    for ( const std::vector<unsigned> &pp : parts )
-			for ( unsigned l : pp )
-			    sound = sound && l >= 1u;
-		    const unsigned c = sound ? cost_of(parts) : 0xFFFFFFFFu;
-		    if ( c < best_cost ) {
-			best_cost = c;
-			best = parts;
-		    }
-		}
-	}
-	if ( best.empty() )
-	    return;
-	segs.clear();
-	for ( size_t i = 0; i < pieces.size(); i++ ) {
-	    unsigned at = pieces[i].rel, total = 0;
-	    for ( unsigned l : best[i] ) {
-		segs.push_back(Seg{at, l});
-		at += l;
-		total += l;
-	    }
-	    if ( total != pieces[i].len )
-		return;				// (cannot happen; leaves valid = 0)
-	}
-	if ( segs.size() > (size_t)SEG_MAX )
-	    return;
-    }
-    const unsigned npass = (unsigned)( ( segs.size() + 63 ) / 64 );
-    // passes: longest pieces first, position order inside a pass
-    std::vector<unsigned> order(segs.size());
-    for ( size_t i = 0; i < order.size(); i++ ) order[i] = (unsigned)i;
-    std::stable_sort(order.begin(), order.end(), [&]( unsigned a, unsigned b ) { return segs[a].len > segs[b].len; });
-    sp.nseg = (unsigned)segs.size();
-    sp.npass = npass;
-    sp.nwin = J * nb;
-    for ( unsigned i = 0; i < (unsigned)SEG_MAX; i++ )
-	sp.slot_seg[i] = 0xFFFFu;
-    unsigned lmax = 0;
-    for ( unsigned pss = 0; pss < npass; pss++ ) {
-	std::vector<unsigned> mine(order.begin() + 64 * pss,
-				   order.begin() + (long)std::min<size_t>(order.size(), 64 * ( pss + 1 )));
-	std::sort(mine.begin(), mine.end());
-	sp.pass_len[pss] = 0;
-	sp.pass_min[pss] = 0xFFFFFFFFu;
-	for ( size_t l = 0; l < mine.size(); l++ ) {
-	    sp.slot_seg[64 * pss + l] = (uint16_t)mine[l];
-	    sp.pass_len[pss] = std::max(sp.pass_len[pss], segs[mine[l]].len);
-	    sp.pass_min[pss] = std::min(sp.pass_min[pss], segs[mine[l]].len);
-	}
-	lmax = std::max(lmax, sp.pass_len[pss]);
-    }
-    for ( size_t i = 0; i < segs.size(); i++ ) {
-	sp.seg_rel[i] = segs[i].rel;
-	sp.seg_len[i] = (uint16_t)segs[i].len;
-	sp.span_hi = std::max(sp.span_hi, segs[i].rel + segs[i].len);
-    }
-    unsigned cmax = 0;
-    for ( unsigned w = 0; w < sp.nwin; w++ ) {
-	unsigned f = 0, n = 0;
-	bool in = false;
-	for ( unsigned i = 0; i < sp.nseg; i++ ) {
-	    const bool inside = segs[i].rel >= wstart[w] && segs[i].rel + segs[i].len <= wstart[w] + B;
-	    if ( inside && !in ) { f = i; in = true; }
-	    if ( inside ) n++;
-	}
-	sp.win_first[w] = (uint16_t)f;
-	sp.win_count[w] = (uint16_t)n;
-	cmax = std::max(cmax, n);
-	// (its pieces are consecutive and tile it but for the uncovered samples, which no
-	// window contains: those lie between windows, never inside one)
-	unsigned total = 0;
-	for ( unsigned i = f; i < f + n; i++ ) total += segs[i].len;
-	if ( total != B )
-	    return;				// (cannot happen; leaves valid = 0)
-    }
-    // DESIGN.md "shared segments": index-order rounding (B - 1) + segment sums
-    // sqrt(2) (L - 1) + assembly 2 n + table entries' own rounding 85, in units of
-    // 2^-53 * sum |x|; rounded up generously
-    // (+ 2: a short scan's windows are assembled as two half sums and one more addition)
-    sp.bound_c = (float)( B + 1.5 * lmax + 2.0 * cmax + 2.0 + 128.0 );
-    // (a pass loads table group ceil(L / 16) + 3 at most; the table has ceil(B / 16) + 1)
-    if ( ( lmax + 15 ) / 16 + 3 > ( B + 15 ) / 16 )
-	return;
-    // packed copies; a plan whose numbers do not fit the fields is not used
-    if ( lmax >= 4096u || sp.span_hi >= ( 1u << 20 ) || sp.nseg > 255u )
-	return;
-    for ( unsigned i = 0; i < (unsigned)SEG_MAX; i++ ) {
-	const unsigned s = sp.slot_seg[i];
-	sp.p_slot_seg[i] = s == 0xFFFFu ? 0xFFu : (uint8_t)s;
-	sp.p_slot[i] = s == 0xFFFFu ? 0u : ( sp.seg_rel[s] | ( (uint32_t)sp.seg_len[s] << 20 ) );
-    }
-    for ( unsigned w = 0; w < sp.nwin; w++ ) {
-	if ( wstart[w] >= 65536u || sp.win_count[w] > 255u )
-	    return;
-	sp.p_win[w] = sp.win_first[w] | ( (uint32_t)sp.win_count[w] << 8 ) | ( wstart[w] << 16 );
-    }
-    sp.valid = 1;
-}
-
-void fill_devcfg( DevCfg &d, const mifsk_rx_config &c )
-{
-    std::memset(&d, 0, sizeof(d));
-    d.n_bits = c.expect_n_bits;
-    d.bit_nsamples = c.bit_nsamples;
-    d.last_reach = c.bit_offset[c.expect_n_bits - 1] + c.bit_nsamples;
-    d.magscalar = 2.0f / (float)c.bit_nsamples;		// fsk.c:132
-    d.frame_nsamples = c.frame_nsamples;
-    d.expect_nsamples = c.expect_nsamples;
-    d.overscan = c.nsamples_overscan;
-    for ( int i = 0; i < 2; i++ ) {
-	d.try_first[i] = c.try_first[i];
-	d.try_max[i] = c.try_max[i];
-	d.try_step[i] = c.try_step[i];
-	d.try_step_fine[i] = c.try_step_fine[i];
-    }
-    d.conf_threshold = c.confidence_threshold;
-    d.search_limit = c.search_limit;
-    d.n_data_bits = c.n_data_bits;
-    d.nstartbits = (uint32_t)c.nstartbits;
-    d.has_stopbits = c.nstopbits != 0.0f ? 1u : 0u;
-    d.msb_first = c.msb_first ? 1u : 0u;
-    d.do_rx_sync = c.do_rx_sync ? 1u : 0u;
-    d.rx_one = c.rx_one ? 1u : 0u;
-    d.sync_byte = c.sync_byte;
-    d.b_mark = c.b_mark;
-    d.b_space = c.b_space;
-    d.fftsize = (uint32_t)c.fftsize;
-
-    // One pad word per bit row of a SCAN slab where that spreads the lanes of a
-    // search over more LDS banks: the first 64 windows of the carrier-held fine
-    // search (lane = candidate * n_bits + bit, ds_read_b32, 32 lanes per LDS
-    // cycle, bank = word mod 32) are laid out both ways and the cheaper pitch
-    // wins; unpadded rows on a tie (no per-sample row test in the correlator).
-    {
-	auto cost = [&]( unsigned skew ) -> unsigned {
-	    const unsigned f = c.try_first[1], mx = c.try_max[1], st = c.try_step_fine[1];
-	    const unsigned nb = c.expect_n_bits ? c.expect_n_bits : 1u, B = c.bit_nsamples ? c.bit_nsamples : 1u;
-	    unsigned U = 0, D = 0;
-	    if ( f < mx && st ) {
-		U = ( mx - f - 1 ) / st + 1;
-		D = U - 1 < f / st ? U - 1 : f / st;
-	    }
-	    const unsigned J = U + D;
-	    unsigned word[64], n = 0;
-	    for ( unsigned i = 0; i < J && n < 64; i++ ) {
-		unsigned t = f;
-		if ( i && i <= 2 * D )
-		    t = ( i & 1u ) ? f + ( ( i + 1 ) / 2 ) * st : f - ( ( i + 1 ) / 2 ) * st;
-		else if ( i )
-		    t = f + ( i - D ) * st;
-		for ( unsigned k = 0; k < nb && n < 64; k++ ) {
-		    const unsigned rel = t + c.bit_offset[k];
-		    word[n++] = rel + ( rel / B ) * skew;
-		}
-	    }
-	    unsigned total = 0;
-	    for ( unsigned h = 0; h < n; h += 32 ) {
-		unsigned worst = 0;
-		for ( unsigned bank = 0; bank < 32; bank++ ) {
-		    unsigned distinct = 0;
-		    for ( unsigned i = h; i < n && i < h + 32; i++ ) {
-			if ( word[i] % 32 != bank )
-			    continue;
-			bool seen = false;
-			for ( unsigned j = h; j < i; j++ )
-			    seen = seen || word[j] == word[i];
-			distinct += seen ? 0u : 1u;
-		    }
-		    worst = distinct > worst ? distinct : worst;
-		}
-		total += worst;
-	    }
-	    return total;
-	};
-	d.skew = cost(1) < cost(0) ? 1u : 0u;
-    }
-    for ( int i = 0; i < 4; i++ ) {
-	const unsigned f = c.try_first[i & 1], mx = c.try_max[i & 1];
-	const unsigned st = ( i & 2 ) ? c.try_step_fine[i & 1] : c.try_step[i & 1];
-	if ( (int)f < (int)mx && st ) {
-	    d.zz_up[i] = ( mx - f - 1 ) / st + 1;
-	    d.zz_down[i] = d.zz_up[i] - 1 < f / st ? d.zz_up[i] - 1 : f / st;
-	}
-    }
-    // long windows (what the wavefront engine reads through its LDS tile): the scans share
-    // their segments' partial sums
-    if ( c.bit_nsamples >= 256u && c.bit_nsamples <= 65535u )
-	for ( int i = 0; i < 4; i++ ) {
-	    std::vector<unsigned> cand;
-	    zigzag_candidates(cand, c.try_first[i & 1], c.try_max[i & 1],
-			      ( i & 2 ) ? c.try_step_fine[i & 1] : c.try_step[i & 1]);
-	    plan_segments(d.seg[i], c, cand);
-	}
-    if ( d.seg[1].valid && d.seg[3].valid ) {
-	std::vector<unsigned> cand;
-	zigzag_candidates(cand, c.try_first[1], c.try_max[1], c.try_step[1]);
-	d.seg_union_first_fine = (uint32_t)cand.size() * c.expect_n_bits;
-	zigzag_candidates(cand, c.try_first[1], c.try_max[1], c.try_step_fine[1]);
-	plan_segments(d.seg[4], c, cand);
-    }
-    d.div_magic = c.bit_nsamples > 1 ? (uint32_t)( 0x100000000ULL / c.bit_nsamples ) : 0xFFFFFFFFu;
-    // minimodem.c:1407 with frame_start == try_first (carrier)
-    d.lock_advance = c.try_first[1] + c.frame_nsamples - c.nsamples_overscan;
-    d.la_magic = d.lock_advance > 1 ? (uint32_t)( 0x100000000ULL / d.lock_advance ) : 0xFFFFFFFFu;
-    d.nbits_magic = c.expect_n_bits > 1 ? (uint32_t)( 0x100000000ULL / c.expect_n_bits ) : 0xFFFFFFFFu;
-    {
-	// lowest candidate of the carrier coarse scan relative to its first try
-	// (fsk.c:477-484), rounded up to whole bit lengths
-	const unsigned f = c.try_first[1], mx = c.try_max[1], st = c.try_step[1];
-	unsigned down = 0;
-	if ( f < mx && st ) {
-	    const unsigned U = ( mx - f - 1 ) / st + 1;
-	    const unsigned D = U - 1 < f / st ? U - 1 : f / st;
-	    down = D * st;
-	}
-	d.lock_back = ( down + c.bit_nsamples - 1 ) / c.bit_nsamples * c.bit_nsamples;
-    }
-    // every lattice window starts a multiple of 4 samples after the first one
-    // when the bit length, all bit offsets and the frame step are multiples of
-    // 4: then an unskewed region read with 16-byte LDS loads is conflict-light
-    d.lat_linear = ( c.bit_nsamples % 4 == 0 && d.lock_advance % 4 == 0 ) ? 1u : 0u;
-    for ( unsigned k = 0; k < c.expect_n_bits; k++ )
-	if ( c.bit_offset[k] % 4 != 0 )
-	    d.lat_linear = 0;
-    d.lat_grid = ( d.lat_linear && c.expect_n_bits >= 2
-		   && d.lock_advance == ( c.expect_n_bits - 1 ) * c.bit_nsamples ) ? 1u : 0u;
-    for ( unsigned k = 0; k < c.expect_n_bits; k++ )
-	if ( c.bit_offset[k] != k * c.bit_nsamples )
-	    d.lat_grid = 0;
-    for ( unsigned k = 0; k < c.expect_n_bits; k++ ) {
-	d.bit_offset[k] = c.bit_offset[k];
-	for ( int s = 0; s < 2; s++ ) {
-	    const char ch = ( s ? c.expect_sync : c.expect_data )[k];
-	    if ( ch != 'd' ) {
-		d.req_mask[s] |= 1ULL << k;
-		if ( ch == '1' )
-		    d.req_val[s] |= 1ULL << k;
-	    }
-	}
-    }
-}
-
-} // namespace mifsk
 
 using mifsk::DevCfg;
 
@@ -798,27 +361,58 @@ int mifsk_check_cfg( const mifsk_rx_config *cfg )
 // batch entry points
 // ---------------------------------------------------------------------------
 
+// What every launching entry point does once its own arguments are checked: bind the device,
+// collect the caches if they are due, take the gate, look the tables up.  The gate stays held
+// (shared) as long as this object lives: from the lookup until the caller has enqueued.
+struct Prepared {
+    std::shared_lock<std::shared_mutex> gate;
+    DevCfg		d;
+    const DevCfg	*d_cfg = nullptr;
+    const double	*d_tw = nullptr;
+    CfgEntry		tables;
+};
+
+static int prepare( mifsk_ctx *ctx, const mifsk_rx_config *cfg, Prepared &p )
+{
+    HIP_OK(hipSetDevice(ctx->device));
+    cache_gc(ctx);
+    p.gate = std::shared_lock<std::shared_mutex>(ctx->gate);	// lookup .. enqueue
+    int rc = get_twiddles(ctx, TwKey{(unsigned)cfg->fftsize, cfg->b_mark, cfg->b_space,
+				     cfg->bit_nsamples}, &p.d_tw);
+    if ( rc )
+	return rc;
+    derive_cfg(ctx, *cfg, p.d);
+    return get_devcfg(ctx, p.d, &p.d_cfg, &p.tables);
+}
+
+// the batch of a demodulating entry point that accepts the flags `accepted`
+static int check_io( const mifsk_rx_config *cfg, const mifsk_demod_io *io, unsigned accepted )
+{
+    if ( io->nstreams < 0 || ( io->nstreams > 0 && !io->d_samples ) )
+	return -EINVAL;
+    if ( io->stream_stride % 4 != 0 || ( (uintptr_t)io->d_samples & 15u ) )
+	return -EINVAL;		// rows must be 16-byte aligned (coalesced float4 staging)
+    if ( ( io->d_bytes || io->d_bits || io->d_frames ) && io->frames_cap == 0 )
+	return -EINVAL;
+    if ( io->flags & ~accepted )
+	return -EINVAL;
+    // the workgroup engine has neither RING addressing nor the in-loop --auto-carrier
+    if ( ( io->flags & MIFSK_IO_ENGINE_WORKGROUP )
+	    && ( ( io->flags & ( MIFSK_IO_ENGINE_WAVE | MIFSK_IO_RING_EXACT ) ) || cfg->auto_carrier_threshold > 0.0f ) )
+	return -EINVAL;
+    return 0;
+}
+
 extern "C" int mifsk_find_frame_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
 	const float *d_samples, const mifsk_search *d_problems,
 	mifsk_search_result *d_results, int nproblems, void *stream )
 {
     if ( !ctx || mifsk_check_cfg(cfg) || ( nproblems > 0 && ( !d_samples || !d_problems || !d_results ) ) )
 	return -EINVAL;
-    HIP_OK(hipSetDevice(ctx->device));
-    cache_gc(ctx);
-    std::shared_lock<std::shared_mutex> gate(ctx->gate);	// lookup .. enqueue
-    const double *d_tw = nullptr;
-    int rc = get_twiddles(ctx, TwKey{(unsigned)cfg->fftsize, cfg->b_mark, cfg->b_space,
-				     cfg->bit_nsamples}, &d_tw);
-    if ( rc )
+    Prepared p;
+    if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    DevCfg d;
-    derive_cfg(ctx, *cfg, d);
-    const DevCfg *d_cfg = nullptr;
-    rc = get_devcfg(ctx, d, &d_cfg);
-    if ( rc )
-	return rc;
-    return mifsk::launch_find_frame_batch(d, d_cfg, d_tw, d_samples, d_problems, d_results,
+    return mifsk::launch_find_frame_batch(p.d, p.d_cfg, p.d_tw, d_samples, d_problems, d_results,
 					  nproblems, stream);
 }
 
@@ -886,43 +480,86 @@ static int chain_prepare( mifsk_ctx *ctx, size_t ns )
     return 0;
 }
 
-// One wavefront per stream (mifsk_wave.hip): --auto-carrier and RING addressing
-// need per-call device scratch; it is allocated and freed in stream order, so
-// concurrent calls on different streams never share it.
-static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const DevCfg &d,
-	const DevCfg *d_cfg, const double *d_tw, const mifsk_demod_io *io, void *stream,
-	mifsk::LaunchInfo *plan_only = nullptr, mifsk_stream_state *d_state = nullptr,
-	const uint64_t *d_origin = nullptr, bool final = true, const CfgEntry *tables = nullptr,
-	float *d_ring_persistent = nullptr )
+// One launch, or -- where the launcher's plan cuts the batch (ha.chain_ok) -- the chained
+// launches, one chain at a time on the context's streams.
+template <class Args>
+static int launch_engine( mifsk_ctx *ctx,
+	int (*launch)( const DevCfg &, const DevCfg *, const double *, const mifsk_demod_io &, const Args &, void *, mifsk::LaunchInfo * ),
+	const Prepared &p, const mifsk_demod_io &io, Args &ha, void *stream )
 {
-    hipStream_t st = (hipStream_t)stream;
-    const size_t ns = (size_t)io->nstreams;
-    mifsk::WaveHostArgs ha;
-    std::memset(&ha, 0, sizeof(ha));
+    if ( ha.chain_ok ) {
+	mifsk::LaunchInfo li;
+	std::memset(&li, 0, sizeof(li));
+	int rc = launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, &li);
+	if ( rc )
+	    return rc;
+	if ( li.chain_groups ) {
+	    std::lock_guard<std::mutex> one(ctx->chain_lock);
+	    rc = chain_prepare(ctx, (size_t)io.nstreams);
+	    if ( rc )
+		return rc;
+	    ha.chain = &ctx->chain;
+	    return launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, nullptr);
+	}
+    }
+    return launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, nullptr);
+}
+
+static void host_args( mifsk::HostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
+{
     ha.ncu = ctx->ncu;
     ha.samplebuf_size = cfg->samplebuf_size;
-    ha.fftsize = (uint32_t)cfg->fftsize;
-    ha.nbands = cfg->nbands;
-    ha.tw_entries = (uint32_t)mifsk::tw_entries(cfg->bit_nsamples);
     ha.d_state = d_state;
     ha.d_origin = d_origin;
     ha.final = final;
+}
+
+// what a plan-only call tells the wavefront engine's launcher (the rest decides nothing)
+static void wave_args( mifsk::WaveHostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
+	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
+{
+    host_args(ha, ctx, cfg, d_state, d_origin, final);
+    ha.fftsize = (uint32_t)cfg->fftsize;
+    ha.nbands = cfg->nbands;
+    ha.tw_entries = (uint32_t)mifsk::tw_entries(cfg->bit_nsamples);
+    ha.ring_exact = ( io->flags & MIFSK_IO_RING_EXACT ) != 0;
+    ha.autodetect = cfg->auto_carrier_threshold > 0.0f;
     // a whole-stream call over a plain batch may be cut into chained launches (the launcher
     // decides by the batch's shape)
-    ha.chain_ok = !d_state && !( io->flags & MIFSK_IO_RING_EXACT ) && !io->d_counters;
+    ha.chain_ok = !d_state && !ha.ring_exact && !io->d_counters;
+}
+
+// per-call device scratch, allocated and freed in stream order
+struct StreamScratch {
+    hipStream_t	st;
+    void	*p = nullptr;
+    explicit StreamScratch( hipStream_t s ) : st(s) {}
+    StreamScratch( const StreamScratch & ) = delete;
+    ~StreamScratch() { if ( p ) (void)hipFreeAsync(p, st); }
+    bool alloc( size_t bytes ) { return hipMallocAsync(&p, bytes, st) == hipSuccess; }
+};
+
+// One wavefront per stream (mifsk_wave.hip): --auto-carrier and RING addressing
+// need per-call device scratch; it is allocated and freed in stream order (behind a chain's
+// groups too: the caller's stream has joined them when the launcher returns), so
+// concurrent calls on different streams never share it.
+static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Prepared &p,
+	const mifsk_demod_io *io, void *stream, mifsk_stream_state *d_state = nullptr,
+	const uint64_t *d_origin = nullptr, bool final = true, float *d_ring_persistent = nullptr )
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ns = (size_t)io->nstreams;
+    mifsk::WaveHostArgs ha = {};
+    wave_args(ha, ctx, cfg, io, d_state, d_origin, final);
     // (--auto-carrier retunes per stream: its rotation factors come from the stream's own table)
-    if ( tables && !( cfg->auto_carrier_threshold > 0.0f ) )
+    if ( !ha.autodetect )
 	for ( int k = 0; k < 5; k++ ) {
-	    ha.d_rot[k] = tables->d_rot[k];
-	    ha.rot_stride[k] = tables->rot_stride[k];
+	    ha.d_rot[k] = p.tables.d_rot[k];
+	    ha.rot_stride[k] = p.tables.rot_stride[k];
 	}
-    if ( plan_only ) {
-	ha.ring_exact = ( io->flags & MIFSK_IO_RING_EXACT ) != 0;
-	ha.autodetect = cfg->auto_carrier_threshold > 0.0f;
-	return mifsk::launch_demod_wave(d, d_cfg, d_tw, *io, ha, stream, plan_only);
-    }
-    void *scratch_tw = nullptr, *scratch_ring = nullptr;
-    if ( cfg->auto_carrier_threshold > 0.0f ) {
+    StreamScratch scratch_tw(st), scratch_ring(st);
+    if ( ha.autodetect ) {
 	// default negative shift, in the reference's float arithmetic (minimodem.c:1203-1206)
 	int b_shift = - (float)( cfg->autodetect_shift + cfg->band_width / 2.0f ) / cfg->band_width;
 	if ( cfg->inverted_freqs )
@@ -931,138 +568,64 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const D
 	    return -EINVAL;			// assert in fsk_set_tones_by_bandshift (fsk.c:587)
 	if ( (unsigned long long)cfg->nbands * cfg->bit_nsamples > 0xFFFFFFFFull )
 	    return -EINVAL;			// (band * n is reduced in 32 bits on the device)
-	const double *d_cs = nullptr;
-	int rc = get_cs(ctx, (unsigned)cfg->fftsize, &d_cs);
+	int rc = get_cs(ctx, (unsigned)cfg->fftsize, &ha.d_cs);
 	if ( rc )
 	    return rc;
-	ha.autodetect = true;
 	ha.auto_threshold = cfg->auto_carrier_threshold;
 	ha.nps = cfg->nsamples_per_bit > (float)cfg->fftsize ? (float)cfg->fftsize
 							      : cfg->nsamples_per_bit;
 	ha.b_shift = b_shift;
-	ha.d_cs = d_cs;
-	if ( hipMallocAsync(&scratch_tw, ns * ha.tw_entries * 4 * sizeof(double), st) != hipSuccess )
+	if ( !scratch_tw.alloc(ns * ha.tw_entries * 4 * sizeof(double)) )
 	    return -ENOMEM;
-	ha.d_tw_scratch = (double *)scratch_tw;
+	ha.d_tw_scratch = (double *)scratch_tw.p;
     }
-    if ( io->flags & MIFSK_IO_RING_EXACT ) {
-	// samplebuf plus what a search at the top of it may touch beyond
-	const size_t reach = (size_t)( cfg->try_max[0] > cfg->try_max[1] ? cfg->try_max[0] : cfg->try_max[1] )
-			   + d.last_reach + 64;
-	ha.ring_exact = true;
-	ha.ring_stride = (uint32_t)( ( (size_t)cfg->samplebuf_size + reach + 3 ) & ~(size_t)3 );
-	if ( d_ring_persistent ) {
-	    // mifsk_demod_slab_ring: the caller's buffer IS the reference's samplebuf between calls
-	    ha.d_ring = d_ring_persistent;
-	} else {
-	    if ( hipMallocAsync(&scratch_ring, ns * ha.ring_stride * sizeof(float), st) != hipSuccess
-		    || hipMemsetAsync(scratch_ring, 0, ns * ha.ring_stride * sizeof(float), st) != hipSuccess ) {
-		if ( scratch_tw ) (void)hipFreeAsync(scratch_tw, st);
+    if ( ha.ring_exact ) {
+	ha.ring_stride = (uint32_t)mifsk::ring_row_floats(*cfg);
+	// mifsk_demod_slab_ring: the caller's buffer IS the reference's samplebuf between calls
+	ha.d_ring = d_ring_persistent;
+	if ( !ha.d_ring ) {
+	    if ( !scratch_ring.alloc(ns * ha.ring_stride * sizeof(float))
+		    || hipMemsetAsync(scratch_ring.p, 0, ns * ha.ring_stride * sizeof(float), st) != hipSuccess )
 		return -ENOMEM;
-	    }
-	    ha.d_ring = (float *)scratch_ring;
+	    ha.d_ring = (float *)scratch_ring.p;
 	}
     }
-    int rc;
-    if ( ha.chain_ok ) {
-	mifsk::LaunchInfo li;
-	std::memset(&li, 0, sizeof(li));
-	rc = mifsk::launch_demod_wave(d, d_cfg, d_tw, *io, ha, stream, &li);
-	if ( rc == 0 && li.chain_groups ) {
-	    std::lock_guard<std::mutex> one(ctx->chain_lock);
-	    rc = chain_prepare(ctx, ns);
-	    if ( rc ) {
-		if ( scratch_tw ) (void)hipFreeAsync(scratch_tw, st);
-		if ( scratch_ring ) (void)hipFreeAsync(scratch_ring, st);
-		return rc;
-	    }
-	    ha.chain = &ctx->chain;
-	    rc = mifsk::launch_demod_wave(d, d_cfg, d_tw, *io, ha, stream);
-	    // (the caller's stream has joined the groups' by now: freed in stream order behind them)
-	    if ( scratch_tw ) (void)hipFreeAsync(scratch_tw, st);
-	    return rc;
-	}
-    }
-    rc = mifsk::launch_demod_wave(d, d_cfg, d_tw, *io, ha, stream);
-    if ( scratch_tw ) (void)hipFreeAsync(scratch_tw, st);
-    if ( scratch_ring ) (void)hipFreeAsync(scratch_ring, st);
-    return rc;
+    return launch_engine(ctx, mifsk::launch_demod_wave, p, *io, ha, stream);
 }
 
 // The workgroup engine: one call over whole streams (maybe cut into chained launches of its
 // resumable instantiation: the launcher decides by the batch's shape) or, with d_state, one
 // slab of streams that arrive in pieces.
-static int demod_batch_workgroup( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const DevCfg &d,
-	const DevCfg *d_cfg, const double *d_tw, const mifsk_demod_io *io, void *stream,
-	mifsk::LaunchInfo *plan_only = nullptr, mifsk_stream_state *d_state = nullptr,
-	const uint64_t *d_origin = nullptr, bool final = true )
+static void workgroup_args( mifsk::HostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
+	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
 {
-    mifsk::WgHostArgs wh;
-    std::memset(&wh, 0, sizeof(wh));
-    wh.ncu = ctx->ncu;
-    wh.samplebuf_size = cfg->samplebuf_size;
-    wh.d_state = d_state;
-    wh.d_origin = d_origin;
-    wh.final = final;
-    wh.chain_ok = !d_state && !io->d_counters;
-    if ( plan_only )
-	return mifsk::launch_demod_batch(d, d_cfg, d_tw, *io, stream, plan_only, &wh);
-    if ( wh.chain_ok && mifsk::experiment_env("MIFSK_CHAIN") ) {	// (this engine's default is one launch)
-	mifsk::LaunchInfo li;
-	std::memset(&li, 0, sizeof(li));
-	int rc = mifsk::launch_demod_batch(d, d_cfg, d_tw, *io, stream, &li, &wh);
-	if ( rc == 0 && li.chain_groups ) {
-	    std::lock_guard<std::mutex> one(ctx->chain_lock);
-	    rc = chain_prepare(ctx, (size_t)io->nstreams);
-	    if ( rc )
-		return rc;
-	    wh.chain = &ctx->chain;
-	    return mifsk::launch_demod_batch(d, d_cfg, d_tw, *io, stream, nullptr, &wh);
-	}
-    }
-    return mifsk::launch_demod_batch(d, d_cfg, d_tw, *io, stream, nullptr, &wh);
+    host_args(ha, ctx, cfg, d_state, d_origin, final);
+    // (this engine's default is one launch: only MIFSK_CHAIN cuts a batch)
+    ha.chain_ok = !d_state && !io->d_counters && mifsk::experiment_env("MIFSK_CHAIN");
+}
+
+// either engine (the same choice everywhere, the same state record), over whole streams or,
+// with d_state, over streams that arrive in pieces
+static int demod_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Prepared &p, const mifsk_demod_io *io,
+	void *stream, mifsk_stream_state *d_state = nullptr, const uint64_t *d_origin = nullptr, bool final = true )
+{
+    if ( !use_workgroup_engine(cfg, p.d, io->flags) )
+	return demod_batch_wave(ctx, cfg, p, io, stream, d_state, d_origin, final);
+    mifsk::HostArgs ha = {};
+    workgroup_args(ha, ctx, cfg, io, d_state, d_origin, final);
+    return launch_engine(ctx, mifsk::launch_demod_batch, p, *io, ha, stream);
 }
 
 extern "C" int mifsk_demod_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
 	const mifsk_demod_io *io, void *stream )
 {
-    if ( !ctx || !io || mifsk_check_cfg(cfg) )
+    if ( !ctx || !io || mifsk_check_cfg(cfg)
+	    || check_io(cfg, io, MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE) )
 	return -EINVAL;
-    if ( io->nstreams < 0 || ( io->nstreams > 0 && !io->d_samples ) )
-	return -EINVAL;
-    if ( io->stream_stride % 4 != 0 || ( (uintptr_t)io->d_samples & 15u ) )
-	return -EINVAL;		// rows must be 16-byte aligned (coalesced float4 staging)
-    if ( ( io->d_bytes || io->d_bits || io->d_frames ) && io->frames_cap == 0 )
-	return -EINVAL;
-    if ( io->flags & ~( MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE ) )
-	return -EINVAL;
-    if ( ( io->flags & MIFSK_IO_ENGINE_WORKGROUP ) && ( io->flags & MIFSK_IO_ENGINE_WAVE ) )
-	return -EINVAL;
-    // the workgroup engine has neither RING addressing nor the in-loop --auto-carrier
-    if ( ( io->flags & MIFSK_IO_ENGINE_WORKGROUP )
-	    && ( ( io->flags & MIFSK_IO_RING_EXACT ) || cfg->auto_carrier_threshold > 0.0f ) )
-	return -EINVAL;
-    HIP_OK(hipSetDevice(ctx->device));
-    cache_gc(ctx);
-    std::shared_lock<std::shared_mutex> gate(ctx->gate);	// lookup .. enqueue
-    const double *d_tw = nullptr;
-    int rc = get_twiddles(ctx, TwKey{(unsigned)cfg->fftsize, cfg->b_mark, cfg->b_space,
-				     cfg->bit_nsamples}, &d_tw);
-    if ( rc )
+    Prepared p;
+    if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    DevCfg d;
-    derive_cfg(ctx, *cfg, d);
-    const DevCfg *d_cfg = nullptr;
-    CfgEntry tables;
-    rc = get_devcfg(ctx, d, &d_cfg, &tables);
-    if ( rc )
-	return rc;
-    if ( io->nstreams == 0 )
-	return 0;
-    const bool workgroup = use_workgroup_engine(cfg, d, io->flags);
-    if ( !workgroup )
-	return demod_batch_wave(ctx, cfg, d, d_cfg, d_tw, io, stream, nullptr, nullptr, nullptr, true, &tables);
-    return demod_batch_workgroup(ctx, cfg, d, d_cfg, d_tw, io, stream);
+    return io->nstreams == 0 ? 0 : demod_batch(ctx, cfg, p, io, stream);
 }
 
 static_assert(sizeof(mifsk_scan_plan) == sizeof(mifsk::SegPlan), "mifsk_scan_plan mirrors SegPlan");
@@ -1071,12 +634,9 @@ extern "C" int mifsk_scan_plan_get( const mifsk_rx_config *cfg, int kind, mifsk_
 {
     if ( mifsk_check_cfg(cfg) || !out || kind < 0 || kind > 4 )
 	return -EINVAL;
-    DevCfg *d = new (std::nothrow) DevCfg();
-    if ( !d )
-	return -ENOMEM;
-    mifsk::fill_devcfg(*d, *cfg);
-    std::memcpy(out, &d->seg[kind], sizeof(*out));
-    delete d;
+    DevCfg d;
+    mifsk::fill_devcfg(d, *cfg);
+    std::memcpy(out, &d.seg[kind], sizeof(*out));
     return 0;
 }
 
@@ -1085,56 +645,20 @@ extern "C" int mifsk_scan_plan_get( const mifsk_rx_config *cfg, int kind, mifsk_
 extern "C" int mifsk_demod_slab( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
 	mifsk_stream_state *d_state, const uint64_t *d_origin, int final, void *stream )
 {
-    if ( !ctx || !io || !d_state || mifsk_check_cfg(cfg) )
+    if ( !ctx || !io || !d_state || mifsk_check_cfg(cfg)
+	    || cfg->samplebuf_size < 2u		// (the loop refills half a buffer at a time)
+	    || check_io(cfg, io, MIFSK_IO_ENGINE_WAVE | MIFSK_IO_ENGINE_WORKGROUP) )	// flat addressing
 	return -EINVAL;
-    if ( cfg->samplebuf_size < 2u )		// (the loop refills half a buffer at a time)
-	return -EINVAL;
-    if ( io->nstreams < 0 || ( io->nstreams > 0 && !io->d_samples ) )
-	return -EINVAL;
-    if ( io->stream_stride % 4 != 0 || ( (uintptr_t)io->d_samples & 15u ) )
-	return -EINVAL;
-    if ( ( io->d_bytes || io->d_bits || io->d_frames ) && io->frames_cap == 0 )
-	return -EINVAL;
-    if ( io->flags & ~( MIFSK_IO_ENGINE_WAVE | MIFSK_IO_ENGINE_WORKGROUP ) )	// flat addressing
-	return -EINVAL;
-    if ( ( io->flags & MIFSK_IO_ENGINE_WORKGROUP )
-	    && ( ( io->flags & MIFSK_IO_ENGINE_WAVE ) || cfg->auto_carrier_threshold > 0.0f ) )
-	return -EINVAL;
-    HIP_OK(hipSetDevice(ctx->device));
-    cache_gc(ctx);
-    std::shared_lock<std::shared_mutex> gate(ctx->gate);	// lookup .. enqueue
-    const double *d_tw = nullptr;
-    int rc = get_twiddles(ctx, TwKey{(unsigned)cfg->fftsize, cfg->b_mark, cfg->b_space,
-				     cfg->bit_nsamples}, &d_tw);
-    if ( rc )
+    Prepared p;
+    if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    DevCfg d;
-    derive_cfg(ctx, *cfg, d);
-    const DevCfg *d_cfg = nullptr;
-    CfgEntry tables;
-    rc = get_devcfg(ctx, d, &d_cfg, &tables);
-    if ( rc )
-	return rc;
-    if ( io->nstreams == 0 )
-	return 0;
-    if ( use_workgroup_engine(cfg, d, io->flags) )
-	return demod_batch_workgroup(ctx, cfg, d, d_cfg, d_tw, io, stream, nullptr, d_state, d_origin, final != 0);
-    return demod_batch_wave(ctx, cfg, d, d_cfg, d_tw, io, stream, nullptr, d_state, d_origin, final != 0, &tables);
+    return io->nstreams == 0 ? 0 : demod_batch(ctx, cfg, p, io, stream, d_state, d_origin, final != 0);
 }
 
 // floats per stream of the buffer mifsk_demod_slab_ring keeps the reference's samplebuf in
 extern "C" size_t mifsk_ring_floats( const mifsk_rx_config *cfg )
 {
-    if ( mifsk_check_cfg(cfg) )
-	return 0;
-    DevCfg *d = new (std::nothrow) DevCfg();
-    if ( !d )
-	return 0;
-    mifsk::fill_devcfg(*d, *cfg);
-    const size_t reach = (size_t)( cfg->try_max[0] > cfg->try_max[1] ? cfg->try_max[0] : cfg->try_max[1] )
-		       + d->last_reach + 64;
-    delete d;
-    return ( (size_t)cfg->samplebuf_size + reach + 3 ) & ~(size_t)3;
+    return mifsk_check_cfg(cfg) ? 0 : mifsk::ring_row_floats(*cfg);
 }
 
 // mifsk_demod_slab with the reference's buffer semantics (MIFSK_IO_RING_EXACT) for streams fed
@@ -1143,37 +667,17 @@ extern "C" size_t mifsk_ring_floats( const mifsk_rx_config *cfg )
 extern "C" int mifsk_demod_slab_ring( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
 	mifsk_stream_state *d_state, const uint64_t *d_origin, float *d_ring, int final, void *stream )
 {
-    if ( !ctx || !io || !d_state || !d_ring || mifsk_check_cfg(cfg) || cfg->samplebuf_size < 2u )
+    if ( !ctx || !io || !d_state || !d_ring || mifsk_check_cfg(cfg) || cfg->samplebuf_size < 2u
+	    || check_io(cfg, io, MIFSK_IO_ENGINE_WAVE | MIFSK_IO_RING_EXACT) )	// (RING addressing is the wavefront engine's)
 	return -EINVAL;
-    if ( io->nstreams < 0 || ( io->nstreams > 0 && !io->d_samples ) )
-	return -EINVAL;
-    if ( io->stream_stride % 4 != 0 || ( (uintptr_t)io->d_samples & 15u ) )
-	return -EINVAL;
-    if ( ( io->d_bytes || io->d_bits || io->d_frames ) && io->frames_cap == 0 )
-	return -EINVAL;
-    if ( io->flags & ~( MIFSK_IO_ENGINE_WAVE | MIFSK_IO_RING_EXACT ) )	// (RING addressing is the wavefront engine's)
-	return -EINVAL;
-    HIP_OK(hipSetDevice(ctx->device));
-    cache_gc(ctx);
-    std::shared_lock<std::shared_mutex> gate(ctx->gate);	// lookup .. enqueue
-    const double *d_tw = nullptr;
-    int rc = get_twiddles(ctx, TwKey{(unsigned)cfg->fftsize, cfg->b_mark, cfg->b_space,
-				     cfg->bit_nsamples}, &d_tw);
-    if ( rc )
-	return rc;
-    DevCfg d;
-    derive_cfg(ctx, *cfg, d);
-    const DevCfg *d_cfg = nullptr;
-    CfgEntry tables;
-    rc = get_devcfg(ctx, d, &d_cfg, &tables);
-    if ( rc )
+    Prepared p;
+    if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
     if ( io->nstreams == 0 )
 	return 0;
     mifsk_demod_io rio = *io;
     rio.flags |= MIFSK_IO_RING_EXACT;
-    return demod_batch_wave(ctx, cfg, d, d_cfg, d_tw, &rio, stream, nullptr, d_state, d_origin, final != 0,
-			    &tables, d_ring);
+    return demod_batch_wave(ctx, cfg, p, &rio, stream, d_state, d_origin, final != 0, d_ring);
 }
 
 // what mifsk_demod_batch would launch for this configuration and batch size
@@ -1198,8 +702,16 @@ extern "C" int mifsk_demod_plan_ex( mifsk_ctx *ctx, const mifsk_rx_config *cfg, 
     mifsk::LaunchInfo li;
     std::memset(&li, 0, sizeof(li));
     const bool workgroup = use_workgroup_engine(cfg, d, flags);
-    int rc = workgroup ? demod_batch_workgroup(ctx, cfg, d, nullptr, nullptr, &io, nullptr, &li)
-		       : demod_batch_wave(ctx, cfg, d, nullptr, nullptr, &io, nullptr, &li);
+    int rc;
+    if ( workgroup ) {
+	mifsk::HostArgs ha = {};
+	workgroup_args(ha, ctx, cfg, &io, nullptr, nullptr, true);
+	rc = mifsk::launch_demod_batch(d, nullptr, nullptr, io, ha, nullptr, &li);
+    } else {
+	mifsk::WaveHostArgs ha = {};
+	wave_args(ha, ctx, cfg, &io, nullptr, nullptr, true);
+	rc = mifsk::launch_demod_wave(d, nullptr, nullptr, io, ha, nullptr, &li);
+    }
     if ( rc )
 	return rc;
     std::memset(out, 0, sizeof(*out));
@@ -1207,11 +719,7 @@ extern "C" int mifsk_demod_plan_ex( mifsk_ctx *ctx, const mifsk_rx_config *cfg, 
     out->engine = workgroup ? MIFSK_IO_ENGINE_WORKGROUP : MIFSK_IO_ENGINE_WAVE;
     out->workgroup_size = li.workgroup_size;
     out->lds_bytes_per_workgroup = li.lds_bytes;
-    const unsigned by_lds = li.lds_bytes ? (unsigned)( 160u * 1024u / li.lds_bytes ) : 32u;
-    // (waves per SIMD the instantiation's VGPR budget allows x 4 SIMDs)
-    const unsigned by_waves = ( li.waves_per_simd ? li.waves_per_simd : 8u ) * 4u * 64u
-			    / ( li.workgroup_size ? li.workgroup_size : 64u );
-    out->workgroups_per_cu = by_lds < by_waves ? by_lds : by_waves;
+    out->workgroups_per_cu = mifsk::workgroups_per_cu(li.lds_bytes, li.waves_per_simd, li.workgroup_size);
     out->lattice_mode = li.lattice_mode;
     out->frames_per_block = li.frames_per_block;
     out->compute_units = (uint32_t)ctx->ncu;
@@ -1253,22 +761,8 @@ extern "C" int mifsk_demod_batch_host_multi( mifsk_ctx *const *ctxs, int nctx,
 	mifsk_shard_range(hio->nstreams, k, nctx, &lo, &hi);
 	if ( hi == lo )
 	    continue;
-	mifsk_demod_io io = *hio;
-	const size_t o = (size_t)lo, fc = hio->frames_cap, ec = hio->episodes_cap;
-	io.nstreams = hi - lo;
-	io.d_samples = (const float *)( (const char *)hio->d_samples
-					+ o * hio->stream_stride * ( ( hio->flags & MIFSK_IO_HOST_S16 ) ? 2u : 4u ) );
-	if ( io.d_nsamples )	 io.d_nsamples += o;
-	if ( io.d_bytes )	 io.d_bytes += o * fc;
-	if ( io.d_nbytes )	 io.d_nbytes += o;
-	if ( io.d_bits )	 io.d_bits += o * fc;
-	if ( io.d_frames )	 io.d_frames += o * fc;
-	if ( io.d_nframes )	 io.d_nframes += o;
-	if ( io.d_episodes )	 io.d_episodes += o * ec;
-	if ( io.d_nepisodes )	 io.d_nepisodes += o;
-	if ( io.d_status )	 io.d_status += o;
-	if ( io.d_counters )	 io.d_counters += o * MIFSK_NCOUNTERS;
-	if ( io.d_carrier_band ) io.d_carrier_band += o;
+	const mifsk_demod_io io = mifsk::io_rows(*hio, (size_t)lo, hi - lo,
+						 ( hio->flags & MIFSK_IO_HOST_S16 ) ? 2u : 4u);
 	mifsk_ctx *ctx = ctxs[k];
 	int *rcp = &rcs[(size_t)k];
 	// one host thread per device: the HIP "current device" is per thread, so

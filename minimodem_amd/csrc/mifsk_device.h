@@ -1,8 +1,12 @@
-// mifsk_device.h -- types shared by the host glue and the HIP kernels.
+// mifsk_device.h -- types shared by the host glue and the HIP kernels, and what the two
+// engines' launchers share (the slice of a batch, occupancy, the chained launch).
 #pragma once
+
+#include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 
 #include "mifsk.h"
@@ -99,7 +103,12 @@ struct DevCfg {
 // twiddles: tw[4*n + {0,1,2,3}] = cos_mark, -sin_mark, cos_space, -sin_space
 // of angle 2*pi*((b*n) mod fftsize)/fftsize, in double.
 
+// (the planner: mifsk_plan.cpp)
 void fill_devcfg( DevCfg &d, const mifsk_rx_config &c );
+
+// floats per stream of a RING row: the reference's samplebuf plus what a search at its top
+// may touch beyond (mifsk_ring_floats; the per-call scratch of MIFSK_IO_RING_EXACT)
+size_t ring_row_floats( const mifsk_rx_config &c );
 
 // entries (samples) of a twiddle table for bit windows of B samples: whole
 // groups of 16 plus one group of look-ahead, never fewer than three groups
@@ -107,6 +116,14 @@ inline size_t tw_entries( unsigned B )
 {
     const size_t n = ( ( (size_t)B + 15 ) & ~(size_t)15 ) + 16;
     return n < 48 ? 48 : n;
+}
+
+// Tuning overrides for experiments (MIFSK_ENGINE, MIFSK_WAVES_PER_CU, MIFSK_SV,
+// MIFSK_LDS_PAD, MIFSK_LAT_ROUNDS, MIFSK_CHAIN): honoured only when MIFSK_EXPERIMENT is set in the
+// environment, so that a stray variable cannot change what production launches.
+inline const char *experiment_env( const char *name )
+{
+    return std::getenv("MIFSK_EXPERIMENT") != nullptr ? std::getenv(name) : nullptr;
 }
 
 // launchers (mifsk_kernels.hip); `stream` is a hipStream_t
@@ -126,11 +143,50 @@ struct LaunchInfo {
     uint32_t	chain_groups, chain_chunks;	// chained launches (WaveChain): groups of streams x time chunks; 0 = one launch
 };
 
+// the instantiation a launcher's plan runs: the function and the name mifsk_demod_plan reports,
+// from one table per engine
+struct KernelPick {
+    const void	*fn;
+    const char	*name;
+    uint32_t	waves_per_simd;
+};
+
+constexpr size_t kLdsPerCu = 160 * 1024;
+
+// workgroups of `workgroup_size` threads a CU holds at once: by their LDS and by the waves per
+// SIMD (x 4 SIMDs) the instantiation's VGPR budget allows
+inline uint32_t workgroups_per_cu( size_t lds_bytes, uint32_t waves_per_simd, uint32_t workgroup_size )
+{
+    const uint32_t by_lds = lds_bytes ? (uint32_t)( kLdsPerCu / lds_bytes ) : 32u;
+    const uint32_t by_waves = ( waves_per_simd ? waves_per_simd : 8u ) * 4u * 64u
+			    / ( workgroup_size ? workgroup_size : 64u );
+    return by_lds < by_waves ? by_lds : by_waves;
+}
+
+// rows lo .. lo + count - 1 of a batch (`sample_bytes`: 2 for MIFSK_IO_HOST_S16 rows)
+inline mifsk_demod_io io_rows( const mifsk_demod_io &io, size_t lo, int count, size_t sample_bytes = sizeof(float) )
+{
+    mifsk_demod_io o = io;
+    o.nstreams = count;
+    o.d_samples = (const float *)( (const char *)io.d_samples + lo * io.stream_stride * sample_bytes );
+    if ( o.d_nsamples )	    o.d_nsamples += lo;
+    if ( o.d_bytes )	    o.d_bytes += lo * io.frames_cap;
+    if ( o.d_nbytes )	    o.d_nbytes += lo;
+    if ( o.d_bits )	    o.d_bits += lo * io.frames_cap;
+    if ( o.d_frames )	    o.d_frames += lo * io.frames_cap;
+    if ( o.d_nframes )	    o.d_nframes += lo;
+    if ( o.d_episodes )	    o.d_episodes += lo * io.episodes_cap;
+    if ( o.d_nepisodes )    o.d_nepisodes += lo;
+    if ( o.d_status )	    o.d_status += lo;
+    if ( o.d_counters )	    o.d_counters += lo * MIFSK_NCOUNTERS;
+    if ( o.d_carrier_band ) o.d_carrier_band += lo;
+    return o;
+}
+
 struct WaveChain;
-// what the host glue hands the workgroup engine's launcher besides cfg / io: the loop state of
-// streams that arrive in pieces (mifsk_demod_slab) and what a chained launch needs (the
-// wavefront engine's WaveHostArgs carries the same)
-struct WgHostArgs {
+// what the host glue hands either engine's launcher besides cfg / io: the loop state of streams
+// that arrive in pieces (mifsk_demod_slab) and what a chained launch needs
+struct HostArgs {
     int		ncu;		// compute units of the device
     uint32_t	samplebuf_size;
     mifsk_stream_state *d_state;	// mifsk_demod_slab: state in / out (nullptr: one call = whole streams)
@@ -143,8 +199,7 @@ struct WgHostArgs {
 };
 
 int launch_demod_batch( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, void *stream, LaunchInfo *plan_only = nullptr,
-	const WgHostArgs *wh = nullptr );
+	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only = nullptr );
 
 // ---- one wavefront per stream (mifsk_wave.hip) ---------------------------
 
@@ -206,10 +261,78 @@ struct WaveChain {
     size_t		state_cap;
 };
 
-// what the host glue hands the launcher besides cfg / io
-struct WaveHostArgs {
-    int		ncu;		// compute units of the device
-    uint32_t	samplebuf_size;
+// MIFSK_CHAIN = "G,K" (experiments and tests only) cuts any batch that may be chained; then the
+// bounds of a cut: at most kMaxGroups groups, none empty, at least two chunks -- else (0, 0)
+inline void chain_shape( bool allowed, int nstreams, uint32_t &groups, uint32_t &chunks )
+{
+    if ( const char *e = experiment_env("MIFSK_CHAIN") ) {
+	int a = 0, b = 0;
+	if ( allowed && std::sscanf(e, "%d,%d", &a, &b) == 2 ) {
+	    groups = (uint32_t)( a < 0 ? 0 : a );
+	    chunks = (uint32_t)( b < 0 ? 0 : b );
+	}
+    }
+    if ( groups > (uint32_t)WaveChain::kMaxGroups ) groups = (uint32_t)WaveChain::kMaxGroups;
+    if ( groups > (uint32_t)nstreams ) groups = (uint32_t)nstreams;
+    if ( groups < 1u || chunks < 2u )
+	groups = chunks = 0u;
+}
+
+// Enqueue a batch as `groups` x `chunks` launches.  `launch(gio, lo, d_state, final, limit, gs)`
+// enqueues the resumable kernel over the rows `gio` (those from row `lo` of the batch) on the
+// group's stream `gs`: state in / out at d_state, the first `limit` samples of every row (0: all),
+// outputs appended behind the chunk before.  The caller's stream waits for all of it, whatever
+// fails on the way.
+template <class Launch>
+int chain_enqueue( const WaveChain &ch, const mifsk_demod_io &io, uint32_t groups, uint32_t chunks,
+	hipStream_t st, Launch launch )
+{
+    if ( (size_t)io.nstreams > ch.state_cap )
+	return -12;
+    hipEvent_t fork = (hipEvent_t)ch.ev_fork;
+    if ( hipEventRecord(fork, st) != hipSuccess )
+	return -5;
+    // (a limit of 0 means "all samples": rows with per-stream lengths only are not cut in time)
+    if ( io.nsamples == 0u )
+	chunks = 1u;
+    mifsk_demod_io gio[WaveChain::kMaxGroups];
+    uint32_t glo[WaveChain::kMaxGroups];
+    bool prepared = true;
+    for ( uint32_t gi = 0; gi < groups; gi++ ) {
+	hipStream_t gs = (hipStream_t)ch.streams[gi];
+	// behind the caller's stream, and behind whatever the call before left on ANY group's
+	// stream (its groups were other ranges of the state array)
+	(void)hipStreamWaitEvent(gs, fork, 0);
+	for ( uint32_t h = 0; h < (uint32_t)WaveChain::kMaxGroups; h++ )
+	    if ( h != gi )
+		(void)hipStreamWaitEvent(gs, (hipEvent_t)ch.ev_done[h], 0);
+	const uint32_t lo = (uint32_t)( (uint64_t)io.nstreams * gi / groups );
+	const uint32_t hi = (uint32_t)( (uint64_t)io.nstreams * ( gi + 1u ) / groups );
+	glo[gi] = lo;
+	gio[gi] = io_rows(io, lo, (int)( hi - lo ));
+	if ( hi > lo
+		&& hipMemsetAsync(ch.d_state + lo, 0, (size_t)( hi - lo ) * sizeof(mifsk_stream_state), gs) != hipSuccess )
+	    prepared = false;		// (no early return: the caller's stream is joined below either way)
+    }
+    const uint32_t chunk = ( io.nsamples + chunks - 1u ) / chunks;
+    for ( uint32_t k = 0; k < chunks && prepared; k++ ) {
+	const bool last = k + 1u == chunks;
+	const uint64_t lim = (uint64_t)( k + 1u ) * chunk;
+	for ( uint32_t gi = 0; gi < groups; gi++ )
+	    if ( gio[gi].nstreams > 0 )
+		launch(gio[gi], glo[gi], ch.d_state + glo[gi], last,
+		       last ? 0u : ( lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim ), (hipStream_t)ch.streams[gi]);
+    }
+    const bool launched = hipGetLastError() == hipSuccess && prepared;
+    for ( uint32_t gi = 0; gi < groups; gi++ ) {
+	(void)hipEventRecord((hipEvent_t)ch.ev_done[gi], (hipStream_t)ch.streams[gi]);
+	(void)hipStreamWaitEvent(st, (hipEvent_t)ch.ev_done[gi], 0);
+    }
+    return launched ? 0 : -5;
+}
+
+// what the host glue hands the wavefront engine's launcher besides that
+struct WaveHostArgs : HostArgs {
     bool	ring_exact;
     uint32_t	ring_stride;
     float	*d_ring;
@@ -221,15 +344,8 @@ struct WaveHostArgs {
     uint32_t	tw_entries;
     const double *d_cs;
     double	*d_tw_scratch;
-    mifsk_stream_state *d_state;
-    const uint64_t *d_origin;
-    bool	final;
     const double *d_rot[5];
     uint32_t	rot_stride[5];
-    // non-NULL: the launcher may chain (it decides by the batch's shape); the caller holds
-    // whatever serialises the chain's users.  chain_ok: what a plan-only call assumes
-    const WaveChain *chain;
-    bool	chain_ok;
 };
 
 int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
@@ -241,14 +357,6 @@ int launch_detect_carrier( const float *d_samples, unsigned nsamples,
 
 // self-test of the short square root of band_mag2() (mifsk_kernels.hip); d_out: four counters
 int launch_selftest_sqrt( uint64_t seed, uint32_t blocks, uint32_t per_thread, unsigned long long *d_out, void *stream );
-
-// Tuning overrides for experiments (MIFSK_ENGINE, MIFSK_WAVES_PER_CU, MIFSK_SV,
-// MIFSK_LDS_PAD, MIFSK_LAT_ROUNDS, MIFSK_CHAIN): honoured only when MIFSK_EXPERIMENT is set in the
-// environment, so that a stray variable cannot change what production launches.
-inline const char *experiment_env( const char *name )
-{
-    return std::getenv("MIFSK_EXPERIMENT") != nullptr ? std::getenv(name) : nullptr;
-}
 
 // the HIP device a context is bound to (mifsk_capi.cpp)
 int ctx_device( const mifsk_ctx *ctx );

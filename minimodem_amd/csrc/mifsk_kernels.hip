@@ -1914,15 +1914,40 @@ int launch_find_frame_batch( const DevCfg &cfg, const DevCfg *d_cfg, const doubl
 }
 
 static constexpr size_t kLdsHeader = offsetof(StreamLds, slab);
-static constexpr size_t kLdsPerCu = 160 * 1024;
 
 // `nworkers` = 2 asks for the Bell-202 instantiation; kNotBell202 if the
 // configuration does not end up there (the caller then plans with three)
 static constexpr int kNotBell202 = -100000;
 
+// Every instantiation of demod_kernel there is, with the name mifsk_demod_plan reports for it and
+// the waves per SIMD its registers allow.  ST: the resumable ones (mifsk_demod_slab, chained
+// launches).
+struct WgKernel {
+    bool	use_slab, bell202, st;
+    KernelPick	pick;
+};
+#define MIFSK_WG_KERNEL(WAVES_, ...)										\
+    { reinterpret_cast<const void *>(&demod_kernel<__VA_ARGS__>), "mifsk::demod_kernel<" #__VA_ARGS__ ">", WAVES_ }
+static const WgKernel kWgKernels[] = {
+    { false, false, true,  MIFSK_WG_KERNEL(4u, false, 0, 3, true) },	// no slab: e.g. 0.5 baud
+    { true,  true,  true,  MIFSK_WG_KERNEL(3u, true, 10, 2, true) },	// Bell-202: two workers, resident table
+    { true,  false, true,  MIFSK_WG_KERNEL(4u, true, 0, 3, true) },
+    { true,  true,  false, MIFSK_WG_KERNEL(3u, true, 10, 2) },
+    { true,  false, false, MIFSK_WG_KERNEL(4u, true, 0, 3) },
+    { false, false, false, MIFSK_WG_KERNEL(4u, false, 0, 3) },
+};
+#undef MIFSK_WG_KERNEL
+
+static const KernelPick &wg_kernel( bool use_slab, bool bell202, bool st )
+{
+    for ( const WgKernel &k : kWgKernels )
+	if ( k.use_slab == use_slab && k.bell202 == bell202 && k.st == st )
+	    return k.pick;
+    return kWgKernels[0].pick;		// (not reached: Bell-202 always has a slab)
+}
+
 static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, void *stream, LaunchInfo *plan_only, const uint32_t nworkers,
-	const WgHostArgs *wh )
+	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only, const uint32_t nworkers )
 {
     const uint32_t B = cfg.bit_nsamples;
     const uint32_t lat_lanes = nworkers * 64u;	// bit windows per lattice round
@@ -2023,7 +2048,6 @@ static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const do
 	}
     }
 
-    hipStream_t st = (hipStream_t)stream;
     const bool bell202 = nworkers == 2u && use_slab && lat_mode == LAT_LINEAR && B == 40u;
     if ( nworkers == 2u && !bell202 )
 	return kNotBell202;
@@ -2039,156 +2063,67 @@ static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const do
     // 0.84-0.90 / 1.43-1.52 / 2.24-2.38 chained (2x2 ... 3x3).  MIFSK_CHAIN forces a cut
     // (experiments and tests).
     uint32_t chain_g = 0, chain_k = 0;
-    if ( wh ) {
-	const bool allowed = ( plan_only ? wh->chain_ok : wh->chain != nullptr ) && !wh->d_state
-			  && !io.d_counters && io.nstreams > 0;
-	if ( const char *e = experiment_env("MIFSK_CHAIN") ) {	// experiments and tests only: "G,K", any batch
-	    int a = 0, b = 0;
-	    if ( allowed && std::sscanf(e, "%d,%d", &a, &b) == 2 ) {
-		chain_g = (uint32_t)( a < 0 ? 0 : a );
-		chain_k = (uint32_t)( b < 0 ? 0 : b );
-	    }
-	}
-	if ( chain_g > (uint32_t)WaveChain::kMaxGroups ) chain_g = (uint32_t)WaveChain::kMaxGroups;
-	if ( chain_g > (uint32_t)io.nstreams ) chain_g = (uint32_t)io.nstreams;
-	// (the cut is made by io.nsamples: with per-stream lengths only -- io.nsamples == 0 -- a
-	// limit of 0 would mean "all samples" to every chunk but the last; such a batch is not cut)
-	if ( chain_g < 1u || chain_k < 2u || io.nsamples == 0u )
-	    chain_g = chain_k = 0u;
-    }
-    const bool resumable = ( wh && wh->d_state ) || chain_g;
+    chain_shape(( plan_only ? ha.chain_ok : ha.chain != nullptr ) && !ha.d_state && !io.d_counters && io.nstreams > 0,
+		io.nstreams, chain_g, chain_k);
+    // (the cut is made by io.nsamples: with per-stream lengths only -- io.nsamples == 0 -- a
+    // limit of 0 would mean "all samples" to every chunk but the last; such a batch is not cut)
+    if ( io.nsamples == 0u )
+	chain_g = chain_k = 0u;
+    const KernelPick &kernel = wg_kernel(use_slab, bell202, ha.d_state || chain_g);
     if ( plan_only ) {
-	plan_only->kernel = !use_slab ? ( resumable ? "mifsk::demod_kernel<false, 0, 3, true>" : "mifsk::demod_kernel<false, 0, 3>" )
-			  : bell202 ? ( resumable ? "mifsk::demod_kernel<true, 10, 2, true>" : "mifsk::demod_kernel<true, 10, 2>" )
-				    : ( resumable ? "mifsk::demod_kernel<true, 0, 3, true>" : "mifsk::demod_kernel<true, 0, 3>" );
+	plan_only->kernel = kernel.name;
 	plan_only->workgroup_size = block;
 	plan_only->lds_bytes = (uint32_t)lds_all;
 	plan_only->lattice_mode = lat_mode;
 	plan_only->frames_per_block = lat_frames * lat_rounds;
-	plan_only->waves_per_simd = bell202 ? 3 : 4;
+	plan_only->waves_per_simd = kernel.waves_per_simd;
 	plan_only->chain_groups = chain_g;
 	plan_only->chain_chunks = chain_k;
 	return 0;
     }
+    // (the plain instantiations ignore all of it)
     WgResume rs;
     std::memset(&rs, 0, sizeof(rs));
-    if ( resumable ) {
-	// mifsk_demod_slab and the chained launches: the instantiations with the state code
-	rs.d_state = wh->d_state;
-	rs.d_origin = wh->d_origin;
-	rs.final = wh->final ? 1u : 0u;
-	rs.bufsize = wh->samplebuf_size;
-	const void *fn = !use_slab ? reinterpret_cast<const void *>(&demod_kernel<false, 0, 3, true>)
-		       : bell202 ? reinterpret_cast<const void *>(&demod_kernel<true, 10, 2, true>)
-				 : reinterpret_cast<const void *>(&demod_kernel<true, 0, 3, true>);
-	if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all) != hipSuccess )
-	    return -5;
-	uint32_t a_slab_cap = use_slab ? slab_cap : 0u, a_lat_frames = use_slab ? lat_frames : 0u;
-	uint32_t a_lat_rounds = use_slab ? lat_rounds : 1u, a_region_floats = use_slab ? (uint32_t)region_floats : 0u;
-	uint32_t a_region_cap = use_slab ? region_cap : 0u, a_lat_mode = use_slab ? lat_mode : (uint32_t)LAT_NONE;
-	if ( !chain_g ) {
-	    mifsk_demod_io o = io;
-	    void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&o, (void *)&a_slab_cap, (void *)&a_lat_frames,
-			      (void *)&a_lat_rounds, (void *)&a_region_floats, (void *)&a_region_cap, (void *)&a_lat_mode, (void *)&rs };
-	    (void)hipLaunchKernel(fn, dim3((unsigned)io.nstreams), dim3(block), kargs, lds_all, st);
-	    return hip_rc(hipGetLastError());
-	}
-	const WaveChain &ch = *wh->chain;
-	if ( (size_t)io.nstreams > ch.state_cap )
-	    return -12;
-	hipEvent_t fork = (hipEvent_t)ch.ev_fork;
-	if ( hipEventRecord(fork, st) != hipSuccess )
-	    return -5;
-	mifsk_demod_io gio[WaveChain::kMaxGroups];
-	uint32_t glo[WaveChain::kMaxGroups];
-	bool prepared = true;
-	for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-	    hipStream_t gs = (hipStream_t)ch.streams[gi];
-	    // behind the caller's stream, and behind whatever the call before left on ANY group's
-	    // stream (its groups were other ranges of the state array)
-	    (void)hipStreamWaitEvent(gs, fork, 0);
-	    for ( uint32_t h = 0; h < (uint32_t)WaveChain::kMaxGroups; h++ )
-		if ( h != gi )
-		    (void)hipStreamWaitEvent(gs, (hipEvent_t)ch.ev_done[h], 0);
-	    const uint32_t lo = (uint32_t)( (uint64_t)io.nstreams * gi / chain_g );
-	    const uint32_t hi = (uint32_t)( (uint64_t)io.nstreams * ( gi + 1u ) / chain_g );
-	    glo[gi] = lo;
-	    mifsk_demod_io &o = gio[gi];
-	    o = io;
-	    o.nstreams = (int)( hi - lo );
-	    o.d_samples = io.d_samples + (size_t)lo * io.stream_stride;
-	    if ( io.d_nsamples ) o.d_nsamples = io.d_nsamples + lo;
-	    if ( io.d_bytes ) o.d_bytes = io.d_bytes + (size_t)lo * io.frames_cap;
-	    if ( io.d_nbytes ) o.d_nbytes = io.d_nbytes + lo;
-	    if ( io.d_bits ) o.d_bits = io.d_bits + (size_t)lo * io.frames_cap;
-	    if ( io.d_frames ) o.d_frames = io.d_frames + (size_t)lo * io.frames_cap;
-	    if ( io.d_nframes ) o.d_nframes = io.d_nframes + lo;
-	    if ( io.d_episodes ) o.d_episodes = io.d_episodes + (size_t)lo * io.episodes_cap;
-	    if ( io.d_nepisodes ) o.d_nepisodes = io.d_nepisodes + lo;
-	    if ( io.d_status ) o.d_status = io.d_status + lo;
-	    if ( o.nstreams > 0
-		    && hipMemsetAsync(ch.d_state + lo, 0, (size_t)o.nstreams * sizeof(mifsk_stream_state), gs) != hipSuccess )
-		prepared = false;		// (no early return: the caller's stream is joined below either way)
-	}
-	const uint32_t chunk = ( io.nsamples + chain_k - 1u ) / chain_k;
+    rs.d_state = ha.d_state;
+    rs.d_origin = ha.d_origin;
+    rs.final = ha.final ? 1u : 0u;
+    rs.bufsize = ha.samplebuf_size;
+    if ( hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all) != hipSuccess )
+	return -5;
+    uint32_t a_slab_cap = use_slab ? slab_cap : 0u, a_lat_frames = use_slab ? lat_frames : 0u;
+    uint32_t a_lat_rounds = use_slab ? lat_rounds : 1u, a_region_floats = use_slab ? (uint32_t)region_floats : 0u;
+    uint32_t a_region_cap = use_slab ? region_cap : 0u, a_lat_mode = use_slab ? lat_mode : (uint32_t)LAT_NONE;
+    auto launch = [&]( const mifsk_demod_io &rows, hipStream_t on ) {
+	void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&a_slab_cap, (void *)&a_lat_frames,
+			  (void *)&a_lat_rounds, (void *)&a_region_floats, (void *)&a_region_cap, (void *)&a_lat_mode, (void *)&rs };
+	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(block), kargs, lds_all, on);
+    };
+    if ( chain_g ) {
 	rs.append = 1u;
 	rs.d_origin = nullptr;
-	for ( uint32_t k = 0; k < chain_k && prepared; k++ ) {
-	    const bool last = k + 1u == chain_k;
-	    rs.final = last ? 1u : 0u;
-	    const uint64_t lim = (uint64_t)( k + 1u ) * chunk;
-	    rs.limit = last ? 0u : ( lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim );
-	    for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-		if ( gio[gi].nstreams <= 0 )
-		    continue;
-		rs.d_state = ch.d_state + glo[gi];
-		void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&gio[gi], (void *)&a_slab_cap, (void *)&a_lat_frames,
-				  (void *)&a_lat_rounds, (void *)&a_region_floats, (void *)&a_region_cap, (void *)&a_lat_mode, (void *)&rs };
-		(void)hipLaunchKernel(fn, dim3((unsigned)gio[gi].nstreams), dim3(block), kargs, lds_all,
-				      (hipStream_t)ch.streams[gi]);
-	    }
-	}
-	const bool launched = hipGetLastError() == hipSuccess && prepared;
-	for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-	    (void)hipEventRecord((hipEvent_t)ch.ev_done[gi], (hipStream_t)ch.streams[gi]);
-	    (void)hipStreamWaitEvent(st, (hipEvent_t)ch.ev_done[gi], 0);
-	}
-	return launched ? 0 : -5;
+	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
+		[&]( const mifsk_demod_io &rows, uint32_t, mifsk_stream_state *d_state, bool last, uint32_t limit, hipStream_t gs ) {
+		    rs.d_state = d_state;
+		    rs.final = last ? 1u : 0u;
+		    rs.limit = limit;
+		    launch(rows, gs);
+		});
     }
-    if ( use_slab ) {
-	const size_t lds_bytes = kLdsHeader + slab_floats * 4;
-	hipError_t e = hipFuncSetAttribute(
-		bell202 ? reinterpret_cast<const void *>(&demod_kernel<true, 10, 2>)
-			: reinterpret_cast<const void *>(&demod_kernel<true, 0, 3>),
-		hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if ( e != hipSuccess )
-	    return hip_rc(e);
-	if ( bell202 )
-	    hipLaunchKernelGGL((demod_kernel<true, 10, 2>), dim3((unsigned)io.nstreams), dim3(block),
-			       lds_bytes, st, d_cfg, d_tw, io, slab_cap, lat_frames, lat_rounds,
-			       (uint32_t)region_floats, region_cap, lat_mode, rs);
-	else
-	    hipLaunchKernelGGL((demod_kernel<true, 0, 3>), dim3((unsigned)io.nstreams), dim3(block),
-			       lds_bytes, st, d_cfg, d_tw, io, slab_cap, lat_frames, lat_rounds,
-			       (uint32_t)region_floats, region_cap, lat_mode, rs);
-    } else {
-	hipLaunchKernelGGL((demod_kernel<false, 0, 3>), dim3((unsigned)io.nstreams), dim3(block),
-			   kLdsHeader + 16, st, d_cfg, d_tw, io, 0u, 0u, 1u, 0u, 0u, (uint32_t)LAT_NONE, rs);
-    }
+    launch(io, (hipStream_t)stream);
     return hip_rc(hipGetLastError());
 }
 
 int launch_demod_batch( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, void *stream, LaunchInfo *plan_only, const WgHostArgs *wh )
+	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only )
 {
     if ( io.nstreams <= 0 && !plan_only )
 	return 0;
     if ( cfg.lat_linear && cfg.bit_nsamples == 40u ) {
-	const int rc = launch_with_workers(cfg, d_cfg, d_tw, io, stream, plan_only, 2u, wh);
+	const int rc = launch_with_workers(cfg, d_cfg, d_tw, io, ha, stream, plan_only, 2u);
 	if ( rc != kNotBell202 )
 	    return rc;
     }
-    return launch_with_workers(cfg, d_cfg, d_tw, io, stream, plan_only, 3u, wh);
+    return launch_with_workers(cfg, d_cfg, d_tw, io, ha, stream, plan_only, 3u);
 }
 
 int launch_detect_carrier( const float *d_samples, unsigned nsamples,

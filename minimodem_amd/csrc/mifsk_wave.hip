@@ -1848,8 +1848,6 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 // launcher: occupancy and LDS geometry per configuration
 // ---------------------------------------------------------------------------
 
-static constexpr size_t kLdsPerCu = 160 * 1024;
-
 namespace {
 
 struct Plan {
@@ -1991,6 +1989,52 @@ bool plan_for( const DevCfg &cfg, const WaveHostArgs &ha, int sv, size_t budget,
     }
 }
 
+// Every instantiation of demod_wave_kernel there is, with the name mifsk_demod_plan reports for
+// it (which does not spell RA) and the waves per SIMD it is compiled for (its __launch_bounds__).
+// The resumable ones (ST) have generic correlators only; mifsk_demod_slab runs them with RA, a
+// chain by --auto-carrier.
+static_assert(kTiled == -1 && kDirect == -2, "the rows below spell them out");
+struct WaveKernel {
+    int		sv, nq;
+    bool	st, ra;
+    KernelPick	pick;
+};
+#define MIFSK_WAVE_KERNEL(SV_, NQ_, ST_, RA_)									\
+    { SV_, NQ_, ST_, RA_,											\
+      { reinterpret_cast<const void *>(&demod_wave_kernel<SV_, NQ_, ST_, RA_>),				\
+	ST_ ? "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ", true>" : "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ">",	\
+	NQ_ == kTiled || SV_ >= 10 ? 2u : 4u } }
+const WaveKernel kWaveKernels[] = {
+    MIFSK_WAVE_KERNEL(10, -1, true, true),	MIFSK_WAVE_KERNEL(10, 0, true, true),	MIFSK_WAVE_KERNEL(10, -2, true, true),
+    MIFSK_WAVE_KERNEL(4, 0, true, true),	MIFSK_WAVE_KERNEL(4, -2, true, true),
+    MIFSK_WAVE_KERNEL(10, -1, true, false),	MIFSK_WAVE_KERNEL(10, 0, true, false),	MIFSK_WAVE_KERNEL(10, -2, true, false),
+    MIFSK_WAVE_KERNEL(4, 0, true, false),	MIFSK_WAVE_KERNEL(4, -2, true, false),
+    MIFSK_WAVE_KERNEL(10, -1, false, true),	MIFSK_WAVE_KERNEL(10, -1, false, false),	// RTTY and slower
+    MIFSK_WAVE_KERNEL(10, 10, false, true),	MIFSK_WAVE_KERNEL(10, 10, false, false),	// 1200 baud at 48 kHz
+    MIFSK_WAVE_KERNEL(10, 5, false, true),	MIFSK_WAVE_KERNEL(10, 5, false, false),		// 2400 baud; 1200 baud at 24 kHz
+    MIFSK_WAVE_KERNEL(10, 0, false, true),	MIFSK_WAVE_KERNEL(10, 0, false, false),
+    MIFSK_WAVE_KERNEL(10, -2, false, true),	MIFSK_WAVE_KERNEL(10, -2, false, false),
+    MIFSK_WAVE_KERNEL(4, 1, false, true),	MIFSK_WAVE_KERNEL(4, 1, false, false),		// 12000 baud
+    MIFSK_WAVE_KERNEL(4, 0, false, true),	MIFSK_WAVE_KERNEL(4, 0, false, false),
+    MIFSK_WAVE_KERNEL(4, -2, false, true),	MIFSK_WAVE_KERNEL(4, -2, false, false),		// SAME
+};
+#undef MIFSK_WAVE_KERNEL
+
+// The instantiation a plan runs.  `nq`: the resident-table correlator of the bit length, where
+// there is one (0: the generic correlators); `st`: resumable; `ra`: with RING addressing and
+// --auto-carrier.
+const KernelPick *wave_kernel( const Plan &plan, uint32_t nq, bool st, bool ra )
+{
+    const int sv = plan.g.tiled ? 10 : plan.sv;
+    int want = plan.g.tiled ? kTiled : plan.g.lat_mode == LAT_LINEAR ? 0 : kDirect;
+    if ( !st && !plan.g.tiled && ( sv == 10 ? nq == 10u || nq == 5u : nq == 1u ) )
+	want = (int)nq;
+    for ( const WaveKernel &k : kWaveKernels )
+	if ( k.sv == sv && k.nq == want && k.st == st && k.ra == ra )
+	    return &k.pick;
+    return nullptr;		// (a staging width no instantiation has)
+}
+
 } // namespace
 
 int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
@@ -2049,16 +2093,22 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
 	if ( !ok )
 	    return -12;
     }
+    const bool lin = plan.g.lat_mode == LAT_LINEAR;
+    // the resident-table correlator of the bit lengths that have one (linear LATTICE only)
+    const uint32_t nq = ( lin && cfg.bit_nsamples % 4u == 0u ) ? cfg.bit_nsamples / 4u : 0u;
+    // (RING addressing and --auto-carrier have their own instantiations: the plain ones carry
+    // neither that code nor the registers it keeps alive; mifsk_demod_slab's all do)
+    const bool ra = ha.d_state || ha.ring_exact || ha.autodetect;
     // Chained launches (WaveChain, mifsk_device.h): where the plain instantiation is one of the
     // resumable ones, the batch is more than the chip holds at once and the streams are long
     // enough to cut (a chunk's last samplebuf waits for the next chunk: at least 8 per chunk).
     uint32_t chain_g = 0, chain_k = 0;
     {
-	const uint32_t nq0 = ( plan.g.lat_mode == LAT_LINEAR && cfg.bit_nsamples % 4u == 0u ) ? cfg.bit_nsamples / 4u : 0u;
-	const bool st_kernel = plan.g.tiled || !( ( plan.sv == 10 && ( nq0 == 10u || nq0 == 5u ) ) || ( plan.sv == 4 && nq0 == 1u ) );
-	const uint32_t by_lds = (uint32_t)( kLdsPerCu / ( plan.lds_bytes ? plan.lds_bytes : 1 ) );
-	const uint32_t by_regs = ( plan.g.tiled || plan.sv == 10 ? 2u : 4u ) * 4u;
-	const uint64_t slots = (uint64_t)( by_lds < by_regs ? by_lds : by_regs ) * (uint64_t)ncu;
+	const KernelPick *plain = wave_kernel(plan, nq, false, ra);
+	if ( !plain )
+	    return -22;
+	const bool st_kernel = plain == wave_kernel(plan, 0u, false, ra);
+	const uint64_t slots = (uint64_t)workgroups_per_cu(plan.lds_bytes, plain->waves_per_simd, 64u) * (uint64_t)ncu;
 	const bool allowed = ( plan_only ? ha.chain_ok : ha.chain != nullptr ) && st_kernel && !ha.d_state
 			  && !ha.ring_exact && !io.d_counters && io.nstreams > 0;
 	if ( allowed && (uint64_t)io.nstreams > slots && ha.samplebuf_size > 0u ) {
@@ -2066,18 +2116,11 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
 	    chain_k = io.nsamples / ( 8u * ha.samplebuf_size );
 	    if ( chain_k > 8u ) chain_k = 8u;
 	}
-	if ( const char *e = experiment_env("MIFSK_CHAIN") ) {	// experiments and tests only: "G,K", any batch
-	    int a = 0, b = 0;
-	    if ( allowed && std::sscanf(e, "%d,%d", &a, &b) == 2 ) {
-		chain_g = (uint32_t)( a < 0 ? 0 : a );
-		chain_k = (uint32_t)( b < 0 ? 0 : b );
-	    }
-	}
-	if ( chain_g > (uint32_t)WaveChain::kMaxGroups ) chain_g = (uint32_t)WaveChain::kMaxGroups;
-	if ( chain_g > (uint32_t)io.nstreams ) chain_g = (uint32_t)io.nstreams;
-	if ( chain_g < 1u || chain_k < 2u )
-	    chain_g = chain_k = 0u;
+	chain_shape(allowed, io.nstreams, chain_g, chain_k);
     }
+    // (mifsk_demod_slab and the chained launches: the instantiations with the state code)
+    const bool resumable = ha.d_state || chain_g;
+    const KernelPick &kernel = *wave_kernel(plan, nq, resumable, ra);
     // Whole rounds.  A batch of more streams than waves fit runs in rounds, and a last round
     // that is a fraction of one leaves the chip mostly idle while its chains finish (4096 RTTY
     // streams at 12 waves per CU are 1.33 rounds: measured 13.8 ms against 13.3 at 8-10).  Among
@@ -2086,9 +2129,7 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
     // to it by its LDS allocation.  (Not for chained launches: their slots are refilled as they
     // come free.)
     {
-	const uint32_t by_lds = (uint32_t)( kLdsPerCu / ( plan.lds_bytes ? plan.lds_bytes : 1 ) );
-	const uint32_t by_regs = ( plan.g.tiled || plan.sv == 10 ? 2u : 4u ) * 4u;
-	const uint32_t most = by_lds < by_regs ? by_lds : by_regs;
+	const uint32_t most = workgroups_per_cu(plan.lds_bytes, kernel.waves_per_simd, 64u);
 	const uint32_t per_cu = ( (uint32_t)( io.nstreams > 0 ? io.nstreams : 0 ) + (uint32_t)ncu - 1u ) / (uint32_t)ncu;
 	if ( most >= 3u && per_cu > most && !chain_g ) {
 	    uint32_t best = most, best_waste = 0xFFFFFFFFu;
@@ -2110,6 +2151,17 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
 	if ( (size_t)std::atoi(e) > plan.lds_bytes )
 	    plan.lds_bytes = (size_t)std::atoi(e);
     WaveGeom &g = plan.g;
+    if ( plan_only ) {
+	plan_only->kernel = kernel.name;
+	plan_only->workgroup_size = 64;
+	plan_only->lds_bytes = (uint32_t)plan.lds_bytes;
+	plan_only->lattice_mode = g.lat_mode;
+	plan_only->frames_per_block = g.lat_mode != LAT_NONE ? g.lat_fmax : 0u;
+	plan_only->waves_per_simd = kernel.waves_per_simd;
+	plan_only->chain_groups = chain_g;
+	plan_only->chain_chunks = chain_k;
+	return 0;
+    }
     g.bufsize = ha.samplebuf_size;
     g.ring_exact = ha.ring_exact ? 1u : 0u;
     g.ring_stride = ha.ring_stride;
@@ -2133,158 +2185,26 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
 	au.d_rot[k] = ha.d_rot[k];
 	au.rot_stride[k] = ha.rot_stride[k];
     }
-
-    // the instantiation: staging width x resident-table correlator for the bit
-    // lengths that have one (linear LATTICE only)
-    const uint32_t nq = ( g.lat_mode == LAT_LINEAR && cfg.bit_nsamples % 4u == 0u ) ? cfg.bit_nsamples / 4u : 0u;
-    if ( plan_only ) {
-	const bool lin = g.lat_mode == LAT_LINEAR;	// (generic instantiations: <., 0> linear lattice, <., -2> direct or none)
-	plan_only->kernel = chain_g ? ( g.tiled ? "mifsk::demod_wave_kernel<10, -1, true>"
-					 : plan.sv == 10 ? ( lin ? "mifsk::demod_wave_kernel<10, 0, true>" : "mifsk::demod_wave_kernel<10, -2, true>" )
-							 : ( lin ? "mifsk::demod_wave_kernel<4, 0, true>" : "mifsk::demod_wave_kernel<4, -2, true>" ) )
-			  : g.tiled ? "mifsk::demod_wave_kernel<10, -1>"
-			  : plan.sv == 10 ? ( nq == 10u ? "mifsk::demod_wave_kernel<10, 10>"
-					   : nq == 5u ? "mifsk::demod_wave_kernel<10, 5>"
-					   : lin ? "mifsk::demod_wave_kernel<10, 0>" : "mifsk::demod_wave_kernel<10, -2>" )
-					  : ( nq == 1u ? "mifsk::demod_wave_kernel<4, 1>"
-					      : lin ? "mifsk::demod_wave_kernel<4, 0>" : "mifsk::demod_wave_kernel<4, -2>" );
-	plan_only->workgroup_size = 64;
-	plan_only->lds_bytes = (uint32_t)plan.lds_bytes;
-	plan_only->lattice_mode = g.lat_mode;
-	plan_only->frames_per_block = g.lat_mode != LAT_NONE ? g.lat_fmax : 0u;
-	plan_only->waves_per_simd = g.tiled || plan.sv == 10 ? 2u : 4u;
-	plan_only->chain_groups = chain_g;
-	plan_only->chain_chunks = chain_k;
-	return 0;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    if ( hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes) != hipSuccess )
+	return -5;
+    auto launch = [&]( const mifsk_demod_io &rows, hipStream_t on ) {
+	void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&g, (void *)&au };
+	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(64), kargs, plan.lds_bytes, on);
+    };
     if ( chain_g ) {
-	const WaveChain &ch = *ha.chain;
-	if ( (size_t)io.nstreams > ch.state_cap )
-	    return -12;
-	const bool lin = g.lat_mode == LAT_LINEAR;
-	// which resumable instantiation: staging width x lattice kind x (--auto-carrier or not)
-#define MIFSK_CHAIN_PICK(RA_)											\
-	( g.tiled ? reinterpret_cast<const void *>(&demod_wave_kernel<10, kTiled, true, RA_>)			\
-	  : plan.sv == 10 ? ( lin ? reinterpret_cast<const void *>(&demod_wave_kernel<10, 0, true, RA_>)		\
-				  : reinterpret_cast<const void *>(&demod_wave_kernel<10, kDirect, true, RA_>) )	\
-			  : ( lin ? reinterpret_cast<const void *>(&demod_wave_kernel<4, 0, true, RA_>)		\
-				  : reinterpret_cast<const void *>(&demod_wave_kernel<4, kDirect, true, RA_>) ) )
-	const void *fn = ha.autodetect ? MIFSK_CHAIN_PICK(true) : MIFSK_CHAIN_PICK(false);
-#undef MIFSK_CHAIN_PICK
-	if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes) != hipSuccess )
-	    return -5;
-	hipEvent_t fork = (hipEvent_t)ch.ev_fork;
-	if ( hipEventRecord(fork, st) != hipSuccess )
-	    return -5;
-	mifsk_demod_io gio[WaveChain::kMaxGroups];
-	uint32_t glo[WaveChain::kMaxGroups];
-	for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-	    hipStream_t gs = (hipStream_t)ch.streams[gi];
-	    // behind the caller's stream, and behind whatever the call before left on ANY group's
-	    // stream (its groups were other ranges of the state array)
-	    (void)hipStreamWaitEvent(gs, fork, 0);
-	    for ( uint32_t h = 0; h < (uint32_t)WaveChain::kMaxGroups; h++ )
-		if ( h != gi )
-		    (void)hipStreamWaitEvent(gs, (hipEvent_t)ch.ev_done[h], 0);
-	    const uint32_t lo = (uint32_t)( (uint64_t)io.nstreams * gi / chain_g );
-	    const uint32_t hi = (uint32_t)( (uint64_t)io.nstreams * ( gi + 1u ) / chain_g );
-	    glo[gi] = lo;
-	    mifsk_demod_io &o = gio[gi];
-	    o = io;
-	    o.nstreams = (int)( hi - lo );
-	    o.d_samples = io.d_samples + (size_t)lo * io.stream_stride;
-	    if ( io.d_nsamples ) o.d_nsamples = io.d_nsamples + lo;
-	    if ( io.d_bytes ) o.d_bytes = io.d_bytes + (size_t)lo * io.frames_cap;
-	    if ( io.d_nbytes ) o.d_nbytes = io.d_nbytes + lo;
-	    if ( io.d_bits ) o.d_bits = io.d_bits + (size_t)lo * io.frames_cap;
-	    if ( io.d_frames ) o.d_frames = io.d_frames + (size_t)lo * io.frames_cap;
-	    if ( io.d_nframes ) o.d_nframes = io.d_nframes + lo;
-	    if ( io.d_episodes ) o.d_episodes = io.d_episodes + (size_t)lo * io.episodes_cap;
-	    if ( io.d_nepisodes ) o.d_nepisodes = io.d_nepisodes + lo;
-	    if ( io.d_status ) o.d_status = io.d_status + lo;
-	    if ( io.d_carrier_band ) o.d_carrier_band = io.d_carrier_band + lo;
-	    if ( o.nstreams > 0
-		    && hipMemsetAsync(ch.d_state + lo, 0, (size_t)o.nstreams * sizeof(mifsk_stream_state), gs) != hipSuccess )
-		return -5;
-	}
-	const uint32_t chunk = ( io.nsamples + chain_k - 1u ) / chain_k;
 	au.append = 1u;
 	au.d_origin = nullptr;
-	for ( uint32_t k = 0; k < chain_k; k++ ) {
-	    const bool last = k + 1u == chain_k;
-	    au.final = last ? 1u : 0u;
-	    au.limit = last ? 0u : ( k + 1u ) * chunk;
-	    for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-		if ( gio[gi].nstreams <= 0 )
-		    continue;
-		hipStream_t gs = (hipStream_t)ch.streams[gi];
-		au.d_state = ch.d_state + glo[gi];
-		if ( ha.d_tw_scratch )		// (--auto-carrier: the group's streams' own tables)
-		    au.d_tw_scratch = ha.d_tw_scratch + (size_t)glo[gi] * g.tw_entries * 4u;
-		void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&gio[gi], (void *)&g, (void *)&au };
-		(void)hipLaunchKernel(fn, dim3((unsigned)gio[gi].nstreams), dim3(64), kargs, plan.lds_bytes, gs);
-	    }
-	}
-	const bool launched = hipGetLastError() == hipSuccess;
-	for ( uint32_t gi = 0; gi < chain_g; gi++ ) {
-	    (void)hipEventRecord((hipEvent_t)ch.ev_done[gi], (hipStream_t)ch.streams[gi]);
-	    (void)hipStreamWaitEvent(st, (hipEvent_t)ch.ev_done[gi], 0);
-	}
-	return launched ? 0 : -5;
+	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
+		[&]( const mifsk_demod_io &rows, uint32_t lo, mifsk_stream_state *d_state, bool last, uint32_t limit, hipStream_t gs ) {
+		    au.d_state = d_state;
+		    au.final = last ? 1u : 0u;
+		    au.limit = limit;
+		    if ( ha.d_tw_scratch )		// (--auto-carrier: the group's streams' own tables)
+			au.d_tw_scratch = ha.d_tw_scratch + (size_t)lo * g.tw_entries * 4u;
+		    launch(rows, gs);
+		});
     }
-#define MIFSK_WAVE_LAUNCH_ST(SV_, NQ_)										\
-    do {													\
-	const void *fn = reinterpret_cast<const void *>(&demod_wave_kernel<SV_, NQ_, true>);			\
-	if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes)		\
-		!= hipSuccess )											\
-	    return -5;												\
-	hipLaunchKernelGGL((demod_wave_kernel<SV_, NQ_, true>), dim3((unsigned)io.nstreams), dim3(64),		\
-			   plan.lds_bytes, st, d_cfg, d_tw, io, g, au);						\
-    } while (0)
-    if ( ha.d_state ) {
-	// mifsk_demod_slab: the instantiations with the state code, generic correlators
-	const bool lin = g.lat_mode == LAT_LINEAR;
-	if ( g.tiled )                 MIFSK_WAVE_LAUNCH_ST(10, kTiled);
-	else if ( plan.sv == 10 && lin ) MIFSK_WAVE_LAUNCH_ST(10, 0);
-	else if ( plan.sv == 10 )      MIFSK_WAVE_LAUNCH_ST(10, kDirect);
-	else if ( lin )                MIFSK_WAVE_LAUNCH_ST(4, 0);
-	else                           MIFSK_WAVE_LAUNCH_ST(4, kDirect);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
-    }
-#undef MIFSK_WAVE_LAUNCH_ST
-    // (RING addressing and --auto-carrier have their own instantiations: the plain ones carry
-    // neither that code nor the registers it keeps alive)
-#define MIFSK_WAVE_LAUNCH_RA(SV_, NQ_, RA_)									\
-    do {													\
-	const void *fn = reinterpret_cast<const void *>(&demod_wave_kernel<SV_, NQ_, false, RA_>);		\
-	if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes)		\
-		!= hipSuccess )											\
-	    return -5;												\
-	hipLaunchKernelGGL((demod_wave_kernel<SV_, NQ_, false, RA_>), dim3((unsigned)io.nstreams), dim3(64),	\
-				   plan.lds_bytes, st, d_cfg, d_tw, io, g, au);						\
-    } while (0)
-#define MIFSK_WAVE_LAUNCH(SV_, NQ_)										\
-    do {													\
-	if ( ha.ring_exact || ha.autodetect )									\
-	    MIFSK_WAVE_LAUNCH_RA(SV_, NQ_, true);								\
-	else													\
-	    MIFSK_WAVE_LAUNCH_RA(SV_, NQ_, false);								\
-    } while (0)
-    if ( g.tiled ) {
-	MIFSK_WAVE_LAUNCH(10, kTiled);				// RTTY and slower
-    } else if ( plan.sv == 10 ) {
-	if ( nq == 10u )     MIFSK_WAVE_LAUNCH(10, 10);		// 1200 baud at 48 kHz
-	else if ( nq == 5u ) MIFSK_WAVE_LAUNCH(10, 5);		// 2400 baud; 1200 baud at 24 kHz
-	else if ( g.lat_mode == LAT_LINEAR ) MIFSK_WAVE_LAUNCH(10, 0);
-	else                 MIFSK_WAVE_LAUNCH(10, kDirect);
-    } else {
-	if ( nq == 1u )      MIFSK_WAVE_LAUNCH(4, 1);		// 12000 baud
-	else if ( g.lat_mode == LAT_LINEAR ) MIFSK_WAVE_LAUNCH(4, 0);
-	else                 MIFSK_WAVE_LAUNCH(4, kDirect);	// SAME
-    }
-#undef MIFSK_WAVE_LAUNCH
-#undef MIFSK_WAVE_LAUNCH_RA
+    launch(io, (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
