@@ -48,6 +48,7 @@
 #include "mifsk_device.h"
 #include "mifsk_devmath.h"
 #include "mifsk_devlib.h"
+#include "mifsk_rxloop.h"
 
 // cycle timers for tools/counters.py; off in the production build because
 // each s_memtime read costs the serial wave a round trip
@@ -805,19 +806,6 @@ struct DemodArgs {
     WgResume		rs;
 };
 
-// where stream s writes its results.  Made once: the serial loop is latency-bound,
-// and a scalar kept in (or spilled to a VGPR lane from) a register costs a cycle where a
-// reload from the kernarg segment costs a scalar-cache round trip per block of frames
-// (measured: 0.45 -> 0.52 ms on configs[1] with the pointers re-made at every use)
-struct StreamOut {
-    uint8_t		*bytes;
-    uint64_t		*bits;
-    mifsk_frame		*frames;
-    mifsk_episode	*eps;
-    size_t		fcap, ecap;
-};
-
-
 // The reference's receive loop (minimodem.c:1137-1463); executed by wave 0 only.
 template <bool USE_SLAB, int NQ, bool ST>
 __device__ __forceinline__ void master_loop( const DevCfg &cfg, const double *__restrict__ tw,
@@ -826,25 +814,10 @@ __device__ __forceinline__ void master_loop( const DevCfg &cfg, const double *__
 {
     const uint32_t s = blockIdx.x;
     const float *x = io.d_samples + (size_t)s * io.stream_stride;
-    uint32_t N = io.d_nsamples ? io.d_nsamples[s] : io.nsamples;
-    if ( io.nstreams > 1 && (size_t)N > io.stream_stride )
-	N = (uint32_t)io.stream_stride;		// never trust a length beyond the row
     // chained launches: this call takes the stream up to rs.limit only
-    bool cut = false;
-    if constexpr ( ST ) {
-	if ( rs.d_state && rs.limit != 0u && rs.limit < N ) {
-	    N = rs.limit;
-	    cut = true;
-	}
-    }
-
-    StreamOut o;
-    o.fcap = io.frames_cap;
-    o.ecap = io.episodes_cap;
-    o.bytes = io.d_bytes ? io.d_bytes + (size_t)s * o.fcap : nullptr;
-    o.bits = io.d_bits ? io.d_bits + (size_t)s * o.fcap : nullptr;
-    o.frames = io.d_frames ? io.d_frames + (size_t)s * o.fcap : nullptr;
-    o.eps = io.d_episodes ? io.d_episodes + (size_t)s * o.ecap : nullptr;
+    uint32_t N = row_nsamples(io, s);
+    const bool cut = chain_cut<ST>(rs.d_state, rs.limit, N);
+    const StreamOut o = StreamOut::make(io, s);
     const uint32_t lane = threadIdx.x;
     const bool t0 = lane == 0;
 
@@ -1774,15 +1747,10 @@ void demod_kernel( const DevCfg *__restrict__ cfgp, const double *__restrict__ t
     // without leaving the batch: the rows after it, or for the last row its own
     // length.  The linear LATTICE fetches whole rounds of 64 * STAGE_VEC float4
     // with no per-lane bounds logic and needs at least one round of room.
-    uint32_t n_own = io.d_nsamples ? io.d_nsamples[blockIdx.x] : io.nsamples;
-    if ( io.nstreams > 1 && (size_t)n_own > io.stream_stride )
-	n_own = (uint32_t)io.stream_stride;
-    const uint32_t n_row = n_own;
-    if constexpr ( ST ) {
-	// a chained launch sees the first rs.limit samples of a row, master and workers alike
-	if ( rs.d_state && rs.limit != 0u && rs.limit < n_own )
-	    n_own = rs.limit;
-    }
+    const uint32_t n_row = row_nsamples(io, blockIdx.x);
+    // a chained launch sees the first rs.limit samples of a row, master and workers alike
+    uint32_t n_own = n_row;
+    chain_cut<ST>(rs.d_state, rs.limit, n_own);
     const uint64_t rows_after = (uint64_t)( io.nstreams - 1 - (int)blockIdx.x ) * io.stream_stride;
     const uint32_t safe_limit = rows_after == 0 ? n_row
 			      : rows_after > 0xFFFF0000ull ? 0xFFFF0000u : (uint32_t)rows_after;

@@ -53,6 +53,7 @@
 #include "mifsk_device.h"
 #include "mifsk_devmath.h"
 #include "mifsk_devlib.h"
+#include "mifsk_rxloop.h"
 
 #ifdef MIFSK_PROFILE
 #define MIFSK_WCLOCK() ((uint32_t)clock64())
@@ -77,17 +78,6 @@ struct WaveArgs {
     mifsk_demod_io	io;
     WaveGeom		g;
     WaveAuto		au;
-};
-
-// where stream s writes its results.  Made once (see StreamOut in mifsk_kernels.hip: the
-// serial loop is latency-bound; re-making these from the kernarg segment at every use cost
-// 12000 baud 1.29 -> 1.79 ms)
-struct WaveOut {
-    uint8_t		*bytes;
-    uint64_t		*bits;
-    mifsk_frame		*frames;
-    mifsk_episode	*eps;
-    uint32_t		fcap, ecap;
 };
 
 // ---------------------------------------------------------------------------
@@ -1201,9 +1191,7 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 	cnt[lane] = 0;
 
     const float *x = io.d_samples + (size_t)s * io.stream_stride;
-    uint32_t N = io.d_nsamples ? io.d_nsamples[s] : io.nsamples;
-    if ( io.nstreams > 1 && (size_t)N > io.stream_stride )
-	N = (uint32_t)io.stream_stride;		// never trust a length beyond the row
+    uint32_t N = row_nsamples(io, s);
     // How far this stream's row may be over-read (in samples from its start)
     // without leaving the batch: the rows after it, or for the last row its own
     // length.  The linear LATTICE fetches whole rounds with no per-lane bounds
@@ -1221,13 +1209,7 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
     if ( ring )
 	lattice_ok = false;			// RING addressing: every frame through the general path
     // chained launches (launch_demod_wave): this call takes the stream up to au.limit only
-    bool cut = false;
-    if constexpr ( ST ) {
-	if ( au.d_state && au.limit != 0u && au.limit < N ) {
-	    N = au.limit;
-	    cut = true;
-	}
-    }
+    const bool cut = chain_cut<ST>(au.d_state, au.limit, N);
     const double *tw = tw_default;
     double *tw_own = nullptr;
     if ( autodetect ) {
@@ -1235,16 +1217,7 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 	tw = tw_own;
     }
 
-
-
-    WaveOut o;
-    o.fcap = (uint32_t)( io.frames_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : io.frames_cap );
-    o.ecap = (uint32_t)( io.episodes_cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : io.episodes_cap );
-    o.bytes = io.d_bytes ? io.d_bytes + (size_t)s * io.frames_cap : nullptr;
-    o.bits = io.d_bits ? io.d_bits + (size_t)s * io.frames_cap : nullptr;
-    o.frames = io.d_frames ? io.d_frames + (size_t)s * io.frames_cap : nullptr;
-    o.eps = io.d_episodes ? io.d_episodes + (size_t)s * io.episodes_cap : nullptr;
-
+    const StreamOut o = StreamOut::make(io, s);
     Wave<SV, NQ> ctx(cfg, g, tw, x, N, mags, slab, ring, safe_limit, cnt, io.d_counters != nullptr);
 
     if constexpr ( NQ == kTiled ) {
