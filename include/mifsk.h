@@ -25,6 +25,7 @@
  *   mifsk_gather_*                (none: one process per GPU) decoded bytes to rank 0, RCCL
  *   mifsk_demod_slab[_ring]       the loop over a stream that arrives in pieces  minimodem.c:1144-1174
  *   mifsk_session_*               ... fed from host memory, bookkeeping included
+ *   mifsk_demod_long[_batch]      the loop over one long stream, or a few, cut in time across the chip
  *   mifsk_demod_batch_host[_ex]   same, host buffers     (chunked H2D | demod | D2H, overlapped)
  *   mifsk_demod_files             --rx --file, N files   simpleaudio-sndfile.c:42-74,
  *                                                        minimodem.c:1014-1032
@@ -662,6 +663,39 @@ int mifsk_time_split_plan_get( const mifsk_rx_config *cfg, uint64_t nsamples,
 int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
 	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,
 	mifsk_time_split_stats *stats, void *stream );
+
+/* Several long recordings at once: eight receivers' one-hour recordings, 32 ten-minute files --
+ * too few streams to fill the chip with one wavefront each.  One `warmup` W and one `chunk` L cut
+ * the whole batch, so that every chunk of every stream is a row of one flat batch and a pass is one
+ * launch.  W is chosen as for one recording; with chunk == 0, L = ceil(sum_m max(0, n_m - W) /
+ * target) rounded up to the lattice, target being params->chunks or the chip's worth (1024 in the
+ * host-only planner), capped so that the rows' warm-up overlap stays within 4 GiB; stream m gets
+ * K_m = (n_m - W) / L + 1 chunks (1 where n_m <= W).  With the library's choices the batch is one
+ * mifsk_demod_batch call (nchunks 1 everywhere, chunk = the stream's length) when no stream is as
+ * long as 4 * W; so it is whenever the plan leaves every stream in one chunk.  Limits and error
+ * codes are mifsk_time_split_plan_get's, the row count (sum of K_m) standing in for K; nstreams
+ * <= 0 or a NULL array is -EINVAL.  For nstreams == 1 the plan is mifsk_time_split_plan_get's.
+ * out[m]: nsamples, chunk, warmup, lattice, nchunks = K_m and samples_speculative of stream m. */
+int mifsk_time_split_plan_batch_get( const mifsk_rx_config *cfg, const uint64_t *nsamples,
+	int nstreams, const mifsk_time_split *params, mifsk_time_split_stats *out /* [nstreams] */ );
+
+/* mifsk_demod_long over `nstreams` recordings: row m of d_samples (16-byte aligned, rows
+ * stream_stride floats apart, stream_stride % 4 == 0) holds nsamples[m] <= stream_stride samples;
+ * nsamples is a HOST array.  Nothing beyond nstreams * stream_stride floats is read.  io_out's
+ * output fields are those of a mifsk_demod_batch over nstreams streams ([nstreams][frames_cap] and
+ * so on), bit for bit; its input fields, d_counters and flags are ignored.  A chunk is verified
+ * against its predecessor only inside its own stream, every pass and every round of re-runs is one
+ * launch over the rows of all streams, and the streams' tails run as one batch: the call's rounds
+ * are the longest chain of rejections in any one stream, not the sum over the streams.  A stream
+ * that finishes early (--rx-one) drops only its own later chunks.  stats (NULL or [nstreams]): the
+ * plan of stream m plus its accepted, rerun, samples_rerun and the rounds in which one of its
+ * chunks was run again (the call's rounds are the largest of them).  Device memory: sum of K_m *
+ * (chunk + warmup) floats plus the rows' output arrays.  Synchronous, as mifsk_demod_long is --
+ * which is this call with nstreams == 1. */
+int mifsk_demod_long_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
+	size_t stream_stride, const uint64_t *nsamples /* host, [nstreams] */, int nstreams,
+	const mifsk_time_split *params, const mifsk_demod_io *io_out,
+	mifsk_time_split_stats *stats /* [nstreams] or NULL */, void *stream );
 
 /* ---- streams fed in pieces from host memory ---------------------------------- */
 

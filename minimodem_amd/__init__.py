@@ -294,29 +294,96 @@ def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("b
         frames_cap = max_frames(cfg, n)
     if episodes_cap is None:
         episodes_cap = max_episodes(cfg, n)
-    dev = samples.device
-    with _on(torch, stream):
-        out = {"nframes": torch.zeros(1, dtype=torch.int32, device=dev),
-               "status": torch.zeros(1, dtype=torch.int32, device=dev)}
-        if "bytes" in want:
-            out["bytes"] = torch.zeros((1, frames_cap), dtype=torch.uint8, device=dev)
-            out["nbytes"] = torch.zeros(1, dtype=torch.int32, device=dev)
-        if "bits" in want:
-            out["bits"] = torch.zeros((1, frames_cap), dtype=torch.int64, device=dev)
-        if "frames" in want:
-            out["frames"] = torch.zeros((1, frames_cap, FRAME_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
-            out["carrier_band"] = torch.full((1,), -1, dtype=torch.int32, device=dev)
-        if "episodes" in want:
-            out["episodes"] = torch.zeros((1, episodes_cap, EPISODE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-            out["nepisodes"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = _long_outputs(torch, cfg, samples.device, 1, want, frames_cap, episodes_cap, stream)
+    io = _long_io(out, 1, frames_cap, episodes_cap)
+    st = _lib.TimeSplitStats()
+    rc = lib.mifsk_demod_long(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), n,
+                              C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
+                              C.byref(io), C.byref(st), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_demod_long failed: %d" % rc)
+    out["stats"] = {k: int(getattr(st, k)) for k, _ in st._fields_}
+    return out
 
+
+def time_split_plan_batch(cfg, nsamples_list, chunk=None, warmup=None, chunks=None, engine=None):
+    """mifsk_time_split_plan_batch_get: how demod_long_batch would cut streams of these lengths with
+    one chunk and one warmup (host only).  A list of dicts, one per stream."""
+    lens = [int(n) for n in nsamples_list]
+    arr = (C.c_uint64 * max(1, len(lens)))(*lens)
+    st = (_lib.TimeSplitStats * max(1, len(lens)))()
+    rc = _lib.load().mifsk_time_split_plan_batch_get(
+        C.byref(cfg), arr, len(lens), C.byref(_time_split_params(chunk, warmup, chunks, engine, False)), st)
+    if rc != 0:
+        raise ValueError("mifsk_time_split_plan_batch_get failed: %d" % rc)
+    return [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(len(lens))]
+
+
+def demod_long_batch(ctx, cfg, samples, nsamples=None, chunk=None, warmup=None, chunks=None,
+                     want=("bytes", "episodes"), frames_cap=None, episodes_cap=None, engine=None,
+                     reject_all=False, stream=None):
+    """mifsk_demod_long_batch: a small batch of long recordings decoded across the whole chip by
+    cutting all of them in time with one plan, bit for bit what demod_batch gives for the batch.
+
+    samples: a 2-D contiguous torch.float32 CUDA tensor [nstreams, stride], stride % 4 == 0 (16-byte
+    aligned).  nsamples: a HOST sequence of ints, the streams' lengths (None: every row is full).
+    chunk / warmup / chunks / reject_all: as for demod_long.  Returns demod_batch's dict for nstreams
+    streams plus "stats", a list of dicts (per stream: the plan and what verification accepted);
+    the default caps come from the longest stream.  Synchronous."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2
+    assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
+    nstreams, width = (int(v) for v in samples.shape)
+    assert nstreams >= 1 and width % 4 == 0, "rows must be whole float4s"
+    lens = [width] * nstreams if nsamples is None else [int(n) for n in nsamples]
+    assert len(lens) == nstreams and all(0 <= n <= width for n in lens)
+    longest = max(lens)
+    if frames_cap is None:
+        frames_cap = max_frames(cfg, longest)
+    if episodes_cap is None:
+        episodes_cap = max_episodes(cfg, longest)
+    out = _long_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream)
+    io = _long_io(out, nstreams, frames_cap, episodes_cap)
+    arr = (C.c_uint64 * nstreams)(*lens)
+    st = (_lib.TimeSplitStats * nstreams)()
+    rc = lib.mifsk_demod_long_batch(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), width, arr,
+                                    nstreams, C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
+                                    C.byref(io), st, _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_demod_long_batch failed: %d" % rc)
+    out["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
+    return out
+
+
+def _long_outputs(torch, cfg, dev, nstreams, want, frames_cap, episodes_cap, stream):
+    """demod_batch's output tensors for demod_long / demod_long_batch, made on the launch stream."""
+    with _on(torch, stream):
+        out = {"nframes": torch.zeros(nstreams, dtype=torch.int32, device=dev),
+               "status": torch.zeros(nstreams, dtype=torch.int32, device=dev)}
+        if "bytes" in want:
+            out["bytes"] = torch.zeros((nstreams, frames_cap), dtype=torch.uint8, device=dev)
+            out["nbytes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+        if "bits" in want:
+            out["bits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=dev)
+        if "frames" in want:
+            out["frames"] = torch.zeros((nstreams, frames_cap, FRAME_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
+            out["carrier_band"] = torch.full((nstreams,), -1, dtype=torch.int32, device=dev)
+        if "episodes" in want:
+            out["episodes"] = torch.zeros((nstreams, episodes_cap, EPISODE_DTYPE.itemsize), dtype=torch.uint8,
+                                          device=dev)
+            out["nepisodes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+    return out
+
+
+def _long_io(out, nstreams, frames_cap, episodes_cap):
     def ptr(name):
         t = out.get(name)
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
     io = _lib.DemodIO()
-    io.nstreams = 1
+    io.nstreams = nstreams
     io.d_bytes = ptr("bytes")
     io.d_nbytes = ptr("nbytes")
     io.d_bits = ptr("bits")
@@ -328,14 +395,7 @@ def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("b
     io.episodes_cap = episodes_cap
     io.d_status = ptr("status")
     io.d_carrier_band = ptr("carrier_band")
-    st = _lib.TimeSplitStats()
-    rc = lib.mifsk_demod_long(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), n,
-                              C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
-                              C.byref(io), C.byref(st), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_demod_long failed: %d" % rc)
-    out["stats"] = {k: int(getattr(st, k)) for k, _ in st._fields_}
-    return out
+    return io
 
 
 def results_to_host(out):

@@ -258,6 +258,7 @@ EXPORTS = [
     "mifsk_gather_start", "mifsk_gather_received",
     "mifsk_session_create", "mifsk_session_destroy", "mifsk_session_feed", "mifsk_session_get",
     "mifsk_session_pending", "mifsk_time_split_plan_get", "mifsk_demod_long",
+    "mifsk_time_split_plan_batch_get", "mifsk_demod_long_batch",
 ]
 
 _lib = None
@@ -435,5 +436,12 @@ def load():
     lib.mifsk_demod_long.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_uint64,
                                      C.POINTER(TimeSplit), C.POINTER(DemodIO), C.POINTER(TimeSplitStats),
                                      C.c_void_p]
+    lib.mifsk_time_split_plan_batch_get.restype = C.c_int
+    lib.mifsk_time_split_plan_batch_get.argtypes = [C.POINTER(RxConfig), C.POINTER(C.c_uint64), C.c_int,
+                                                    C.POINTER(TimeSplit), C.POINTER(TimeSplitStats)]
+    lib.mifsk_demod_long_batch.restype = C.c_int
+    lib.mifsk_demod_long_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_uint64), C.c_int, C.POINTER(TimeSplit),
+                                           C.POINTER(DemodIO), C.POINTER(TimeSplitStats), C.c_void_p]
     _lib = lib
     return lib

@@ -1,4 +1,5 @@
-// mifsk_timesplit.hip -- one long recording across the whole chip (mifsk_demod_long).
+// mifsk_timesplit.hip -- long recordings across the whole chip: one (mifsk_demod_long) or a small
+// batch of them (mifsk_demod_long_batch), the same code.
 //
 // The receive loop is serial in its state (minimodem.c:1137-1463), so one stream runs on one
 // wavefront.  A long recording is cut in time instead: chunk k starts at s_k = k * L, and
@@ -71,17 +72,24 @@ __device__ inline bool same_control( const mifsk_stream_state &p, const mifsk_st
 	&& p.carrier_band == x.carrier_band && p.b_mark == x.b_mark;
 }
 
-// rows[k][i] = x[k * L + i] for i < row_len, 0.0 behind the recording's end (the loop kernels
-// take no row longer than the batch stride, so the overlapping chunks are laid out apart)
-__global__ void ts_gather_rows( const float *__restrict__ x, uint64_t n, float *__restrict__ rows,
-	uint64_t stride, uint64_t L, int nrows )
+// Several recordings are cut by one plan (mifsk_demod_long_batch): all streams' chunks are rows of
+// one flat batch, row rowbase[m] + k being chunk k of stream m, and stream m's tail is row R + m
+// behind the R chunk rows.  A row is verified against its predecessor only inside its own stream.
+struct RowRef {
+    uint32_t	m, k;		// chunk k of stream m (k == K of the stream: its tail)
+};
+
+struct StreamRef {
+    uint64_t	n;		// the stream's length
+    uint64_t	tail_off;	// where its tail starts
+    uint32_t	rowbase, K;	// its chunks are rows rowbase .. rowbase + K - 1
+};
+
+// dst[i] = x[s0 + i] for i < 4 * nvec, 0.0 behind the stream's end n (x + s0 is 16-byte aligned)
+__device__ inline void copy_row( const float *__restrict__ x, uint64_t n, uint64_t s0,
+	float *__restrict__ dst, uint64_t nvec )
 {
-    const int k = blockIdx.y;
-    if ( k >= nrows )
-	return;
-    const uint64_t s0 = (uint64_t)k * L;
-    float4 *dst = reinterpret_cast<float4 *>(rows + (uint64_t)k * stride);
-    const uint64_t nvec = stride / 4u;
+    float4 *d4 = reinterpret_cast<float4 *>(dst);
     for ( uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
 	  v += (uint64_t)gridDim.x * blockDim.x ) {
 	const uint64_t i = s0 + v * 4u;
@@ -94,58 +102,97 @@ __global__ void ts_gather_rows( const float *__restrict__ x, uint64_t n, float *
 	    f.z = i + 2u < n ? x[i + 2u] : 0.0f;
 	    f.w = i + 3u < n ? x[i + 3u] : 0.0f;
 	}
-	dst[v] = f;
+	d4[v] = f;
     }
 }
 
-// pass B's starting states: I_0 = 0, I_k = X_k with the bookkeeping zeroed
-__global__ void ts_prepare( const mifsk_stream_state *__restrict__ X, mifsk_stream_state *I,
-	mifsk_stream_state *S, int K )
+// rows[r][i] = x_m[k * L + i] for row r = (m, k) of the row table (the loop kernels take no row
+// longer than the batch stride, so the overlapping chunks are laid out apart)
+__global__ void ts_gather_rows( const float *__restrict__ x, uint64_t xstride,
+	const StreamRef *__restrict__ streams, const RowRef *__restrict__ rowref,
+	float *__restrict__ rows, uint64_t stride, uint64_t L, int nrows )
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if ( k >= K )
-	return;
-    mifsk_stream_state r = {};
-    if ( k > 0 )
-	r = reset_book(X[k], 0);
-    I[k] = r;
-    S[k] = r;
+    for ( int r = blockIdx.y; r < nrows; r += gridDim.y ) {
+	const RowRef ref = rowref[r];
+	copy_row(x + (uint64_t)ref.m * xstride, streams[ref.m].n, (uint64_t)ref.k * L,
+		 rows + (uint64_t)r * stride, stride / 4u);
+    }
 }
 
-// code[k] (k >= 1): 1 = the state row k started from (X_k, or S_{k-1} of a re-run) agrees with
-// S_{k-1} in every control field, 2 = S_{k-1} finished the stream (--rx-one, an aborted loop):
-// the rows behind it decode nothing
-__global__ void ts_verify( const mifsk_stream_state *__restrict__ X,
-	const mifsk_stream_state *__restrict__ S, uint32_t *code, int K, uint64_t L, int reject_all )
+// the streams' tails do not sit at one stride in the rows: tails[m][i] = x_m[tail_off_m + i]
+__global__ void ts_gather_tails( const float *__restrict__ x, uint64_t xstride,
+	const StreamRef *__restrict__ streams, float *__restrict__ tails, uint64_t stride, int nstreams )
 {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if ( k < 1 || k >= K )
+    for ( int m = blockIdx.y; m < nstreams; m += gridDim.y )
+	copy_row(x + (uint64_t)m * xstride, streams[m].n, streams[m].tail_off,
+		 tails + (uint64_t)m * stride, stride / 4u);
+}
+
+// pass A's starting states: zero, but a stream's row 0 needs no guess (a finished state: the
+// loop skips the row)
+__global__ void ts_guess_init( mifsk_stream_state *X, const RowRef *__restrict__ rowref, int R )
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( r >= R )
 	return;
-    const mifsk_stream_state p = S[k - 1];
+    mifsk_stream_state s = {};
+    if ( rowref[r].k == 0u )
+	s.flags = MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
+    X[r] = s;
+}
+
+// pass B's starting states: a stream's row 0 starts from zero, row k from X_k with the
+// bookkeeping zeroed
+__global__ void ts_prepare( const mifsk_stream_state *__restrict__ X, mifsk_stream_state *I,
+	mifsk_stream_state *S, const RowRef *__restrict__ rowref, int R )
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( r >= R )
+	return;
+    mifsk_stream_state s = {};
+    if ( rowref[r].k > 0u )
+	s = reset_book(X[r], 0);
+    I[r] = s;
+    S[r] = s;
+}
+
+// code[r] of row r = (m, k >= 1): 1 = the state the row started from (X_k, or S_{k-1} of a
+// re-run) agrees with S_{k-1} of its own stream in every control field, 2 = S_{k-1} finished the
+// stream (--rx-one, an aborted loop): the stream's rows behind it decode nothing
+__global__ void ts_verify( const mifsk_stream_state *__restrict__ X,
+	const mifsk_stream_state *__restrict__ S, const RowRef *__restrict__ rowref, uint32_t *code,
+	int R, uint64_t L, int reject_all )
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( r >= R || rowref[r].k == 0u )
+	return;
+    const mifsk_stream_state p = S[r - 1];
     uint32_t c = 0;
     if ( p.flags & MIFSK_STATE_FINISHED )
 	c = 2u;
-    else if ( !reject_all && same_control(p, X[k], L) )
+    else if ( !reject_all && same_control(p, X[r], L) )
 	c = 1u;
-    code[k] = c;
+    code[r] = c;
 }
 
-// one round of re-runs over rows lo..hi: the marked rows start from S_{k-1}, moved into their
-// own coordinates; the others are skipped by the loop (a finished state)
+// one round of re-runs over rows lo..hi (of any streams): the marked rows start from S_{k-1} of
+// their stream, moved into their own coordinates; the others are skipped by the loop (a finished
+// state)
 __global__ void ts_seed( const mifsk_stream_state *__restrict__ S, const uint8_t *__restrict__ mark,
-	mifsk_stream_state *R, mifsk_stream_state *I, int lo, int hi, uint64_t L )
+	const RowRef *__restrict__ rowref, mifsk_stream_state *R, mifsk_stream_state *I, int lo, int hi,
+	uint64_t L )
 {
-    const int k = lo + (int)( blockIdx.x * blockDim.x + threadIdx.x );
-    if ( k > hi )
+    const int r = lo + (int)( blockIdx.x * blockDim.x + threadIdx.x );
+    if ( r > hi )
 	return;
-    mifsk_stream_state r = {};
-    if ( mark[k] ) {
-	r = reset_book(S[k - 1], L);
-	I[k] = r;
+    mifsk_stream_state s = {};
+    if ( mark[r] && rowref[r].k > 0u ) {
+	s = reset_book(S[r - 1], L);
+	I[r] = s;
     } else {
-	r.flags = MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
+	s.flags = MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
     }
-    R[k] = r;
+    R[r] = s;
 }
 
 // ... and what they made replaces pass B's (counts: nframes, nbytes, nepisodes, status)
@@ -161,11 +208,20 @@ __global__ void ts_merge( const mifsk_stream_state *__restrict__ R, const uint8_
 	cnt[j * nrows + k] = rcnt[j * nrows + k];
 }
 
+// last[m] = the paused state of stream m's last chunk, which its tail starts from
+__global__ void ts_last_states( const mifsk_stream_state *__restrict__ S,
+	const StreamRef *__restrict__ streams, mifsk_stream_state *last, int nstreams )
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if ( m < nstreams )
+	last[m] = S[streams[m].rowbase + streams[m].K - 1u];
+}
+
 // ---- stitch ---------------------------------------------------------------------------------
 
-// The prefix of rows 0..k-1: output counts, and the episode that is open behind them (its true
-// carrier_nsamples, nframes_decoded and first frame).  A row either carries the open episode
-// through (a = 1: its running values are deltas) or sets it anew (a = 0).
+// The prefix of a stream's rows 0..k-1: output counts, and the episode that is open behind them
+// (its true carrier_nsamples, nframes_decoded and first frame).  A row either carries the open
+// episode through (a = 1: its running values are deltas) or sets it anew (a = 0).
 struct Agg {
     uint64_t	nf, nb, ne, cn, ep;
     uint32_t	nd, a, status;
@@ -203,16 +259,30 @@ struct StitchArgs {
     const mifsk_stream_state	*I, *S;
     const uint32_t		*cnt;		// [4][nrows]: nframes, nbytes, nepisodes, status
     const uint8_t		*drop;		// [nrows]
-    int				nrows;
+    const StreamRef		*streams;	// [nstreams]
+    const RowRef		*rowref;	// [nrows]
+    int				nrows, R;	// R chunk rows, then the nstreams tails
     const mifsk_frame		*rframes;	// [nrows][fcap]
     const uint8_t		*rbytes;	// [nrows][fcap] or NULL
     const mifsk_episode		*reps;		// [nrows][ecap]
     size_t			fcap, ecap;
-    uint64_t			L, tail_off;	// row k < nrows - 1 starts at k * L, the last at tail_off
-    Agg				*pref;		// [nrows + 1] exclusive prefixes, [nrows] = total
+    uint64_t			L;		// chunk k of a stream starts at k * L, its tail at tail_off
+    Agg				*pref;		// per stream K + 2: exclusive prefixes of its K + 1 rows, the total
     mifsk_demod_io		out;
     int				autodetect;
 };
+
+// the row of stream m's j-th piece (its K chunks, then its tail) ...
+__device__ inline int piece_row( const StitchArgs &a, const StreamRef &sr, int m, int j )
+{
+    return j < (int)sr.K ? (int)sr.rowbase + j : a.R + m;
+}
+
+// ... and the stream's prefixes: pref[j] is what lies before piece j
+__device__ inline Agg *stream_pref( const StitchArgs &a, const StreamRef &sr, int m )
+{
+    return a.pref + sr.rowbase + 2 * (size_t)m;
+}
 
 __device__ inline Agg row_agg( const StitchArgs &a, int k )
 {
@@ -235,16 +305,20 @@ __device__ inline Agg row_agg( const StitchArgs &a, int k )
 
 constexpr int kScanThreads = 1024;
 
-// one workgroup: K is in the thousands
+// one workgroup per stream (K is in the thousands): the stream's counts, status and band go to
+// index blockIdx.x of the caller's arrays
 __global__ __launch_bounds__(kScanThreads) void ts_scan( StitchArgs a )
 {
     __shared__ Agg lds[kScanThreads];
-    const int t = threadIdx.x;
-    const int per = ( a.nrows + kScanThreads - 1 ) / kScanThreads;
-    const int lo = min(a.nrows, t * per), hi = min(a.nrows, lo + per);
+    const int t = threadIdx.x, m = blockIdx.x;
+    const StreamRef sr = a.streams[m];
+    Agg *pref = stream_pref(a, sr, m);
+    const int np = (int)sr.K + 1;
+    const int per = ( np + kScanThreads - 1 ) / kScanThreads;
+    const int lo = min(np, t * per), hi = min(np, lo + per);
     Agg mine = agg_identity();
-    for ( int k = lo; k < hi; k++ )
-	mine = agg_combine(mine, row_agg(a, k));
+    for ( int j = lo; j < hi; j++ )
+	mine = agg_combine(mine, row_agg(a, piece_row(a, sr, m, j)));
     lds[t] = mine;
     __syncthreads();
     for ( int d = 1; d < kScanThreads; d <<= 1 ) {		// inclusive scan of the threads' parts
@@ -256,81 +330,90 @@ __global__ __launch_bounds__(kScanThreads) void ts_scan( StitchArgs a )
 	__syncthreads();
     }
     Agg run = t ? lds[t - 1] : agg_identity();
-    for ( int k = lo; k < hi; k++ ) {
-	a.pref[k] = run;
-	run = agg_combine(run, row_agg(a, k));
+    for ( int j = lo; j < hi; j++ ) {
+	pref[j] = run;
+	run = agg_combine(run, row_agg(a, piece_row(a, sr, m, j)));
     }
     if ( t == kScanThreads - 1 ) {
 	const Agg tot = lds[t];
-	a.pref[a.nrows] = tot;
+	pref[np] = tot;
 	uint32_t status = tot.status & ~( MIFSK_STREAM_FRAMES_TRUNCATED | MIFSK_STREAM_EPISODES_TRUNCATED );
 	if ( tot.nf > a.out.frames_cap && ( a.out.d_frames || a.out.d_bits || a.out.d_bytes ) )
 	    status |= MIFSK_STREAM_FRAMES_TRUNCATED;
 	if ( tot.ne > a.out.episodes_cap && a.out.d_episodes )
 	    status |= MIFSK_STREAM_EPISODES_TRUNCATED;
-	if ( a.out.d_nframes ) a.out.d_nframes[0] = (uint32_t)tot.nf;
-	if ( a.out.d_nbytes ) a.out.d_nbytes[0] = (uint32_t)tot.nb;
-	if ( a.out.d_nepisodes ) a.out.d_nepisodes[0] = (uint32_t)tot.ne;
-	if ( a.out.d_status ) a.out.d_status[0] = status;
-	if ( a.out.d_carrier_band && a.autodetect ) a.out.d_carrier_band[0] = tot.band;
+	if ( a.out.d_nframes ) a.out.d_nframes[m] = (uint32_t)tot.nf;
+	if ( a.out.d_nbytes ) a.out.d_nbytes[m] = (uint32_t)tot.nb;
+	if ( a.out.d_nepisodes ) a.out.d_nepisodes[m] = (uint32_t)tot.ne;
+	if ( a.out.d_status ) a.out.d_status[m] = status;
+	if ( a.out.d_carrier_band && a.autodetect ) a.out.d_carrier_band[m] = tot.band;
     }
 }
 
-// frames, bits and bytes of row blockIdx.x to their places in the stream's arrays
+// frames, bits and bytes of row blockIdx.x to their places in its stream's arrays
 __global__ void ts_scatter( StitchArgs a )
 {
-    const int k = blockIdx.x;
+    const int r = blockIdx.x;
+    const RowRef ref = a.rowref[r];
+    const StreamRef sr = a.streams[ref.m];
+    const Agg *pref = stream_pref(a, sr, ref.m) + ref.k;
     // (a row holds at most fcap frames: mifsk_max_frames of the longest row)
-    const uint64_t f0 = a.pref[k].nf, nf = min(a.pref[k + 1].nf - f0, (uint64_t)a.fcap);
-    const uint64_t b0 = a.pref[k].nb, nb = min(a.pref[k + 1].nb - b0, (uint64_t)a.fcap);
-    const uint64_t off = k == a.nrows - 1 ? a.tail_off : (uint64_t)k * a.L;
-    const mifsk_frame *src = a.rframes + (size_t)k * a.fcap;
+    const uint64_t f0 = pref[0].nf, nf = min(pref[1].nf - f0, (uint64_t)a.fcap);
+    const uint64_t b0 = pref[0].nb, nb = min(pref[1].nb - b0, (uint64_t)a.fcap);
+    const uint64_t off = ref.k == sr.K ? sr.tail_off : (uint64_t)ref.k * a.L;
+    const size_t o0 = (size_t)ref.m * a.out.frames_cap;
+    const mifsk_frame *src = a.rframes + (size_t)r * a.fcap;
     for ( uint64_t i = threadIdx.x; i < nf && f0 + i < a.out.frames_cap; i += blockDim.x ) {
 	mifsk_frame f = src[i];
 	f.start += off;
 	if ( a.out.d_frames )
-	    a.out.d_frames[f0 + i] = f;
+	    a.out.d_frames[o0 + f0 + i] = f;
 	if ( a.out.d_bits )
-	    a.out.d_bits[f0 + i] = f.bits;
+	    a.out.d_bits[o0 + f0 + i] = f.bits;
     }
     if ( a.out.d_bytes && a.rbytes ) {
-	const uint8_t *bs = a.rbytes + (size_t)k * a.fcap;
+	const uint8_t *bs = a.rbytes + (size_t)r * a.fcap;
 	for ( uint64_t i = threadIdx.x; i < nb && b0 + i < a.out.frames_cap; i += blockDim.x )
-	    a.out.d_bytes[b0 + i] = bs[i];
+	    a.out.d_bytes[o0 + b0 + i] = bs[i];
     }
 }
 
 // episodes of row blockIdx.x; the one that began before the row gets its true count, length,
 // first frame and totals -- the float totals summed again over its frames in loop order, as
-// the loop sums them (minimodem.c:1397-1398)
+// the loop sums them (minimodem.c:1397-1398).  Only the row's own stream is searched.
 __global__ void ts_episodes( StitchArgs a )
 {
-    const int k = blockIdx.x;
-    const uint64_t e0 = a.pref[k].ne, ne = min(a.pref[k + 1].ne - e0, (uint64_t)a.ecap);
-    const uint64_t f0 = a.pref[k].nf;
+    const int r = blockIdx.x;
+    const RowRef ref = a.rowref[r];
+    const int m = (int)ref.m, k = (int)ref.k;
+    const StreamRef sr = a.streams[m];
+    const Agg *pref = stream_pref(a, sr, m);
+    const uint64_t e0 = pref[k].ne, ne = min(pref[k + 1].ne - e0, (uint64_t)a.ecap);
+    const uint64_t f0 = pref[k].nf;
+    mifsk_episode *dst = a.out.d_episodes + (size_t)m * a.out.episodes_cap;
     for ( uint64_t j = threadIdx.x; j < ne && e0 + j < a.out.episodes_cap; j += blockDim.x ) {
-	mifsk_episode e = a.reps[(size_t)k * a.ecap + j];
-	if ( j == 0 && ( a.I[k].flags & MIFSK_STATE_CARRIER ) ) {
-	    const Agg &p = a.pref[k];
+	mifsk_episode e = a.reps[(size_t)r * a.ecap + j];
+	if ( j == 0 && ( a.I[r].flags & MIFSK_STATE_CARRIER ) ) {
+	    const Agg &p = pref[k];
 	    const uint64_t g0 = p.ep;
 	    const uint64_t count = (uint64_t)p.nd + e.nframes;
 	    e.carrier_nsamples += p.cn;
 	    e.nframes = (uint32_t)count;
 	    e.first_frame = (uint32_t)g0;
-	    // the row that holds frame g0: the last one whose prefix does not pass it
+	    // the piece that holds frame g0: the last one whose prefix does not pass it
 	    int lo = 0, hi = k;
 	    while ( lo < hi ) {
 		const int mid = ( lo + hi + 1 ) / 2;
-		if ( a.pref[mid].nf <= g0 )
+		if ( pref[mid].nf <= g0 )
 		    lo = mid;
 		else
 		    hi = mid - 1;
 	    }
 	    float ct = 0.0f, at = 0.0f;
-	    uint64_t left = count, i = g0 - a.pref[lo].nf;
-	    for ( int r = lo; r <= k && left; r++ ) {
-		const uint64_t nr = min(a.pref[r + 1].nf - a.pref[r].nf, (uint64_t)a.fcap);
-		const mifsk_frame *fr = a.rframes + (size_t)r * a.fcap;
+	    uint64_t left = count, i = g0 - pref[lo].nf;
+	    for ( int q = lo; q <= k && left; q++ ) {
+		const uint64_t nr = min(pref[q + 1].nf - pref[q].nf, (uint64_t)a.fcap);
+		const mifsk_frame *fr = a.rframes + (size_t)piece_row(a, sr, m, q) * a.fcap;
 		for ( ; i < nr && left; i++, left-- ) {
 		    ct += fr[i].confidence;
 		    at += fr[i].amplitude;
@@ -342,7 +425,7 @@ __global__ void ts_episodes( StitchArgs a )
 	} else {
 	    e.first_frame = (uint32_t)( f0 + e.first_frame );
 	}
-	a.out.d_episodes[e0 + j] = e;
+	dst[e0 + j] = e;
     }
 }
 
@@ -359,12 +442,13 @@ uint64_t gcd64( uint64_t a, uint64_t b )
 const unsigned kKnownFlags = MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE
 			   | MIFSK_TIME_SPLIT_REJECT_ALL;
 
-// the planner; chunks_hint: the chunk count that fills the chip (0: params->chunks or the
-// default of a host-only call)
-int plan( const mifsk_rx_config *cfg, uint64_t n, const mifsk_time_split *params,
+// the planner, for a batch of recordings cut by one W and one L (every row has the same stride,
+// a pass is one launch); chunks_hint: the chunk count that fills the chip (0: params->chunks or
+// the default of a host-only call)
+int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mifsk_time_split *params,
 	uint32_t chunks_hint, mifsk_time_split_stats *out )
 {
-    if ( !cfg || !out || mifsk_check_cfg(cfg) )
+    if ( !cfg || !out || !n || nstreams <= 0 || mifsk_check_cfg(cfg) )
 	return -EINVAL;
     mifsk_time_split p;
     std::memset(&p, 0, sizeof(p));
@@ -385,42 +469,58 @@ int plan( const mifsk_rx_config *cfg, uint64_t n, const mifsk_time_split *params
 	return -EINVAL;
     if ( p.chunk && ( p.chunk % lattice || p.chunk >= 0x7FFFFFF0ull ) )
 	return -EINVAL;
-    if ( p.warmup >= 0x7FFFFFF0ull || n >= ( 1ull << 62 ) )
+    if ( p.warmup >= 0x7FFFFFF0ull )
 	return -EINVAL;		// (rows are uint32 lengths; keeps the arithmetic below exact)
     uint64_t W = p.warmup;
     if ( !W ) {
 	W = (uint64_t)( kDefaultWarmupSeconds * cfg->sample_rate );
 	W = std::max(W, wmin);
     }
-    std::memset(out, 0, sizeof(*out));
-    out->nsamples = n;
-    out->warmup = W;
-    out->lattice = lattice;
+    // what the chunks have to cover, and the longest stream
+    uint64_t cover = 0, longest = 0;
+    for ( int m = 0; m < nstreams; m++ ) {
+	if ( n[m] >= ( 1ull << 62 ) )
+	    return -EINVAL;
+	longest = std::max(longest, n[m]);
+	if ( n[m] > W )
+	    cover += n[m] - W;
+	if ( cover >= ( 1ull << 62 ) )
+	    return -EINVAL;
+    }
     uint64_t L = p.chunk;
-    uint64_t K = 1;
-    if ( n > W ) {
+    uint64_t rows = (uint64_t)nstreams;
+    bool split = false;
+    if ( cover ) {
 	if ( !L ) {
+	    // (sum of K_m - 1 <= cover / L <= target: the cap bounds the rows' warm-up overlap)
 	    uint64_t target = p.chunks ? p.chunks : ( chunks_hint ? chunks_hint : 1024u );
 	    target = std::min(target, std::max<uint64_t>(2, kOverlapBudget / ( W * sizeof(float) )));
-	    L = ( n - W + target - 1 ) / target;
+	    L = ( cover + target - 1 ) / target;
 	    L = std::max(lattice, ( L + lattice - 1 ) / lattice * lattice);
 	}
-	K = ( n - W ) / L + 1;
+	rows = 0;
+	for ( int m = 0; m < nstreams; m++ )
+	    rows += n[m] > W ? ( n[m] - W ) / L + 1 : 1;
+	split = rows > (uint64_t)nstreams;
 	// the library's choice: a split pays when a row (about L + 2 W) is well short of the whole
-	if ( !p.chunk && !p.warmup && 4 * W > n )
-	    K = 1;
+	if ( !p.chunk && !p.warmup && 4 * W > longest )
+	    split = false;
     }
-    if ( K < 2 ) {
-	K = 1;
-	L = n;
+    if ( split && ( L + W >= 0x7FFFFFF0ull || rows > 0x7FFFFFFull ) )
+	return -EINVAL;
+    if ( !split && longest > 0xFFFFFFF0ull )
+	return -EINVAL;
+    for ( int m = 0; m < nstreams; m++ ) {
+	const uint64_t K = split && n[m] > W ? ( n[m] - W ) / L + 1 : 1;
+	mifsk_time_split_stats &o = out[m];
+	std::memset(&o, 0, sizeof(o));
+	o.nsamples = n[m];
+	o.warmup = W;
+	o.lattice = lattice;
+	o.nchunks = (uint32_t)K;
+	o.chunk = split ? L : n[m];		// (one chunk everywhere: the single call, no cut)
+	o.samples_speculative = 2 * ( K - 1 ) * W;
     }
-    if ( K > 1 && ( L + W >= 0x7FFFFFF0ull || K > 0x7FFFFFFull ) )
-	return -EINVAL;
-    if ( K == 1 && n > 0xFFFFFFF0ull )
-	return -EINVAL;
-    out->nchunks = (uint32_t)K;
-    out->chunk = L;
-    out->samples_speculative = K > 1 ? ( K - 1 ) * W + ( K - 1 ) * W : 0;
     return 0;
 }
 
@@ -436,21 +536,24 @@ int alloc( DevBuf &b, size_t bytes, hipStream_t st )
     return hipMallocAsync(&b.p, bytes ? bytes : 16, st) == hipSuccess ? 0 : -ENOMEM;
 }
 
-} // namespace
-
-extern "C" int mifsk_time_split_plan_get( const mifsk_rx_config *cfg, uint64_t nsamples,
-	const mifsk_time_split *params, mifsk_time_split_stats *out )
+unsigned blocks_for( uint64_t stride )
 {
-    return plan(cfg, nsamples, params, 0, out);
+    return (unsigned)std::min<uint64_t>(64, std::max<uint64_t>(1, ( stride / 4 + 255 ) / 256));
 }
 
-extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
-	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,
-	mifsk_time_split_stats *stats, void *stream )
+// mifsk_demod_long_batch (which has checked the rows against xstride); mifsk_demod_long is its
+// nstreams == 1 case, whose one row holds just nsamples[0] floats (xstride is not used then)
+int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, size_t xstride,
+	const uint64_t *nsamples, int nstreams, const mifsk_time_split *params,
+	const mifsk_demod_io *io_out, mifsk_time_split_stats *stats, void *stream )
 {
-    if ( !ctx || !io_out || mifsk_check_cfg(cfg) || ( nsamples && !d_samples )
+    if ( !ctx || !io_out || !nsamples || nstreams <= 0 || mifsk_check_cfg(cfg)
 	    || ( (uintptr_t)d_samples & 15u ) )
 	return -EINVAL;
+    const int M = nstreams;
+    for ( int m = 0; m < M; m++ )
+	if ( nsamples[m] && !d_samples )
+	    return -EINVAL;
     if ( ( io_out->d_bytes || io_out->d_bits || io_out->d_frames ) && io_out->frames_cap == 0 )
 	return -EINVAL;
     if ( io_out->d_episodes && io_out->episodes_cap == 0 )
@@ -469,34 +572,57 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
 	if ( mifsk_demod_plan_ex(ctx, cfg, 1, 0xFFFFFFFFu, flags & ~MIFSK_TIME_SPLIT_REJECT_ALL, &li) == 0 )
 	    hint = li.compute_units * kChunksPerCu;
     }
-    mifsk_time_split_stats ps;
-    int rc = plan(cfg, nsamples, params, hint, &ps);
+    std::vector<mifsk_time_split_stats> ps(M);
+    int rc = plan(cfg, nsamples, M, params, hint, ps.data());
     if ( rc )
 	return rc;
-    const uint64_t K = ps.nchunks, L = ps.chunk, W = ps.warmup;
+    const uint64_t L = ps[0].chunk, W = ps[0].warmup;
+    uint64_t nchunkrows = 0;
+    for ( int m = 0; m < M; m++ )
+	nchunkrows += ps[m].nchunks;
 
     mifsk_demod_io base;
     std::memset(&base, 0, sizeof(base));
     base.flags = engine;
 
-    if ( K == 1 ) {
-	// the existing single call (over a padded copy unless the row is whole float4s already)
-	DevBuf pad;
-	const float *x = d_samples;
-	const uint64_t stride = ( nsamples + 3u ) & ~3ull;
-	if ( stride != nsamples ) {
-	    if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
-		return rc;
-	    hipLaunchKernelGGL(ts_gather_rows, dim3(64, 1), dim3(256), 0, st, d_samples, nsamples,
-			       (float *)pad.p, stride, (uint64_t)0, 1);
-	    x = (const float *)pad.p;
-	}
+    if ( nchunkrows == (uint64_t)M ) {
+	// no stream is cut: the existing call over the batch (a lone row over a padded copy unless
+	// it is whole float4s already)
+	DevBuf pad, dn;
 	mifsk_demod_io io = *io_out;
-	io.d_samples = x;
-	io.stream_stride = stride ? stride : 4;
+	io.d_samples = d_samples;
 	io.d_nsamples = nullptr;
-	io.nsamples = (uint32_t)nsamples;
-	io.nstreams = 1;
+	io.nstreams = M;
+	if ( M == 1 ) {
+	    const uint64_t stride = ( nsamples[0] + 3u ) & ~3ull;
+	    if ( stride != nsamples[0] ) {
+		if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
+		    return rc;
+		// (the one row's table, synchronised: it goes out of scope with this block)
+		const struct { StreamRef s; RowRef r; } one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
+		if ( ( rc = alloc(dn, sizeof(one), st) ) )
+		    return rc;
+		HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
+		HIP_OK(hipStreamSynchronize(st));
+		hipLaunchKernelGGL(ts_gather_rows, dim3(64, 1), dim3(256), 0, st, d_samples, (uint64_t)0,
+				   (const StreamRef *)dn.p, (const RowRef *)( (char *)dn.p + sizeof(StreamRef) ),
+				   (float *)pad.p, stride, (uint64_t)0, 1);
+		io.d_samples = (const float *)pad.p;
+	    }
+	    io.stream_stride = stride ? stride : 4;
+	    io.nsamples = (uint32_t)nsamples[0];
+	} else {
+	    std::vector<uint32_t> hn(M);
+	    for ( int m = 0; m < M; m++ )
+		hn[m] = (uint32_t)nsamples[m];
+	    if ( ( rc = alloc(dn, M * sizeof(uint32_t), st) ) )
+		return rc;
+	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
+	    io.stream_stride = xstride;
+	    io.d_nsamples = (const uint32_t *)dn.p;
+	    io.nsamples = (uint32_t)std::min<uint64_t>(xstride, 0xFFFFFFFFull);
+	}
 	io.d_counters = nullptr;
 	io.flags = engine;
 	io.reserved = 0;
@@ -504,72 +630,88 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
 	if ( rc )
 	    return rc;
 	HIP_OK(hipStreamSynchronize(st));
-	if ( stats ) {
-	    *stats = ps;
-	    stats->accepted = 0;
-	}
+	if ( stats )
+	    std::copy(ps.begin(), ps.end(), stats);
 	return 0;
     }
 
-    const int nrows = (int)K + 1;			// the K chunks and the final tail
+    // The rows: stream m's chunks are rows rowbase[m] .. rowbase[m] + K_m - 1, its tail (the
+    // final slab) is row R + m
+    const int R = (int)nchunkrows, nrows = R + M;
+    std::vector<StreamRef> hs(M);
+    std::vector<RowRef> hrow(nrows);
+    std::vector<uint32_t> hns(nrows, 0);
+    for ( int m = 0, r = 0; m < M; m++ ) {
+	hs[m].n = nsamples[m];
+	hs[m].tail_off = 0;
+	hs[m].rowbase = (uint32_t)r;
+	hs[m].K = ps[m].nchunks;
+	for ( uint32_t k = 0; k < hs[m].K; k++, r++ ) {
+	    hrow[r].m = (uint32_t)m;
+	    hrow[r].k = k;
+	    hns[r] = (uint32_t)( k + 1 < hs[m].K ? L + W : nsamples[m] - k * L );
+	}
+	hrow[R + m].m = (uint32_t)m;
+	hrow[R + m].k = hs[m].K;
+    }
     const uint64_t rstride = ( L + W + 3u ) & ~3ull;
     const size_t fcap = mifsk_max_frames(cfg, L + W);
     const size_t ecap = mifsk_max_episodes(cfg, L + W) + 1;
     const bool want_bytes = io_out->d_bytes != nullptr;
-    DevBuf rows, X, I, S, R, cnt, rcnt, code, mark, rframes, rbytes, reps, pref, ns;
+    DevBuf rows, X, I, S, Rr, cnt, rcnt, code, mark, rframes, rbytes, reps, pref, ns, streams, rowref, tails;
     const size_t stsz = sizeof(mifsk_stream_state);
-    if ( ( rc = alloc(rows, K * rstride * sizeof(float), st) )
+    if ( ( rc = alloc(rows, (size_t)R * rstride * sizeof(float), st) )
 	    || ( rc = alloc(X, nrows * stsz, st) ) || ( rc = alloc(I, nrows * stsz, st) )
-	    || ( rc = alloc(S, nrows * stsz, st) ) || ( rc = alloc(R, nrows * stsz, st) )
-	    || ( rc = alloc(cnt, 4 * nrows * sizeof(uint32_t), st) )
-	    || ( rc = alloc(rcnt, 4 * nrows * sizeof(uint32_t), st) )
+	    || ( rc = alloc(S, nrows * stsz, st) ) || ( rc = alloc(Rr, nrows * stsz, st) )
+	    || ( rc = alloc(cnt, 4 * (size_t)nrows * sizeof(uint32_t), st) )
+	    || ( rc = alloc(rcnt, 4 * (size_t)nrows * sizeof(uint32_t), st) )
 	    || ( rc = alloc(code, nrows * sizeof(uint32_t), st) )
 	    || ( rc = alloc(mark, nrows, st) )
 	    || ( rc = alloc(rframes, nrows * fcap * sizeof(mifsk_frame), st) )
 	    || ( want_bytes && ( rc = alloc(rbytes, nrows * fcap, st) ) )
 	    || ( rc = alloc(reps, nrows * ecap * sizeof(mifsk_episode), st) )
-	    || ( rc = alloc(pref, ( nrows + 1 ) * sizeof(Agg), st) )
-	    || ( rc = alloc(ns, nrows * sizeof(uint32_t), st) ) )
+	    || ( rc = alloc(pref, ( (size_t)nrows + M ) * sizeof(Agg), st) )
+	    || ( rc = alloc(ns, nrows * sizeof(uint32_t), st) )
+	    || ( rc = alloc(streams, M * sizeof(StreamRef), st) )
+	    || ( rc = alloc(rowref, nrows * sizeof(RowRef), st) ) )
 	return rc;
     auto *dX = (mifsk_stream_state *)X.p, *dI = (mifsk_stream_state *)I.p;
-    auto *dS = (mifsk_stream_state *)S.p, *dR = (mifsk_stream_state *)R.p;
+    auto *dS = (mifsk_stream_state *)S.p, *dR = (mifsk_stream_state *)Rr.p;
     auto *dcnt = (uint32_t *)cnt.p, *drcnt = (uint32_t *)rcnt.p;
     auto *dframes = (mifsk_frame *)rframes.p;
     auto *deps = (mifsk_episode *)reps.p;
     float *drows = (float *)rows.p;
+    const auto *dstreams = (const StreamRef *)streams.p;
+    const auto *drowref = (const RowRef *)rowref.p;
 
-    HIP_OK(hipMemsetAsync(X.p, 0, nrows * stsz, st));
-    HIP_OK(hipMemsetAsync(cnt.p, 0, 4 * nrows * sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(cnt.p, 0, 4 * (size_t)nrows * sizeof(uint32_t), st));
     HIP_OK(hipMemsetAsync(mark.p, 0, nrows, st));
-    {
-	const unsigned bx = (unsigned)std::min<uint64_t>(64, ( rstride / 4 + 255 ) / 256);
-	hipLaunchKernelGGL(ts_gather_rows, dim3(bx, (unsigned)K), dim3(256), 0, st, d_samples,
-			   nsamples, drows, rstride, L, (int)K);
-    }
-    std::vector<uint32_t> hns(nrows, 0);
-    for ( uint64_t k = 0; k < K; k++ )
-	hns[k] = (uint32_t)( k + 1 < K ? L + W : nsamples - k * L );
+    HIP_OK(hipMemcpyAsync(streams.p, hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(rowref.p, hrow.data(), nrows * sizeof(RowRef), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(ns.p, hns.data(), nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ts_gather_rows, dim3(blocks_for(rstride), (unsigned)std::min(R, 65535)), dim3(256),
+		       0, st, d_samples, (uint64_t)xstride, dstreams, drowref, drows, rstride, L, R);
 
-    // pass A: rows 1 .. K-1, W samples each, from a zeroed state
+    // pass A: rows 1 .. R-1, W samples each, from a zeroed state (a stream's row 0 is skipped)
+    const unsigned tb = 256, gb = (unsigned)( ( nrows + tb - 1 ) / tb );
+    hipLaunchKernelGGL(ts_guess_init, dim3(gb), dim3(tb), 0, st, dX, drowref, R);
     mifsk_demod_io a = base;
     a.d_samples = drows + rstride;
     a.stream_stride = rstride;
     a.nsamples = (uint32_t)W;
-    a.nstreams = (int)K - 1;
+    a.nstreams = R - 1;
     if ( ( rc = mifsk_demod_slab(ctx, cfg, &a, dX + 1, nullptr, 0, stream) ) )
 	return rc;
-    const unsigned tb = 256, gb = (unsigned)( ( nrows + tb - 1 ) / tb );
-    hipLaunchKernelGGL(ts_prepare, dim3(gb), dim3(tb), 0, st, dX, dI, dS, (int)K);
+    hipLaunchKernelGGL(ts_prepare, dim3(gb), dim3(tb), 0, st, dX, dI, dS, drowref, R);
 
-    // pass B: rows 0 .. K-1 up to W samples into the next chunk (the last one to the end; it
-    // stays a non-final slab: the tail below finishes it)
+    // pass B: every row up to W samples into its stream's next chunk (a stream's last one to the
+    // end; it stays a non-final slab: the tail below finishes it)
     mifsk_demod_io b = base;
     b.d_samples = drows;
     b.stream_stride = rstride;
     b.d_nsamples = (const uint32_t *)ns.p;
     b.nsamples = (uint32_t)( L + W );
-    b.nstreams = (int)K;
+    b.nstreams = R;
     b.d_frames = dframes;
     b.d_bytes = (uint8_t *)rbytes.p;
     b.frames_cap = fcap;
@@ -582,57 +724,67 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
     if ( ( rc = mifsk_demod_slab(ctx, cfg, &b, dS, nullptr, 0, stream) ) )
 	return rc;
 
-    // Verify, and re-run what was rejected, in rounds.  Row k is CONSISTENT when the state it
-    // started from agrees in control with the state row k-1 paused in; the settled rows are the
-    // consistent prefix.  A round re-runs every inconsistent row at once from its predecessor's
-    // current state (settled or not: a row whose predecessor changes again is simply
-    // inconsistent again), so the rounds follow the longest run of rejections, not their number.
+    // Verify, and re-run what was rejected, in rounds.  Row k of a stream is CONSISTENT when the
+    // state it started from agrees in control with the state row k-1 of that stream paused in;
+    // a stream's settled rows are its consistent prefix.  A round re-runs every inconsistent row
+    // of every stream at once from its predecessor's current state (settled or not: a row whose
+    // predecessor changes again is simply inconsistent again), so the rounds follow the longest
+    // run of rejections in any one stream, not their number and not the sum over the streams.
     std::vector<uint8_t> settled(nrows, 0), drop(nrows, 0), hmark(nrows, 0), ran(nrows, 0);
     std::vector<uint32_t> hcode(nrows, 0);
-    settled[0] = 1;
-    uint32_t accepted = 0, rerun = 0, rounds = 0;
-    uint64_t rerun_samples = 0;
+    for ( int m = 0; m < M; m++ )
+	settled[hs[m].rowbase] = 1;
+    uint32_t rounds = 0;
     for ( ;; ) {
 	// (MIFSK_TIME_SPLIT_REJECT_ALL: every guess of pass A is rejected)
 	const int reject = rounds == 0 && ( flags & MIFSK_TIME_SPLIT_REJECT_ALL );
 	hipLaunchKernelGGL(ts_verify, dim3(gb), dim3(tb), 0, st, (const mifsk_stream_state *)dI,
-			   (const mifsk_stream_state *)dS, (uint32_t *)code.p, (int)K, L, reject);
-	HIP_OK(hipMemcpyAsync(hcode.data(), code.p, K * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+			   (const mifsk_stream_state *)dS, drowref, (uint32_t *)code.p, R, L, reject);
+	HIP_OK(hipMemcpyAsync(hcode.data(), code.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
-	for ( uint64_t k = 1; k < K; k++ ) {
-	    if ( settled[k] )
-		continue;
-	    if ( !settled[k - 1] )
-		break;
-	    if ( drop[k - 1] || ( hcode[k] & 2u ) ) {
-		drop[k] = settled[k] = 1;
-	    } else if ( hcode[k] & 1u ) {
-		settled[k] = 1;
-		accepted += !ran[k];
-	    } else {
-		break;
-	    }
-	}
 	int lo = -1, hi = -1;
 	std::fill(hmark.begin(), hmark.end(), 0);
-	for ( uint64_t k = 1; k < K; k++ )
-	    if ( !settled[k] && hcode[k] == 0u ) {	// (behind a finished row: wait for it to settle)
-		hmark[k] = 1;
-		if ( lo < 0 )
-		    lo = (int)k;
-		hi = (int)k;
+	for ( int m = 0; m < M; m++ ) {
+	    const int r0 = (int)hs[m].rowbase, r1 = r0 + (int)hs[m].K;
+	    for ( int r = r0 + 1; r < r1; r++ ) {
+		if ( settled[r] )
+		    continue;
+		if ( !settled[r - 1] )
+		    break;
+		if ( drop[r - 1] || ( hcode[r] & 2u ) ) {
+		    drop[r] = settled[r] = 1;
+		} else if ( hcode[r] & 1u ) {
+		    settled[r] = 1;
+		    ps[m].accepted += !ran[r];
+		} else {
+		    break;
+		}
 	    }
+	    bool any = false;
+	    for ( int r = r0 + 1; r < r1; r++ )
+		if ( !settled[r] && hcode[r] == 0u ) {	// (behind a finished row: wait for it to settle)
+		    hmark[r] = 1;
+		    any = true;
+		    if ( lo < 0 )
+			lo = r;
+		    hi = r;
+		    ran[r] = 1;
+		    ps[m].rerun++;
+		    ps[m].samples_rerun += hns[r];
+		}
+	    ps[m].rounds += any;
+	}
 	if ( lo < 0 )
 	    break;
 	HIP_OK(hipMemcpyAsync(mark.p, hmark.data(), nrows, hipMemcpyHostToDevice, st));
-	const int m = hi - lo + 1;
-	const unsigned gm = (unsigned)( ( m + tb - 1 ) / tb );
-	hipLaunchKernelGGL(ts_seed, dim3(gm), dim3(tb), 0, st, dS, (const uint8_t *)mark.p, dR, dI,
+	const int nr = hi - lo + 1;
+	const unsigned gm = (unsigned)( ( nr + tb - 1 ) / tb );
+	hipLaunchKernelGGL(ts_seed, dim3(gm), dim3(tb), 0, st, dS, (const uint8_t *)mark.p, drowref, dR, dI,
 			   lo, hi, L);
 	mifsk_demod_io r = b;
 	r.d_samples = drows + (size_t)lo * rstride;
 	r.d_nsamples = (const uint32_t *)ns.p + lo;
-	r.nstreams = m;
+	r.nstreams = nr;
 	r.d_frames = dframes + (size_t)lo * fcap;
 	r.d_bytes = rbytes.p ? (uint8_t *)rbytes.p + (size_t)lo * fcap : nullptr;
 	r.d_episodes = deps + (size_t)lo * ecap;
@@ -644,43 +796,58 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
 	    return rc;
 	hipLaunchKernelGGL(ts_merge, dim3(gm), dim3(tb), 0, st, (const mifsk_stream_state *)dR,
 			   (const uint8_t *)mark.p, (const uint32_t *)drcnt, dS, dcnt, lo, hi, nrows);
-	for ( int k = lo; k <= hi; k++ )
-	    if ( hmark[k] ) {
-		ran[k] = 1;
-		rerun++;
-		rerun_samples += hns[k];
-	    }
 	rounds++;
     }
 
-    // the tail: the last chunk's loop finished as a final slab, from its paused state
-    uint64_t tail_off = 0;
-    mifsk_stream_state last;
-    HIP_OK(hipMemcpyAsync(&last, dS + ( K - 1 ), stsz, hipMemcpyDeviceToHost, st));
+    // the tails: every stream's last chunk finished as a final slab from its paused state, all of
+    // them one batch over a small buffer of their own (they do not sit at one stride in the rows)
+    std::vector<mifsk_stream_state> last(M);
+    hipLaunchKernelGGL(ts_last_states, dim3((unsigned)( ( M + tb - 1 ) / tb )), dim3(tb), 0, st,
+		       (const mifsk_stream_state *)dS, dstreams, dR + R, M);
+    HIP_OK(hipMemcpyAsync(last.data(), dR + R, M * stsz, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if ( drop[K - 1] || ( last.flags & MIFSK_STATE_FINISHED ) ) {
-	drop[K] = 1;
-    } else {
-	const uint64_t rel = last.base & ~3ull;	// (rows start 16-byte aligned)
-	tail_off = ( K - 1 ) * L + rel;
-	const mifsk_stream_state it = reset_book(last, rel);
-	HIP_OK(hipMemcpyAsync(dI + K, &it, stsz, hipMemcpyHostToDevice, st));
-	HIP_OK(hipMemcpyAsync(dS + K, &it, stsz, hipMemcpyHostToDevice, st));
-	const uint64_t nt = nsamples - tail_off;
+    uint64_t longest_tail = 0;
+    bool live = false;
+    for ( int m = 0; m < M; m++ ) {
+	const uint64_t K = hs[m].K;
+	if ( drop[hs[m].rowbase + K - 1] || ( last[m].flags & MIFSK_STATE_FINISHED ) ) {
+	    drop[R + m] = 1;
+	    hs[m].tail_off = nsamples[m];
+	    std::memset(&last[m], 0, stsz);
+	    last[m].flags = MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
+	    continue;
+	}
+	const uint64_t rel = last[m].base & ~3ull;	// (rows start 16-byte aligned)
+	hs[m].tail_off = ( K - 1 ) * L + rel;
+	last[m] = reset_book(last[m], rel);
+	hns[R + m] = (uint32_t)( nsamples[m] - hs[m].tail_off );
+	longest_tail = std::max<uint64_t>(longest_tail, hns[R + m]);
+	live = true;
+    }
+    HIP_OK(hipMemcpyAsync(streams.p, hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(dI + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(dS + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
+    if ( live ) {
+	const uint64_t tstride = std::max<uint64_t>(4, ( longest_tail + 3u ) & ~3ull);
+	if ( ( rc = alloc(tails, (size_t)M * tstride * sizeof(float), st) ) )
+	    return rc;
+	HIP_OK(hipMemcpyAsync((uint32_t *)ns.p + R, hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(ts_gather_tails, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), dim3(256),
+			   0, st, d_samples, (uint64_t)xstride, dstreams, (float *)tails.p, tstride, M);
 	mifsk_demod_io t = b;
-	t.d_samples = drows + ( K - 1 ) * rstride + rel;
-	t.stream_stride = ( nt + 3u ) & ~3ull;
-	t.d_nsamples = nullptr;
-	t.nsamples = (uint32_t)nt;
-	t.nstreams = 1;
-	t.d_frames = dframes + K * fcap;
-	t.d_bytes = rbytes.p ? (uint8_t *)rbytes.p + K * fcap : nullptr;
-	t.d_episodes = deps + K * ecap;
-	t.d_nframes = dcnt + K;
-	t.d_nbytes = dcnt + nrows + K;
-	t.d_nepisodes = dcnt + 2 * nrows + K;
-	t.d_status = dcnt + 3 * nrows + K;
-	if ( ( rc = mifsk_demod_slab(ctx, cfg, &t, dS + K, nullptr, 1, stream) ) )
+	t.d_samples = (const float *)tails.p;
+	t.stream_stride = tstride;
+	t.d_nsamples = (const uint32_t *)ns.p + R;
+	t.nsamples = (uint32_t)longest_tail;
+	t.nstreams = M;
+	t.d_frames = dframes + (size_t)R * fcap;
+	t.d_bytes = rbytes.p ? (uint8_t *)rbytes.p + (size_t)R * fcap : nullptr;
+	t.d_episodes = deps + (size_t)R * ecap;
+	t.d_nframes = dcnt + R;
+	t.d_nbytes = dcnt + nrows + R;
+	t.d_nepisodes = dcnt + 2 * nrows + R;
+	t.d_status = dcnt + 3 * nrows + R;
+	if ( ( rc = mifsk_demod_slab(ctx, cfg, &t, dS + R, nullptr, 1, stream) ) )
 	    return rc;
     }
     HIP_OK(hipMemcpyAsync(mark.p, drop.data(), nrows, hipMemcpyHostToDevice, st));
@@ -692,30 +859,61 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
     sa.S = dS;
     sa.cnt = dcnt;
     sa.drop = (const uint8_t *)mark.p;
+    sa.streams = dstreams;
+    sa.rowref = drowref;
     sa.nrows = nrows;
+    sa.R = R;
     sa.rframes = dframes;
     sa.rbytes = (const uint8_t *)rbytes.p;
     sa.reps = deps;
     sa.fcap = fcap;
     sa.ecap = ecap;
     sa.L = L;
-    sa.tail_off = tail_off;
     sa.pref = (Agg *)pref.p;
     sa.out = *io_out;
     sa.autodetect = cfg->auto_carrier_threshold > 0.0f;
-    hipLaunchKernelGGL(ts_scan, dim3(1), dim3(kScanThreads), 0, st, sa);
+    hipLaunchKernelGGL(ts_scan, dim3(M), dim3(kScanThreads), 0, st, sa);
     if ( io_out->d_frames || io_out->d_bits || io_out->d_bytes )
 	hipLaunchKernelGGL(ts_scatter, dim3(nrows), dim3(256), 0, st, sa);
     if ( io_out->d_episodes )
 	hipLaunchKernelGGL(ts_episodes, dim3(nrows), dim3(64), 0, st, sa);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(st));
-    if ( stats ) {
-	*stats = ps;
-	stats->accepted = accepted;
-	stats->rerun = rerun;
-	stats->rounds = rounds;
-	stats->samples_rerun = rerun_samples;
-    }
+    if ( stats )
+	std::copy(ps.begin(), ps.end(), stats);
     return 0;
+}
+
+} // namespace
+
+extern "C" int mifsk_time_split_plan_get( const mifsk_rx_config *cfg, uint64_t nsamples,
+	const mifsk_time_split *params, mifsk_time_split_stats *out )
+{
+    return plan(cfg, &nsamples, 1, params, 0, out);
+}
+
+extern "C" int mifsk_time_split_plan_batch_get( const mifsk_rx_config *cfg, const uint64_t *nsamples,
+	int nstreams, const mifsk_time_split *params, mifsk_time_split_stats *out )
+{
+    return plan(cfg, nsamples, nstreams, params, 0, out);
+}
+
+extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
+	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,
+	mifsk_time_split_stats *stats, void *stream )
+{
+    return run(ctx, cfg, d_samples, 0, &nsamples, 1, params, io_out, stats, stream);
+}
+
+extern "C" int mifsk_demod_long_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const float *d_samples, size_t stream_stride, const uint64_t *nsamples, int nstreams,
+	const mifsk_time_split *params, const mifsk_demod_io *io_out, mifsk_time_split_stats *stats,
+	void *stream )
+{
+    if ( stream_stride % 4u || !nsamples || nstreams <= 0 )
+	return -EINVAL;
+    for ( int m = 0; m < nstreams; m++ )
+	if ( nsamples[m] > stream_stride )
+	    return -EINVAL;
+    return run(ctx, cfg, d_samples, stream_stride, nsamples, nstreams, params, io_out, stats, stream);
 }
