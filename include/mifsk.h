@@ -26,9 +26,12 @@
  *   mifsk_demod_slab[_ring]       the loop over a stream that arrives in pieces  minimodem.c:1144-1174
  *   mifsk_session_*               ... fed from host memory, bookkeeping included
  *   mifsk_demod_long[_batch]      the loop over one long stream, or a few, cut in time across the chip
+ *   mifsk_demod_long_batch_s16    ... from PCM16 in device memory (rows gathered straight from it)
+ *   mifsk_demod_long_batch_host   ... from host memory, float32 or PCM16
  *   mifsk_demod_batch_host[_ex]   same, host buffers     (chunked H2D | demod | D2H, overlapped)
  *   mifsk_demod_files             --rx --file, N files   simpleaudio-sndfile.c:42-74,
  *                                                        minimodem.c:1014-1032
+ *   mifsk_demod_files_long        ... long recordings: every group cut in time across the chip
  */
 #ifndef MIFSK_H
 #define MIFSK_H
@@ -697,6 +700,43 @@ int mifsk_demod_long_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const fl
 	const mifsk_time_split *params, const mifsk_demod_io *io_out,
 	mifsk_time_split_stats *stats /* [nstreams] or NULL */, void *stream );
 
+/* mifsk_demod_long_batch over PCM16 as a WAV file holds it: row m of d_pcm (16-byte aligned, rows
+ * pcm_stride int16 elements apart, pcm_stride % 8 == 0) holds nsamples[m] <= pcm_stride samples.
+ * The chunks' rows are gathered straight from the PCM16 -- value / 32768 plus the --Xrxnoise term
+ * (rxnoise: the option's factor, 0 = off), mifsk_ingest_s16's arithmetic -- so the recording never
+ * exists as floats: device memory is the 2-byte source plus the rows, not source, a float copy and
+ * the rows.  The outputs are bit for bit those of mifsk_ingest_s16(..., rxnoise) into float rows
+ * followed by one mifsk_demod_batch; nstreams == 1 is the single recording.  A batch the plan
+ * leaves uncut is converted by mifsk_ingest_s16 into a temporary buffer and decoded by one
+ * mifsk_demod_batch call.  Checked in this order, before any HIP call: -EINVAL for a NULL ctx, cfg,
+ * io_out or nsamples; for nstreams <= 0; for a base that is not 16-byte aligned or a pcm_stride
+ * that is not a multiple of 8; for nsamples[m] > pcm_stride; then the planner's codes
+ * (MIFSK_IO_RING_EXACT: -ENOTSUP).  Everything else is mifsk_demod_long_batch's. */
+int mifsk_demod_long_batch_s16( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const int16_t *d_pcm, size_t pcm_stride /* int16 elements, % 8 == 0 */,
+	const uint64_t *nsamples /* host, [nstreams] */, int nstreams, float rxnoise,
+	const mifsk_time_split *params, const mifsk_demod_io *io_out,
+	mifsk_time_split_stats *stats /* [nstreams] or NULL */, void *stream );
+
+/* mifsk_demod_long_batch for recordings in HOST memory: rows[m] points to nsamples[m] samples,
+ * float32 (src_flags 0) or PCM16 (MIFSK_IO_HOST_S16) -- one pointer per recording, long recordings
+ * do not sit at a common stride.  The samples cross the bus as they are (PCM16 as 16-bit) into one
+ * device buffer with a common stride, in pieces of the size mifsk_demod_batch_host uses: by DMA
+ * from where they are when every row is page-locked, otherwise through the context's pinned
+ * staging buffers, one piece being staged by the worker threads while the piece before is copied;
+ * no pinned memory of the recording's size is made.  PCM16 is then decoded by
+ * mifsk_demod_long_batch_s16, floats by mifsk_ingest_rxnoise_f32 (rxnoise != 0) and
+ * mifsk_demod_long_batch.  io_out holds HOST pointers, laid out as mifsk_demod_batch_host writes
+ * them; stats ([nstreams] or NULL) as mifsk_demod_long_batch fills it; hstats (may be NULL): bytes
+ * each way, staging seconds, source_pinned, chunks = the number of pieces.  -EINVAL for a NULL
+ * argument, nstreams <= 0, other src_flags or a NULL row of samples, then the planner's codes for
+ * `params`, all before any HIP call.  Synchronous; one host call at a time per context. */
+int mifsk_demod_long_batch_host( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const void *const *rows /* host, [nstreams]: one pointer per recording */,
+	const uint64_t *nsamples, int nstreams, unsigned src_flags /* 0 or MIFSK_IO_HOST_S16 */,
+	float rxnoise, const mifsk_time_split *params, const mifsk_demod_io *io_out /* HOST pointers */,
+	mifsk_time_split_stats *stats, mifsk_host_stats *hstats /* may be NULL */ );
+
 /* ---- streams fed in pieces from host memory ---------------------------------- */
 
 /* mifsk_demod_slab with the bookkeeping done (reference: the loop that reads its stream half a
@@ -860,6 +900,20 @@ typedef struct mifsk_files mifsk_files;
  * could not. */
 int mifsk_demod_files( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files **out );
+/* mifsk_demod_files for long recordings: header parsing, per-file errors and the result object
+ * are mifsk_demod_files's, but every group -- the files of one sample rate and one sample format
+ * -- is decoded as one batch of long recordings cut in time: the files are pread() into pinned
+ * pieces that are copied to the group's device buffer, PCM16 is decoded by
+ * mifsk_demod_long_batch_s16 and float32 by mifsk_ingest_rxnoise_f32 and mifsk_demod_long_batch.
+ * params: NULL for the library's choices (its flags are ORed with the engine flags of `flags`).
+ * flags: MIFSK_IO_ENGINE_* and MIFSK_FILES_WANT_FRAMES; MIFSK_IO_RING_EXACT is -ENOTSUP, before
+ * any file is opened.  -EINVAL as mifsk_demod_files, before any HIP call. */
+int mifsk_demod_files_long( mifsk_ctx *ctx, const mifsk_modem_args *args,
+	const char *const *paths, int nfiles, float rxnoise, unsigned flags,
+	const mifsk_time_split *params /* NULL: the library's choices */, mifsk_files **out );
+/* file i's plan and verification figures; NULL for a file with an error and for an object made by
+ * mifsk_demod_files */
+const mifsk_time_split_stats *mifsk_files_time_split( const mifsk_files *f, int i );
 int mifsk_files_count( const mifsk_files *f );
 const mifsk_file_result *mifsk_files_get( const mifsk_files *f, int i );
 const mifsk_host_stats *mifsk_files_stats( const mifsk_files *f );

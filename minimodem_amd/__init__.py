@@ -277,18 +277,34 @@ def time_split_plan(cfg, nsamples, chunk=None, warmup=None, chunks=None, engine=
 
 
 def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("bytes", "episodes"),
-               frames_cap=None, episodes_cap=None, engine=None, reject_all=False, stream=None):
+               frames_cap=None, episodes_cap=None, engine=None, reject_all=False, stream=None,
+               rxnoise=0.0):
     """mifsk_demod_long: ONE long recording decoded across the whole chip by cutting it in
     time (DESIGN.md "cutting a stream in time"), bit for bit what demod_batch gives for it.
 
-    samples: a 1-D torch.float32 CUDA tensor (16-byte aligned).  chunk / warmup / chunks: the
-    planner's parameters (None: the library's choice).  reject_all: every speculative chunk is
-    re-run (tests).  Returns demod_batch's dict for a batch of one stream plus "stats" (the
-    planner's figures and what verification accepted); synchronous."""
+    samples: a 1-D torch.float32 CUDA tensor (16-byte aligned), or torch.int16 (PCM16: the chunks'
+    rows are gathered straight from it, mifsk_demod_long_batch_s16 -- what ingest_s16 and this call
+    give, without the float copy).  chunk / warmup / chunks: the planner's parameters (None: the
+    library's choice).  reject_all: every speculative chunk is re-run (tests).  rxnoise: the
+    --Xrxnoise factor (a float tensor is decoded as ingest_rxnoise on a copy; the caller's stays
+    untouched).  Returns demod_batch's dict for a batch of one stream plus "stats" (the planner's
+    figures and what verification accepted); synchronous."""
     torch = _torch()
     lib = _lib.load()
+    if samples.dtype == torch.int16:
+        assert samples.is_cuda and samples.dim() == 1
+        assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
+        n = int(samples.shape[0])
+        out = _demod_long_s16(torch, lib, ctx, cfg, samples, (n + 7) & ~7, [n], 1, rxnoise, want, frames_cap,
+                              episodes_cap, _time_split_params(chunk, warmup, chunks, engine, reject_all), stream)
+        out["stats"] = out["stats"][0]
+        return out
     assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 1
     assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
+    if rxnoise:
+        with _on(torch, stream):
+            samples = samples.clone()
+        ingest_rxnoise(ctx, samples[None, :], rxnoise, stream=stream)
     n = int(samples.shape[0])
     if frames_cap is None:
         frames_cap = max_frames(cfg, n)
@@ -321,23 +337,39 @@ def time_split_plan_batch(cfg, nsamples_list, chunk=None, warmup=None, chunks=No
 
 def demod_long_batch(ctx, cfg, samples, nsamples=None, chunk=None, warmup=None, chunks=None,
                      want=("bytes", "episodes"), frames_cap=None, episodes_cap=None, engine=None,
-                     reject_all=False, stream=None):
+                     reject_all=False, stream=None, rxnoise=0.0):
     """mifsk_demod_long_batch: a small batch of long recordings decoded across the whole chip by
     cutting all of them in time with one plan, bit for bit what demod_batch gives for the batch.
 
     samples: a 2-D contiguous torch.float32 CUDA tensor [nstreams, stride], stride % 4 == 0 (16-byte
-    aligned).  nsamples: a HOST sequence of ints, the streams' lengths (None: every row is full).
-    chunk / warmup / chunks / reject_all: as for demod_long.  Returns demod_batch's dict for nstreams
-    streams plus "stats", a list of dicts (per stream: the plan and what verification accepted);
-    the default caps come from the longest stream.  Synchronous."""
+    aligned), or torch.int16 with stride % 8 == 0 (PCM16, mifsk_demod_long_batch_s16: what
+    ingest_s16 and this call give, without the float copy).  nsamples: a HOST sequence of ints, the
+    streams' lengths (None: every row is full).  chunk / warmup / chunks / reject_all / rxnoise: as
+    for demod_long.  Returns demod_batch's dict for nstreams streams plus "stats", a list of dicts
+    (per stream: the plan and what verification accepted); the default caps come from the longest
+    stream.  Synchronous."""
     torch = _torch()
     lib = _lib.load()
+    if samples.dtype == torch.int16:
+        assert samples.is_cuda and samples.dim() == 2
+        assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
+        nstreams, width = (int(v) for v in samples.shape)
+        assert nstreams >= 1 and width % 8 == 0, "PCM16 rows must be whole 16-byte vectors"
+        lens = [width] * nstreams if nsamples is None else [int(n) for n in nsamples]
+        assert len(lens) == nstreams and all(0 <= n <= width for n in lens)
+        return _demod_long_s16(torch, lib, ctx, cfg, samples, width, lens, nstreams, rxnoise, want, frames_cap,
+                               episodes_cap, _time_split_params(chunk, warmup, chunks, engine, reject_all), stream)
     assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2
     assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
     nstreams, width = (int(v) for v in samples.shape)
     assert nstreams >= 1 and width % 4 == 0, "rows must be whole float4s"
     lens = [width] * nstreams if nsamples is None else [int(n) for n in nsamples]
     assert len(lens) == nstreams and all(0 <= n <= width for n in lens)
+    if rxnoise:
+        with _on(torch, stream):
+            samples = samples.clone()
+            dn = torch.tensor(lens, dtype=torch.int32, device=samples.device)
+        ingest_rxnoise(ctx, samples, rxnoise, nsamples=dn, stream=stream)
     longest = max(lens)
     if frames_cap is None:
         frames_cap = max_frames(cfg, longest)
@@ -352,6 +384,28 @@ def demod_long_batch(ctx, cfg, samples, nsamples=None, chunk=None, warmup=None, 
                                     C.byref(io), st, _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_demod_long_batch failed: %d" % rc)
+    out["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
+    return out
+
+
+def _demod_long_s16(torch, lib, ctx, cfg, pcm, stride, lens, nstreams, rxnoise, want, frames_cap, episodes_cap,
+                    params, stream):
+    """demod_long / demod_long_batch over a torch.int16 tensor: mifsk_demod_long_batch_s16.  A lone
+    row's stride means nothing to the library; it is given as the length rounded up to 8."""
+    longest = max(lens)
+    if frames_cap is None:
+        frames_cap = max_frames(cfg, longest)
+    if episodes_cap is None:
+        episodes_cap = max_episodes(cfg, longest)
+    out = _long_outputs(torch, cfg, pcm.device, nstreams, want, frames_cap, episodes_cap, stream)
+    io = _long_io(out, nstreams, frames_cap, episodes_cap)
+    arr = (C.c_uint64 * nstreams)(*lens)
+    st = (_lib.TimeSplitStats * nstreams)()
+    rc = lib.mifsk_demod_long_batch_s16(ctx.handle, C.byref(cfg), C.c_void_p(pcm.data_ptr()), stride, arr, nstreams,
+                                        C.c_float(rxnoise), C.byref(params), C.byref(io), st,
+                                        _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_demod_long_batch_s16 failed: %d" % rc)
     out["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
     return out
 
@@ -1103,13 +1157,87 @@ def demod_batch_host(ctx, cfg, samples, nsamples=None, frames_cap=None, episodes
     return res
 
 
+def demod_long_host(ctx, cfg, arrays, chunk=None, warmup=None, chunks=None,
+                    want=("bytes", "bits", "frames", "episodes"), rxnoise=0.0, engine=None, reject_all=False,
+                    stats=False, frames_cap=None, episodes_cap=None):
+    """mifsk_demod_long_batch_host: a few long recordings in HOST memory decoded across the whole
+    chip by cutting them in time.  arrays: a list of 1-D numpy arrays, all int16 (PCM16 as a WAV
+    file holds it: it crosses the bus as 16-bit and the chunks' rows are gathered straight from it)
+    or all float32; arrays from host_alloc() are copied by DMA from where they are.  chunk / warmup
+    / chunks / reject_all: as for demod_long.  Returns numpy results as demod_batch_host does, plus
+    "stats" (a list of per-stream dicts: the plan and what verification accepted) and, with
+    stats=True, "host_stats"."""
+    lib = _lib.load()
+    arrays = list(arrays)
+    assert arrays and all(a.ndim == 1 for a in arrays)
+    s16 = arrays[0].dtype == np.int16
+    assert all(a.dtype == (np.int16 if s16 else np.float32) and a.flags.c_contiguous for a in arrays), \
+        "all int16 or all float32, contiguous"
+    nstreams = len(arrays)
+    lens = [int(a.shape[0]) for a in arrays]
+    longest = max(lens)
+    if frames_cap is None:
+        frames_cap = max_frames(cfg, longest)
+    if episodes_cap is None:
+        episodes_cap = max_episodes(cfg, longest)
+    res = {"nframes": np.zeros(nstreams, np.uint32), "status": np.zeros(nstreams, np.uint32),
+           "carrier_band": np.full(nstreams, -1, np.int32)}
+    if "bytes" in want:
+        res["bytes"] = np.zeros((nstreams, frames_cap), np.uint8)
+        res["nbytes"] = np.zeros(nstreams, np.uint32)
+    if "bits" in want:
+        res["bits"] = np.zeros((nstreams, frames_cap), np.uint64)
+    if "frames" in want:
+        res["frames"] = np.zeros((nstreams, frames_cap), FRAME_DTYPE)
+    if "episodes" in want:
+        res["episodes"] = np.zeros((nstreams, episodes_cap), EPISODE_DTYPE)
+        res["nepisodes"] = np.zeros(nstreams, np.uint32)
+
+    def ptr(name):
+        return res[name].ctypes.data if name in res else None
+
+    io = _lib.DemodIO()
+    io.nstreams = nstreams
+    io.d_bytes = ptr("bytes")
+    io.d_nbytes = ptr("nbytes")
+    io.d_bits = ptr("bits")
+    io.d_frames = ptr("frames")
+    io.d_nframes = ptr("nframes")
+    io.frames_cap = frames_cap
+    io.d_episodes = ptr("episodes")
+    io.d_nepisodes = ptr("nepisodes")
+    io.episodes_cap = episodes_cap
+    io.d_status = ptr("status")
+    io.d_carrier_band = ptr("carrier_band")
+    rows = (C.c_void_p * nstreams)(*[a.ctypes.data for a in arrays])
+    arr = (C.c_uint64 * nstreams)(*lens)
+    st = (_lib.TimeSplitStats * nstreams)()
+    hst = _lib.HostStats()
+    rc = lib.mifsk_demod_long_batch_host(ctx.handle, C.byref(cfg), rows, arr, nstreams,
+                                         _lib.IO_HOST_S16 if s16 else 0, C.c_float(rxnoise),
+                                         C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
+                                         C.byref(io), st, C.byref(hst))
+    if rc != 0:
+        raise RuntimeError("mifsk_demod_long_batch_host failed: %d" % rc)
+    res["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
+    if stats:
+        res["host_stats"] = {k: getattr(hst, k) for k, _ in hst._fields_ if k != "reserved"}
+    return res
+
+
 def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want_frames=False,
-                engine=None, **opts):
+                engine=None, time_split=False, **opts):
     """mifsk_demod_files: `minimodem --rx --file F <baudmode>` for a list of WAV files (PCM16 or
     float32, any mix of lengths and sample rates) as batches on the device: raw samples are
     pread() into pinned memory by worker threads, cross PCIe as they are in the file and are
     converted there.  Returns (list of per-file dicts, stats dict); a file that could not be
-    decoded has {"error": -errno}.  Each dict carries the RxConfig it was decoded with."""
+    decoded has {"error": -errno}.  Each dict carries the RxConfig it was decoded with.
+    time_split: True, or a dict with any of chunk / warmup / chunks / reject_all, decodes every
+    (sample rate, sample format) group of files as long recordings cut in time across the chip
+    (mifsk_demod_files_long); each decoded file's dict then carries "time_split", its plan and
+    verification figures.  Not with ring_exact."""
+    if time_split is not False and time_split is not None and ring_exact:
+        raise ValueError("time_split cannot be combined with ring_exact")
     lib = _lib.load()
     a = ModemArgs()
     lib.mifsk_modem_args_default(C.byref(a))
@@ -1126,11 +1254,21 @@ def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want
         (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
         (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
     h = C.c_void_p()
-    rc = lib.mifsk_demod_files(ctx.handle, C.byref(a), arr, len(enc), C.c_float(rxnoise), flags, C.byref(h))
+    split = time_split is not False and time_split is not None
+    if split:
+        kw = dict(time_split) if isinstance(time_split, dict) else {}
+        unknown = set(kw) - {"chunk", "warmup", "chunks", "reject_all"}
+        if unknown:
+            raise TypeError("unknown time_split option(s) %s" % sorted(unknown))
+        p = _time_split_params(kw.get("chunk"), kw.get("warmup"), kw.get("chunks"), None, kw.get("reject_all", False))
+        rc = lib.mifsk_demod_files_long(ctx.handle, C.byref(a), arr, len(enc), C.c_float(rxnoise), flags,
+                                        C.byref(p), C.byref(h))
+    else:
+        rc = lib.mifsk_demod_files(ctx.handle, C.byref(a), arr, len(enc), C.c_float(rxnoise), flags, C.byref(h))
     if rc != 0:
         if h:
             lib.mifsk_files_free(h)
-        raise RuntimeError("mifsk_demod_files failed: %d" % rc)
+        raise RuntimeError("mifsk_demod_files%s failed: %d" % ("_long" if split else "", rc))
     out = []
     try:
         for i in range(lib.mifsk_files_count(h)):
@@ -1152,6 +1290,10 @@ def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want
                     d["frames"] = np.frombuffer(
                         (C.c_char * (max(1, fr.nframes) * FRAME_DTYPE.itemsize)).from_address(fr.frames),
                         dtype=FRAME_DTYPE)[:fr.nframes].copy()
+                if split:
+                    ts = lib.mifsk_files_time_split(h, i)
+                    if ts:
+                        d["time_split"] = {k: int(getattr(ts.contents, k)) for k, _ in ts.contents._fields_}
             out.append(d)
         st = lib.mifsk_files_stats(h).contents
         stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}

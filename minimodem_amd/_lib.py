@@ -259,6 +259,8 @@ EXPORTS = [
     "mifsk_session_create", "mifsk_session_destroy", "mifsk_session_feed", "mifsk_session_get",
     "mifsk_session_pending", "mifsk_time_split_plan_get", "mifsk_demod_long",
     "mifsk_time_split_plan_batch_get", "mifsk_demod_long_batch",
+    "mifsk_demod_long_batch_s16", "mifsk_demod_long_batch_host", "mifsk_demod_files_long",
+    "mifsk_files_time_split",
 ]
 
 _lib = None
@@ -443,5 +445,19 @@ def load():
     lib.mifsk_demod_long_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_uint64), C.c_int, C.POINTER(TimeSplit),
                                            C.POINTER(DemodIO), C.POINTER(TimeSplitStats), C.c_void_p]
+    lib.mifsk_demod_long_batch_s16.restype = C.c_int
+    lib.mifsk_demod_long_batch_s16.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_uint64), C.c_int, C.c_float, C.POINTER(TimeSplit),
+                                               C.POINTER(DemodIO), C.POINTER(TimeSplitStats), C.c_void_p]
+    lib.mifsk_demod_long_batch_host.restype = C.c_int
+    lib.mifsk_demod_long_batch_host.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_uint64), C.c_int, C.c_uint, C.c_float,
+                                                C.POINTER(TimeSplit), C.POINTER(DemodIO),
+                                                C.POINTER(TimeSplitStats), C.POINTER(HostStats)]
+    lib.mifsk_demod_files_long.restype = C.c_int
+    lib.mifsk_demod_files_long.argtypes = [C.c_void_p, C.POINTER(ModemArgs), C.POINTER(C.c_char_p), C.c_int,
+                                           C.c_float, C.c_uint, C.POINTER(TimeSplit), C.POINTER(C.c_void_p)]
+    lib.mifsk_files_time_split.restype = C.POINTER(TimeSplitStats)
+    lib.mifsk_files_time_split.argtypes = [C.c_void_p, C.c_int]
     _lib = lib
     return lib

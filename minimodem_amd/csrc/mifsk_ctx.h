@@ -15,6 +15,8 @@
 namespace mifsk {
 struct HostWork;
 void host_work_destroy( HostWork *w );		// (mifsk_hostpipe.cpp)
+// what the time split's planner refuses whatever the lengths are, host only (mifsk_timesplit.hip)
+int time_split_check_params( const mifsk_rx_config *cfg, const mifsk_time_split *params );
 }
 
 using mifsk::DevCfg;

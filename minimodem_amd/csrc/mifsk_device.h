@@ -361,4 +361,15 @@ int launch_selftest_sqrt( uint64_t seed, uint32_t blocks, uint32_t per_thread, u
 // the HIP device a context is bound to (mifsk_capi.cpp)
 int ctx_device( const mifsk_ctx *ctx );
 
+// What --Xrxnoise really adds to every sample: (0 - 0.5f) * (factor * 2), in float as at
+// simpleaudio-sndfile.c:67-69 (`rand()/RAND_MAX` is an integer division, i.e. 0).  Shared by the
+// ingest kernels (mifsk_ingest.hip) and the time split's PCM16 gather (mifsk_timesplit.hip).
+inline float rxnoise_term( float factor )
+{
+    if ( factor == 0.0f )
+	return 0.0f;
+    const float f = factor * 2;
+    return ( 0 - 0.5f ) * f;
+}
+
 } // namespace mifsk

@@ -527,10 +527,220 @@ int run_job( mifsk_ctx *ctx, Job &job )
     return 0;		// (what a row could not read is in its own error slot)
 }
 
+// ---- long recordings, cut in time (mifsk_timesplit.hip), from host memory or from files ----
+//
+// A few long recordings instead of many short ones: the samples cross the bus as they are (PCM16
+// as 16-bit) into ONE device buffer with a common stride, in pieces of kChunkBytes -- by DMA from
+// where they are when every row is page-locked, through the context's two pinned staging buffers
+// otherwise, piece k+1 being staged while piece k is copied -- and the buffer is decoded by
+// mifsk_demod_long_batch_s16 (PCM16: the rows are gathered straight from it, no float copy of the
+// recording) or mifsk_demod_long_batch (floats, --Xrxnoise added in place first).
+
+// one recording: `n` samples at `mem`, or in the file `path` from byte `off`
+struct LongRow {
+    const void	*mem;
+    const char	*path;
+    uint64_t	off;
+    uint64_t	n;
+    int		*err;		// file rows: where a read error is reported
+};
+
+struct Piece {
+    size_t	row;
+    uint64_t	first, count;	// samples of the row
+};
+
+struct DevMem {
+    void *p = nullptr;
+    ~DevMem() { if ( p ) (void)hipFree(p); }
+    int get( size_t bytes )
+    {
+	if ( hipMalloc(&p, bytes ? bytes : 16) != hipSuccess ) {
+	    p = nullptr;
+	    return -ENOMEM;
+	}
+	// (the fill is done before another stream copies into the buffer)
+	return hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess
+	     ? 0 : -EIO;
+    }
+};
+
+int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<LongRow> &rows, bool s16,
+	float rxnoise, const mifsk_time_split *params, const mifsk_demod_io &ho,
+	mifsk_time_split_stats *tstats, mifsk_host_stats *hstats )
+{
+    const size_t M = rows.size();
+    if ( M == 0 )
+	return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    HostWork *w = nullptr;
+    int rc = host_work_get(ctx, &w);
+    if ( rc )
+	return rc;
+    std::lock_guard<std::mutex> g(w->lock);
+    const double t_begin = now_s();
+    const size_t esz = s16 ? 2 : 4, align = s16 ? 8 : 4;
+    uint64_t longest = 0;
+    std::vector<uint64_t> lens(M);
+    for ( size_t m = 0; m < M; m++ ) {
+	lens[m] = rows[m].n;
+	longest = std::max(longest, rows[m].n);
+    }
+    const size_t stride = std::max<size_t>(align, ( (size_t)longest + align - 1 ) & ~( align - 1 ));
+
+    // pieces of one row each, kChunkBytes at most
+    const uint64_t per = kChunkBytes / esz;
+    std::vector<Piece> pieces;
+    for ( size_t m = 0; m < M; m++ )
+	for ( uint64_t first = 0; first < rows[m].n; first += per )
+	    pieces.push_back(Piece{ m, first, std::min<uint64_t>(per, rows[m].n - first) });
+    const bool single = pieces.size() <= 1;
+    if ( ( rc = host_work_init(w, !single) ) )
+	return rc;
+    const hipStream_t st_in = single ? nullptr : w->s_in, st_comp = single ? nullptr : w->s_comp;
+
+    // page-locked source rows are copied from where they are
+    bool direct = !pieces.empty();
+    for ( size_t m = 0; m < M && direct; m++ )
+	if ( rows[m].n )
+	    direct = rows[m].mem && is_pinned(rows[m].mem)
+		  && is_pinned((const char *)rows[m].mem + (size_t)rows[m].n * esz - 1);
+    if ( !direct && ( rc = pin_reserve(w, (size_t)std::min<uint64_t>(per, longest) * esz, 0) ) )
+	return rc;
+
+    DevMem d_in;
+    if ( ( rc = d_in.get(M * stride * esz) ) )
+	return rc;
+    const unsigned nthreads = staging_threads();
+    const char *fault_tag = experiment_env("MIFSK_TEST_FAULT_READ");	// (as in run_job)
+    if ( fault_tag && !*fault_tag )
+	fault_tag = nullptr;
+    constexpr size_t kBlock = 1u << 20;		// of a piece per staging task
+    double t_stage = 0.0;
+    uint64_t bytes_in = 0, bytes_out = 0;
+    for ( size_t k = 0; k < pieces.size(); k++ ) {
+	const Piece &pc = pieces[k];
+	const LongRow &row = rows[pc.row];
+	const int sl = (int)( k & 1 );
+	const size_t bytes = (size_t)pc.count * esz;
+	char *dst = (char *)d_in.p + ( pc.row * stride + (size_t)pc.first ) * esz;
+	const void *src;
+	if ( direct ) {
+	    src = (const char *)row.mem + (size_t)pc.first * esz;
+	} else {
+	    if ( k >= 2 )
+		HIP_OK(hipEventSynchronize(w->ev_in[sl]));	// piece k - 2 has left this buffer
+	    const double t0 = now_s();
+	    char *pin = (char *)w->pin[sl];
+	    std::atomic<int> err(0);
+	    int fd = -1;
+	    if ( !row.mem ) {
+		fd = open(row.path, O_RDONLY | O_CLOEXEC);
+		if ( fd < 0 )
+		    err = -errno;
+		else if ( fault_tag && std::strstr(row.path, fault_tag) )
+		    err = -EIO;
+	    }
+	    if ( !err )
+		parallel_for(( bytes + kBlock - 1 ) / kBlock, nthreads, [&]( size_t b ) {
+		    const size_t o = b * kBlock, len = std::min(kBlock, bytes - o);
+		    if ( row.mem ) {
+			std::memcpy(pin + o, (const char *)row.mem + (size_t)pc.first * esz + o, len);
+		    } else if ( const int e = read_fully(fd, pin + o, len, row.off + pc.first * esz + o) ) {
+			err = e;
+		    }
+		});
+	    if ( fd >= 0 )
+		close(fd);
+	    if ( err ) {
+		// this file's error: reported through its own row, the batch goes on with zeros
+		std::memset(pin, 0, bytes);
+		if ( row.err )
+		    *row.err = err;
+	    }
+	    t_stage += now_s() - t0;
+	    src = pin;
+	}
+	HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st_in));
+	if ( !direct && !single )
+	    HIP_OK(hipEventRecord(w->ev_in[sl], st_in));
+	bytes_in += bytes;
+    }
+    HIP_OK(hipStreamSynchronize(st_in));
+
+    // --Xrxnoise on floats, in place (PCM16: added as the rows are gathered)
+    if ( !s16 && rxnoise != 0.0f )
+	for ( size_t m = 0; m < M; m++ )
+	    for ( uint64_t o = 0; o < rows[m].n; o += 1ull << 30 ) {
+		const uint32_t cnt = (uint32_t)std::min<uint64_t>(1ull << 30, rows[m].n - o);
+		if ( ( rc = mifsk_ingest_rxnoise_f32(ctx, (float *)d_in.p + m * stride + o, stride, nullptr, cnt,
+						      1, rxnoise, st_comp) ) )
+		    return rc;
+	    }
+
+    // the outputs, as mifsk_demod_batch_host lays them out
+    const size_t fc = ho.frames_cap, ec = ho.episodes_cap;
+    const bool band = ho.d_carrier_band && cfg->auto_carrier_threshold > 0.0f;
+    DevMem o_bytes, o_bits, o_frames, o_eps, o_nbytes, o_nframes, o_neps, o_status, o_band;
+    if ( ( ho.d_bytes && ( rc = o_bytes.get(M * fc) ) )
+	    || ( ho.d_bits && ( rc = o_bits.get(M * fc * sizeof(uint64_t)) ) )
+	    || ( ho.d_frames && ( rc = o_frames.get(M * fc * sizeof(mifsk_frame)) ) )
+	    || ( ho.d_episodes && ( rc = o_eps.get(M * ec * sizeof(mifsk_episode)) ) )
+	    || ( ho.d_nbytes && ( rc = o_nbytes.get(M * sizeof(uint32_t)) ) )
+	    || ( ho.d_nframes && ( rc = o_nframes.get(M * sizeof(uint32_t)) ) )
+	    || ( ho.d_nepisodes && ( rc = o_neps.get(M * sizeof(uint32_t)) ) )
+	    || ( ho.d_status && ( rc = o_status.get(M * sizeof(uint32_t)) ) )
+	    || ( band && ( rc = o_band.get(M * sizeof(int32_t)) ) ) )
+	return rc;
+    mifsk_demod_io io;
+    std::memset(&io, 0, sizeof(io));
+    io.nstreams = (int)M;
+    io.d_bytes = (uint8_t *)o_bytes.p;		io.d_nbytes = (uint32_t *)o_nbytes.p;
+    io.d_bits = (uint64_t *)o_bits.p;		io.d_frames = (mifsk_frame *)o_frames.p;
+    io.d_nframes = (uint32_t *)o_nframes.p;	io.frames_cap = fc;
+    io.d_episodes = (mifsk_episode *)o_eps.p;	io.d_nepisodes = (uint32_t *)o_neps.p;
+    io.episodes_cap = ec;
+    io.d_status = (uint32_t *)o_status.p;	io.d_carrier_band = (int32_t *)o_band.p;
+    rc = s16 ? mifsk_demod_long_batch_s16(ctx, cfg, (const int16_t *)d_in.p, stride, lens.data(), (int)M, rxnoise,
+					  params, &io, tstats, st_comp)
+	     : mifsk_demod_long_batch(ctx, cfg, (const float *)d_in.p, stride, lens.data(), (int)M, params, &io,
+				      tstats, st_comp);
+    if ( rc )
+	return rc;
+    // (the call has waited for its stream)
+#define MIFSK_OUT(HOSTP, DEVP, PER_ROW)									\
+    if ( (HOSTP) && (DEVP).p ) {									\
+	const size_t nb = M * (PER_ROW) * sizeof(*(HOSTP));						\
+	HIP_OK(hipMemcpy((HOSTP), (DEVP).p, nb, hipMemcpyDeviceToHost));				\
+	bytes_out += nb;										\
+    }
+    MIFSK_OUT(ho.d_bytes, o_bytes, fc)
+    MIFSK_OUT(ho.d_bits, o_bits, fc)
+    MIFSK_OUT(ho.d_frames, o_frames, fc)
+    MIFSK_OUT(ho.d_episodes, o_eps, ec)
+    MIFSK_OUT(ho.d_nbytes, o_nbytes, 1)
+    MIFSK_OUT(ho.d_nframes, o_nframes, 1)
+    MIFSK_OUT(ho.d_nepisodes, o_neps, 1)
+    MIFSK_OUT(ho.d_status, o_status, 1)
+    MIFSK_OUT(ho.d_carrier_band, o_band, 1)
+#undef MIFSK_OUT
+    if ( hstats ) {
+	hstats->seconds_total += now_s() - t_begin;
+	hstats->seconds_staging += t_stage;
+	hstats->bytes_h2d += bytes_in;
+	hstats->bytes_d2h += bytes_out;
+	hstats->chunks += (uint32_t)pieces.size();
+	hstats->streams += (uint32_t)M;
+	hstats->source_pinned = direct ? 1u : 0u;
+    }
+    return 0;
+}
+
 } // namespace
 } // namespace mifsk
 
 using mifsk::Job;
+using mifsk::LongRow;
 using mifsk::Row;
 
 // ---------------------------------------------------------------------------
@@ -601,6 +811,35 @@ extern "C" int mifsk_demod_batch_host( mifsk_ctx *ctx, const mifsk_rx_config *cf
     return mifsk_demod_batch_host_ex(ctx, cfg, hio, 0.0f, nullptr);
 }
 
+extern "C" int mifsk_demod_long_batch_host( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const void *const *rows, const uint64_t *nsamples, int nstreams, unsigned src_flags, float rxnoise,
+	const mifsk_time_split *params, const mifsk_demod_io *io_out, mifsk_time_split_stats *stats,
+	mifsk_host_stats *hstats )
+{
+    if ( !ctx || !cfg || !io_out || !nsamples || !rows || nstreams <= 0 )
+	return -EINVAL;
+    if ( src_flags & ~MIFSK_IO_HOST_S16 )
+	return -EINVAL;
+    for ( int m = 0; m < nstreams; m++ )
+	if ( nsamples[m] && !rows[m] )
+	    return -EINVAL;
+    if ( const int rc = mifsk::time_split_check_params(cfg, params) )
+	return rc;
+    if ( hstats )
+	std::memset(hstats, 0, sizeof(*hstats));
+    try {		// (no exception crosses the C ABI)
+	std::vector<LongRow> lr((size_t)nstreams);
+	for ( int m = 0; m < nstreams; m++ )
+	    lr[(size_t)m] = LongRow{ rows[m], nullptr, 0, nsamples[m], nullptr };
+	return mifsk::run_long(ctx, cfg, lr, ( src_flags & MIFSK_IO_HOST_S16 ) != 0, rxnoise, params, *io_out,
+			       stats, hstats);
+    } catch ( const std::bad_alloc & ) {
+	return -ENOMEM;
+    } catch ( ... ) {
+	return -EIO;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // a list of files -> one batch (what `minimodem --rx --file` does for one)
 // ---------------------------------------------------------------------------
@@ -621,6 +860,9 @@ struct mifsk_files {
     std::vector<Group>			groups;
     std::vector<std::string>		paths;
     mifsk_host_stats			stats;
+    // mifsk_demod_files_long: file i's plan and verification figures
+    bool				time_split = false;
+    std::vector<mifsk_time_split_stats>	tsplit;
 };
 
 extern "C" size_t mifsk_max_episodes( const mifsk_rx_config *cfg, size_t nsamples )
@@ -634,10 +876,16 @@ extern "C" size_t mifsk_max_episodes( const mifsk_rx_config *cfg, size_t nsample
     return nsamples / ( adv + 21 * ( tm ? tm : 1 ) ) + 2;
 }
 
+// `long_params`: the groups are decoded through the time split (mifsk_demod_files_long) with these
+// parameters, each (sample rate, sample format) group as one batch of long recordings
 static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
-	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files *F )
+	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files *F,
+	const mifsk_time_split *long_params )
 {
     std::memset(&F->stats, 0, sizeof(F->stats));
+    F->time_split = long_params != nullptr;
+    if ( long_params )
+	F->tsplit.assign((size_t)nfiles, mifsk_time_split_stats{});
     F->files.resize((size_t)nfiles);
     F->paths.resize((size_t)nfiles);
     const double t0 = mifsk::now_s();
@@ -700,8 +948,9 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
     // back) are sized by its LONGEST file, so one hour-long recording among ten thousand short
     // ones would cost every one of them the long one's capacity.  Each (rate, format) group is
     // therefore cut, by length, into classes whose longest file is at most twice the shortest:
-    // a class is one batch with its own capacities, at most 2 x what its files need.
-    {
+    // a class is one batch with its own capacities, at most 2 x what its files need.  (Not for
+    // the time split: a few long recordings, and one plan cuts the whole group.)
+    if ( !long_params ) {
 	std::vector<mifsk_files::Group> classes;
 	for ( mifsk_files::Group &g : F->groups ) {
 	    std::stable_sort(g.members.begin(), g.members.end(), [&]( int a, int b ) {
@@ -737,6 +986,30 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	g.eps.resize(n * g.ecap);
 	g.nbytes.assign(n, 0); g.nframes.assign(n, 0); g.neps.assign(n, 0); g.status.assign(n, 0);
 	g.band.assign(n, -1);
+	if ( long_params ) {
+	    mifsk_demod_io ho;
+	    std::memset(&ho, 0, sizeof(ho));
+	    ho.d_bytes = g.bytes.data();	ho.d_nbytes = g.nbytes.data();
+	    ho.d_bits = g.bits.data();
+	    ho.d_frames = g.frames.empty() ? nullptr : g.frames.data();
+	    ho.d_nframes = g.nframes.data();	ho.frames_cap = g.fcap;
+	    ho.d_episodes = g.eps.data();	ho.d_nepisodes = g.neps.data();	ho.episodes_cap = g.ecap;
+	    ho.d_status = g.status.data();
+	    ho.d_carrier_band = g.band.data();
+	    std::vector<LongRow> lr(n);
+	    for ( size_t k = 0; k < n; k++ ) {
+		mifsk_file_result &fr = F->files[(size_t)g.members[k]];
+		lr[k] = LongRow{ nullptr, F->paths[(size_t)g.members[k]].c_str(), fr.info.data_offset,
+				 fr.info.nframes, &fr.error };
+	    }
+	    std::vector<mifsk_time_split_stats> ts(n);
+	    const int rc = mifsk::run_long(ctx, &g.cfg, lr, !F->files[(size_t)g.members[0]].info.is_float, rxnoise,
+					   long_params, ho, ts.data(), &F->stats);
+	    if ( rc && !rc_all )
+		rc_all = rc;
+	    for ( size_t k = 0; k < n; k++ )
+		F->tsplit[(size_t)g.members[k]] = ts[k];
+	}
 	Job job;
 	job.cfg = &g.cfg;
 	job.s16 = !F->files[(size_t)g.members[0]].info.is_float;
@@ -762,7 +1035,7 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	    r.n = (uint32_t)fr.info.nframes;
 	    r.err = &fr.error;
 	}
-	const int rc = mifsk::run_job(ctx, job);
+	const int rc = long_params ? 0 : mifsk::run_job(ctx, job);
 	if ( rc && !rc_all )
 	    rc_all = rc;
 	for ( size_t k = 0; k < n; k++ ) {
@@ -787,8 +1060,8 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
     return rc_all;
 }
 
-extern "C" int mifsk_demod_files( mifsk_ctx *ctx, const mifsk_modem_args *args,
-	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files **out )
+static int demod_files_entry( mifsk_ctx *ctx, const mifsk_modem_args *args, const char *const *paths,
+	int nfiles, float rxnoise, unsigned flags, const mifsk_time_split *long_params, mifsk_files **out )
 {
     if ( !ctx || !args || !out || nfiles < 0 || ( nfiles && !paths ) )
 	return -EINVAL;
@@ -798,7 +1071,7 @@ extern "C" int mifsk_demod_files( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	return -ENOMEM;
     int rc;
     try {		// (no exception crosses the C ABI: the vectors above can throw)
-	rc = demod_files_impl(ctx, args, paths, nfiles, rxnoise, flags, F);
+	rc = demod_files_impl(ctx, args, paths, nfiles, rxnoise, flags, F, long_params);
     } catch ( const std::bad_alloc & ) {
 	delete F;
 	return -ENOMEM;
@@ -808,6 +1081,36 @@ extern "C" int mifsk_demod_files( mifsk_ctx *ctx, const mifsk_modem_args *args,
     }
     *out = F;
     return rc;
+}
+
+extern "C" int mifsk_demod_files( mifsk_ctx *ctx, const mifsk_modem_args *args,
+	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files **out )
+{
+    return demod_files_entry(ctx, args, paths, nfiles, rxnoise, flags, nullptr, out);
+}
+
+extern "C" int mifsk_demod_files_long( mifsk_ctx *ctx, const mifsk_modem_args *args,
+	const char *const *paths, int nfiles, float rxnoise, unsigned flags, const mifsk_time_split *params,
+	mifsk_files **out )
+{
+    if ( !ctx || !args || !out || nfiles < 0 || ( nfiles && !paths ) )
+	return -EINVAL;
+    *out = nullptr;
+    mifsk_time_split p;
+    std::memset(&p, 0, sizeof(p));
+    if ( params )
+	p = *params;
+    p.flags |= flags & ( MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WAVE | MIFSK_IO_ENGINE_WORKGROUP );
+    if ( p.flags & MIFSK_IO_RING_EXACT )
+	return -ENOTSUP;		// (before any file is opened)
+    return demod_files_entry(ctx, args, paths, nfiles, rxnoise, flags, &p, out);
+}
+
+extern "C" const mifsk_time_split_stats *mifsk_files_time_split( const mifsk_files *f, int i )
+{
+    if ( !f || !f->time_split || i < 0 || (size_t)i >= f->files.size() || f->files[(size_t)i].error )
+	return nullptr;
+    return &f->tsplit[(size_t)i];
 }
 
 extern "C" int mifsk_files_count( const mifsk_files *f ) { return f ? (int)f->files.size() : 0; }

@@ -76,14 +76,7 @@ void offset_f32_kernel( float *__restrict__ x, size_t stride,
 
 } // namespace mifsk
 
-// (0 - 0.5f) * (factor * 2), in float as at simpleaudio-sndfile.c:67-69
-static float rxnoise_term( float factor )
-{
-    if ( factor == 0.0f )
-	return 0.0f;
-    const float f = factor * 2;
-    return ( 0 - 0.5f ) * f;
-}
+using mifsk::rxnoise_term;	// (mifsk_device.h)
 
 extern "C" int mifsk_ingest_s16( mifsk_ctx *ctx, const int16_t *d_pcm, size_t pcm_stride,
 	float *d_samples, size_t stream_stride, const uint32_t *d_nsamples, uint32_t nsamples,

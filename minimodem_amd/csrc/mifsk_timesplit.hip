@@ -85,47 +85,110 @@ struct StreamRef {
     uint32_t	rowbase, K;	// its chunks are rows rowbase .. rowbase + K - 1
 };
 
-// dst[i] = x[s0 + i] for i < 4 * nvec, 0.0 behind the stream's end n (x + s0 is 16-byte aligned)
-__device__ inline void copy_row( const float *__restrict__ x, uint64_t n, uint64_t s0,
-	float *__restrict__ dst, uint64_t nvec )
+// One PCM16 sample as a float: the expression of ingest_s16_kernel (mifsk_ingest.hip), so that a
+// row gathered from PCM16 is bit for bit the row gathered from mifsk_ingest_s16's floats.
+__device__ inline float s16_sample( int v, float dc )
+{
+    return (float)v / 32768.0f + dc;
+}
+
+__device__ inline float4 s16_pair( int lo, int hi, float dc )
+{
+    return make_float4(s16_sample((int16_t)( lo & 0xFFFF ), dc), s16_sample((int16_t)( (uint32_t)lo >> 16 ), dc),
+		       s16_sample((int16_t)( hi & 0xFFFF ), dc), s16_sample((int16_t)( (uint32_t)hi >> 16 ), dc));
+}
+
+// dst[i] = x[s0 + i] for i < 4 * nvec, 0.0 behind the stream's end n.  A float source is copied as
+// it is (x + s0 is 16-byte aligned; dc is not used).  A PCM16 source (T = int16_t) is converted on
+// the way, x[i] / 32768 + dc: 2 B read and 4 B written per sample, the recording never exists as
+// floats.  Its row start is s0 = k * L with L a multiple of 4, not of 8, so x + s0 is 8-byte
+// aligned and only sometimes 16-byte aligned: 16-byte loads of 8 samples per thread where it is,
+// 8-byte loads of 4 samples where it is not; 16-byte stores always.  The vector that straddles the
+// stream's end is done per element.
+template <typename T>
+__device__ inline void copy_row( const T *__restrict__ x, uint64_t n, uint64_t s0,
+	float *__restrict__ dst, uint64_t nvec, float dc )
 {
     float4 *d4 = reinterpret_cast<float4 *>(dst);
-    for ( uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvec;
-	  v += (uint64_t)gridDim.x * blockDim.x ) {
-	const uint64_t i = s0 + v * 4u;
-	float4 f;
-	if ( i + 4u <= n ) {
-	    f = reinterpret_cast<const float4 *>(x + s0)[v];
-	} else {
-	    f.x = i < n ? x[i] : 0.0f;
-	    f.y = i + 1u < n ? x[i + 1u] : 0.0f;
-	    f.z = i + 2u < n ? x[i + 2u] : 0.0f;
-	    f.w = i + 3u < n ? x[i + 3u] : 0.0f;
+    const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t nt = (uint64_t)gridDim.x * blockDim.x;
+    if constexpr ( sizeof(T) == sizeof(float) ) {
+	for ( uint64_t v = t0; v < nvec; v += nt ) {
+	    const uint64_t i = s0 + v * 4u;
+	    float4 f;
+	    if ( i + 4u <= n ) {
+		f = reinterpret_cast<const float4 *>(x + s0)[v];
+	    } else {
+		f.x = i < n ? x[i] : 0.0f;
+		f.y = i + 1u < n ? x[i + 1u] : 0.0f;
+		f.z = i + 2u < n ? x[i + 2u] : 0.0f;
+		f.w = i + 3u < n ? x[i + 3u] : 0.0f;
+	    }
+	    d4[v] = f;
 	}
-	d4[v] = f;
+    } else if ( ( s0 & 7u ) == 0u ) {
+	for ( uint64_t p = t0; p * 2u < nvec; p += nt ) {		// 8 samples: float4s 2p and 2p + 1
+	    const uint64_t i = s0 + p * 8u;
+	    float4 f, g;
+	    if ( i + 8u <= n ) {
+		const int4 raw = reinterpret_cast<const int4 *>(x + s0)[p];
+		f = s16_pair(raw.x, raw.y, dc);
+		g = s16_pair(raw.z, raw.w, dc);
+	    } else {
+		float e[8];
+#pragma unroll
+		for ( uint32_t j = 0; j < 8u; j++ )
+		    e[j] = i + j < n ? s16_sample(x[i + j], dc) : 0.0f;
+		f = make_float4(e[0], e[1], e[2], e[3]);
+		g = make_float4(e[4], e[5], e[6], e[7]);
+	    }
+	    d4[p * 2u] = f;
+	    if ( p * 2u + 1u < nvec )
+		d4[p * 2u + 1u] = g;
+	}
+    } else {
+	for ( uint64_t v = t0; v < nvec; v += nt ) {
+	    const uint64_t i = s0 + v * 4u;
+	    float4 f;
+	    if ( i + 4u <= n ) {
+		const int2 raw = reinterpret_cast<const int2 *>(x + s0)[v];
+		f = s16_pair(raw.x, raw.y, dc);
+	    } else {
+		f.x = i < n ? s16_sample(x[i], dc) : 0.0f;
+		f.y = i + 1u < n ? s16_sample(x[i + 1u], dc) : 0.0f;
+		f.z = i + 2u < n ? s16_sample(x[i + 2u], dc) : 0.0f;
+		f.w = i + 3u < n ? s16_sample(x[i + 3u], dc) : 0.0f;
+	    }
+	    d4[v] = f;
+	}
     }
 }
 
 // rows[r][i] = x_m[k * L + i] for row r = (m, k) of the row table (the loop kernels take no row
 // longer than the batch stride, so the overlapping chunks are laid out apart)
-__global__ void ts_gather_rows( const float *__restrict__ x, uint64_t xstride,
+template <typename T>
+__global__ void ts_gather_rows( const T *__restrict__ x, uint64_t xstride,
 	const StreamRef *__restrict__ streams, const RowRef *__restrict__ rowref,
-	float *__restrict__ rows, uint64_t stride, uint64_t L, int nrows )
+	float *__restrict__ rows, uint64_t stride, uint64_t L, int nrows, float dc )
 {
     for ( int r = blockIdx.y; r < nrows; r += gridDim.y ) {
 	const RowRef ref = rowref[r];
 	copy_row(x + (uint64_t)ref.m * xstride, streams[ref.m].n, (uint64_t)ref.k * L,
-		 rows + (uint64_t)r * stride, stride / 4u);
+		 rows + (uint64_t)r * stride, stride / 4u, dc);
     }
 }
 
 // the streams' tails do not sit at one stride in the rows: tails[m][i] = x_m[tail_off_m + i]
-__global__ void ts_gather_tails( const float *__restrict__ x, uint64_t xstride,
-	const StreamRef *__restrict__ streams, float *__restrict__ tails, uint64_t stride, int nstreams )
+// (tail_off is a multiple of 4, or the stream's length where the tail is dropped: nothing of the
+// source is read then)
+template <typename T>
+__global__ void ts_gather_tails( const T *__restrict__ x, uint64_t xstride,
+	const StreamRef *__restrict__ streams, float *__restrict__ tails, uint64_t stride, int nstreams,
+	float dc )
 {
     for ( int m = blockIdx.y; m < nstreams; m += gridDim.y )
 	copy_row(x + (uint64_t)m * xstride, streams[m].n, streams[m].tail_off,
-		 tails + (uint64_t)m * stride, stride / 4u);
+		 tails + (uint64_t)m * stride, stride / 4u, dc);
 }
 
 // pass A's starting states: zero, but a stream's row 0 needs no guess (a finished state: the
@@ -442,13 +505,14 @@ uint64_t gcd64( uint64_t a, uint64_t b )
 const unsigned kKnownFlags = MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE
 			   | MIFSK_TIME_SPLIT_REJECT_ALL;
 
-// the planner, for a batch of recordings cut by one W and one L (every row has the same stride,
-// a pass is one launch); chunks_hint: the chunk count that fills the chip (0: params->chunks or
-// the default of a host-only call)
-int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mifsk_time_split *params,
-	uint32_t chunks_hint, mifsk_time_split_stats *out )
+} // namespace
+
+// What the planner refuses whatever the lengths are (host only; the entry points that take host
+// memory or files ask this before they touch the device or a file): the configuration, the flags,
+// a warmup below 2 * samplebuf_size, a chunk off the lattice.
+int mifsk::time_split_check_params( const mifsk_rx_config *cfg, const mifsk_time_split *params )
 {
-    if ( !cfg || !out || !n || nstreams <= 0 || mifsk_check_cfg(cfg) )
+    if ( mifsk_check_cfg(cfg) )
 	return -EINVAL;
     mifsk_time_split p;
     std::memset(&p, 0, sizeof(p));
@@ -464,13 +528,34 @@ int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mif
 	return -EINVAL;
     const uint64_t half = cfg->samplebuf_size / 2u;
     const uint64_t lattice = half / gcd64(half, 4) * 4;		// lcm(samplebuf_size / 2, 4)
-    const uint64_t wmin = 2ull * cfg->samplebuf_size;
-    if ( p.warmup && p.warmup < wmin )
+    if ( p.warmup && p.warmup < 2ull * cfg->samplebuf_size )
 	return -EINVAL;
     if ( p.chunk && ( p.chunk % lattice || p.chunk >= 0x7FFFFFF0ull ) )
 	return -EINVAL;
     if ( p.warmup >= 0x7FFFFFF0ull )
-	return -EINVAL;		// (rows are uint32 lengths; keeps the arithmetic below exact)
+	return -EINVAL;		// (rows are uint32 lengths; keeps the planner's arithmetic exact)
+    return 0;
+}
+
+namespace {
+
+// the planner, for a batch of recordings cut by one W and one L (every row has the same stride,
+// a pass is one launch); chunks_hint: the chunk count that fills the chip (0: params->chunks or
+// the default of a host-only call)
+int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mifsk_time_split *params,
+	uint32_t chunks_hint, mifsk_time_split_stats *out )
+{
+    if ( !cfg || !out || !n || nstreams <= 0 )
+	return -EINVAL;
+    if ( const int rc = mifsk::time_split_check_params(cfg, params) )
+	return rc;
+    mifsk_time_split p;
+    std::memset(&p, 0, sizeof(p));
+    if ( params )
+	p = *params;
+    const uint64_t half = cfg->samplebuf_size / 2u;
+    const uint64_t lattice = half / gcd64(half, 4) * 4;		// lcm(samplebuf_size / 2, 4)
+    const uint64_t wmin = 2ull * cfg->samplebuf_size;
     uint64_t W = p.warmup;
     if ( !W ) {
 	W = (uint64_t)( kDefaultWarmupSeconds * cfg->sample_rate );
@@ -541,18 +626,52 @@ unsigned blocks_for( uint64_t stride )
     return (unsigned)std::min<uint64_t>(64, std::max<uint64_t>(1, ( stride / 4 + 255 ) / 256));
 }
 
-// mifsk_demod_long_batch (which has checked the rows against xstride); mifsk_demod_long is its
-// nstreams == 1 case, whose one row holds just nsamples[0] floats (xstride is not used then)
-int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, size_t xstride,
+// Where the recordings are: float rows (`dc` is not used: --Xrxnoise is applied to floats in
+// place, before the call) or PCM16 rows, converted as they are gathered.
+struct Src {
+    const void	*p;		// device, 16-byte aligned
+    size_t	stride;		// elements between the streams' rows
+    bool	s16;		// int16_t elements (else float)
+    float	dc;		// s16: the --Xrxnoise term, added to every sample
+};
+
+void gather_rows( const Src &src, dim3 grid, hipStream_t st, const StreamRef *streams, const RowRef *rowref,
+	float *rows, uint64_t stride, uint64_t L, int nrows )
+{
+    if ( src.s16 )
+	hipLaunchKernelGGL(ts_gather_rows<int16_t>, grid, dim3(256), 0, st, (const int16_t *)src.p,
+			   (uint64_t)src.stride, streams, rowref, rows, stride, L, nrows, src.dc);
+    else
+	hipLaunchKernelGGL(ts_gather_rows<float>, grid, dim3(256), 0, st, (const float *)src.p,
+			   (uint64_t)src.stride, streams, rowref, rows, stride, L, nrows, 0.0f);
+}
+
+void gather_tails( const Src &src, dim3 grid, hipStream_t st, const StreamRef *streams, float *tails,
+	uint64_t stride, int nstreams )
+{
+    if ( src.s16 )
+	hipLaunchKernelGGL(ts_gather_tails<int16_t>, grid, dim3(256), 0, st, (const int16_t *)src.p,
+			   (uint64_t)src.stride, streams, tails, stride, nstreams, src.dc);
+    else
+	hipLaunchKernelGGL(ts_gather_tails<float>, grid, dim3(256), 0, st, (const float *)src.p,
+			   (uint64_t)src.stride, streams, tails, stride, nstreams, 0.0f);
+}
+
+// The entry points (which have checked the rows against the source's stride); mifsk_demod_long is
+// the nstreams == 1 case of a float source, whose one row holds just nsamples[0] floats (the
+// stride is not used then)
+int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoise,
 	const uint64_t *nsamples, int nstreams, const mifsk_time_split *params,
 	const mifsk_demod_io *io_out, mifsk_time_split_stats *stats, void *stream )
 {
+    const size_t xstride = src.stride;
     if ( !ctx || !io_out || !nsamples || nstreams <= 0 || mifsk_check_cfg(cfg)
-	    || ( (uintptr_t)d_samples & 15u ) )
+	    || ( (uintptr_t)src.p & 15u ) )
 	return -EINVAL;
     const int M = nstreams;
+    int rc;
     for ( int m = 0; m < M; m++ )
-	if ( nsamples[m] && !d_samples )
+	if ( nsamples[m] && !src.p )
 	    return -EINVAL;
     if ( ( io_out->d_bytes || io_out->d_bits || io_out->d_frames ) && io_out->frames_cap == 0 )
 	return -EINVAL;
@@ -562,6 +681,8 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
     const unsigned engine = flags & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE );
     if ( ( flags & MIFSK_IO_ENGINE_WORKGROUP ) && cfg->auto_carrier_threshold > 0.0f )
 	return -EINVAL;
+    if ( ( rc = mifsk::time_split_check_params(cfg, params) ) )
+	return rc;		// (before any HIP call)
     HIP_OK(hipSetDevice(ctx->device));
     hipStream_t st = (hipStream_t)stream;
 
@@ -573,7 +694,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
 	    hint = li.compute_units * kChunksPerCu;
     }
     std::vector<mifsk_time_split_stats> ps(M);
-    int rc = plan(cfg, nsamples, M, params, hint, ps.data());
+    rc = plan(cfg, nsamples, M, params, hint, ps.data());
     if ( rc )
 	return rc;
     const uint64_t L = ps[0].chunk, W = ps[0].warmup;
@@ -589,11 +710,32 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
 	// no stream is cut: the existing call over the batch (a lone row over a padded copy unless
 	// it is whole float4s already)
 	DevBuf pad, dn;
+	const float *d_samples = (const float *)src.p;
 	mifsk_demod_io io = *io_out;
-	io.d_samples = d_samples;
 	io.d_nsamples = nullptr;
 	io.nstreams = M;
-	if ( M == 1 ) {
+	if ( src.s16 ) {
+	    // PCM16: the floats of the uncut batch through mifsk_ingest_s16, as the host pipeline
+	    // makes them (every row defined up to its stride)
+	    const uint64_t stride = M == 1 ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : xstride;
+	    std::vector<uint32_t> hn(M);
+	    for ( int m = 0; m < M; m++ )
+		hn[m] = (uint32_t)nsamples[m];
+	    if ( ( rc = alloc(pad, (size_t)M * stride * sizeof(float), st) )
+		    || ( rc = alloc(dn, M * sizeof(uint32_t), st) ) )
+		return rc;
+	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
+	    if ( !src.p )
+		HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
+	    else if ( ( rc = mifsk_ingest_s16(ctx, (const int16_t *)src.p, xstride,
+					      (float *)pad.p, stride, (const uint32_t *)dn.p, 0, M, rxnoise, stream) ) )
+		return rc;
+	    d_samples = (const float *)pad.p;
+	    io.stream_stride = stride;
+	    io.d_nsamples = M == 1 ? nullptr : (const uint32_t *)dn.p;
+	    io.nsamples = (uint32_t)( M == 1 ? nsamples[0] : std::min<uint64_t>(stride, 0xFFFFFFFFull) );
+	} else if ( M == 1 ) {
 	    const uint64_t stride = ( nsamples[0] + 3u ) & ~3ull;
 	    if ( stride != nsamples[0] ) {
 		if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
@@ -604,10 +746,9 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
 		    return rc;
 		HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
 		HIP_OK(hipStreamSynchronize(st));
-		hipLaunchKernelGGL(ts_gather_rows, dim3(64, 1), dim3(256), 0, st, d_samples, (uint64_t)0,
-				   (const StreamRef *)dn.p, (const RowRef *)( (char *)dn.p + sizeof(StreamRef) ),
-				   (float *)pad.p, stride, (uint64_t)0, 1);
-		io.d_samples = (const float *)pad.p;
+		gather_rows(src, dim3(64, 1), st, (const StreamRef *)dn.p,
+			    (const RowRef *)( (char *)dn.p + sizeof(StreamRef) ), (float *)pad.p, stride, 0, 1);
+		d_samples = (const float *)pad.p;
 	    }
 	    io.stream_stride = stride ? stride : 4;
 	    io.nsamples = (uint32_t)nsamples[0];
@@ -623,6 +764,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
 	    io.d_nsamples = (const uint32_t *)dn.p;
 	    io.nsamples = (uint32_t)std::min<uint64_t>(xstride, 0xFFFFFFFFull);
 	}
+	io.d_samples = d_samples;
 	io.d_counters = nullptr;
 	io.flags = engine;
 	io.reserved = 0;
@@ -689,8 +831,8 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
     HIP_OK(hipMemcpyAsync(streams.p, hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(rowref.p, hrow.data(), nrows * sizeof(RowRef), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(ns.p, hns.data(), nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(ts_gather_rows, dim3(blocks_for(rstride), (unsigned)std::min(R, 65535)), dim3(256),
-		       0, st, d_samples, (uint64_t)xstride, dstreams, drowref, drows, rstride, L, R);
+    gather_rows(src, dim3(blocks_for(rstride), (unsigned)std::min(R, 65535)), st, dstreams, drowref, drows,
+		rstride, L, R);
 
     // pass A: rows 1 .. R-1, W samples each, from a zeroed state (a stream's row 0 is skipped)
     const unsigned tb = 256, gb = (unsigned)( ( nrows + tb - 1 ) / tb );
@@ -832,8 +974,8 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples, siz
 	if ( ( rc = alloc(tails, (size_t)M * tstride * sizeof(float), st) ) )
 	    return rc;
 	HIP_OK(hipMemcpyAsync((uint32_t *)ns.p + R, hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(ts_gather_tails, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), dim3(256),
-			   0, st, d_samples, (uint64_t)xstride, dstreams, (float *)tails.p, tstride, M);
+	gather_tails(src, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), st, dstreams, (float *)tails.p,
+		     tstride, M);
 	mifsk_demod_io t = b;
 	t.d_samples = (const float *)tails.p;
 	t.stream_stride = tstride;
@@ -902,7 +1044,8 @@ extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
 	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,
 	mifsk_time_split_stats *stats, void *stream )
 {
-    return run(ctx, cfg, d_samples, 0, &nsamples, 1, params, io_out, stats, stream);
+    const Src src = { d_samples, 0, false, 0.0f };
+    return run(ctx, cfg, src, 0.0f, &nsamples, 1, params, io_out, stats, stream);
 }
 
 extern "C" int mifsk_demod_long_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
@@ -915,5 +1058,24 @@ extern "C" int mifsk_demod_long_batch( mifsk_ctx *ctx, const mifsk_rx_config *cf
     for ( int m = 0; m < nstreams; m++ )
 	if ( nsamples[m] > stream_stride )
 	    return -EINVAL;
-    return run(ctx, cfg, d_samples, stream_stride, nsamples, nstreams, params, io_out, stats, stream);
+    const Src src = { d_samples, stream_stride, false, 0.0f };
+    return run(ctx, cfg, src, 0.0f, nsamples, nstreams, params, io_out, stats, stream);
+}
+
+extern "C" int mifsk_demod_long_batch_s16( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const int16_t *d_pcm, size_t pcm_stride, const uint64_t *nsamples, int nstreams, float rxnoise,
+	const mifsk_time_split *params, const mifsk_demod_io *io_out, mifsk_time_split_stats *stats,
+	void *stream )
+{
+    if ( !ctx || !cfg || !io_out || !nsamples )
+	return -EINVAL;
+    if ( nstreams <= 0 )
+	return -EINVAL;
+    if ( ( (uintptr_t)d_pcm & 15u ) || pcm_stride % 8u )
+	return -EINVAL;
+    for ( int m = 0; m < nstreams; m++ )
+	if ( nsamples[m] > pcm_stride )
+	    return -EINVAL;
+    const Src src = { d_pcm, pcm_stride, true, mifsk::rxnoise_term(rxnoise) };
+    return run(ctx, cfg, src, rxnoise, nsamples, nstreams, params, io_out, stats, stream);
 }

@@ -1,0 +1,370 @@
+"""The time split fed from where long recordings are: PCM16 in device memory (the chunks' rows are
+gathered straight from it: mifsk_demod_long_batch_s16), host memory (mifsk_demod_long_batch_host)
+and WAV files (mifsk_demod_files_long).  The yardstick everywhere is ONE demod_batch call over the
+floats that ingest_s16(pcm, rxnoise=...) makes of the same PCM16 (for a float source: the floats
+themselves), compared per stream and bit for bit with test_gpu_time_split_batch._same: frames, bits,
+bytes, episodes, counts, status and the --auto-carrier band.  No tolerance anywhere."""
+import os
+import struct
+import time
+import zlib
+
+import numpy as np
+import pytest
+
+import _golden as G
+import _oracle as O
+from test_gpu_time_split import WANT, _bursty, _lattice, _recording
+from test_gpu_time_split_batch import _one_call, _same
+
+pytestmark = pytest.mark.gpu
+
+GOLDENS = ["t01_1200", "t03_rtty", "t80_same", "t50_auto_300", "t40_rxnoise_0p05_rxone"]
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    import minimodem_amd as M
+    ctx = M.Context()
+    yield M, torch, ctx
+    ctx.close()
+
+
+def _quantise(x):
+    return np.clip(np.rint(x * 32768.0), -32768, 32767).astype(np.int16)
+
+
+def _upload_pcm(torch, pcm):
+    lens = [len(x) for x in pcm]
+    host = np.zeros((len(pcm), max(8, (max(lens) + 7) & ~7)), np.int16)
+    for i, x in enumerate(pcm):
+        host[i, :len(x)] = x
+    return torch.from_numpy(host).cuda(), lens
+
+
+_pcm = {}
+_wants = {}
+
+
+def _streams(M, torch, name):
+    """Five unequal PCM16 streams of one golden, as test_gpu_time_split_batch._unequal builds them
+    (1, 2, 3 and 5 copies and one shorter than W), trimmed so that their lengths leave at least
+    three different non-zero remainders mod 8 -- made once per golden and left unchanged."""
+    if name not in _pcm:
+        g = G.load(name)
+        cfg = M.rx_config(**g["cfg_kwargs"])
+        W = 2 * cfg.samplebuf_size
+        s = g["stored"]          # (without the --Xrxnoise term: the device adds it)
+        base = s.astype(np.float32) / np.float32(32768.0) if s.dtype == np.int16 else s.astype(np.float32)
+        seed = zlib.crc32(name.encode())
+        streams = [_recording(base, np.random.default_rng(seed + c), copies=c, sample_rate=cfg.sample_rate)
+                   for c in (1, 2, 3, 5)]
+        streams.insert(2, streams[0][:W - 7].copy())
+        for i, r in ((0, 1), (1, 4), (3, 6), (4, 3)):
+            n = len(streams[i])
+            streams[i] = streams[i][:n - ((n - r) % 8)]
+        pcm = [_quantise(x) for x in streams]
+        d, lens = _upload_pcm(torch, pcm)
+        assert len({n % 8 for n in lens} - {0}) >= 3, lens
+        lat = _lattice(cfg)
+        L = lat * max(1, (max(lens) // 12) // lat)
+        _pcm[name] = (cfg, pcm, d, lens, L, W, g["rxnoise"])
+    return _pcm[name]
+
+
+def _yardstick(M, torch, ctx, name, engine):
+    """one demod_batch call over ingest_s16's floats of the same PCM16"""
+    key = (name, engine)
+    if key not in _wants:
+        cfg, pcm, d, lens, L, W, rxnoise = _streams(M, torch, name)
+        dn = torch.tensor(lens, dtype=torch.int32, device="cuda")
+        floats = M.ingest_s16(ctx, d, nsamples=dn, rxnoise=rxnoise)
+        _wants[key] = _one_call(M, torch, ctx, cfg, floats, lens, engine=engine)
+    return _wants[key]
+
+
+def _split(M, ctx, cfg, d, lens, **kw):
+    out = M.demod_long_batch(ctx, cfg, d, nsamples=lens, want=WANT, **kw)
+    stats = out.pop("stats")
+    return M.results_to_host(out), stats
+
+
+# ---- B: PCM16 on the device -------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", GOLDENS)
+@pytest.mark.parametrize("engine", [None, "wave", "workgroup"])
+def test_pcm16_streams_cut_small_equal_one_call_over_ingested_floats(gpu, name, engine):
+    M, torch, ctx = gpu
+    if engine == "workgroup" and G.load(name)["cfg_kwargs"].get("auto_carrier_threshold", 0) > 0:
+        pytest.skip("the workgroup engine has no in-loop --auto-carrier")
+    cfg, pcm, d, lens, L, W, rxnoise = _streams(M, torch, name)
+    assert (rxnoise == 0.05) == (name == "t40_rxnoise_0p05_rxone")
+    want = _yardstick(M, torch, ctx, name, engine)
+    got, st = _split(M, ctx, cfg, d, lens, chunk=L, warmup=W, engine=engine, rxnoise=rxnoise)
+    assert [s["nsamples"] for s in st] == lens
+    assert all(s["chunk"] == L and s["warmup"] == W for s in st)
+    assert [s["nchunks"] for s in st] == [(n - W) // L + 1 if n > W else 1 for n in lens]
+    assert sum(s["nchunks"] >= 2 for s in st) >= 3 and st[2]["nchunks"] == 1, st
+    for i in range(len(lens)):
+        _same(got, i, want, i, cfg, (name, engine, i, st[i]))
+    assert cfg.rx_one or sum(int(v) for v in got["nframes"]) > 0
+    if engine is None:
+        # the single recording: a 1-D int16 tensor through demod_long
+        i = 3
+        out = M.demod_long(ctx, cfg, d[i, :lens[i]], want=WANT, chunk=L, warmup=W, rxnoise=rxnoise)
+        st1 = out.pop("stats")
+        assert st1["nchunks"] == st[i]["nchunks"] >= 2
+        _same(M.results_to_host(out), 0, want, i, cfg, (name, "demod_long", st1))
+
+
+def test_float_tensor_with_rxnoise_is_ingest_rxnoise_on_a_copy(gpu):
+    M, torch, ctx = gpu
+    name = "t40_rxnoise_0p05_rxone"
+    cfg, pcm, d, lens, L, W, rxnoise = _streams(M, torch, name)
+    dn = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    floats = M.ingest_s16(ctx, d, nsamples=dn)
+    keep = floats.clone()
+    want = _one_call(M, torch, ctx, cfg, M.ingest_rxnoise(ctx, floats.clone(), rxnoise, nsamples=dn), lens)
+    got, st = _split(M, ctx, cfg, floats, lens, chunk=L, warmup=W, rxnoise=rxnoise)
+    assert torch.equal(floats, keep)                 # the caller's tensor stays untouched
+    for i in range(len(lens)):
+        _same(got, i, want, i, cfg, (name, i, st[i]))
+    # (x / 32768 + dc in one pass and in two are the same float operations)
+    for i in range(len(lens)):
+        _same(got, i, _yardstick(M, torch, ctx, name, None), i, cfg, (name, "two passes", i))
+
+
+# ---- C: row starts on both alignments, re-runs, the uncut path ----------------------------------
+
+@pytest.mark.parametrize("mult,reject_all", [(1, True), (2, False), (3, False)])
+def test_rtty_row_starts_8_and_16_byte_aligned(gpu, mult, reject_all):
+    M, torch, ctx = gpu
+    cfg, pcm, d, lens, _L, W, rxnoise = _streams(M, torch, "t03_rtty")
+    lat = _lattice(cfg)
+    assert lat == 38052 and lat % 8 == 4
+    L = mult * lat
+    assert L % 8 == (4 if mult % 2 else 0)
+    want = _yardstick(M, torch, ctx, "t03_rtty", None)
+    got, st = _split(M, ctx, cfg, d, lens, chunk=L, warmup=W, reject_all=reject_all)
+    assert sum(s["nchunks"] >= 2 for s in st) >= 3, st
+    for i in range(len(lens)):
+        _same(got, i, want, i, cfg, (mult, reject_all, i, st[i]))
+        if reject_all:
+            assert st[i]["accepted"] == 0 and st[i]["rerun"] >= st[i]["nchunks"] - 1, st[i]
+
+
+@pytest.mark.parametrize("name", ["t01_1200", "t40_rxnoise_0p05_rxone"])
+def test_pcm16_streams_all_shorter_than_warmup_take_the_uncut_path(gpu, name):
+    """W above every length: the plan leaves every stream whole, and the batch goes through
+    mifsk_ingest_s16 into a temporary buffer and one mifsk_demod_batch call"""
+    M, torch, ctx = gpu
+    cfg, pcm, d, lens, L, _W, rxnoise = _streams(M, torch, name)
+    want = _yardstick(M, torch, ctx, name, None)
+    got, st = _split(M, ctx, cfg, d, lens, chunk=L, warmup=max(lens) + 1, rxnoise=rxnoise)
+    assert [s["nchunks"] for s in st] == [1] * len(lens) and [s["chunk"] for s in st] == lens
+    for i in range(len(lens)):
+        _same(got, i, want, i, cfg, (name, i))
+    assert sum(int(v) for v in got["nframes"]) > 0
+    # a lone uncut recording whose length is no multiple of 8, and an empty stream beside a short one
+    assert lens[0] % 8
+    out = M.demod_long(ctx, cfg, d[0, :lens[0]], want=WANT, warmup=lens[0] + 1, rxnoise=rxnoise)
+    assert out.pop("stats")["nchunks"] == 1
+    _same(M.results_to_host(out), 0, want, 0, cfg, (name, "lone"))
+    d2, lens2 = _upload_pcm(torch, [pcm[0][:0], pcm[2]])
+    got2, st2 = _split(M, ctx, cfg, d2, lens2, rxnoise=rxnoise)
+    assert [s["nchunks"] for s in st2] == [1, 1] and int(got2["nframes"][0]) == 0
+    _same(got2, 1, want, 2, cfg, (name, "beside an empty stream"))
+
+
+# ---- D: host memory ---------------------------------------------------------------------------
+
+_device_results = {}
+
+
+@pytest.mark.parametrize("name", ["t01_1200", "t03_rtty"])
+@pytest.mark.parametrize("source", ["s16_pageable", "s16_pinned", "f32_pageable", "f32_rxnoise"])
+def test_host_memory_equals_the_device_source(gpu, name, source):
+    M, torch, ctx = gpu
+    cfg, pcm, d, lens, L, W, _rx = _streams(M, torch, name)
+    want = _yardstick(M, torch, ctx, name, None)
+    if name not in _device_results:
+        _device_results[name] = _split(M, ctx, cfg, d, lens, chunk=L, warmup=W)
+    dev, dev_st = _device_results[name]
+    pinned, rxnoise = [], 0.0
+    if source == "s16_pageable":
+        arrays = [x.copy() for x in pcm]
+    elif source == "s16_pinned":
+        for x in pcm:
+            a = M.host_alloc(max(1, len(x)), np.int16)
+            a[:len(x)] = x
+            pinned.append(a)
+        arrays = [a[:len(x)] for a, x in zip(pinned, pcm)]
+    else:
+        arrays = [x.astype(np.float32) / np.float32(32768.0) for x in pcm]
+        if source == "f32_rxnoise":
+            rxnoise = 0.05
+            dn = torch.tensor(lens, dtype=torch.int32, device="cuda")
+            f = torch.zeros((len(lens), (max(lens) + 3) & ~3), dtype=torch.float32, device="cuda")
+            for i, a in enumerate(arrays):
+                f[i, :len(a)] = torch.from_numpy(a).cuda()
+            want = _one_call(M, torch, ctx, cfg, M.ingest_rxnoise(ctx, f, rxnoise, nsamples=dn), lens)
+    try:
+        got = M.demod_long_host(ctx, cfg, arrays, chunk=L, warmup=W, want=WANT, rxnoise=rxnoise, stats=True)
+    finally:
+        for a in pinned:
+            M.host_free(a)
+    st, hs = got["stats"], got["host_stats"]
+    assert [s["nchunks"] for s in st] == [s["nchunks"] for s in dev_st]
+    for i in range(len(lens)):
+        _same(got, i, want, i, cfg, (name, source, i, st[i]))
+        if not rxnoise:
+            _same(got, i, dev, i, cfg, (name, source, "device source", i))
+    esz = 2 if source.startswith("s16") else 4
+    assert hs["source_pinned"] == (1 if source == "s16_pinned" else 0), hs
+    assert sum(lens) * esz <= hs["bytes_h2d"] <= sum(lens) * esz + 16 * len(lens), hs
+    assert hs["streams"] == len(lens) and hs["chunks"] == len(lens), hs      # (every stream is one piece)
+    assert hs["bytes_d2h"] > 0
+    assert (hs["seconds_staging"] > 0) == (source != "s16_pinned"), hs
+
+
+# ---- E: files ---------------------------------------------------------------------------------
+
+def _write_stereo(path, rate):
+    data = np.zeros(2 * 4800, "<i2").tobytes()
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVEfmt ")
+        f.write(struct.pack("<IHHIIHH", 16, 1, 2, rate, rate * 4, 4, 16))
+        f.write(b"data" + struct.pack("<I", len(data)) + data)
+
+
+def test_files_time_split_equals_demod_files(gpu, tmp_path):
+    M, torch, ctx = gpu
+    g = G.load("t01_1200")
+    cfg = M.rx_config("1200")
+    assert cfg.sample_rate == 48000
+    rng = np.random.default_rng(77)
+    burst = _bursty(M, cfg, 70, rng, snr_db=20)
+    rec = _recording(g["samples"], rng, copies=3, sample_rate=48000)
+    paths = []
+    for i, seconds in enumerate((45.3, 70.0, 58.1, 52.7)):
+        x = np.roll(burst, int(rng.integers(0, len(burst))))[:int(seconds * 48000) - i]
+        x[1000:1000 + len(rec)] = rec[:len(x) - 1000]      # a stretch of the golden recording in each
+        p = str(tmp_path / ("long%d.wav" % i))
+        if i == 3:
+            O.write_wav(p, x, 48000, False)
+        else:
+            O.write_wav(p, _quantise(x * np.float32(0.8)), 48000, True)
+        paths.append(p)
+    stereo, bad = str(tmp_path / "stereo.wav"), str(tmp_path / "bad.wav")
+    _write_stereo(stereo, 48000)
+    with open(bad, "wb") as f:
+        f.write(rng.integers(0, 256, 5000, dtype=np.uint8).tobytes())
+    paths[2:2] = [stereo, bad]
+    want, _ = M.demod_files(ctx, paths, "1200")
+    W = 2 * cfg.samplebuf_size
+    for ts in (True, dict(chunk=_lattice(cfg) * 24, warmup=W), dict(chunk=_lattice(cfg) * 24, warmup=W, reject_all=True)):
+        got, hs = M.demod_files(ctx, paths, "1200", time_split=ts)
+        assert [d["error"] for d in got] == [d["error"] for d in want] == [0, 0, -95, -22, 0, 0]
+        for a, b in zip(got, want):
+            if a["error"]:
+                assert "time_split" not in a
+                continue
+            assert len(b["bytes"]) > 100 and a["bytes"] == b["bytes"], a["path"]
+            assert a["bits"].tobytes() == b["bits"].tobytes(), a["path"]
+            assert a["episodes"].tobytes() == b["episodes"].tobytes(), a["path"]
+            assert a["status"] == b["status"] and a["carrier_band"] == b["carrier_band"]
+            t = a["time_split"]
+            assert t["nsamples"] == a["info"]["nframes"] > 4 * 10 * 48000
+            assert t["nchunks"] >= 2, t
+            if ts is True:
+                assert t["warmup"] == 10 * 48000            # the library's own plan cuts them
+            else:
+                assert t["chunk"] == _lattice(cfg) * 24 and t["warmup"] == W
+                assert t["nchunks"] == (t["nsamples"] - W) // t["chunk"] + 1
+                if ts.get("reject_all"):
+                    assert t["accepted"] == 0 and t["rerun"] >= t["nchunks"] - 1
+        assert hs["streams"] == 4 and hs["bytes_h2d"] == sum(os.path.getsize(p) - 44 for p in paths
+                                                             if "long" in p)
+    assert all("time_split" not in d for d in want)
+
+
+# ---- F: speed ---------------------------------------------------------------------------------
+
+def test_speed_ten_minutes_of_pcm16_from_pinned_host_memory(gpu):
+    """Ten minutes of bursty Bell-202 at 20 dB as PCM16 in host_alloc memory, the library's choices.
+    (a) what a user did by hand before: a copy from the pinned buffer to the device with torch,
+    ingest_s16 into a float copy, demod_long, results to the host; (b) demod_long_host; (c)
+    demod_long on the int16 tensor already on the device against ingest_s16 + demod_long there.
+    Wall time in one process after a preheat, the smallest of three repeats each.  What is claimed
+    is parity of time (with one copy of the recording less in device memory): (b) <= 1.15 x (a)
+    and (c, PCM16) <= 1.15 x (c, float); the margin is about twice the run-to-run spread DESIGN.md
+    section 9 records for the one-hour test (164 to 174 ms)."""
+    M, torch, ctx = gpu
+    cfg = M.rx_config("1200")
+    x = _bursty(M, cfg, 600, np.random.default_rng(2024), snr_db=20)
+    n = len(x)
+    pin = M.host_alloc(n, np.int16)
+    pin[:] = _quantise(x * np.float32(0.5))
+    want = ("bytes", "episodes")
+
+    def sync():
+        torch.cuda.synchronize()
+
+    def by_hand():
+        d = torch.from_numpy(pin).cuda()
+        f = M.ingest_s16(ctx, d[None, :])
+        out = M.demod_long(ctx, cfg, f[0, :n], want=want)
+        st = out.pop("stats")
+        return M.results_to_host(out), st
+
+    def host_entry():
+        out = M.demod_long_host(ctx, cfg, [pin], want=want)
+        return out, out["stats"][0]
+
+    d_pcm = torch.from_numpy(pin).cuda()
+
+    def dev_float():
+        f = M.ingest_s16(ctx, d_pcm[None, :])
+        out = M.demod_long(ctx, cfg, f[0, :n], want=want)
+        sync()
+        return out, out["stats"]
+
+    def dev_pcm():
+        out = M.demod_long(ctx, cfg, d_pcm, want=want)
+        sync()
+        return out, out["stats"]
+
+    try:
+        paths = (("a_by_hand", by_hand), ("b_host_entry", host_entry), ("c_device_float", dev_float),
+                 ("c_device_pcm16", dev_pcm))
+        res, times = {}, {k: [] for k, _ in paths}
+        for k, fn in paths:                      # preheat: tables, allocator, staging
+            fn()
+        sync()
+        for _ in range(3):
+            for k, fn in paths:
+                sync()
+                t0 = time.perf_counter()
+                res[k] = fn()
+                times[k].append(1e3 * (time.perf_counter() - t0))
+    finally:
+        M.host_free(pin)
+    st = res["b_host_entry"][1]
+    best = {k: min(v) for k, v in times.items()}
+    msg = ("ms (three repeats) " + "; ".join("%s %s" % (k, " ".join("%.1f" % t for t in v)) for k, v in times.items())
+           + "; K=%d L=%d W=%d accepted %d of %d, rerun %d, rounds %d" % (
+               st["nchunks"], st["chunk"], st["warmup"], st["accepted"], st["nchunks"] - 1, st["rerun"], st["rounds"])
+           + "; b/a %.3f, c pcm16/float %.3f" % (best["b_host_entry"] / best["a_by_hand"],
+                                                 best["c_device_pcm16"] / best["c_device_float"]))
+    print(msg)
+    ref = res["a_by_hand"][0]
+    nb, ne = int(ref["nbytes"][0]), int(ref["nepisodes"][0])
+    assert nb > 10000 and st["nchunks"] >= 2, msg
+    for k in ("b_host_entry", "c_device_float", "c_device_pcm16"):
+        out = res[k][0] if k == "b_host_entry" else M.results_to_host({q: v for q, v in res[k][0].items() if q != "stats"})
+        assert int(out["nbytes"][0]) == nb and out["bytes"][0, :nb].tobytes() == ref["bytes"][0, :nb].tobytes(), (k, msg)
+        assert int(out["nepisodes"][0]) == ne and out["episodes"][0, :ne].tobytes() == ref["episodes"][0, :ne].tobytes(), (k, msg)
+        assert {q: v for q, v in res[k][1].items()} == res["a_by_hand"][1], (k, msg)
+    assert best["b_host_entry"] <= 1.15 * best["a_by_hand"], msg
+    assert best["c_device_pcm16"] <= 1.15 * best["c_device_float"], msg
