@@ -141,6 +141,100 @@ def max_frames(cfg, nsamples):
     return int(_lib.load().mifsk_max_frames(C.byref(cfg), int(nsamples)))
 
 
+def max_episodes(cfg, nsamples):
+    return int(_lib.load().mifsk_max_episodes(C.byref(cfg), int(nsamples)))
+
+
+def _default_caps(cfg, longest, frames_cap, episodes_cap):
+    """The capacities a caller left open, from the longest stream."""
+    return (max_frames(cfg, longest) if frames_cap is None else frames_cap,
+            max_episodes(cfg, longest) if episodes_cap is None else episodes_cap)
+
+
+def _io_flags(ring_exact=False, engine=None):
+    return (_lib.IO_RING_EXACT if ring_exact else 0) | \
+        (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
+        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+
+
+def _struct_dict(st, drop_reserved=False):
+    return {k: getattr(st, k) for k, _ in st._fields_ if not (drop_reserved and k == "reserved")}
+
+
+def _torch_outputs(torch, cfg, dev, nstreams, want, frames_cap, episodes_cap, stream, counters=False):
+    """demod_batch's output tensors; "counters" only where the caller can get them (demod_batch)."""
+    # (allocated and zero-filled ON the launch stream: a fill queued on torch's current
+    # stream would race a kernel launched on another one)
+    with _on(torch, stream):
+        out = {}
+        out["nframes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+        out["status"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+        if "bytes" in want:
+            out["bytes"] = torch.zeros((nstreams, frames_cap), dtype=torch.uint8, device=dev)
+            out["nbytes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+        if "bits" in want:
+            out["bits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=dev)
+        if "frames" in want:
+            out["frames"] = torch.zeros((nstreams, frames_cap, FRAME_DTYPE.itemsize),
+                                        dtype=torch.uint8, device=dev)
+        if counters and "counters" in want:
+            out["counters"] = torch.zeros((nstreams, NCOUNTERS), dtype=torch.int64, device=dev)
+        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
+            out["carrier_band"] = torch.full((nstreams,), -1, dtype=torch.int32, device=dev)
+        if "episodes" in want:
+            out["episodes"] = torch.zeros((nstreams, episodes_cap, EPISODE_DTYPE.itemsize),
+                                          dtype=torch.uint8, device=dev)
+            out["nepisodes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
+    if stream is not None:
+        # The tensors belong to `stream` in torch's caching allocator.  Whoever reads them on
+        # another stream must order that read behind `stream` (an event, wait_stream); marking
+        # them used on the current stream as well keeps the allocator from handing a dropped
+        # tensor's block back out -- and its zero-fill onto `stream` -- under such a reader.
+        cur = torch.cuda.current_stream()
+        for t in out.values():
+            t.record_stream(cur)
+    return out
+
+
+def _numpy_outputs(nstreams, want, frames_cap, episodes_cap):
+    """The host entry points' result arrays."""
+    res = {"nframes": np.zeros(nstreams, np.uint32), "status": np.zeros(nstreams, np.uint32),
+           "carrier_band": np.full(nstreams, -1, np.int32)}
+    if "bytes" in want:
+        res["bytes"] = np.zeros((nstreams, frames_cap), np.uint8)
+        res["nbytes"] = np.zeros(nstreams, np.uint32)
+    if "bits" in want:
+        res["bits"] = np.zeros((nstreams, frames_cap), np.uint64)
+    if "frames" in want:
+        res["frames"] = np.zeros((nstreams, frames_cap), FRAME_DTYPE)
+    if "episodes" in want:
+        res["episodes"] = np.zeros((nstreams, episodes_cap), EPISODE_DTYPE)
+        res["nepisodes"] = np.zeros(nstreams, np.uint32)
+    return res
+
+
+def _result_io(out, nstreams, frames_cap, episodes_cap, address):
+    """A DemodIO whose result pointers are the arrays of `out` (a dict as the two functions above
+    make it; what it lacks stays NULL); address: how one of its values turns into an address."""
+    io = _lib.DemodIO()
+    io.nstreams = nstreams
+    io.frames_cap = frames_cap
+    io.episodes_cap = episodes_cap
+    for name in ("bytes", "nbytes", "bits", "frames", "nframes", "episodes", "nepisodes", "status", "counters",
+                 "carrier_band"):
+        if out.get(name) is not None:
+            setattr(io, "d_" + name, address(out[name]))
+    return io
+
+
+def _tensor_address(t):
+    return t.data_ptr()
+
+
+def _array_address(a):
+    return a.ctypes.data
+
+
 def demod_batch(ctx, cfg, samples, nsamples=None, want=("bytes", "episodes"),
                 frames_cap=None, episodes_cap=8, stream=None, out=None, ring_exact=False,
                 engine=None, force_engine=False):
@@ -169,66 +263,17 @@ def demod_batch(ctx, cfg, samples, nsamples=None, want=("bytes", "episodes"),
     n_uniform = int(width)
     if frames_cap is None:
         frames_cap = max_frames(cfg, n_uniform)
-    dev = samples.device
     if out is None:
-        # (allocated and zero-filled ON the launch stream: a fill queued on torch's current
-        # stream would race a kernel launched on another one)
-        with _on(torch, stream):
-            out = {}
-            out["nframes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-            out["status"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-            if "bytes" in want:
-                out["bytes"] = torch.zeros((nstreams, frames_cap), dtype=torch.uint8, device=dev)
-                out["nbytes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-            if "bits" in want:
-                out["bits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=dev)
-            if "frames" in want:
-                out["frames"] = torch.zeros((nstreams, frames_cap, FRAME_DTYPE.itemsize),
-                                            dtype=torch.uint8, device=dev)
-            if "counters" in want:
-                out["counters"] = torch.zeros((nstreams, NCOUNTERS), dtype=torch.int64, device=dev)
-            if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
-                out["carrier_band"] = torch.full((nstreams,), -1, dtype=torch.int32, device=dev)
-            if "episodes" in want:
-                out["episodes"] = torch.zeros((nstreams, episodes_cap, EPISODE_DTYPE.itemsize),
-                                              dtype=torch.uint8, device=dev)
-                out["nepisodes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-        if stream is not None:
-            # The tensors belong to `stream` in torch's caching allocator.  Whoever reads them on
-            # another stream must order that read behind `stream` (an event, wait_stream); marking
-            # them used on the current stream as well keeps the allocator from handing a dropped
-            # tensor's block back out -- and its zero-fill onto `stream` -- under such a reader.
-            cur = torch.cuda.current_stream()
-            for t in out.values():
-                t.record_stream(cur)
-
-    def ptr(name):
-        t = out.get(name)
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    io = _lib.DemodIO()
+        out = _torch_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream,
+                             counters=True)
+    io = _result_io(out, nstreams, frames_cap, episodes_cap, _tensor_address)
     io.d_samples = samples.data_ptr()
     io.stream_stride = stride
     io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
     io.nsamples = n_uniform
-    io.nstreams = nstreams
-    io.d_bytes = ptr("bytes")
-    io.d_nbytes = ptr("nbytes")
-    io.d_bits = ptr("bits")
-    io.d_frames = ptr("frames")
-    io.d_nframes = ptr("nframes")
-    io.frames_cap = frames_cap
-    io.d_episodes = ptr("episodes")
-    io.d_nepisodes = ptr("nepisodes")
-    io.episodes_cap = episodes_cap
-    io.d_status = ptr("status")
-    io.d_counters = ptr("counters")
-    io.d_carrier_band = ptr("carrier_band")
     if engine is None and force_engine:
         engine = "wave"
-    io.flags = (_lib.IO_RING_EXACT if ring_exact else 0) | \
-        (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+    io.flags = _io_flags(ring_exact, engine)
     rc = lib.mifsk_demod_batch(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_demod_batch failed: %d" % rc)
@@ -241,14 +286,12 @@ def demod_plan(ctx, cfg, nstreams, ring_exact=False, engine=None, nsamples=None)
     for rows of `nsamples` samples; None: long ones -- the groups x time chunks a large batch
     is cut into)."""
     info = _lib.LaunchInfo()
-    flags = (_lib.IO_RING_EXACT if ring_exact else 0) | \
-        (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+    flags = _io_flags(ring_exact, engine)
     rc = _lib.load().mifsk_demod_plan_ex(ctx.handle, C.byref(cfg), int(nstreams),
                                          0xFFFFFFFF if nsamples is None else int(nsamples), flags, C.byref(info))
     if rc != 0:
         raise RuntimeError("mifsk_demod_plan failed: %d" % rc)
-    d = {k: getattr(info, k) for k, _ in info._fields_}
+    d = _struct_dict(info)
     d["kernel"] = d["kernel"].decode()
     d["engine"] = "workgroup" if d["engine"] == _lib.IO_ENGINE_WORKGROUP else "wave"
     return d
@@ -259,9 +302,7 @@ def _time_split_params(chunk, warmup, chunks, engine, reject_all):
     p.chunk = int(chunk or 0)
     p.warmup = int(warmup or 0)
     p.chunks = int(chunks or 0)
-    p.flags = (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0) | \
-        (_lib.TIME_SPLIT_REJECT_ALL if reject_all else 0)
+    p.flags = _io_flags(False, engine) | (_lib.TIME_SPLIT_REJECT_ALL if reject_all else 0)
     return p
 
 
@@ -273,7 +314,7 @@ def time_split_plan(cfg, nsamples, chunk=None, warmup=None, chunks=None, engine=
                                                C.byref(st))
     if rc != 0:
         raise ValueError("mifsk_time_split_plan_get failed: %d" % rc)
-    return {k: int(getattr(st, k)) for k, _ in st._fields_}
+    return _struct_dict(st)
 
 
 def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("bytes", "episodes"),
@@ -290,35 +331,17 @@ def demod_long(ctx, cfg, samples, chunk=None, warmup=None, chunks=None, want=("b
     untouched).  Returns demod_batch's dict for a batch of one stream plus "stats" (the planner's
     figures and what verification accepted); synchronous."""
     torch = _torch()
-    lib = _lib.load()
-    if samples.dtype == torch.int16:
-        assert samples.is_cuda and samples.dim() == 1
-        assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
-        n = int(samples.shape[0])
-        out = _demod_long_s16(torch, lib, ctx, cfg, samples, (n + 7) & ~7, [n], 1, rxnoise, want, frames_cap,
-                              episodes_cap, _time_split_params(chunk, warmup, chunks, engine, reject_all), stream)
-        out["stats"] = out["stats"][0]
-        return out
-    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 1
+    assert samples.is_cuda and samples.dtype in (torch.int16, torch.float32) and samples.dim() == 1
     assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
-    if rxnoise:
+    n = int(samples.shape[0])
+    if samples.dtype == torch.float32 and rxnoise:
         with _on(torch, stream):
             samples = samples.clone()
         ingest_rxnoise(ctx, samples[None, :], rxnoise, stream=stream)
-    n = int(samples.shape[0])
-    if frames_cap is None:
-        frames_cap = max_frames(cfg, n)
-    if episodes_cap is None:
-        episodes_cap = max_episodes(cfg, n)
-    out = _long_outputs(torch, cfg, samples.device, 1, want, frames_cap, episodes_cap, stream)
-    io = _long_io(out, 1, frames_cap, episodes_cap)
-    st = _lib.TimeSplitStats()
-    rc = lib.mifsk_demod_long(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), n,
-                              C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
-                              C.byref(io), C.byref(st), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_demod_long failed: %d" % rc)
-    out["stats"] = {k: int(getattr(st, k)) for k, _ in st._fields_}
+    # (a lone row's stride means nothing to the library; PCM16: the length rounded up to 8)
+    out = _demod_long(torch, ctx, cfg, samples, (n + 7) & ~7, [n], rxnoise, want, frames_cap, episodes_cap,
+                      _time_split_params(chunk, warmup, chunks, engine, reject_all), stream, lone=True)
+    out["stats"] = out["stats"][0]
     return out
 
 
@@ -332,7 +355,7 @@ def time_split_plan_batch(cfg, nsamples_list, chunk=None, warmup=None, chunks=No
         C.byref(cfg), arr, len(lens), C.byref(_time_split_params(chunk, warmup, chunks, engine, False)), st)
     if rc != 0:
         raise ValueError("mifsk_time_split_plan_batch_get failed: %d" % rc)
-    return [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(len(lens))]
+    return [_struct_dict(st[m]) for m in range(len(lens))]
 
 
 def demod_long_batch(ctx, cfg, samples, nsamples=None, chunk=None, warmup=None, chunks=None,
@@ -349,107 +372,51 @@ def demod_long_batch(ctx, cfg, samples, nsamples=None, chunk=None, warmup=None, 
     (per stream: the plan and what verification accepted); the default caps come from the longest
     stream.  Synchronous."""
     torch = _torch()
-    lib = _lib.load()
-    if samples.dtype == torch.int16:
-        assert samples.is_cuda and samples.dim() == 2
-        assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
-        nstreams, width = (int(v) for v in samples.shape)
-        assert nstreams >= 1 and width % 8 == 0, "PCM16 rows must be whole 16-byte vectors"
-        lens = [width] * nstreams if nsamples is None else [int(n) for n in nsamples]
-        assert len(lens) == nstreams and all(0 <= n <= width for n in lens)
-        return _demod_long_s16(torch, lib, ctx, cfg, samples, width, lens, nstreams, rxnoise, want, frames_cap,
-                               episodes_cap, _time_split_params(chunk, warmup, chunks, engine, reject_all), stream)
-    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2
+    s16 = samples.dtype == torch.int16
+    assert samples.is_cuda and (s16 or samples.dtype == torch.float32) and samples.dim() == 2
     assert samples.is_contiguous() and samples.data_ptr() % 16 == 0
     nstreams, width = (int(v) for v in samples.shape)
-    assert nstreams >= 1 and width % 4 == 0, "rows must be whole float4s"
+    if s16:
+        assert nstreams >= 1 and width % 8 == 0, "PCM16 rows must be whole 16-byte vectors"
+    else:
+        assert nstreams >= 1 and width % 4 == 0, "rows must be whole float4s"
     lens = [width] * nstreams if nsamples is None else [int(n) for n in nsamples]
     assert len(lens) == nstreams and all(0 <= n <= width for n in lens)
-    if rxnoise:
+    if not s16 and rxnoise:
         with _on(torch, stream):
             samples = samples.clone()
             dn = torch.tensor(lens, dtype=torch.int32, device=samples.device)
         ingest_rxnoise(ctx, samples, rxnoise, nsamples=dn, stream=stream)
-    longest = max(lens)
-    if frames_cap is None:
-        frames_cap = max_frames(cfg, longest)
-    if episodes_cap is None:
-        episodes_cap = max_episodes(cfg, longest)
-    out = _long_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream)
-    io = _long_io(out, nstreams, frames_cap, episodes_cap)
+    return _demod_long(torch, ctx, cfg, samples, width, lens, rxnoise, want, frames_cap, episodes_cap,
+                       _time_split_params(chunk, warmup, chunks, engine, reject_all), stream)
+
+
+def _demod_long(torch, ctx, cfg, samples, stride, lens, rxnoise, want, frames_cap, episodes_cap, params, stream,
+                lone=False):
+    """demod_long / demod_long_batch once the samples are checked: outputs, the C call, stats.  An
+    int16 tensor goes to mifsk_demod_long_batch_s16, which adds rxnoise as it gathers the rows
+    (floats: the callers have added it to a copy); a 1-D float tensor (`lone`) to mifsk_demod_long,
+    whose one row need not be whole float4s; a float batch to mifsk_demod_long_batch."""
+    lib = _lib.load()
+    nstreams = len(lens)
+    frames_cap, episodes_cap = _default_caps(cfg, max(lens), frames_cap, episodes_cap)
+    out = _torch_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream)
+    io = _result_io(out, nstreams, frames_cap, episodes_cap, _tensor_address)
     arr = (C.c_uint64 * nstreams)(*lens)
     st = (_lib.TimeSplitStats * nstreams)()
-    rc = lib.mifsk_demod_long_batch(ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()), width, arr,
-                                    nstreams, C.byref(_time_split_params(chunk, warmup, chunks, engine, reject_all)),
-                                    C.byref(io), st, _stream_ptr(torch, stream))
+    head = (ctx.handle, C.byref(cfg), C.c_void_p(samples.data_ptr()))
+    tail = (C.byref(params), C.byref(io), st, _stream_ptr(torch, stream))
+    if samples.dtype == torch.int16:
+        name, args = "mifsk_demod_long_batch_s16", head + (stride, arr, nstreams, C.c_float(rxnoise)) + tail
+    elif lone:
+        name, args = "mifsk_demod_long", head + (lens[0],) + tail
+    else:
+        name, args = "mifsk_demod_long_batch", head + (stride, arr, nstreams) + tail
+    rc = getattr(lib, name)(*args)
     if rc != 0:
-        raise RuntimeError("mifsk_demod_long_batch failed: %d" % rc)
-    out["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
+        raise RuntimeError("%s failed: %d" % (name, rc))
+    out["stats"] = [_struct_dict(st[m]) for m in range(nstreams)]
     return out
-
-
-def _demod_long_s16(torch, lib, ctx, cfg, pcm, stride, lens, nstreams, rxnoise, want, frames_cap, episodes_cap,
-                    params, stream):
-    """demod_long / demod_long_batch over a torch.int16 tensor: mifsk_demod_long_batch_s16.  A lone
-    row's stride means nothing to the library; it is given as the length rounded up to 8."""
-    longest = max(lens)
-    if frames_cap is None:
-        frames_cap = max_frames(cfg, longest)
-    if episodes_cap is None:
-        episodes_cap = max_episodes(cfg, longest)
-    out = _long_outputs(torch, cfg, pcm.device, nstreams, want, frames_cap, episodes_cap, stream)
-    io = _long_io(out, nstreams, frames_cap, episodes_cap)
-    arr = (C.c_uint64 * nstreams)(*lens)
-    st = (_lib.TimeSplitStats * nstreams)()
-    rc = lib.mifsk_demod_long_batch_s16(ctx.handle, C.byref(cfg), C.c_void_p(pcm.data_ptr()), stride, arr, nstreams,
-                                        C.c_float(rxnoise), C.byref(params), C.byref(io), st,
-                                        _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_demod_long_batch_s16 failed: %d" % rc)
-    out["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
-    return out
-
-
-def _long_outputs(torch, cfg, dev, nstreams, want, frames_cap, episodes_cap, stream):
-    """demod_batch's output tensors for demod_long / demod_long_batch, made on the launch stream."""
-    with _on(torch, stream):
-        out = {"nframes": torch.zeros(nstreams, dtype=torch.int32, device=dev),
-               "status": torch.zeros(nstreams, dtype=torch.int32, device=dev)}
-        if "bytes" in want:
-            out["bytes"] = torch.zeros((nstreams, frames_cap), dtype=torch.uint8, device=dev)
-            out["nbytes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-        if "bits" in want:
-            out["bits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=dev)
-        if "frames" in want:
-            out["frames"] = torch.zeros((nstreams, frames_cap, FRAME_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
-            out["carrier_band"] = torch.full((nstreams,), -1, dtype=torch.int32, device=dev)
-        if "episodes" in want:
-            out["episodes"] = torch.zeros((nstreams, episodes_cap, EPISODE_DTYPE.itemsize), dtype=torch.uint8,
-                                          device=dev)
-            out["nepisodes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-    return out
-
-
-def _long_io(out, nstreams, frames_cap, episodes_cap):
-    def ptr(name):
-        t = out.get(name)
-        return C.c_void_p(t.data_ptr()) if t is not None else None
-
-    io = _lib.DemodIO()
-    io.nstreams = nstreams
-    io.d_bytes = ptr("bytes")
-    io.d_nbytes = ptr("nbytes")
-    io.d_bits = ptr("bits")
-    io.d_frames = ptr("frames")
-    io.d_nframes = ptr("nframes")
-    io.frames_cap = frames_cap
-    io.d_episodes = ptr("episodes")
-    io.d_nepisodes = ptr("nepisodes")
-    io.episodes_cap = episodes_cap
-    io.d_status = ptr("status")
-    io.d_carrier_band = ptr("carrier_band")
-    return io
 
 
 def results_to_host(out):
@@ -632,7 +599,7 @@ class Pipeline:
     def info(self):
         info = _lib.PipelineInfo()
         self._lib.mifsk_pipeline_info_get(self.handle, C.byref(info))
-        return {k: int(getattr(info, k)) for k, _ in info._fields_}
+        return _struct_dict(info)
 
     def outputs(self, nstreams, frames_cap, episodes_cap=8, want=("bytes",)):
         flags = (_lib.WANT_BYTES if "bytes" in want else 0) | (_lib.WANT_BITS if "bits" in want else 0) | \
@@ -688,9 +655,7 @@ class Pipeline:
         io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
         io.nsamples = int(width)
         io.nstreams = nstreams
-        io.flags = (_lib.IO_RING_EXACT if ring_exact else 0) | \
-            (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-            (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+        io.flags = _io_flags(ring_exact, engine)
         if after == "current":
             after = torch.cuda.current_stream()
         prod = _lib.PIPELINE_NO_PRODUCER if after is None else C.c_void_p(after.cuda_stream)
@@ -871,7 +836,7 @@ class NativeGatherer:
     def info(self):
         gi = _lib.GatherInfo()
         self._lib.mifsk_gather_info_get(self.handle, C.byref(gi))
-        return {k: int(getattr(gi, k)) for k, _ in gi._fields_}
+        return _struct_dict(gi)
 
     def bytes_per_peer(self, nstreams):
         return int(nstreams) * (int(self.cols) if self.cols else 0) + 4 * int(nstreams)
@@ -985,7 +950,7 @@ def wav_parse(data):
     rc = _lib.load().mifsk_wav_parse(data, len(data), C.byref(info))
     if rc != 0:
         raise ValueError("mifsk_wav_parse -> %d" % rc)
-    return {k: getattr(info, k) for k, _ in info._fields_}
+    return _struct_dict(info)
 
 
 def ingest_s16(ctx, pcm, nsamples=None, rxnoise=0.0, stride=None, stream=None):
@@ -1082,10 +1047,6 @@ def host_free(arr):
         _lib.load().mifsk_host_free(ptr)
 
 
-def max_episodes(cfg, nsamples):
-    return int(_lib.load().mifsk_max_episodes(C.byref(cfg), int(nsamples)))
-
-
 def demod_batch_host(ctx, cfg, samples, nsamples=None, frames_cap=None, episodes_cap=8,
                      ring_exact=False, want=("bytes", "bits", "frames", "episodes"), rxnoise=0.0,
                      stats=False, engine=None):
@@ -1104,44 +1065,15 @@ def demod_batch_host(ctx, cfg, samples, nsamples=None, frames_cap=None, episodes
     nstreams, stride = samples.shape
     if frames_cap is None:
         frames_cap = max_frames(cfg, stride)
-    res = {"nframes": np.zeros(nstreams, np.uint32), "status": np.zeros(nstreams, np.uint32),
-           "carrier_band": np.full(nstreams, -1, np.int32)}
-    if "bytes" in want:
-        res["bytes"] = np.zeros((nstreams, frames_cap), np.uint8)
-        res["nbytes"] = np.zeros(nstreams, np.uint32)
-    if "bits" in want:
-        res["bits"] = np.zeros((nstreams, frames_cap), np.uint64)
-    if "frames" in want:
-        res["frames"] = np.zeros((nstreams, frames_cap), FRAME_DTYPE)
-    if "episodes" in want:
-        res["episodes"] = np.zeros((nstreams, episodes_cap), EPISODE_DTYPE)
-        res["nepisodes"] = np.zeros(nstreams, np.uint32)
-
-    def ptr(name):
-        return res[name].ctypes.data if name in res else None
-
-    io = _lib.DemodIO()
+    res = _numpy_outputs(nstreams, want, frames_cap, episodes_cap)
+    io = _result_io(res, nstreams, frames_cap, episodes_cap, _array_address)
     io.d_samples = samples.ctypes.data
     io.stream_stride = stride
     if nsamples is not None:
         nsamples = np.ascontiguousarray(nsamples, dtype=np.uint32)
         io.d_nsamples = nsamples.ctypes.data
     io.nsamples = stride
-    io.nstreams = nstreams
-    io.d_bytes = ptr("bytes")
-    io.d_nbytes = ptr("nbytes")
-    io.d_bits = ptr("bits")
-    io.d_frames = ptr("frames")
-    io.d_nframes = ptr("nframes")
-    io.frames_cap = frames_cap
-    io.d_episodes = ptr("episodes")
-    io.d_nepisodes = ptr("nepisodes")
-    io.episodes_cap = episodes_cap
-    io.d_status = ptr("status")
-    io.d_carrier_band = ptr("carrier_band")
-    io.flags = (_lib.IO_RING_EXACT if ring_exact else 0) | (_lib.IO_HOST_S16 if s16 else 0) | \
-        (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+    io.flags = _io_flags(ring_exact, engine) | (_lib.IO_HOST_S16 if s16 else 0)
     if isinstance(ctx, (list, tuple)):
         assert not s16 and not rxnoise
         handles = (C.c_void_p * len(ctx))(*[c.handle for c in ctx])
@@ -1151,7 +1083,7 @@ def demod_batch_host(ctx, cfg, samples, nsamples=None, frames_cap=None, episodes
         rc = lib.mifsk_demod_batch_host_ex(ctx.handle, C.byref(cfg), C.byref(io), C.c_float(rxnoise),
                                            C.byref(st))
         if stats:
-            res["stats"] = {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+            res["stats"] = _struct_dict(st, drop_reserved=True)
     if rc != 0:
         raise RuntimeError("mifsk_demod_batch_host failed: %d" % rc)
     return res
@@ -1175,40 +1107,9 @@ def demod_long_host(ctx, cfg, arrays, chunk=None, warmup=None, chunks=None,
         "all int16 or all float32, contiguous"
     nstreams = len(arrays)
     lens = [int(a.shape[0]) for a in arrays]
-    longest = max(lens)
-    if frames_cap is None:
-        frames_cap = max_frames(cfg, longest)
-    if episodes_cap is None:
-        episodes_cap = max_episodes(cfg, longest)
-    res = {"nframes": np.zeros(nstreams, np.uint32), "status": np.zeros(nstreams, np.uint32),
-           "carrier_band": np.full(nstreams, -1, np.int32)}
-    if "bytes" in want:
-        res["bytes"] = np.zeros((nstreams, frames_cap), np.uint8)
-        res["nbytes"] = np.zeros(nstreams, np.uint32)
-    if "bits" in want:
-        res["bits"] = np.zeros((nstreams, frames_cap), np.uint64)
-    if "frames" in want:
-        res["frames"] = np.zeros((nstreams, frames_cap), FRAME_DTYPE)
-    if "episodes" in want:
-        res["episodes"] = np.zeros((nstreams, episodes_cap), EPISODE_DTYPE)
-        res["nepisodes"] = np.zeros(nstreams, np.uint32)
-
-    def ptr(name):
-        return res[name].ctypes.data if name in res else None
-
-    io = _lib.DemodIO()
-    io.nstreams = nstreams
-    io.d_bytes = ptr("bytes")
-    io.d_nbytes = ptr("nbytes")
-    io.d_bits = ptr("bits")
-    io.d_frames = ptr("frames")
-    io.d_nframes = ptr("nframes")
-    io.frames_cap = frames_cap
-    io.d_episodes = ptr("episodes")
-    io.d_nepisodes = ptr("nepisodes")
-    io.episodes_cap = episodes_cap
-    io.d_status = ptr("status")
-    io.d_carrier_band = ptr("carrier_band")
+    frames_cap, episodes_cap = _default_caps(cfg, max(lens), frames_cap, episodes_cap)
+    res = _numpy_outputs(nstreams, want, frames_cap, episodes_cap)
+    io = _result_io(res, nstreams, frames_cap, episodes_cap, _array_address)
     rows = (C.c_void_p * nstreams)(*[a.ctypes.data for a in arrays])
     arr = (C.c_uint64 * nstreams)(*lens)
     st = (_lib.TimeSplitStats * nstreams)()
@@ -1219,9 +1120,9 @@ def demod_long_host(ctx, cfg, arrays, chunk=None, warmup=None, chunks=None,
                                          C.byref(io), st, C.byref(hst))
     if rc != 0:
         raise RuntimeError("mifsk_demod_long_batch_host failed: %d" % rc)
-    res["stats"] = [{k: int(getattr(st[m], k)) for k, _ in st[m]._fields_} for m in range(nstreams)]
+    res["stats"] = [_struct_dict(st[m]) for m in range(nstreams)]
     if stats:
-        res["host_stats"] = {k: getattr(hst, k) for k, _ in hst._fields_ if k != "reserved"}
+        res["host_stats"] = _struct_dict(hst, drop_reserved=True)
     return res
 
 
@@ -1250,9 +1151,7 @@ def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want
         setattr(a, k, v)
     enc = [os.fsencode(p) for p in paths]
     arr = (C.c_char_p * max(1, len(enc)))(*enc)
-    flags = (_lib.IO_RING_EXACT if ring_exact else 0) | (_lib.FILES_WANT_FRAMES if want_frames else 0) | \
-        (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | \
-        (_lib.IO_ENGINE_WAVE if engine == "wave" else 0)
+    flags = _io_flags(ring_exact, engine) | (_lib.FILES_WANT_FRAMES if want_frames else 0)
     h = C.c_void_p()
     split = time_split is not False and time_split is not None
     if split:
@@ -1274,7 +1173,7 @@ def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want
         for i in range(lib.mifsk_files_count(h)):
             fr = lib.mifsk_files_get(h, i).contents
             d = {"error": fr.error, "path": paths[i],
-                 "info": {k: getattr(fr.info, k) for k, _ in fr.info._fields_}}
+                 "info": _struct_dict(fr.info)}
             if fr.error == 0:
                 cfg = RxConfig()
                 C.memmove(C.byref(cfg), fr.cfg, C.sizeof(RxConfig))
@@ -1293,10 +1192,10 @@ def demod_files(ctx, paths, baudmode="1200", rxnoise=0.0, ring_exact=False, want
                 if split:
                     ts = lib.mifsk_files_time_split(h, i)
                     if ts:
-                        d["time_split"] = {k: int(getattr(ts.contents, k)) for k, _ in ts.contents._fields_}
+                        d["time_split"] = _struct_dict(ts.contents)
             out.append(d)
         st = lib.mifsk_files_stats(h).contents
-        stats = {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+        stats = _struct_dict(st, drop_reserved=True)
     finally:
         lib.mifsk_files_free(h)
     return out, stats
@@ -1394,8 +1293,7 @@ class SlabSession:
         io.episodes_cap = self.episodes_cap
         io.d_status = out["status"].data_ptr()
         io.d_carrier_band = out["carrier_band"].data_ptr()
-        io.flags = (_lib.IO_ENGINE_WORKGROUP if self.engine == "workgroup" else 0) | \
-            (_lib.IO_ENGINE_WAVE if self.engine == "wave" else 0)
+        io.flags = _io_flags(False, self.engine)
         if self.ring is not None:
             io.flags = _lib.IO_RING_EXACT
             rc = lib.mifsk_demod_slab_ring(self.ctx.handle, C.byref(self.cfg), C.byref(io),
@@ -1428,8 +1326,7 @@ class Session:
     def __init__(self, ctx, cfg, nstreams, engine=None, ring_exact=False, want_frames=True):
         self._lib = _lib.load()
         self.n = int(nstreams)
-        flags = (_lib.IO_ENGINE_WORKGROUP if engine == "workgroup" else 0) | (_lib.IO_ENGINE_WAVE if engine == "wave" else 0) \
-            | (_lib.IO_RING_EXACT if ring_exact else 0) | (_lib.SESSION_WANT_FRAMES if want_frames else 0)
+        flags = _io_flags(ring_exact, engine) | (_lib.SESSION_WANT_FRAMES if want_frames else 0)
         h = C.c_void_p()
         rc = self._lib.mifsk_session_create(C.byref(h), ctx.handle, C.byref(cfg), self.n, flags)
         if rc != 0:

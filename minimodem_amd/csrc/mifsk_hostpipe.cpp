@@ -50,7 +50,7 @@ struct HostWork {
     hipEvent_t	ev_in[2] = { nullptr, nullptr }, ev_comp[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
     void	*pin[2] = { nullptr, nullptr };	// staging for sources that are not page-locked
     size_t	pin_cap = 0;
-    uint32_t	*pin_n[2] = { nullptr, nullptr };	// per-chunk stream lengths
+    void	*pin_n[2] = { nullptr, nullptr };	// per-chunk stream lengths (uint32_t)
     size_t	pin_n_cap = 0;
     bool	ready = false;
 };
@@ -113,31 +113,28 @@ int host_work_init( HostWork *w, bool overlapped )
     return 0;
 }
 
+// both pinned buffers of one kind, `bytes` long at least
+int pin_grow( void *( &buf )[2], size_t &cap, size_t bytes )
+{
+    if ( bytes <= cap )
+	return 0;
+    for ( void *&p : buf ) {
+	if ( p ) (void)hipHostFree(p);
+	p = nullptr;
+    }
+    cap = 0;
+    for ( void *&p : buf )
+	if ( hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess )
+	    return -ENOMEM;
+    cap = bytes;
+    return 0;
+}
+
 int pin_reserve( HostWork *w, size_t bytes, size_t nrows )
 {
-    if ( bytes > w->pin_cap ) {
-	for ( int i = 0; i < 2; i++ ) {
-	    if ( w->pin[i] ) (void)hipHostFree(w->pin[i]);
-	    w->pin[i] = nullptr;
-	}
-	w->pin_cap = 0;
-	for ( int i = 0; i < 2; i++ )
-	    if ( hipHostMalloc(&w->pin[i], bytes, hipHostMallocDefault) != hipSuccess )
-		return -ENOMEM;
-	w->pin_cap = bytes;
-    }
-    if ( nrows > w->pin_n_cap ) {
-	for ( int i = 0; i < 2; i++ ) {
-	    if ( w->pin_n[i] ) (void)hipHostFree(w->pin_n[i]);
-	    w->pin_n[i] = nullptr;
-	}
-	w->pin_n_cap = 0;
-	for ( int i = 0; i < 2; i++ )
-	    if ( hipHostMalloc((void **)&w->pin_n[i], nrows * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess )
-		return -ENOMEM;
-	w->pin_n_cap = nrows;
-    }
-    return 0;
+    if ( const int rc = pin_grow(w->pin, w->pin_cap, bytes) )
+	return rc;
+    return pin_grow(w->pin_n, w->pin_n_cap, nrows * sizeof(uint32_t));
 }
 
 bool is_pinned( const void *p )
@@ -210,64 +207,14 @@ unsigned staging_threads()
     return t;
 }
 
-// one stream of a job: `n` samples at `mem`, or in the file `path` from byte `off`
+// one stream: `n` samples at `mem`, or in the file `path` from byte `off`
 struct Row {
     const void	*mem;
     const char	*path;
     uint64_t	off;
-    uint32_t	n;
+    uint64_t	n;
     int		*err;		// file rows: where a read error is reported
 };
-
-struct Job {
-    const mifsk_rx_config	*cfg;
-    std::vector<Row>		rows;
-    bool			s16;		// rows are int16_t (else float)
-    float			rxnoise;
-    unsigned			flags;		// MIFSK_IO_* for mifsk_demod_batch
-    // rows are equally spaced in one host array (mem rows only): pitch in elements
-    size_t			src_pitch;
-    // host result arrays, [rows][cap] (any may be NULL)
-    mifsk_demod_io		out;
-    mifsk_host_stats		*stats;
-};
-
-struct Chunk {
-    size_t	lo, hi;		// rows
-    size_t	stride;		// elements per device row
-};
-
-struct Slot {
-    void		*d_in = nullptr;	// the chunk as it crossed the bus
-    float		*d_x = nullptr;		// S16 input: the converted samples
-    uint32_t		*d_n = nullptr;
-    uint8_t		*d_bytes = nullptr;
-    uint64_t		*d_bits = nullptr;
-    mifsk_frame		*d_frames = nullptr;
-    mifsk_episode	*d_eps = nullptr;
-    uint32_t		*d_nbytes = nullptr, *d_nframes = nullptr, *d_neps = nullptr, *d_status = nullptr;
-    int32_t		*d_band = nullptr;
-    uint64_t		*d_cnt = nullptr;
-};
-
-struct SlotGuard {
-    Slot s[2];
-    ~SlotGuard()
-    {
-	for ( Slot &x : s ) {
-	    void *ps[] = { x.d_in, x.d_x, x.d_n, x.d_bytes, x.d_bits, x.d_frames, x.d_eps, x.d_nbytes,
-			   x.d_nframes, x.d_neps, x.d_status, x.d_band, x.d_cnt };
-	    for ( void *p : ps )
-		if ( p ) (void)hipFree(p);
-	}
-    }
-};
-
-template <typename T>
-int dev_alloc( T **p, size_t n )
-{
-    return hipMalloc((void **)p, ( n ? n : 1 ) * sizeof(T)) == hipSuccess ? 0 : -ENOMEM;
-}
 
 int read_fully( int fd, void *buf, size_t n, uint64_t off )
 {
@@ -285,9 +232,216 @@ int read_fully( int fd, void *buf, size_t n, uint64_t off )
     return 0;
 }
 
-int run_job( mifsk_ctx *ctx, Job &job )
+// MIFSK_TEST_FAULT_READ: file rows whose path holds this tag cannot be read (fault injection for
+// tests/test_gpu_files.py: a file that shrinks between its header and its samples cannot be staged
+// without a race).  A test hook like every other knob: honoured only with MIFSK_EXPERIMENT set, so
+// that a stray variable cannot turn production reads into rows of zeros.
+const char *read_fault_tag()
 {
-    const size_t nrows = job.rows.size();
+    const char *tag = experiment_env("MIFSK_TEST_FAULT_READ");
+    return tag && *tag ? tag : nullptr;
+}
+
+// a file row's descriptor for as long as the row is staged (memory rows, empty rows: none)
+struct RowFile {
+    int fd = -1, err = 0;
+    RowFile( const Row &row, const char *fault_tag )
+    {
+	if ( row.mem || !row.n )
+	    return;
+	fd = open(row.path, O_RDONLY | O_CLOEXEC);
+	if ( fd < 0 )
+	    err = -errno;
+	else if ( fault_tag && std::strstr(row.path, fault_tag) )
+	    err = -EIO;
+    }
+    ~RowFile() { if ( fd >= 0 ) close(fd); }
+    RowFile( const RowFile & ) = delete;
+    RowFile &operator=( const RowFile & ) = delete;
+};
+
+// Bytes [first, first + count) of a row's samples into pinned memory at `dst`, from the caller's
+// memory or from the row's file.  What cannot be read (a file that shrank after its header was
+// read, a read error) is this row's error, not the batch's: zeros stand in its place, the error
+// goes to the row's own slot -- several blocks of one row may report at once -- and is returned.
+int stage( const Row &row, const RowFile &file, uint64_t first, size_t count, void *dst )
+{
+    if ( row.mem ) {
+	std::memcpy(dst, (const char *)row.mem + first, count);
+	return 0;
+    }
+    const int e = file.err ? file.err : count ? read_fully(file.fd, dst, count, row.off + first) : 0;
+    if ( e ) {
+	std::memset(dst, 0, count);
+	if ( row.err )
+	    __atomic_store_n(row.err, e, __ATOMIC_RELAXED);
+    }
+    return e;
+}
+
+// Page-locked source rows are copied from where they are.  Rows at one pitch in one host array
+// (`src_pitch` set): its first and its last byte answer for all of them; otherwise every row that
+// has samples is asked, and there has to be one.
+bool rows_pinned( const std::vector<Row> &rows, size_t esz, size_t src_pitch )
+{
+    auto last_byte = [esz]( const Row &r ) { return (const char *)r.mem + (size_t)r.n * esz - ( r.n ? 1 : 0 ); };
+    if ( src_pitch )
+	return rows.front().mem && is_pinned(rows.front().mem) && is_pinned(last_byte(rows.back()));
+    bool any = false;
+    for ( const Row &r : rows )
+	if ( r.n ) {
+	    if ( !( r.mem && is_pinned(r.mem) && is_pinned(last_byte(r)) ) )
+		return false;
+	    any = true;
+	}
+    return any;
+}
+
+void host_stats_add( mifsk_host_stats *st, double t_begin, double t_stage, uint64_t bytes_in, uint64_t bytes_out,
+	size_t chunks, size_t streams, bool direct )
+{
+    if ( !st )
+	return;
+    st->seconds_total += now_s() - t_begin;
+    st->seconds_staging += t_stage;
+    st->bytes_h2d += bytes_in;
+    st->bytes_d2h += bytes_out;
+    st->chunks += (uint32_t)chunks;
+    st->streams += (uint32_t)streams;
+    st->source_pinned = direct ? 1u : 0u;
+}
+
+// ---- the result arrays of mifsk_demod_io: the one place that lists them ----
+
+enum PerRow { kOne, kFramesCap, kEpisodesCap, kCounters };
+
+struct OutArray {
+    size_t	member;		// where its pointer is in mifsk_demod_io
+    size_t	esz;		// bytes per element
+    PerRow	per;		// elements per row
+};
+
+const OutArray kOutArrays[] = {
+    { offsetof(mifsk_demod_io, d_bytes), sizeof(uint8_t), kFramesCap },
+    { offsetof(mifsk_demod_io, d_nbytes), sizeof(uint32_t), kOne },
+    { offsetof(mifsk_demod_io, d_bits), sizeof(uint64_t), kFramesCap },
+    { offsetof(mifsk_demod_io, d_frames), sizeof(mifsk_frame), kFramesCap },
+    { offsetof(mifsk_demod_io, d_nframes), sizeof(uint32_t), kOne },
+    { offsetof(mifsk_demod_io, d_episodes), sizeof(mifsk_episode), kEpisodesCap },
+    { offsetof(mifsk_demod_io, d_nepisodes), sizeof(uint32_t), kOne },
+    { offsetof(mifsk_demod_io, d_status), sizeof(uint32_t), kOne },
+    { offsetof(mifsk_demod_io, d_counters), sizeof(uint64_t), kCounters },
+    { offsetof(mifsk_demod_io, d_carrier_band), sizeof(int32_t), kOne },
+};
+
+void *out_get( const mifsk_demod_io &io, const OutArray &a )
+{
+    void *p;
+    std::memcpy(&p, (const char *)&io + a.member, sizeof(p));
+    return p;
+}
+
+void out_set( mifsk_demod_io &io, const OutArray &a, void *p )
+{
+    std::memcpy((char *)&io + a.member, &p, sizeof(p));
+}
+
+size_t out_row_bytes( const mifsk_demod_io &io, const OutArray &a )
+{
+    const size_t per = a.per == kFramesCap ? io.frames_cap : a.per == kEpisodesCap ? io.episodes_cap
+		     : a.per == kCounters ? (size_t)MIFSK_NCOUNTERS : 1;
+    return per * a.esz;
+}
+
+void mirror_free( mifsk_demod_io &d )
+{
+    for ( const OutArray &a : kOutArrays ) {
+	if ( void *p = out_get(d, a) )
+	    (void)hipFree(p);
+	out_set(d, a, nullptr);
+    }
+}
+
+// The device mirror of the result arrays `want` for `nrows` rows: a mifsk_demod_io with `want`'s
+// capacities and a device array wherever `want` has an array (everything else 0), which the
+// receive calls take as it is.  `zero`: the arrays are zero-filled, and the fill is done when this
+// returns (before another stream writes into them).  What was allocated is the caller's to
+// mirror_free(), after an error as well.
+int mirror_alloc( const mifsk_demod_io &want, size_t nrows, bool zero, mifsk_demod_io &d )
+{
+    std::memset(&d, 0, sizeof(d));
+    d.frames_cap = want.frames_cap;
+    d.episodes_cap = want.episodes_cap;
+    for ( const OutArray &a : kOutArrays ) {
+	if ( !out_get(want, a) )
+	    continue;
+	const size_t bytes = std::max<size_t>(nrows * out_row_bytes(want, a), 16);
+	void *p = nullptr;
+	if ( hipMalloc(&p, bytes) != hipSuccess )
+	    return -ENOMEM;
+	out_set(d, a, p);
+	if ( zero && hipMemset(p, 0, bytes) != hipSuccess )
+	    return -EIO;
+    }
+    return zero && hipStreamSynchronize(nullptr) != hipSuccess ? -EIO : 0;
+}
+
+// Rows [lo, hi) of the host arrays `ho` from the first hi - lo rows of a mirror, on `st`.  An
+// array that either side lacks is passed over.
+int mirror_copy_out( const mifsk_demod_io &d, const mifsk_demod_io &ho, size_t lo, size_t hi, hipStream_t st,
+	uint64_t *bytes_out )
+{
+    for ( const OutArray &a : kOutArrays ) {
+	void *host = out_get(ho, a), *dev = out_get(d, a);
+	if ( !host || !dev )
+	    continue;
+	const size_t row = out_row_bytes(ho, a), nb = ( hi - lo ) * row;
+	HIP_OK(hipMemcpyAsync((char *)host + lo * row, dev, nb, hipMemcpyDeviceToHost, st));
+	*bytes_out += nb;
+    }
+    return 0;
+}
+
+struct Chunk {
+    size_t	lo, hi;		// rows
+    size_t	stride;		// elements per device row
+};
+
+struct MirrorGuard {
+    mifsk_demod_io io = {};
+    ~MirrorGuard() { mirror_free(io); }
+};
+
+struct DevMem {
+    void *p = nullptr;
+    ~DevMem() { if ( p ) (void)hipFree(p); }
+    int get( size_t bytes, bool zero )
+    {
+	if ( hipMalloc(&p, bytes ? bytes : 16) != hipSuccess ) {
+	    p = nullptr;
+	    return -ENOMEM;
+	}
+	// (the fill is done before another stream copies into the buffer)
+	return !zero || ( hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess )
+	     ? 0 : -EIO;
+    }
+};
+
+struct Slot {
+    DevMem	in;		// the chunk as it crossed the bus
+    DevMem	x;		// S16 input: the converted samples
+    DevMem	n;		// the chunk's stream lengths
+    MirrorGuard	out;		// the mirror of the host's result arrays
+};
+
+// A batch of streams (`s16`: rows are int16_t, else float) through the chunked pipeline the head
+// of this file draws.  `flags`: MIFSK_IO_* for mifsk_demod_batch; `src_pitch`: the rows are
+// equally spaced in one host array (memory rows only), in elements; `ho`: the host result arrays,
+// [rows][cap], any of which may be NULL.
+int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> &rows, bool s16, float rxnoise,
+	unsigned flags, size_t src_pitch, const mifsk_demod_io &ho, mifsk_host_stats *stats )
+{
+    const size_t nrows = rows.size();
     if ( nrows == 0 )
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
@@ -299,7 +453,7 @@ int run_job( mifsk_ctx *ctx, Job &job )
     // MIFSK_CLI_TIMING=1: the phases of a job on stderr (what a batch of ONE pays: INTEGRATION.md 1b)
     const bool timing = std::getenv("MIFSK_CLI_TIMING") != nullptr;
     const double t_enter = now_s();
-    const size_t esz = job.s16 ? 2 : 4;
+    const size_t esz = s16 ? 2 : 4;
 
     // chunks of whole streams, ~kChunkBytes of input each
     std::vector<Chunk> chunks;
@@ -308,16 +462,14 @@ int run_job( mifsk_ctx *ctx, Job &job )
     for ( size_t lo = 0; lo < nrows; ) {
 	size_t hi = lo, maxn = 0;
 	while ( hi < nrows ) {
-	    const size_t m = std::max(maxn, (size_t)job.rows[hi].n);
+	    const size_t m = std::max(maxn, (size_t)rows[hi].n);
 	    const size_t stride = ( m + 7 ) & ~(size_t)7;
 	    if ( hi > lo && ( hi - lo + 1 ) * stride * esz > kChunkBytes )
 		break;
 	    maxn = m;
 	    hi++;
 	}
-	Chunk c;
-	c.lo = lo; c.hi = hi;
-	c.stride = std::max<size_t>(( maxn + 7 ) & ~(size_t)7, 8);
+	const Chunk c = { lo, hi, std::max<size_t>(( maxn + 7 ) & ~(size_t)7, 8) };
 	chunks.push_back(c);
 	max_bytes = std::max(max_bytes, ( hi - lo ) * c.stride * esz);
 	max_floats = std::max(max_floats, ( hi - lo ) * c.stride);
@@ -325,7 +477,7 @@ int run_job( mifsk_ctx *ctx, Job &job )
 	lo = hi;
     }
     for ( size_t i = 1; i < nrows; i++ )
-	uniform_n = uniform_n && job.rows[i].n == job.rows[0].n;
+	uniform_n = uniform_n && rows[i].n == rows[0].n;
     const bool single = chunks.size() == 1;
     rc = host_work_init(w, !single);
     if ( rc )
@@ -335,67 +487,36 @@ int run_job( mifsk_ctx *ctx, Job &job )
     const hipStream_t st_comp = single ? nullptr : w->s_comp;
     const hipStream_t st_in = single ? st_comp : w->s_in, st_out = single ? st_comp : w->s_out;
 
-    // page-locked source rows are copied from where they are
-    const bool direct = job.rows[0].mem && job.src_pitch && is_pinned(job.rows[0].mem)
-		     && is_pinned((const char *)job.rows[nrows - 1].mem + (size_t)job.rows[nrows - 1].n * esz - ( job.rows[nrows - 1].n ? 1 : 0 ));
+    const bool direct = rows_pinned(rows, esz, src_pitch);
     rc = pin_reserve(w, direct ? 0 : max_bytes, max_rows);
     if ( rc )
 	return rc;
 
-    const mifsk_demod_io &ho = job.out;
-    const size_t fc = ho.frames_cap, ec = ho.episodes_cap;
-    SlotGuard sg;
-    for ( Slot &s : sg.s ) {
-	if ( dev_alloc((unsigned char **)&s.d_in, max_bytes + 64) ) return -ENOMEM;
-	if ( job.s16 && dev_alloc(&s.d_x, max_floats + 16) ) return -ENOMEM;
-	if ( dev_alloc(&s.d_n, max_rows) ) return -ENOMEM;
-	if ( ho.d_bytes && dev_alloc(&s.d_bytes, max_rows * fc) ) return -ENOMEM;
-	if ( ho.d_bits && dev_alloc(&s.d_bits, max_rows * fc) ) return -ENOMEM;
-	if ( ho.d_frames && dev_alloc(&s.d_frames, max_rows * fc) ) return -ENOMEM;
-	if ( ho.d_episodes && dev_alloc(&s.d_eps, max_rows * ec) ) return -ENOMEM;
-	if ( ho.d_nbytes && dev_alloc(&s.d_nbytes, max_rows) ) return -ENOMEM;
-	if ( ho.d_nframes && dev_alloc(&s.d_nframes, max_rows) ) return -ENOMEM;
-	if ( ho.d_nepisodes && dev_alloc(&s.d_neps, max_rows) ) return -ENOMEM;
-	if ( ho.d_status && dev_alloc(&s.d_status, max_rows) ) return -ENOMEM;
-	if ( ho.d_carrier_band && dev_alloc(&s.d_band, max_rows) ) return -ENOMEM;
-	if ( ho.d_counters && dev_alloc(&s.d_cnt, max_rows * MIFSK_NCOUNTERS) ) return -ENOMEM;
-    }
+    // every array the host asked for is mirrored, counters included, and left as allocated (the
+    // receive loop writes every row of them); d_carrier_band comes back only under --auto-carrier
+    mifsk_demod_io back = ho;
+    if ( !( cfg->auto_carrier_threshold > 0.0f ) )
+	back.d_carrier_band = nullptr;
+    Slot slots[2];
+    for ( Slot &s : slots )
+	if ( ( rc = s.in.get(max_bytes + 64, false) )
+		|| ( s16 && ( rc = s.x.get(( max_floats + 16 ) * sizeof(float), false) ) )
+		|| ( rc = s.n.get(max_rows * sizeof(uint32_t), false) )
+		|| ( rc = mirror_alloc(ho, max_rows, false, s.out.io) ) )
+	    return rc;
 
     const double t_alloc = now_s();
     const unsigned nthreads = staging_threads();
-    // (a test hook like every other knob: honoured only with MIFSK_EXPERIMENT set, so that a stray
-    // variable cannot turn production reads into rows of zeros)
-    const char *fault_tag = experiment_env("MIFSK_TEST_FAULT_READ");
-    if ( fault_tag && !*fault_tag )
-	fault_tag = nullptr;
+    const char *fault_tag = read_fault_tag();
     double t_stage = 0.0;
     uint64_t bytes_in = 0, bytes_out = 0;
 
     auto copy_out = [&]( size_t ci ) -> int {		// results of chunk ci -> host, on s_out
 	const Chunk &c = chunks[ci];
-	const Slot &s = sg.s[ci & 1];
-	const size_t r = c.hi - c.lo;
 	if ( !single )
 	    HIP_OK(hipStreamWaitEvent(st_out, w->ev_comp[ci & 1], 0));
-#define MIFSK_OUT(HOSTP, DEVP, PER_ROW)										\
-	if ( HOSTP ) {												\
-	    const size_t nb = r * (PER_ROW) * sizeof(*(HOSTP));							\
-	    HIP_OK(hipMemcpyAsync((HOSTP) + c.lo * (PER_ROW), DEVP, nb, hipMemcpyDeviceToHost, st_out));	\
-	    bytes_out += nb;											\
-	}
-	MIFSK_OUT(ho.d_bytes, s.d_bytes, fc)
-	MIFSK_OUT(ho.d_bits, s.d_bits, fc)
-	MIFSK_OUT(ho.d_frames, s.d_frames, fc)
-	MIFSK_OUT(ho.d_episodes, s.d_eps, ec)
-	MIFSK_OUT(ho.d_nbytes, s.d_nbytes, 1)
-	MIFSK_OUT(ho.d_nframes, s.d_nframes, 1)
-	MIFSK_OUT(ho.d_nepisodes, s.d_neps, 1)
-	MIFSK_OUT(ho.d_status, s.d_status, 1)
-	MIFSK_OUT(ho.d_counters, s.d_cnt, MIFSK_NCOUNTERS)
-	if ( ho.d_carrier_band && job.cfg->auto_carrier_threshold > 0.0f ) {
-	    MIFSK_OUT(ho.d_carrier_band, s.d_band, 1)
-	}
-#undef MIFSK_OUT
+	if ( const int e = mirror_copy_out(slots[ci & 1].out.io, back, c.lo, c.hi, st_out, &bytes_out) )
+	    return e;
 	if ( !single )
 	    HIP_OK(hipEventRecord(w->ev_out[ci & 1], st_out));
 	return 0;
@@ -404,7 +525,8 @@ int run_job( mifsk_ctx *ctx, Job &job )
     for ( size_t ci = 0; ci < chunks.size(); ci++ ) {
 	const Chunk &c = chunks[ci];
 	const int sl = (int)( ci & 1 );
-	Slot &s = sg.s[sl];
+	Slot &s = slots[sl];
+	uint32_t *const d_n = (uint32_t *)s.n.p;
 	const size_t r = c.hi - c.lo;
 	if ( ci >= 2 )
 	    HIP_OK(hipEventSynchronize(w->ev_out[sl]));	// chunk ci - 2 has left this slot
@@ -412,82 +534,58 @@ int run_job( mifsk_ctx *ctx, Job &job )
 	const void *src = nullptr;
 	size_t src_pitch_bytes = 0;
 	if ( direct ) {
-	    src = job.rows[c.lo].mem;
-	    src_pitch_bytes = job.src_pitch * esz;
+	    src = rows[c.lo].mem;
+	    src_pitch_bytes = src_pitch * esz;
 	} else {
 	    const double t0 = now_s();
 	    unsigned char *dst = (unsigned char *)w->pin[sl];
 	    parallel_for(r, nthreads, [&]( size_t i ) {
-		const Row &row = job.rows[c.lo + i];
-		unsigned char *d = dst + i * c.stride * esz;
-		if ( row.mem ) {
-		    std::memcpy(d, row.mem, (size_t)row.n * esz);
-		} else if ( row.n ) {
-		    const int fd = open(row.path, O_RDONLY | O_CLOEXEC);
-		    int e = fd < 0 ? -errno : read_fully(fd, d, (size_t)row.n * esz, row.off);
-		    // (fault injection for tests/test_gpu_files.py: a file that shrinks between
-		    // its header and its samples cannot be staged without a race)
-		    if ( fault_tag && std::strstr(row.path, fault_tag) )
-			e = -EIO;
-		    if ( fd >= 0 ) close(fd);
-		    if ( e ) {
-			// this file's error (a file that shrank after its header was read, a
-			// read error): reported through its own row, the batch goes on with
-			// a row of zeros in its place
-			std::memset(d, 0, (size_t)row.n * esz);
-			if ( row.err ) *row.err = e;
-		    }
-		}
+		const Row &row = rows[c.lo + i];
+		(void)stage(row, RowFile(row, fault_tag), 0, (size_t)row.n * esz, dst + i * c.stride * esz);
 	    });
 	    t_stage += now_s() - t0;
 	    src = dst;
 	    src_pitch_bytes = c.stride * esz;
 	}
 	for ( size_t i = 0; i < r; i++ )
-	    w->pin_n[sl][i] = job.rows[c.lo + i].n;
+	    ( (uint32_t *)w->pin_n[sl] )[i] = (uint32_t)rows[c.lo + i].n;
 	// ---- host -> device
 	size_t width = std::min(src_pitch_bytes, c.stride * esz);
 	if ( direct && nrows == 1 ) {
 	    // a lone row's stride means nothing (its length is not clipped to it either)
-	    width = (size_t)job.rows[0].n * esz;
+	    width = (size_t)rows[0].n * esz;
 	    src_pitch_bytes = c.stride * esz;
 	}
 	if ( src_pitch_bytes == c.stride * esz )	// rows back to back on both sides: one linear copy
-	    HIP_OK(hipMemcpyAsync(s.d_in, src, width * r, hipMemcpyHostToDevice, st_in));
+	    HIP_OK(hipMemcpyAsync(s.in.p, src, width * r, hipMemcpyHostToDevice, st_in));
 	else
-	    HIP_OK(hipMemcpy2DAsync(s.d_in, c.stride * esz, src, src_pitch_bytes, width, r,
+	    HIP_OK(hipMemcpy2DAsync(s.in.p, c.stride * esz, src, src_pitch_bytes, width, r,
 				    hipMemcpyHostToDevice, st_in));
-	HIP_OK(hipMemcpyAsync(s.d_n, w->pin_n[sl], r * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
+	HIP_OK(hipMemcpyAsync(d_n, w->pin_n[sl], r * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
 	bytes_in += width * r;
 	// ---- convert + receive loop
 	if ( !single ) {
 	    HIP_OK(hipEventRecord(w->ev_in[sl], st_in));
 	    HIP_OK(hipStreamWaitEvent(st_comp, w->ev_in[sl], 0));
 	}
-	const float *d_x = (const float *)s.d_in;
-	if ( job.s16 ) {
-	    rc = mifsk_ingest_s16(ctx, (const int16_t *)s.d_in, c.stride, s.d_x, c.stride, s.d_n, 0,
-				  (int)r, job.rxnoise, st_comp);
-	    d_x = s.d_x;
-	} else if ( job.rxnoise != 0.0f ) {
-	    rc = mifsk_ingest_rxnoise_f32(ctx, (float *)s.d_in, c.stride, s.d_n, 0, (int)r, job.rxnoise, st_comp);
+	const float *d_x = (const float *)s.in.p;
+	if ( s16 ) {
+	    rc = mifsk_ingest_s16(ctx, (const int16_t *)s.in.p, c.stride, (float *)s.x.p, c.stride, d_n, 0,
+				  (int)r, rxnoise, st_comp);
+	    d_x = (const float *)s.x.p;
+	} else if ( rxnoise != 0.0f ) {
+	    rc = mifsk_ingest_rxnoise_f32(ctx, (float *)s.in.p, c.stride, d_n, 0, (int)r, rxnoise, st_comp);
 	}
 	if ( rc )
 	    return rc;
-	mifsk_demod_io io;
-	std::memset(&io, 0, sizeof(io));
+	mifsk_demod_io io = s.out.io;
 	io.d_samples = d_x;
 	io.stream_stride = c.stride;
-	io.d_nsamples = uniform_n ? nullptr : s.d_n;
-	io.nsamples = job.rows[c.lo].n;
+	io.d_nsamples = uniform_n ? nullptr : d_n;
+	io.nsamples = (uint32_t)rows[c.lo].n;
 	io.nstreams = (int)r;
-	io.d_bytes = s.d_bytes;	io.d_nbytes = s.d_nbytes;
-	io.d_bits = s.d_bits;	io.d_frames = s.d_frames;	io.d_nframes = s.d_nframes;
-	io.frames_cap = fc;
-	io.d_episodes = s.d_eps;	io.d_nepisodes = s.d_neps;	io.episodes_cap = ec;
-	io.d_status = s.d_status;	io.d_counters = s.d_cnt;	io.d_carrier_band = s.d_band;
-	io.flags = job.flags;
-	rc = mifsk_demod_batch(ctx, job.cfg, &io, st_comp);
+	io.flags = flags;
+	rc = mifsk_demod_batch(ctx, cfg, &io, st_comp);
 	if ( rc )
 	    return rc;
 	if ( !single )
@@ -514,16 +612,7 @@ int run_job( mifsk_ctx *ctx, Job &job )
 			     "read + queue (incl. the first launch: code object, tables) %.1f ms, device until done %.1f ms\n",
 		     nrows, 1e3 * ( t_begin - t_enter ), 1e3 * ( t_alloc - t_begin ), 1e3 * ( t_queued - t_alloc ),
 		     1e3 * ( now_s() - t_queued ));
-    if ( job.stats ) {
-	mifsk_host_stats &st = *job.stats;
-	st.seconds_total += now_s() - t_begin;
-	st.seconds_staging += t_stage;
-	st.bytes_h2d += bytes_in;
-	st.bytes_d2h += bytes_out;
-	st.chunks += (uint32_t)chunks.size();
-	st.streams += (uint32_t)nrows;
-	st.source_pinned = direct ? 1u : 0u;
-    }
+    host_stats_add(stats, t_begin, t_stage, bytes_in, bytes_out, chunks.size(), nrows, direct);
     return 0;		// (what a row could not read is in its own error slot)
 }
 
@@ -536,36 +625,12 @@ int run_job( mifsk_ctx *ctx, Job &job )
 // mifsk_demod_long_batch_s16 (PCM16: the rows are gathered straight from it, no float copy of the
 // recording) or mifsk_demod_long_batch (floats, --Xrxnoise added in place first).
 
-// one recording: `n` samples at `mem`, or in the file `path` from byte `off`
-struct LongRow {
-    const void	*mem;
-    const char	*path;
-    uint64_t	off;
-    uint64_t	n;
-    int		*err;		// file rows: where a read error is reported
-};
-
 struct Piece {
     size_t	row;
     uint64_t	first, count;	// samples of the row
 };
 
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem() { if ( p ) (void)hipFree(p); }
-    int get( size_t bytes )
-    {
-	if ( hipMalloc(&p, bytes ? bytes : 16) != hipSuccess ) {
-	    p = nullptr;
-	    return -ENOMEM;
-	}
-	// (the fill is done before another stream copies into the buffer)
-	return hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess
-	     ? 0 : -EIO;
-    }
-};
-
-int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<LongRow> &rows, bool s16,
+int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> &rows, bool s16,
 	float rxnoise, const mifsk_time_split *params, const mifsk_demod_io &ho,
 	mifsk_time_split_stats *tstats, mifsk_host_stats *hstats )
 {
@@ -599,28 +664,21 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Long
 	return rc;
     const hipStream_t st_in = single ? nullptr : w->s_in, st_comp = single ? nullptr : w->s_comp;
 
-    // page-locked source rows are copied from where they are
-    bool direct = !pieces.empty();
-    for ( size_t m = 0; m < M && direct; m++ )
-	if ( rows[m].n )
-	    direct = rows[m].mem && is_pinned(rows[m].mem)
-		  && is_pinned((const char *)rows[m].mem + (size_t)rows[m].n * esz - 1);
+    const bool direct = rows_pinned(rows, esz, 0);
     if ( !direct && ( rc = pin_reserve(w, (size_t)std::min<uint64_t>(per, longest) * esz, 0) ) )
 	return rc;
 
     DevMem d_in;
-    if ( ( rc = d_in.get(M * stride * esz) ) )
+    if ( ( rc = d_in.get(M * stride * esz, true) ) )
 	return rc;
     const unsigned nthreads = staging_threads();
-    const char *fault_tag = experiment_env("MIFSK_TEST_FAULT_READ");	// (as in run_job)
-    if ( fault_tag && !*fault_tag )
-	fault_tag = nullptr;
+    const char *fault_tag = read_fault_tag();
     constexpr size_t kBlock = 1u << 20;		// of a piece per staging task
     double t_stage = 0.0;
     uint64_t bytes_in = 0, bytes_out = 0;
     for ( size_t k = 0; k < pieces.size(); k++ ) {
 	const Piece &pc = pieces[k];
-	const LongRow &row = rows[pc.row];
+	const Row &row = rows[pc.row];
 	const int sl = (int)( k & 1 );
 	const size_t bytes = (size_t)pc.count * esz;
 	char *dst = (char *)d_in.p + ( pc.row * stride + (size_t)pc.first ) * esz;
@@ -632,32 +690,11 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Long
 		HIP_OK(hipEventSynchronize(w->ev_in[sl]));	// piece k - 2 has left this buffer
 	    const double t0 = now_s();
 	    char *pin = (char *)w->pin[sl];
-	    std::atomic<int> err(0);
-	    int fd = -1;
-	    if ( !row.mem ) {
-		fd = open(row.path, O_RDONLY | O_CLOEXEC);
-		if ( fd < 0 )
-		    err = -errno;
-		else if ( fault_tag && std::strstr(row.path, fault_tag) )
-		    err = -EIO;
-	    }
-	    if ( !err )
-		parallel_for(( bytes + kBlock - 1 ) / kBlock, nthreads, [&]( size_t b ) {
-		    const size_t o = b * kBlock, len = std::min(kBlock, bytes - o);
-		    if ( row.mem ) {
-			std::memcpy(pin + o, (const char *)row.mem + (size_t)pc.first * esz + o, len);
-		    } else if ( const int e = read_fully(fd, pin + o, len, row.off + pc.first * esz + o) ) {
-			err = e;
-		    }
-		});
-	    if ( fd >= 0 )
-		close(fd);
-	    if ( err ) {
-		// this file's error: reported through its own row, the batch goes on with zeros
-		std::memset(pin, 0, bytes);
-		if ( row.err )
-		    *row.err = err;
-	    }
+	    const RowFile file(row, fault_tag);		// (opened once per piece, not per block)
+	    parallel_for(( bytes + kBlock - 1 ) / kBlock, nthreads, [&]( size_t b ) {
+		const size_t o = b * kBlock;
+		(void)stage(row, file, pc.first * esz + o, std::min(kBlock, bytes - o), pin + o);
+	    });
 	    t_stage += now_s() - t0;
 	    src = pin;
 	}
@@ -678,29 +715,17 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Long
 		    return rc;
 	    }
 
-    // the outputs, as mifsk_demod_batch_host lays them out
-    const size_t fc = ho.frames_cap, ec = ho.episodes_cap;
-    const bool band = ho.d_carrier_band && cfg->auto_carrier_threshold > 0.0f;
-    DevMem o_bytes, o_bits, o_frames, o_eps, o_nbytes, o_nframes, o_neps, o_status, o_band;
-    if ( ( ho.d_bytes && ( rc = o_bytes.get(M * fc) ) )
-	    || ( ho.d_bits && ( rc = o_bits.get(M * fc * sizeof(uint64_t)) ) )
-	    || ( ho.d_frames && ( rc = o_frames.get(M * fc * sizeof(mifsk_frame)) ) )
-	    || ( ho.d_episodes && ( rc = o_eps.get(M * ec * sizeof(mifsk_episode)) ) )
-	    || ( ho.d_nbytes && ( rc = o_nbytes.get(M * sizeof(uint32_t)) ) )
-	    || ( ho.d_nframes && ( rc = o_nframes.get(M * sizeof(uint32_t)) ) )
-	    || ( ho.d_nepisodes && ( rc = o_neps.get(M * sizeof(uint32_t)) ) )
-	    || ( ho.d_status && ( rc = o_status.get(M * sizeof(uint32_t)) ) )
-	    || ( band && ( rc = o_band.get(M * sizeof(int32_t)) ) ) )
+    // the outputs, as mifsk_demod_batch_host lays them out: no counters, d_carrier_band only under
+    // --auto-carrier, and zero-filled
+    mifsk_demod_io want = ho;
+    want.d_counters = nullptr;
+    if ( !( cfg->auto_carrier_threshold > 0.0f ) )
+	want.d_carrier_band = nullptr;
+    MirrorGuard out;
+    if ( ( rc = mirror_alloc(want, M, true, out.io) ) )
 	return rc;
-    mifsk_demod_io io;
-    std::memset(&io, 0, sizeof(io));
+    mifsk_demod_io io = out.io;
     io.nstreams = (int)M;
-    io.d_bytes = (uint8_t *)o_bytes.p;		io.d_nbytes = (uint32_t *)o_nbytes.p;
-    io.d_bits = (uint64_t *)o_bits.p;		io.d_frames = (mifsk_frame *)o_frames.p;
-    io.d_nframes = (uint32_t *)o_nframes.p;	io.frames_cap = fc;
-    io.d_episodes = (mifsk_episode *)o_eps.p;	io.d_nepisodes = (uint32_t *)o_neps.p;
-    io.episodes_cap = ec;
-    io.d_status = (uint32_t *)o_status.p;	io.d_carrier_band = (int32_t *)o_band.p;
     rc = s16 ? mifsk_demod_long_batch_s16(ctx, cfg, (const int16_t *)d_in.p, stride, lens.data(), (int)M, rxnoise,
 					  params, &io, tstats, st_comp)
 	     : mifsk_demod_long_batch(ctx, cfg, (const float *)d_in.p, stride, lens.data(), (int)M, params, &io,
@@ -708,39 +733,16 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Long
     if ( rc )
 	return rc;
     // (the call has waited for its stream)
-#define MIFSK_OUT(HOSTP, DEVP, PER_ROW)									\
-    if ( (HOSTP) && (DEVP).p ) {									\
-	const size_t nb = M * (PER_ROW) * sizeof(*(HOSTP));						\
-	HIP_OK(hipMemcpy((HOSTP), (DEVP).p, nb, hipMemcpyDeviceToHost));				\
-	bytes_out += nb;										\
-    }
-    MIFSK_OUT(ho.d_bytes, o_bytes, fc)
-    MIFSK_OUT(ho.d_bits, o_bits, fc)
-    MIFSK_OUT(ho.d_frames, o_frames, fc)
-    MIFSK_OUT(ho.d_episodes, o_eps, ec)
-    MIFSK_OUT(ho.d_nbytes, o_nbytes, 1)
-    MIFSK_OUT(ho.d_nframes, o_nframes, 1)
-    MIFSK_OUT(ho.d_nepisodes, o_neps, 1)
-    MIFSK_OUT(ho.d_status, o_status, 1)
-    MIFSK_OUT(ho.d_carrier_band, o_band, 1)
-#undef MIFSK_OUT
-    if ( hstats ) {
-	hstats->seconds_total += now_s() - t_begin;
-	hstats->seconds_staging += t_stage;
-	hstats->bytes_h2d += bytes_in;
-	hstats->bytes_d2h += bytes_out;
-	hstats->chunks += (uint32_t)pieces.size();
-	hstats->streams += (uint32_t)M;
-	hstats->source_pinned = direct ? 1u : 0u;
-    }
+    if ( ( rc = mirror_copy_out(out.io, ho, 0, M, nullptr, &bytes_out) ) )
+	return rc;
+    HIP_OK(hipStreamSynchronize(nullptr));
+    host_stats_add(hstats, t_begin, t_stage, bytes_in, bytes_out, pieces.size(), M, direct);
     return 0;
 }
 
 } // namespace
 } // namespace mifsk
 
-using mifsk::Job;
-using mifsk::LongRow;
 using mifsk::Row;
 
 // ---------------------------------------------------------------------------
@@ -776,28 +778,17 @@ extern "C" int mifsk_demod_batch_host_ex( mifsk_ctx *ctx, const mifsk_rx_config 
     if ( !hio->d_samples )
 	return -EINVAL;
     try {		// (no exception crosses the C ABI)
-    Job job;
-    job.cfg = cfg;
-    job.s16 = ( hio->flags & MIFSK_IO_HOST_S16 ) != 0;
-    job.rxnoise = rxnoise;
-    job.flags = hio->flags & ~MIFSK_IO_HOST_S16;
-    job.src_pitch = hio->stream_stride;
-    job.out = *hio;
-    job.stats = stats;
-    const size_t esz = job.s16 ? 2 : 4;
-    job.rows.resize(ns);
+    const bool s16 = ( hio->flags & MIFSK_IO_HOST_S16 ) != 0;
+    const size_t esz = s16 ? 2 : 4;
+    std::vector<Row> rows(ns);
     for ( size_t i = 0; i < ns; i++ ) {
-	Row &r = job.rows[i];
-	r.mem = (const char *)hio->d_samples + i * hio->stream_stride * esz;
-	r.path = nullptr;
-	r.off = 0;
 	uint32_t n = hio->d_nsamples ? hio->d_nsamples[i] : hio->nsamples;
 	if ( ns > 1 && (size_t)n > hio->stream_stride )
 	    n = (uint32_t)hio->stream_stride;		// never trust a length beyond the row
-	r.n = n;
-	r.err = nullptr;
+	rows[i] = Row{ (const char *)hio->d_samples + i * hio->stream_stride * esz, nullptr, 0, n, nullptr };
     }
-    return mifsk::run_job(ctx, job);
+    return mifsk::run_job(ctx, cfg, rows, s16, rxnoise, hio->flags & ~MIFSK_IO_HOST_S16, hio->stream_stride, *hio,
+			  stats);
     } catch ( const std::bad_alloc & ) {
 	return -ENOMEM;
     } catch ( ... ) {
@@ -828,9 +819,9 @@ extern "C" int mifsk_demod_long_batch_host( mifsk_ctx *ctx, const mifsk_rx_confi
     if ( hstats )
 	std::memset(hstats, 0, sizeof(*hstats));
     try {		// (no exception crosses the C ABI)
-	std::vector<LongRow> lr((size_t)nstreams);
+	std::vector<Row> lr((size_t)nstreams);
 	for ( int m = 0; m < nstreams; m++ )
-	    lr[(size_t)m] = LongRow{ rows[m], nullptr, 0, nsamples[m], nullptr };
+	    lr[(size_t)m] = Row{ rows[m], nullptr, 0, nsamples[m], nullptr };
 	return mifsk::run_long(ctx, cfg, lr, ( src_flags & MIFSK_IO_HOST_S16 ) != 0, rxnoise, params, *io_out,
 			       stats, hstats);
     } catch ( const std::bad_alloc & ) {
@@ -876,20 +867,11 @@ extern "C" size_t mifsk_max_episodes( const mifsk_rx_config *cfg, size_t nsample
     return nsamples / ( adv + 21 * ( tm ? tm : 1 ) ) + 2;
 }
 
-// `long_params`: the groups are decoded through the time split (mifsk_demod_files_long) with these
-// parameters, each (sample rate, sample format) group as one batch of long recordings
-static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
-	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files *F,
-	const mifsk_time_split *long_params )
+// ---- headers (threads): format, rate, where the samples start, how many
+static void read_headers( mifsk_files *F, const char *const *paths, int nfiles )
 {
-    std::memset(&F->stats, 0, sizeof(F->stats));
-    F->time_split = long_params != nullptr;
-    if ( long_params )
-	F->tsplit.assign((size_t)nfiles, mifsk_time_split_stats{});
     F->files.resize((size_t)nfiles);
     F->paths.resize((size_t)nfiles);
-    const double t0 = mifsk::now_s();
-    // ---- headers (threads): format, rate, where the samples start, how many
     for ( int i = 0; i < nfiles; i++ ) {
 	std::memset(&F->files[(size_t)i], 0, sizeof(mifsk_file_result));
 	F->paths[(size_t)i] = paths[i] ? paths[i] : "";
@@ -921,11 +903,15 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	if ( !fr.error && fr.info.nframes > 0xFFFFFF00ull )
 	    fr.error = -EFBIG;			// stream lengths are 32-bit on the device
     });
-    // ---- one batch per (sample rate, sample format): the reference takes its sample rate
-    // from the file and derives everything from it (minimodem.c:1021-1032)
+}
+
+// ---- one group per (sample rate, sample format): the reference takes its sample rate from the
+// file and derives everything from it (minimodem.c:1021-1032)
+static void group_by_rate_and_format( mifsk_files *F, const mifsk_modem_args *args )
+{
     std::map<std::pair<unsigned, int>, size_t> index;
-    for ( int i = 0; i < nfiles; i++ ) {
-	const mifsk_file_result &fr = F->files[(size_t)i];
+    for ( size_t i = 0; i < F->files.size(); i++ ) {
+	const mifsk_file_result &fr = F->files[i];
 	if ( fr.error )
 	    continue;
 	const std::pair<unsigned, int> key(fr.info.sample_rate, fr.info.is_float);
@@ -936,106 +922,110 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
 	    a.sample_rate = fr.info.sample_rate;
 	    const int rc = mifsk_rx_config_init(&g.cfg, &a);
 	    if ( rc ) {
-		F->files[(size_t)i].error = rc;		// (e.g. tones above this file's Nyquist rate)
+		F->files[i].error = rc;		// (e.g. tones above this file's Nyquist rate)
 		continue;
 	    }
 	    F->groups.push_back(std::move(g));
 	    it = index.emplace(key, F->groups.size() - 1).first;
 	}
-	F->groups[it->second].members.push_back(i);
+	F->groups[it->second].members.push_back((int)i);
     }
-    // ---- length classes.  A batch's output arrays (host vectors, device slots, the copies
-    // back) are sized by its LONGEST file, so one hour-long recording among ten thousand short
-    // ones would cost every one of them the long one's capacity.  Each (rate, format) group is
-    // therefore cut, by length, into classes whose longest file is at most twice the shortest:
-    // a class is one batch with its own capacities, at most 2 x what its files need.  (Not for
-    // the time split: a few long recordings, and one plan cuts the whole group.)
-    if ( !long_params ) {
-	std::vector<mifsk_files::Group> classes;
-	for ( mifsk_files::Group &g : F->groups ) {
-	    std::stable_sort(g.members.begin(), g.members.end(), [&]( int a, int b ) {
-		return F->files[(size_t)a].info.nframes < F->files[(size_t)b].info.nframes;
-	    });
-	    size_t lo = 0;
-	    while ( lo < g.members.size() ) {
-		const uint64_t shortest = std::max<uint64_t>(F->files[(size_t)g.members[lo]].info.nframes, 4096);
-		size_t hi = lo;
-		while ( hi < g.members.size() && F->files[(size_t)g.members[hi]].info.nframes <= 2 * shortest )
-		    hi++;
-		mifsk_files::Group c;
-		c.cfg = g.cfg;
-		c.members.assign(g.members.begin() + (long)lo, g.members.begin() + (long)hi);
-		classes.push_back(std::move(c));
-		lo = hi;
-	    }
+}
+
+// ---- length classes.  A batch's output arrays (host vectors, device slots, the copies back) are
+// sized by its LONGEST file, so one hour-long recording among ten thousand short ones would cost
+// every one of them the long one's capacity.  Each (rate, format) group is therefore cut, by
+// length, into classes whose longest file is at most twice the shortest: a class is one batch with
+// its own capacities, at most 2 x what its files need.
+static void cut_into_length_classes( mifsk_files *F )
+{
+    std::vector<mifsk_files::Group> classes;
+    for ( mifsk_files::Group &g : F->groups ) {
+	std::stable_sort(g.members.begin(), g.members.end(), [&]( int a, int b ) {
+	    return F->files[(size_t)a].info.nframes < F->files[(size_t)b].info.nframes;
+	});
+	size_t lo = 0;
+	while ( lo < g.members.size() ) {
+	    const uint64_t shortest = std::max<uint64_t>(F->files[(size_t)g.members[lo]].info.nframes, 4096);
+	    size_t hi = lo;
+	    while ( hi < g.members.size() && F->files[(size_t)g.members[hi]].info.nframes <= 2 * shortest )
+		hi++;
+	    mifsk_files::Group c;
+	    c.cfg = g.cfg;
+	    c.members.assign(g.members.begin() + (long)lo, g.members.begin() + (long)hi);
+	    classes.push_back(std::move(c));
+	    lo = hi;
 	}
-	F->groups.swap(classes);
     }
+    F->groups.swap(classes);
+}
+
+// a group's result vectors, sized by its longest file, as the host result arrays of either decode
+static mifsk_demod_io size_group( const mifsk_files *F, mifsk_files::Group &g, unsigned flags )
+{
+    const size_t n = g.members.size();
+    size_t maxn = 0;
+    for ( int i : g.members )
+	maxn = std::max(maxn, F->files[(size_t)i].info.nframes);
+    g.fcap = mifsk_max_frames(&g.cfg, maxn);
+    g.ecap = mifsk_max_episodes(&g.cfg, maxn);
+    g.bits.assign(n * g.fcap, 0);
+    g.bytes.assign(n * g.fcap, 0);
+    if ( flags & MIFSK_FILES_WANT_FRAMES )
+	g.frames.resize(n * g.fcap);
+    g.eps.resize(n * g.ecap);
+    g.nbytes.assign(n, 0); g.nframes.assign(n, 0); g.neps.assign(n, 0); g.status.assign(n, 0);
+    g.band.assign(n, -1);
+    mifsk_demod_io ho;
+    std::memset(&ho, 0, sizeof(ho));
+    ho.d_bytes = g.bytes.data();	ho.d_nbytes = g.nbytes.data();
+    ho.d_bits = g.bits.data();
+    ho.d_frames = g.frames.empty() ? nullptr : g.frames.data();
+    ho.d_nframes = g.nframes.data();	ho.frames_cap = g.fcap;
+    ho.d_episodes = g.eps.data();	ho.d_nepisodes = g.neps.data();	ho.episodes_cap = g.ecap;
+    ho.d_status = g.status.data();
+    ho.d_carrier_band = g.band.data();
+    return ho;
+}
+
+// `long_params`: the groups are decoded through the time split (mifsk_demod_files_long) with these
+// parameters, each (sample rate, sample format) group as one batch of long recordings -- a few
+// long recordings, and one plan cuts the whole group: no length classes
+static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
+	const char *const *paths, int nfiles, float rxnoise, unsigned flags, mifsk_files *F,
+	const mifsk_time_split *long_params )
+{
+    std::memset(&F->stats, 0, sizeof(F->stats));
+    F->time_split = long_params != nullptr;
+    if ( long_params )
+	F->tsplit.assign((size_t)nfiles, mifsk_time_split_stats{});
+    const double t0 = mifsk::now_s();
+    read_headers(F, paths, nfiles);
+    group_by_rate_and_format(F, args);
+    if ( !long_params )
+	cut_into_length_classes(F);
     int rc_all = 0;
     for ( mifsk_files::Group &g : F->groups ) {
 	const size_t n = g.members.size();
-	size_t maxn = 0;
-	for ( int i : g.members )
-	    maxn = std::max(maxn, F->files[(size_t)i].info.nframes);
-	g.fcap = mifsk_max_frames(&g.cfg, maxn);
-	g.ecap = mifsk_max_episodes(&g.cfg, maxn);
-	g.bits.assign(n * g.fcap, 0);
-	g.bytes.assign(n * g.fcap, 0);
-	if ( flags & MIFSK_FILES_WANT_FRAMES )
-	    g.frames.resize(n * g.fcap);
-	g.eps.resize(n * g.ecap);
-	g.nbytes.assign(n, 0); g.nframes.assign(n, 0); g.neps.assign(n, 0); g.status.assign(n, 0);
-	g.band.assign(n, -1);
-	if ( long_params ) {
-	    mifsk_demod_io ho;
-	    std::memset(&ho, 0, sizeof(ho));
-	    ho.d_bytes = g.bytes.data();	ho.d_nbytes = g.nbytes.data();
-	    ho.d_bits = g.bits.data();
-	    ho.d_frames = g.frames.empty() ? nullptr : g.frames.data();
-	    ho.d_nframes = g.nframes.data();	ho.frames_cap = g.fcap;
-	    ho.d_episodes = g.eps.data();	ho.d_nepisodes = g.neps.data();	ho.episodes_cap = g.ecap;
-	    ho.d_status = g.status.data();
-	    ho.d_carrier_band = g.band.data();
-	    std::vector<LongRow> lr(n);
-	    for ( size_t k = 0; k < n; k++ ) {
-		mifsk_file_result &fr = F->files[(size_t)g.members[k]];
-		lr[k] = LongRow{ nullptr, F->paths[(size_t)g.members[k]].c_str(), fr.info.data_offset,
-				 fr.info.nframes, &fr.error };
-	    }
-	    std::vector<mifsk_time_split_stats> ts(n);
-	    const int rc = mifsk::run_long(ctx, &g.cfg, lr, !F->files[(size_t)g.members[0]].info.is_float, rxnoise,
-					   long_params, ho, ts.data(), &F->stats);
-	    if ( rc && !rc_all )
-		rc_all = rc;
-	    for ( size_t k = 0; k < n; k++ )
-		F->tsplit[(size_t)g.members[k]] = ts[k];
-	}
-	Job job;
-	job.cfg = &g.cfg;
-	job.s16 = !F->files[(size_t)g.members[0]].info.is_float;
-	job.rxnoise = rxnoise;
-	job.flags = flags & ( MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WAVE | MIFSK_IO_ENGINE_WORKGROUP );
-	job.src_pitch = 0;
-	job.stats = &F->stats;
-	std::memset(&job.out, 0, sizeof(job.out));
-	job.out.d_bytes = g.bytes.data();	job.out.d_nbytes = g.nbytes.data();
-	job.out.d_bits = g.bits.data();
-	job.out.d_frames = g.frames.empty() ? nullptr : g.frames.data();
-	job.out.d_nframes = g.nframes.data();	job.out.frames_cap = g.fcap;
-	job.out.d_episodes = g.eps.data();	job.out.d_nepisodes = g.neps.data();	job.out.episodes_cap = g.ecap;
-	job.out.d_status = g.status.data();
-	job.out.d_carrier_band = g.band.data();
-	job.rows.resize(n);
+	const mifsk_demod_io ho = size_group(F, g, flags);
+	const bool s16 = !F->files[(size_t)g.members[0]].info.is_float;
+	std::vector<Row> rows(n);
 	for ( size_t k = 0; k < n; k++ ) {
 	    mifsk_file_result &fr = F->files[(size_t)g.members[k]];
-	    Row &r = job.rows[k];
-	    r.mem = nullptr;
-	    r.path = F->paths[(size_t)g.members[k]].c_str();
-	    r.off = fr.info.data_offset;
-	    r.n = (uint32_t)fr.info.nframes;
-	    r.err = &fr.error;
+	    rows[k] = Row{ nullptr, F->paths[(size_t)g.members[k]].c_str(), fr.info.data_offset, fr.info.nframes,
+			   &fr.error };
 	}
-	const int rc = long_params ? 0 : mifsk::run_job(ctx, job);
+	int rc;
+	if ( long_params ) {
+	    std::vector<mifsk_time_split_stats> ts(n);
+	    rc = mifsk::run_long(ctx, &g.cfg, rows, s16, rxnoise, long_params, ho, ts.data(), &F->stats);
+	    for ( size_t k = 0; k < n; k++ )
+		F->tsplit[(size_t)g.members[k]] = ts[k];
+	} else {
+	    rc = mifsk::run_job(ctx, &g.cfg, rows, s16, rxnoise,
+				flags & ( MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WAVE | MIFSK_IO_ENGINE_WORKGROUP ), 0, ho,
+				&F->stats);
+	}
 	if ( rc && !rc_all )
 	    rc_all = rc;
 	for ( size_t k = 0; k < n; k++ ) {
@@ -1056,7 +1046,7 @@ static int demod_files_impl( mifsk_ctx *ctx, const mifsk_modem_args *args,
     }
     F->stats.seconds_total = mifsk::now_s() - t0;	// headers and grouping included
     // a file that could not be read is that file's error (mifsk_file_result.error), not the
-    // batch's: run_job reports only what stopped the pipeline (HIP, allocation)
+    // batch's: the decodes report only what stopped the pipeline (HIP, allocation)
     return rc_all;
 }
 

@@ -657,6 +657,89 @@ void gather_tails( const Src &src, dim3 grid, hipStream_t st, const StreamRef *s
 			   (uint64_t)src.stride, streams, tails, stride, nstreams, 0.0f);
 }
 
+// The rows: stream m's chunks are rows rowbase[m] .. rowbase[m] + K_m - 1, its tail (the final
+// slab) is row R + m
+void row_table( const uint64_t *nsamples, const std::vector<mifsk_time_split_stats> &ps, int R,
+	std::vector<StreamRef> &hs, std::vector<RowRef> &hrow, std::vector<uint32_t> &hns )
+{
+    const int M = (int)ps.size();
+    const uint64_t L = ps[0].chunk, W = ps[0].warmup;
+    for ( int m = 0, r = 0; m < M; m++ ) {
+	hs[m].n = nsamples[m];
+	hs[m].tail_off = 0;
+	hs[m].rowbase = (uint32_t)r;
+	hs[m].K = ps[m].nchunks;
+	for ( uint32_t k = 0; k < hs[m].K; k++, r++ ) {
+	    hrow[r].m = (uint32_t)m;
+	    hrow[r].k = k;
+	    hns[r] = (uint32_t)( k + 1 < hs[m].K ? L + W : nsamples[m] - k * L );
+	}
+	hrow[R + m].m = (uint32_t)m;
+	hrow[R + m].k = hs[m].K;
+    }
+}
+
+// Rows [lo, lo + count) of `b`, the batch of all rows from row 0 on: their samples and lengths,
+// their part of the per-row result buffers, and their four counts, which lie nrows apart in `cnt`.
+mifsk_demod_io rows_of( mifsk_demod_io b, uint32_t *cnt, int nrows, int lo, int count )
+{
+    b.d_samples += (size_t)lo * b.stream_stride;
+    b.d_nsamples += lo;
+    b.nstreams = count;
+    b.d_frames += (size_t)lo * b.frames_cap;
+    if ( b.d_bytes )
+	b.d_bytes += (size_t)lo * b.frames_cap;
+    b.d_episodes += (size_t)lo * b.episodes_cap;
+    b.d_nframes = cnt + lo;
+    b.d_nbytes = cnt + nrows + lo;
+    b.d_nepisodes = cnt + 2 * nrows + lo;
+    b.d_status = cnt + 3 * nrows + lo;
+    return b;
+}
+
+// The host half of a round, which launches nothing.  From the codes of ts_verify: every stream's
+// settled prefix grows over the rows that are consistent (accepted, unless they ran again) or
+// dropped, and every unsettled row whose code is 0 is marked to run again in `hmark` -- rows
+// [lo, hi] hold them all; lo < 0: there is none, the rounds are over.
+void settle_round( const std::vector<uint32_t> &hcode, const std::vector<StreamRef> &hs,
+	const std::vector<uint32_t> &hns, std::vector<uint8_t> &settled, std::vector<uint8_t> &drop,
+	std::vector<uint8_t> &ran, std::vector<mifsk_time_split_stats> &ps, std::vector<uint8_t> &hmark,
+	int &lo, int &hi )
+{
+    lo = hi = -1;
+    std::fill(hmark.begin(), hmark.end(), 0);
+    for ( size_t m = 0; m < hs.size(); m++ ) {
+	const int r0 = (int)hs[m].rowbase, r1 = r0 + (int)hs[m].K;
+	for ( int r = r0 + 1; r < r1; r++ ) {
+	    if ( settled[r] )
+		continue;
+	    if ( !settled[r - 1] )
+		break;
+	    if ( drop[r - 1] || ( hcode[r] & 2u ) ) {
+		drop[r] = settled[r] = 1;
+	    } else if ( hcode[r] & 1u ) {
+		settled[r] = 1;
+		ps[m].accepted += !ran[r];
+	    } else {
+		break;
+	    }
+	}
+	bool any = false;
+	for ( int r = r0 + 1; r < r1; r++ )
+	    if ( !settled[r] && hcode[r] == 0u ) {	// (behind a finished row: wait for it to settle)
+		hmark[r] = 1;
+		any = true;
+		if ( lo < 0 )
+		    lo = r;
+		hi = r;
+		ran[r] = 1;
+		ps[m].rerun++;
+		ps[m].samples_rerun += hns[r];
+	    }
+	ps[m].rounds += any;
+    }
+}
+
 // The entry points (which have checked the rows against the source's stride); mifsk_demod_long is
 // the nstreams == 1 case of a float source, whose one row holds just nsamples[0] floats (the
 // stride is not used then)
@@ -664,7 +747,6 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	const uint64_t *nsamples, int nstreams, const mifsk_time_split *params,
 	const mifsk_demod_io *io_out, mifsk_time_split_stats *stats, void *stream )
 {
-    const size_t xstride = src.stride;
     if ( !ctx || !io_out || !nsamples || nstreams <= 0 || mifsk_check_cfg(cfg)
 	    || ( (uintptr_t)src.p & 15u ) )
 	return -EINVAL;
@@ -707,52 +789,16 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     base.flags = engine;
 
     if ( nchunkrows == (uint64_t)M ) {
-	// no stream is cut: the existing call over the batch (a lone row over a padded copy unless
-	// it is whole float4s already)
+	// no stream is cut: the existing call over the batch.  A batch of floats is taken where it
+	// is, and so is a lone row of whole float4s (no allocation, no copy); any other lone row goes
+	// over a padded copy, its stride being its length in whole float4s; PCM16 becomes floats
+	// through mifsk_ingest_s16, as the host pipeline makes them (every row defined up to its stride)
 	DevBuf pad, dn;
-	const float *d_samples = (const float *)src.p;
+	const bool lone = M == 1;
+	const uint64_t stride = lone ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : src.stride;
 	mifsk_demod_io io = *io_out;
-	io.d_nsamples = nullptr;
-	io.nstreams = M;
-	if ( src.s16 ) {
-	    // PCM16: the floats of the uncut batch through mifsk_ingest_s16, as the host pipeline
-	    // makes them (every row defined up to its stride)
-	    const uint64_t stride = M == 1 ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : xstride;
-	    std::vector<uint32_t> hn(M);
-	    for ( int m = 0; m < M; m++ )
-		hn[m] = (uint32_t)nsamples[m];
-	    if ( ( rc = alloc(pad, (size_t)M * stride * sizeof(float), st) )
-		    || ( rc = alloc(dn, M * sizeof(uint32_t), st) ) )
-		return rc;
-	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
-	    if ( !src.p )
-		HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
-	    else if ( ( rc = mifsk_ingest_s16(ctx, (const int16_t *)src.p, xstride,
-					      (float *)pad.p, stride, (const uint32_t *)dn.p, 0, M, rxnoise, stream) ) )
-		return rc;
-	    d_samples = (const float *)pad.p;
-	    io.stream_stride = stride;
-	    io.d_nsamples = M == 1 ? nullptr : (const uint32_t *)dn.p;
-	    io.nsamples = (uint32_t)( M == 1 ? nsamples[0] : std::min<uint64_t>(stride, 0xFFFFFFFFull) );
-	} else if ( M == 1 ) {
-	    const uint64_t stride = ( nsamples[0] + 3u ) & ~3ull;
-	    if ( stride != nsamples[0] ) {
-		if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
-		    return rc;
-		// (the one row's table, synchronised: it goes out of scope with this block)
-		const struct { StreamRef s; RowRef r; } one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
-		if ( ( rc = alloc(dn, sizeof(one), st) ) )
-		    return rc;
-		HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
-		HIP_OK(hipStreamSynchronize(st));
-		gather_rows(src, dim3(64, 1), st, (const StreamRef *)dn.p,
-			    (const RowRef *)( (char *)dn.p + sizeof(StreamRef) ), (float *)pad.p, stride, 0, 1);
-		d_samples = (const float *)pad.p;
-	    }
-	    io.stream_stride = stride ? stride : 4;
-	    io.nsamples = (uint32_t)nsamples[0];
-	} else {
+	io.d_samples = (const float *)src.p;
+	if ( src.s16 || !lone ) {		// the lengths: for mifsk_ingest_s16, and of a batch's rows
 	    std::vector<uint32_t> hn(M);
 	    for ( int m = 0; m < M; m++ )
 		hn[m] = (uint32_t)nsamples[m];
@@ -760,11 +806,33 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 		return rc;
 	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
 	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
-	    io.stream_stride = xstride;
-	    io.d_nsamples = (const uint32_t *)dn.p;
-	    io.nsamples = (uint32_t)std::min<uint64_t>(xstride, 0xFFFFFFFFull);
 	}
-	io.d_samples = d_samples;
+	if ( src.s16 ) {
+	    if ( ( rc = alloc(pad, (size_t)M * stride * sizeof(float), st) ) )
+		return rc;
+	    if ( !src.p )
+		HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
+	    else if ( ( rc = mifsk_ingest_s16(ctx, (const int16_t *)src.p, src.stride,
+					      (float *)pad.p, stride, (const uint32_t *)dn.p, 0, M, rxnoise, stream) ) )
+		return rc;
+	    io.d_samples = (const float *)pad.p;
+	} else if ( lone && nsamples[0] % 4u ) {
+	    if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
+		return rc;
+	    // (the one row's table, synchronised: it goes out of scope with this block)
+	    const struct { StreamRef s; RowRef r; } one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
+	    if ( ( rc = alloc(dn, sizeof(one), st) ) )
+		return rc;
+	    HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
+	    HIP_OK(hipStreamSynchronize(st));
+	    gather_rows(src, dim3(64, 1), st, (const StreamRef *)dn.p,
+			(const RowRef *)( (char *)dn.p + sizeof(StreamRef) ), (float *)pad.p, stride, 0, 1);
+	    io.d_samples = (const float *)pad.p;
+	}
+	io.stream_stride = stride;
+	io.d_nsamples = lone ? nullptr : (const uint32_t *)dn.p;
+	io.nsamples = (uint32_t)( lone ? nsamples[0] : std::min<uint64_t>(stride, 0xFFFFFFFFull) );
+	io.nstreams = M;
 	io.d_counters = nullptr;
 	io.flags = engine;
 	io.reserved = 0;
@@ -777,29 +845,14 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	return 0;
     }
 
-    // The rows: stream m's chunks are rows rowbase[m] .. rowbase[m] + K_m - 1, its tail (the
-    // final slab) is row R + m
     const int R = (int)nchunkrows, nrows = R + M;
     std::vector<StreamRef> hs(M);
     std::vector<RowRef> hrow(nrows);
     std::vector<uint32_t> hns(nrows, 0);
-    for ( int m = 0, r = 0; m < M; m++ ) {
-	hs[m].n = nsamples[m];
-	hs[m].tail_off = 0;
-	hs[m].rowbase = (uint32_t)r;
-	hs[m].K = ps[m].nchunks;
-	for ( uint32_t k = 0; k < hs[m].K; k++, r++ ) {
-	    hrow[r].m = (uint32_t)m;
-	    hrow[r].k = k;
-	    hns[r] = (uint32_t)( k + 1 < hs[m].K ? L + W : nsamples[m] - k * L );
-	}
-	hrow[R + m].m = (uint32_t)m;
-	hrow[R + m].k = hs[m].K;
-    }
+    row_table(nsamples, ps, R, hs, hrow, hns);
     const uint64_t rstride = ( L + W + 3u ) & ~3ull;
     const size_t fcap = mifsk_max_frames(cfg, L + W);
     const size_t ecap = mifsk_max_episodes(cfg, L + W) + 1;
-    const bool want_bytes = io_out->d_bytes != nullptr;
     DevBuf rows, X, I, S, Rr, cnt, rcnt, code, mark, rframes, rbytes, reps, pref, ns, streams, rowref, tails;
     const size_t stsz = sizeof(mifsk_stream_state);
     if ( ( rc = alloc(rows, (size_t)R * rstride * sizeof(float), st) )
@@ -810,7 +863,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	    || ( rc = alloc(code, nrows * sizeof(uint32_t), st) )
 	    || ( rc = alloc(mark, nrows, st) )
 	    || ( rc = alloc(rframes, nrows * fcap * sizeof(mifsk_frame), st) )
-	    || ( want_bytes && ( rc = alloc(rbytes, nrows * fcap, st) ) )
+	    || ( io_out->d_bytes && ( rc = alloc(rbytes, nrows * fcap, st) ) )
 	    || ( rc = alloc(reps, nrows * ecap * sizeof(mifsk_episode), st) )
 	    || ( rc = alloc(pref, ( (size_t)nrows + M ) * sizeof(Agg), st) )
 	    || ( rc = alloc(ns, nrows * sizeof(uint32_t), st) )
@@ -820,8 +873,6 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     auto *dX = (mifsk_stream_state *)X.p, *dI = (mifsk_stream_state *)I.p;
     auto *dS = (mifsk_stream_state *)S.p, *dR = (mifsk_stream_state *)Rr.p;
     auto *dcnt = (uint32_t *)cnt.p, *drcnt = (uint32_t *)rcnt.p;
-    auto *dframes = (mifsk_frame *)rframes.p;
-    auto *deps = (mifsk_episode *)reps.p;
     float *drows = (float *)rows.p;
     const auto *dstreams = (const StreamRef *)streams.p;
     const auto *drowref = (const RowRef *)rowref.p;
@@ -853,16 +904,12 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     b.stream_stride = rstride;
     b.d_nsamples = (const uint32_t *)ns.p;
     b.nsamples = (uint32_t)( L + W );
-    b.nstreams = R;
-    b.d_frames = dframes;
+    b.d_frames = (mifsk_frame *)rframes.p;
     b.d_bytes = (uint8_t *)rbytes.p;
     b.frames_cap = fcap;
-    b.d_episodes = deps;
+    b.d_episodes = (mifsk_episode *)reps.p;
     b.episodes_cap = ecap;
-    b.d_nframes = dcnt;
-    b.d_nbytes = dcnt + nrows;
-    b.d_nepisodes = dcnt + 2 * nrows;
-    b.d_status = dcnt + 3 * nrows;
+    b = rows_of(b, dcnt, nrows, 0, R);
     if ( ( rc = mifsk_demod_slab(ctx, cfg, &b, dS, nullptr, 0, stream) ) )
 	return rc;
 
@@ -884,38 +931,8 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 			   (const mifsk_stream_state *)dS, drowref, (uint32_t *)code.p, R, L, reject);
 	HIP_OK(hipMemcpyAsync(hcode.data(), code.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
 	HIP_OK(hipStreamSynchronize(st));
-	int lo = -1, hi = -1;
-	std::fill(hmark.begin(), hmark.end(), 0);
-	for ( int m = 0; m < M; m++ ) {
-	    const int r0 = (int)hs[m].rowbase, r1 = r0 + (int)hs[m].K;
-	    for ( int r = r0 + 1; r < r1; r++ ) {
-		if ( settled[r] )
-		    continue;
-		if ( !settled[r - 1] )
-		    break;
-		if ( drop[r - 1] || ( hcode[r] & 2u ) ) {
-		    drop[r] = settled[r] = 1;
-		} else if ( hcode[r] & 1u ) {
-		    settled[r] = 1;
-		    ps[m].accepted += !ran[r];
-		} else {
-		    break;
-		}
-	    }
-	    bool any = false;
-	    for ( int r = r0 + 1; r < r1; r++ )
-		if ( !settled[r] && hcode[r] == 0u ) {	// (behind a finished row: wait for it to settle)
-		    hmark[r] = 1;
-		    any = true;
-		    if ( lo < 0 )
-			lo = r;
-		    hi = r;
-		    ran[r] = 1;
-		    ps[m].rerun++;
-		    ps[m].samples_rerun += hns[r];
-		}
-	    ps[m].rounds += any;
-	}
+	int lo, hi;
+	settle_round(hcode, hs, hns, settled, drop, ran, ps, hmark, lo, hi);
 	if ( lo < 0 )
 	    break;
 	HIP_OK(hipMemcpyAsync(mark.p, hmark.data(), nrows, hipMemcpyHostToDevice, st));
@@ -923,17 +940,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	const unsigned gm = (unsigned)( ( nr + tb - 1 ) / tb );
 	hipLaunchKernelGGL(ts_seed, dim3(gm), dim3(tb), 0, st, dS, (const uint8_t *)mark.p, drowref, dR, dI,
 			   lo, hi, L);
-	mifsk_demod_io r = b;
-	r.d_samples = drows + (size_t)lo * rstride;
-	r.d_nsamples = (const uint32_t *)ns.p + lo;
-	r.nstreams = nr;
-	r.d_frames = dframes + (size_t)lo * fcap;
-	r.d_bytes = rbytes.p ? (uint8_t *)rbytes.p + (size_t)lo * fcap : nullptr;
-	r.d_episodes = deps + (size_t)lo * ecap;
-	r.d_nframes = drcnt + lo;
-	r.d_nbytes = drcnt + nrows + lo;
-	r.d_nepisodes = drcnt + 2 * nrows + lo;
-	r.d_status = drcnt + 3 * nrows + lo;
+	const mifsk_demod_io r = rows_of(b, drcnt, nrows, lo, nr);
 	if ( ( rc = mifsk_demod_slab(ctx, cfg, &r, dR + lo, nullptr, 0, stream) ) )
 	    return rc;
 	hipLaunchKernelGGL(ts_merge, dim3(gm), dim3(tb), 0, st, (const mifsk_stream_state *)dR,
@@ -976,19 +983,10 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	HIP_OK(hipMemcpyAsync((uint32_t *)ns.p + R, hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
 	gather_tails(src, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), st, dstreams, (float *)tails.p,
 		     tstride, M);
-	mifsk_demod_io t = b;
+	mifsk_demod_io t = rows_of(b, dcnt, nrows, R, M);
 	t.d_samples = (const float *)tails.p;
 	t.stream_stride = tstride;
-	t.d_nsamples = (const uint32_t *)ns.p + R;
 	t.nsamples = (uint32_t)longest_tail;
-	t.nstreams = M;
-	t.d_frames = dframes + (size_t)R * fcap;
-	t.d_bytes = rbytes.p ? (uint8_t *)rbytes.p + (size_t)R * fcap : nullptr;
-	t.d_episodes = deps + (size_t)R * ecap;
-	t.d_nframes = dcnt + R;
-	t.d_nbytes = dcnt + nrows + R;
-	t.d_nepisodes = dcnt + 2 * nrows + R;
-	t.d_status = dcnt + 3 * nrows + R;
 	if ( ( rc = mifsk_demod_slab(ctx, cfg, &t, dS + R, nullptr, 1, stream) ) )
 	    return rc;
     }
@@ -1005,9 +1003,9 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     sa.rowref = drowref;
     sa.nrows = nrows;
     sa.R = R;
-    sa.rframes = dframes;
-    sa.rbytes = (const uint8_t *)rbytes.p;
-    sa.reps = deps;
+    sa.rframes = b.d_frames;
+    sa.rbytes = b.d_bytes;
+    sa.reps = b.d_episodes;
     sa.fcap = fcap;
     sa.ecap = ecap;
     sa.L = L;

@@ -228,6 +228,46 @@ def test_host_memory_equals_the_device_source(gpu, name, source):
     assert (hs["seconds_staging"] > 0) == (source != "s16_pinned"), hs
 
 
+@pytest.mark.parametrize("source", ["s16", "f32_rxnoise"])
+def test_pageable_recording_of_three_staging_pieces_equals_the_device_source(gpu, source):
+    """A staging piece is 64 MB of input, and three pieces are the least with which one of the two
+    staging buffers is used again: a recording of two whole pieces and 100,003 samples in ordinary
+    numpy memory, beside one of a few seconds (the second row's offset in the device buffer), under
+    the library's own plan.  Bit for bit demod_long_batch over the same samples as a tensor (the
+    floats: after ingest_rxnoise)."""
+    M, torch, ctx = gpu
+    s16 = source == "s16"
+    g = G.load("t01_1200")
+    cfg = M.rx_config(**g["cfg_kwargs"])
+    assert g["stored"].dtype == np.int16 and cfg.sample_rate == 48000
+    unit = _quantise(_recording(g["stored"].astype(np.float32) / np.float32(32768.0), np.random.default_rng(31)))
+    esz, rxnoise = (2, 0.0) if s16 else (4, 0.05)
+    n = 2 * ((64 << 20) // esz) + 100003
+    assert n == (2 * 33554432 if s16 else 2 * 16777216) + 100003
+    pcm = [np.tile(unit, n // len(unit) + 1)[:n], np.tile(unit, 2)[:4 * 48000 + 5]]
+    lens = [len(x) for x in pcm]
+    if s16:
+        arrays = pcm
+        d, _ = _upload_pcm(torch, pcm)
+    else:
+        arrays = [x.astype(np.float32) / np.float32(32768.0) for x in pcm]
+        d = torch.zeros((2, (n + 3) & ~3), dtype=torch.float32, device="cuda")
+        for i, a in enumerate(arrays):
+            d[i, :len(a)] = torch.from_numpy(a).cuda()
+        d = M.ingest_rxnoise(ctx, d, rxnoise, nsamples=torch.tensor(lens, dtype=torch.int32, device="cuda"))
+    want, want_st = _split(M, ctx, cfg, d, lens)
+    del d
+    got = M.demod_long_host(ctx, cfg, arrays, want=WANT, rxnoise=rxnoise, stats=True)
+    st, hs = got["stats"], got["host_stats"]
+    assert st == want_st and st[0]["nchunks"] >= 2 and st[1]["nchunks"] == 1, st
+    for i in range(2):
+        _same(got, i, want, i, cfg, (source, i, st[i]))
+    assert int(got["nframes"][0]) > 1000 and int(got["nframes"][1]) > 0
+    assert hs["chunks"] == 4 and hs["streams"] == 2, hs
+    assert hs["source_pinned"] == 0 and hs["seconds_staging"] > 0, hs
+    assert hs["bytes_h2d"] == sum(lens) * esz, hs
+
+
 # ---- E: files ---------------------------------------------------------------------------------
 
 def _write_stereo(path, rate):
@@ -287,6 +327,46 @@ def test_files_time_split_equals_demod_files(gpu, tmp_path):
         assert hs["streams"] == 4 and hs["bytes_h2d"] == sum(os.path.getsize(p) - 44 for p in paths
                                                              if "long" in p)
     assert all("time_split" not in d for d in want)
+
+
+def test_unreadable_file_under_the_time_split_is_its_own_error(gpu, tmp_path, monkeypatch):
+    """tests/test_gpu_files.py's unreadable file, under the time split: four long WAVs as above, the
+    samples of one cannot be read after its header was parsed.  It fails alone (-EIO, no plan
+    figures), the call returns normally, and every other file -- the two of its own group, whose
+    rows lie beside its row of zeros, included -- is what plain demod_files gives for it."""
+    M, torch, ctx = gpu
+    g = G.load("t01_1200")
+    cfg = M.rx_config("1200")
+    rng = np.random.default_rng(78)
+    burst = _bursty(M, cfg, 70, rng, snr_db=20)
+    rec = _recording(g["samples"], rng, copies=3, sample_rate=48000)
+    paths = []
+    for i, seconds in enumerate((45.3, 70.0, 58.1, 52.7)):
+        x = np.roll(burst, int(rng.integers(0, len(burst))))[:int(seconds * 48000) - i]
+        x[1000:1000 + len(rec)] = rec[:len(x) - 1000]
+        p = str(tmp_path / ("%s%d.wav" % ("shrunk" if i == 1 else "long", i)))
+        if i == 3:
+            O.write_wav(p, x, 48000, False)
+        else:
+            O.write_wav(p, _quantise(x * np.float32(0.8)), 48000, True)
+        paths.append(p)
+    want, _ = M.demod_files(ctx, paths, "1200")
+    assert [d["error"] for d in want] == [0, 0, 0, 0]
+    monkeypatch.setenv("MIFSK_EXPERIMENT", "1")
+    monkeypatch.setenv("MIFSK_TEST_FAULT_READ", "shrunk")
+    got, hs = M.demod_files(ctx, paths, "1200", time_split=True)
+    assert len(got) == 4 and hs["streams"] == 4
+    for a, b in zip(got, want):
+        if "shrunk" in a["path"]:
+            assert a["error"] == -5, a["error"]            # -EIO, this file only
+            assert "time_split" not in a
+            continue
+        assert a["error"] == 0, (a["path"], a["error"])
+        assert len(b["bytes"]) > 100 and a["bytes"] == b["bytes"], a["path"]
+        assert a["bits"].tobytes() == b["bits"].tobytes(), a["path"]
+        assert a["episodes"].tobytes() == b["episodes"].tobytes(), a["path"]
+        assert a["status"] == b["status"] and a["carrier_band"] == b["carrier_band"]
+        assert a["time_split"]["nchunks"] >= 2, a["time_split"]
 
 
 # ---- F: speed ---------------------------------------------------------------------------------
