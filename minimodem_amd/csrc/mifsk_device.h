@@ -227,23 +227,36 @@ struct WaveGeom {
     uint32_t	tw_entries;	// samples per per-stream twiddle table
 };
 
+// Streams that arrive in pieces (mifsk_demod_slab) and chained launches: what a resumable
+// instantiation of either engine's kernel needs beyond the batch itself.
+// The plain instantiations ignore all of it.
+struct ResumeArgs {
+    mifsk_stream_state	*d_state;	// [nstreams] the loop's state between calls (NULL: one call = whole streams)
+    const uint64_t	*d_origin;	// [nstreams] stream index of each row's first sample (NULL: 0)
+    uint32_t		final;		// the rows end where the streams end
+    uint32_t		limit;		// chained launch: this call sees the first `limit` samples of every
+					// row (a row that ends before is complete); 0 = all
+    uint32_t		append;		// chained launch: outputs continue behind the chunk before (state: n*_total)
+};
+// ... filled here and nowhere else: by the launchers for one launch over the caller's rows, by
+// chain_enqueue for a chunk of a chained launch
+inline ResumeArgs resume_args( mifsk_stream_state *d_state, const uint64_t *d_origin, bool final,
+	uint32_t limit = 0u, uint32_t append = 0u )
+{
+    return ResumeArgs{d_state, d_origin, final ? 1u : 0u, limit, append};
+}
+
 struct WaveAuto {
     const double	*d_cs;		// [fftsize][2]: cos, -sin of 2 pi k / fftsize
     double		*d_tw_scratch;	// [nstreams][tw_entries][4]
     float		*d_ring;	// [nstreams][ring_stride], zero-initialised
-    // mifsk_demod_slab: the loop's state between calls (NULL: one call = one whole stream)
-    mifsk_stream_state	*d_state;
-    const uint64_t	*d_origin;	// stream index of each row's first sample (NULL: 0)
-    uint32_t		final;		// the rows end where the streams end
-    uint32_t		limit;		// chained launches: this call sees the first `limit` samples of
-					// every row (a row that ends before is complete); 0 = all
+    ResumeArgs		rs;
     // shared segments: the rotation factor of segment i of window w of scan `kind`, laid out
     // [i][w] so that the lanes of the assembly (lane = window) read consecutive entries:
     // d_rot[kind][(i * rot_stride[kind] + w) * 4 .. + 3] = table entry of the segment's offset
     // inside the window (NULL: gathered from the stream's own table -- --auto-carrier)
     const double	*d_rot[5];
     uint32_t		rot_stride[5];
-    uint32_t		append;		// outputs continue behind the call before (state: n*_total)
 };
 
 // Chained launches.  A batch of more streams than the chip holds runs in rounds of serial
@@ -278,11 +291,11 @@ inline void chain_shape( bool allowed, int nstreams, uint32_t &groups, uint32_t 
 	groups = chunks = 0u;
 }
 
-// Enqueue a batch as `groups` x `chunks` launches.  `launch(gio, lo, d_state, final, limit, gs)`
-// enqueues the resumable kernel over the rows `gio` (those from row `lo` of the batch) on the
-// group's stream `gs`: state in / out at d_state, the first `limit` samples of every row (0: all),
-// outputs appended behind the chunk before.  The caller's stream waits for all of it, whatever
-// fails on the way.
+// Enqueue a batch as `groups` x `chunks` launches.  `launch(gio, lo, rs, gs)` enqueues the
+// resumable kernel over the rows `gio` (those from row `lo` of the batch) on the group's stream
+// `gs` with the resume arguments `rs`: state in / out, the first `limit` samples of every row
+// (0: all), outputs appended behind the chunk before.  The caller's stream waits for all of it,
+// whatever fails on the way.
 template <class Launch>
 int chain_enqueue( const WaveChain &ch, const mifsk_demod_io &io, uint32_t groups, uint32_t chunks,
 	hipStream_t st, Launch launch )
@@ -320,8 +333,8 @@ int chain_enqueue( const WaveChain &ch, const mifsk_demod_io &io, uint32_t group
 	const uint64_t lim = (uint64_t)( k + 1u ) * chunk;
 	for ( uint32_t gi = 0; gi < groups; gi++ )
 	    if ( gio[gi].nstreams > 0 )
-		launch(gio[gi], glo[gi], ch.d_state + glo[gi], last,
-		       last ? 0u : ( lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim ), (hipStream_t)ch.streams[gi]);
+		launch(gio[gi], glo[gi], resume_args(ch.d_state + glo[gi], nullptr, last,
+			last ? 0u : ( lim > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)lim ), 1u), (hipStream_t)ch.streams[gi]);
     }
     const bool launched = hipGetLastError() == hipSuccess && prepared;
     for ( uint32_t gi = 0; gi < groups; gi++ ) {

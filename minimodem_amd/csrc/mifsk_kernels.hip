@@ -786,15 +786,9 @@ struct Master {
 // kernel stores can change *cfgp, and without that every configuration read inside the loop
 // is a vector load plus v_readfirstlane instead of a scalar load (measured with a struct
 // parameter: configs[1] 0.45 -> 0.54 ms, 12000 baud 1.29 -> 1.89 ms).
-// streams that arrive in pieces (mifsk_demod_slab) and chained launches: what the resumable
-// instantiation demod_kernel<., ., ., true> needs beyond the batch itself (DESIGN.md 4.10,
-// 4.11; the wavefront engine's WaveAuto carries the same five)
-struct WgResume {
-    mifsk_stream_state	*d_state;	// [nstreams] or null (then the kernel behaves as the plain one)
-    const uint64_t	*d_origin;	// [nstreams] index of each row's first sample in its stream, or null
-    uint32_t		final;		// no more samples will follow these rows
-    uint32_t		limit;		// chained launch: this call sees the first `limit` samples of a row (0: all)
-    uint32_t		append;		// chained launch: outputs continue behind the chunk before
+// what the resumable instantiation demod_kernel<., ., ., true> needs beyond the batch itself:
+// the resume arguments both engines take (mifsk_device.h), and
+struct WgResume : ResumeArgs {
     uint32_t		bufsize;	// the reference's samplebuf_size (minimodem.c:1056-1069)
 };
 
@@ -1191,19 +1185,9 @@ __device__ __forceinline__ void master_loop( const DevCfg &cfg, const double *__
 
 	if ( confidence <= h_thr ) {				// minimodem.c:1292-1321
 	    if ( ++noconfidence > 20u ) {
-		    if ( carrier ) {
-
-			if ( t0 && o.eps && n_out_eps < o.ecap ) {
-			    mifsk_episode e;
-			e.carrier_nsamples = carrier_nsamples;
-			e.first_frame = ep_first;
-			e.nframes = nframes_decoded;
-			e.confidence_total = confidence_total;
-			e.amplitude_total = amplitude_total;
-			e.end_reason = 1;
-			e.b_mark = cfg.b_mark;
-			o.eps[n_out_eps] = e;
-		    }
+		if ( carrier ) {
+		    store_episode(o, t0, n_out_eps, carrier_nsamples, ep_first, nframes_decoded,
+				  confidence_total, amplitude_total, 1u, cfg.b_mark);
 		    n_out_eps++;
 		    carrier = false;
 		    carrier_nsamples = 0;
@@ -1358,17 +1342,8 @@ __device__ __forceinline__ void master_loop( const DevCfg &cfg, const double *__
 	}
     }
     if ( carrier && !( ST && ( paused || !resumable ) ) ) {	// minimodem.c:1469-1474
-	if ( t0 && o.eps && n_out_eps < o.ecap ) {
-	    mifsk_episode e;
-	    e.carrier_nsamples = carrier_nsamples;
-	    e.first_frame = ep_first;
-	    e.nframes = nframes_decoded;
-	    e.confidence_total = confidence_total;
-	    e.amplitude_total = amplitude_total;
-	    e.end_reason = 2;
-	    e.b_mark = cfg.b_mark;
-	    o.eps[n_out_eps] = e;
-	}
+	store_episode(o, t0, n_out_eps, carrier_nsamples, ep_first, nframes_decoded,
+		      confidence_total, amplitude_total, 2u, cfg.b_mark);
 	n_out_eps++;
     }
     // (append: a stream the call before finished keeps the outputs that call wrote)
@@ -2052,9 +2027,7 @@ static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const do
     // (the plain instantiations ignore all of it)
     WgResume rs;
     std::memset(&rs, 0, sizeof(rs));
-    rs.d_state = ha.d_state;
-    rs.d_origin = ha.d_origin;
-    rs.final = ha.final ? 1u : 0u;
+    static_cast<ResumeArgs &>(rs) = resume_args(ha.d_state, ha.d_origin, ha.final);
     rs.bufsize = ha.samplebuf_size;
     if ( hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all) != hipSuccess )
 	return -5;
@@ -2067,13 +2040,9 @@ static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const do
 	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(block), kargs, lds_all, on);
     };
     if ( chain_g ) {
-	rs.append = 1u;
-	rs.d_origin = nullptr;
 	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
-		[&]( const mifsk_demod_io &rows, uint32_t, mifsk_stream_state *d_state, bool last, uint32_t limit, hipStream_t gs ) {
-		    rs.d_state = d_state;
-		    rs.final = last ? 1u : 0u;
-		    rs.limit = limit;
+		[&]( const mifsk_demod_io &rows, uint32_t, const ResumeArgs &chunk, hipStream_t gs ) {
+		    static_cast<ResumeArgs &>(rs) = chunk;
 		    launch(rows, gs);
 		});
     }

@@ -1,6 +1,6 @@
 // mifsk_rxloop.h -- what the two receive-loop kernels (master_loop in mifsk_kernels.hip,
 // demod_wave_kernel in mifsk_wave.hip) set up in the same way: the length of a row, the cut of
-// a chained launch, and where a stream's results go.
+// a chained launch, where a stream's results go, and a carrier episode's record.
 // gfx950 only; included by .hip files only.
 #pragma once
 
@@ -55,5 +55,26 @@ struct StreamOut {
 	return o;
     }
 };
+
+// One carrier episode (minimodem.c:1292-1321 at carrier loss: end_reason 1; :1469-1474 at the
+// end of the stream: 2), stored at index n_out_eps by the lane that is `writer`, if the caller
+// wants episodes and has room.  The kernel counts it either way.  The loop state is taken by
+// value: the kernels keep it in plain local scalars.
+__device__ __forceinline__ void store_episode( const StreamOut &o, bool writer, uint32_t n_out_eps,
+	uint64_t carrier_nsamples, uint32_t ep_first, uint32_t nframes_decoded, float confidence_total,
+	float amplitude_total, uint32_t end_reason, uint32_t b_mark )
+{
+    if ( writer && o.eps && n_out_eps < o.ecap ) {
+	mifsk_episode e;
+	e.carrier_nsamples = carrier_nsamples;
+	e.first_frame = ep_first;
+	e.nframes = nframes_decoded;
+	e.confidence_total = confidence_total;
+	e.amplitude_total = amplitude_total;
+	e.end_reason = end_reason;
+	e.b_mark = b_mark;
+	o.eps[n_out_eps] = e;
+    }
+}
 
 } // namespace mifsk

@@ -1208,8 +1208,9 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
     const bool autodetect = RA && g.autodetect;
     if ( ring )
 	lattice_ok = false;			// RING addressing: every frame through the general path
-    // chained launches (launch_demod_wave): this call takes the stream up to au.limit only
-    const bool cut = chain_cut<ST>(au.d_state, au.limit, N);
+    // chained launches (launch_demod_wave): this call takes the stream up to au.rs.limit only
+    const bool cut = chain_cut<ST>(au.rs.d_state, au.rs.limit, N);
+    const ResumeArgs &rs = au.rs;
     const double *tw = tw_default;
     double *tw_own = nullptr;
     if ( autodetect ) {
@@ -1249,20 +1250,20 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
     // from the state the call before left (minimodem.c:1079-1088,1132-1133,1144-1174).
     // Positions inside the kernel are relative to the row; what leaves it (frame starts,
     // episode frame indices, the saved state) counts from the start of the stream.
-    const bool stateful = ST && au.d_state != nullptr;
-    const bool last_slab = !stateful || au.final != 0u || ( au.limit != 0u && !cut );
+    const bool stateful = ST && rs.d_state != nullptr;
+    const bool last_slab = !stateful || rs.final != 0u || ( rs.limit != 0u && !cut );
     uint64_t origin = 0;
     uint32_t frame_base = 0;			// frames emitted by the calls before
     bool resumable = true;
     if ( stateful ) {
-	if ( au.d_origin )
-	    origin = au.d_origin[s];
-	const mifsk_stream_state st = au.d_state[s];
+	if ( rs.d_origin )
+	    origin = rs.d_origin[s];
+	const mifsk_stream_state st = rs.d_state[s];
 	if ( st.flags & MIFSK_STATE_FINISHED ) {
 	    resumable = false;			// nothing more to do for this stream
 	    // (a stream whose loop was aborted stays aborted for its caller; a chained launch's
 	    // later chunks leave the status word the failed chunk wrote alone -- below)
-	    if ( au.append == 0u )
+	    if ( rs.append == 0u )
 		status |= st.status & MIFSK_STREAM_ABORTED;
 	} else if ( st.flags & MIFSK_STATE_STARTED ) {
 	    if ( st.base < origin || st.base - origin > (uint64_t)N || st.rp < st.base ) {
@@ -1286,7 +1287,7 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 		ep_b_mark = st.ep_b_mark;
 		ep_first = st.ep_first;
 		frame_base = (uint32_t)st.nframes_total;
-		if ( au.append ) {
+		if ( rs.append ) {
 		    // the outputs continue where the call before stopped instead of at index 0
 		    n_out_frames = frame_base;
 		    n_out_bytes = st.nbytes_total;
@@ -1323,7 +1324,7 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
     // and carried in the saved state: nowhere else (the lattice replay skips them otherwise)
     // (a chained launch saves state too, but only for its own next chunk, which wants what this
     // one wants)
-    const bool want_totals = o.eps != nullptr || ( ST && au.append == 0u );
+    const bool want_totals = o.eps != nullptr || ( ST && rs.append == 0u );
 
     // every pass through the loop moves the cursor forward (or ends the loop):
     // a bound far above anything reachable turns a logic error into a flagged
@@ -1627,19 +1628,9 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 	if ( confidence <= cfg.conf_threshold ) {		// minimodem.c:1292-1321
 	    if ( ++noconfidence > 20u ) {
 		carrier_band = -1;				// :1297
-		    if ( carrier ) {
-
-			if ( t0 && o.eps && n_out_eps < o.ecap ) {
-			mifsk_episode e;
-			e.carrier_nsamples = carrier_nsamples;
-			e.first_frame = ep_first;
-			e.nframes = nframes_decoded;
-			e.confidence_total = confidence_total;
-			e.amplitude_total = amplitude_total;
-			e.end_reason = 1;
-			e.b_mark = ep_b_mark;
-			o.eps[n_out_eps] = e;
-		    }
+		if ( carrier ) {
+		    store_episode(o, t0, n_out_eps, carrier_nsamples, ep_first, nframes_decoded,
+				  confidence_total, amplitude_total, 1u, ep_b_mark);
 		    n_out_eps++;
 		    carrier = false;
 		    carrier_nsamples = 0;
@@ -1725,7 +1716,6 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 	cyc_general += MIFSK_WCLOCK() - t_gen;
     }
 
-
     if ( stateful && t0 && !( status & MIFSK_STREAM_ABORTED ) && resumable ) {
 	mifsk_stream_state st;
 	st.base = origin + base;
@@ -1747,35 +1737,26 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 	st.ep_b_mark = ep_b_mark;
 	st.ep_first = ep_first;
 	// (totals: read back rather than carried through the loop)
-	const uint32_t b0 = au.append ? 0u : au.d_state[s].nbytes_total, e0 = au.append ? 0u : au.d_state[s].nepisodes_total;
+	const uint32_t b0 = rs.append ? 0u : rs.d_state[s].nbytes_total, e0 = rs.append ? 0u : rs.d_state[s].nepisodes_total;
 	st.nbytes_total = b0 + n_out_bytes;
 	st.nepisodes_total = e0 + n_out_eps;
-	st.status = au.d_state[s].status | status;
-	au.d_state[s] = st;
+	st.status = rs.d_state[s].status | status;
+	rs.d_state[s] = st;
     } else if ( stateful && t0 && ( status & MIFSK_STREAM_ABORTED ) ) {
 	// aborted in this call: no later call (or chunk of a chained launch) resumes the
 	// stream from the state of the call before and re-emits over the same outputs
-	mifsk_stream_state st = au.d_state[s];
+	mifsk_stream_state st = rs.d_state[s];
 	st.flags |= MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
 	st.status |= MIFSK_STREAM_ABORTED;
-	au.d_state[s] = st;
+	rs.d_state[s] = st;
     }
     if ( carrier && !paused && resumable ) {			// minimodem.c:1469-1474
-	if ( t0 && o.eps && n_out_eps < o.ecap ) {
-	    mifsk_episode e;
-	    e.carrier_nsamples = carrier_nsamples;
-	    e.first_frame = ep_first;
-	    e.nframes = nframes_decoded;
-	    e.confidence_total = confidence_total;
-	    e.amplitude_total = amplitude_total;
-	    e.end_reason = 2;
-	    e.b_mark = ep_b_mark;
-	    o.eps[n_out_eps] = e;
-	}
+	store_episode(o, t0, n_out_eps, carrier_nsamples, ep_first, nframes_decoded,
+		      confidence_total, amplitude_total, 2u, ep_b_mark);
 	n_out_eps++;
     }
     // (append: a stream the call before finished keeps the outputs that call wrote)
-    if ( t0 && !( ST && au.append != 0u && !resumable && status == 0u ) ) {
+    if ( t0 && !( ST && rs.append != 0u && !resumable && status == 0u ) ) {
 	if ( n_out_frames > o.fcap && ( o.bits || o.frames || o.bytes ) )
 	    status |= MIFSK_STREAM_FRAMES_TRUNCATED;
 	if ( n_out_eps > o.ecap && o.eps )
@@ -2149,11 +2130,7 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
     au.d_cs = ha.d_cs;
     au.d_tw_scratch = ha.d_tw_scratch;
     au.d_ring = ha.d_ring;
-    au.d_state = ha.d_state;
-    au.d_origin = ha.d_origin;
-    au.final = ha.final ? 1u : 0u;
-    au.limit = 0u;
-    au.append = 0u;
+    au.rs = resume_args(ha.d_state, ha.d_origin, ha.final);
     for ( int k = 0; k < 5; k++ ) {
 	au.d_rot[k] = ha.d_rot[k];
 	au.rot_stride[k] = ha.rot_stride[k];
@@ -2165,13 +2142,9 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
 	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(64), kargs, plan.lds_bytes, on);
     };
     if ( chain_g ) {
-	au.append = 1u;
-	au.d_origin = nullptr;
 	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
-		[&]( const mifsk_demod_io &rows, uint32_t lo, mifsk_stream_state *d_state, bool last, uint32_t limit, hipStream_t gs ) {
-		    au.d_state = d_state;
-		    au.final = last ? 1u : 0u;
-		    au.limit = limit;
+		[&]( const mifsk_demod_io &rows, uint32_t lo, const ResumeArgs &rs, hipStream_t gs ) {
+		    au.rs = rs;
 		    if ( ha.d_tw_scratch )		// (--auto-carrier: the group's streams' own tables)
 			au.d_tw_scratch = ha.d_tw_scratch + (size_t)lo * g.tw_entries * 4u;
 		    launch(rows, gs);

@@ -201,3 +201,66 @@ def test_stream_longer_than_one_call_keeps_only_a_samplebuf_of_history(gpu, engi
             assert len(sess.tail[0]) == fed - int(res["state"]["base"][0])
     ref = O.oracle_rx_stream(ocfg, x)
     assert np.concatenate(frames).tobytes() == ref["frames"].tobytes()
+
+
+STREAM_ABORTED = 4                      # MIFSK_STREAM_ABORTED (include/mifsk.h)
+STATE_STARTED = 1                       # MIFSK_STATE_STARTED
+
+
+@pytest.fixture(scope="module")
+def dropped(gpu):
+    """Two streams of t02_300 on each engine: a first, non-final half; then stream 0's caller
+    drops four samples the loop still needs (d_origin four past the saved base); the rest, final;
+    one further empty final feed.  Made once: {engine: the three feeds' results}, and the oracle."""
+    M, torch, ctx = gpu
+    g = G.load("t02_300")
+    cfg = M.rx_config(**g["cfg_kwargs"])
+    x = g["samples"]
+    cut = len(x) // 2
+    assert cut > 2 * int(cfg.samplebuf_size)
+    feeds = {}
+    for engine in ("wave", "workgroup"):
+        sess = M.SlabSession(ctx, cfg, 2, episodes_cap=32, engine=engine)
+        f = [sess.feed([x[:cut], x[:cut]], final=False)]
+        assert int(sess.origin[0]) == int(f[0]["state"]["base"][0]) and len(sess.tail[0]) > 4
+        sess.origin[0] += 4
+        sess.tail[0] = sess.tail[0][4:]
+        f.append(sess.feed([x[cut:], x[cut:]], final=True))
+        f.append(sess.feed([None, None], final=True))
+        feeds[engine] = f
+    return feeds, O.oracle_rx_stream(O.oracle_config(**g["cfg_kwargs"]), x)
+
+
+@pytest.mark.parametrize("engine", ["wave", "workgroup"])
+def test_dropped_samples_flag_the_stream_and_spare_its_neighbour(gpu, dropped, engine):
+    """A caller that drops samples the loop still needs: the stream's status gets
+    MIFSK_STREAM_ABORTED, its record is marked finished and later calls leave it alone
+    (include/mifsk.h; the kernels' "the caller dropped samples the loop still needs").  The
+    stream beside it in the batch is decoded as if nothing had happened, and both engines report
+    the same status words and state flags."""
+    M, torch, ctx = gpu
+    all_feeds, ref = dropped
+    feeds = all_feeds[engine]
+    for fl in feeds[0]["state"]["flags"]:
+        assert int(fl) & STATE_STARTED and not int(fl) & M.STATE_FINISHED
+
+    n0 = int(feeds[0]["nframes"][0])
+    assert int(feeds[0]["status"][0]) == 0
+    assert feeds[0]["frames"][0, :n0].tobytes() == ref["frames"][:n0].tobytes()
+    for res in feeds[1:]:
+        assert int(res["status"][0]) & STREAM_ABORTED
+        assert int(res["nframes"][0]) == 0
+        flags = int(res["state"]["flags"][0])
+        assert flags & STATE_STARTED and flags & M.STATE_FINISHED
+
+    frames = np.concatenate([r["frames"][1, :int(r["nframes"][1])] for r in feeds])
+    eps = np.concatenate([r["episodes"][1, :int(r["nepisodes"][1])] for r in feeds])
+    data = b"".join(r["bytes"][1, :int(r["nbytes"][1])].tobytes() for r in feeds)
+    assert all(int(r["status"][1]) == 0 for r in feeds)
+    assert frames.tobytes() == ref["frames"].tobytes()
+    assert data == ref["bytes"]
+    assert eps.tobytes() == ref["episodes"].tobytes()
+
+    def words(e):
+        return [(int(r["status"][0]), int(r["state"]["flags"][0])) for r in all_feeds[e]]
+    assert words("wave") == words("workgroup")
