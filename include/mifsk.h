@@ -172,6 +172,33 @@ size_t mifsk_abi_sizeof( const char *name );
  * [3] values evaluated.  Synchronous. */
 int mifsk_selftest_sqrt( mifsk_ctx *ctx, uint64_t seed, uint64_t nvalues, uint64_t counts[4] );
 
+/* Diagnostics: the device arithmetic the receive kernels rest on (csrc/mifsk_devlib.h,
+ * csrc/mifsk_devmath.h), evaluated per value on HOST arrays (copied in and out; synchronous) so
+ * that a caller can compare it with a reference of its own (tests/test_gpu_devmath.py).  The
+ * kernels call the routines themselves.  -EINVAL for a null pointer; n = 0 does nothing.
+ *
+ * _rcp: rcp_out[i] = the double reciprocal of c[i] that stands in for a float division,
+ *   quot_out[i] = x[i] / c[i] made with it (exact for finite non-zero c[i] and a quotient that
+ *   is not subnormal).
+ * _mag: with s = (float)re[i]^2 + (float)im[i]^2 as the magnitude of a band builds it:
+ *   sqrt_out[i] = the exact sequence's sqrt(s), g_out[i] / unsafe_out[i] = the short sequence's
+ *   root and its verdict (1: this value needs the exact sequence), mag_out[i] = the band
+ *   magnitude (float)sqrt(s) * scalar.
+ * _confidence: `ncases` frames of `n_bits` bits, mags[case][bit] = { mark, space } magnitude,
+ *   through the confidence pass -- variant 0: the generic one, 1: the wavefront engine's choice
+ *   (specialised at 8, 10 and 11 bits), 2: the workgroup engine's.  Case i runs on lane i % 64 of
+ *   wave i / 64: the specialised passes send a whole wave through their division arm when any of
+ *   its lanes needs it, and say so in fell_back_out[i].  req_mask / req_val: the required bits;
+ *   a frame that misses them gives 0, 0, 0.  -EINVAL for n_bits = 0 or > MIFSK_MAX_FRAME_BITS
+ *   and for a variant that does not exist. */
+int mifsk_selftest_rcp( mifsk_ctx *ctx, const float *c, const float *x, uint64_t n,
+	double *rcp_out, float *quot_out );
+int mifsk_selftest_mag( mifsk_ctx *ctx, const double *re, const double *im, float scalar, uint64_t n,
+	double *sqrt_out, double *g_out, uint8_t *unsafe_out, float *mag_out );
+int mifsk_selftest_confidence( mifsk_ctx *ctx, int variant, uint32_t n_bits, uint64_t req_mask,
+	uint64_t req_val, const float *mags, uint64_t ncases, float *conf_out, float *ampl_out,
+	uint64_t *bits_out, uint32_t *fell_back_out );
+
 /* ---- N independent fsk_find_frame() problems --------------------------- */
 
 typedef struct mifsk_search {

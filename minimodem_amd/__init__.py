@@ -98,6 +98,51 @@ class Context:
             raise RuntimeError("mifsk_selftest_sqrt failed: %d" % rc)
         return tuple(int(c) for c in counts)
 
+    def selftest_rcp(self, c, x):
+        """mifsk_selftest_rcp: float arrays c, x -> (the device's double reciprocal of c, the
+        quotient x / c it makes with it)."""
+        c = np.ascontiguousarray(c, np.float32)
+        x = np.ascontiguousarray(x, np.float32)
+        assert c.shape == x.shape and c.ndim == 1
+        rc_out, q = np.empty(c.shape, np.float64), np.empty(c.shape, np.float32)
+        rc = self._lib.mifsk_selftest_rcp(self.handle, c.ctypes.data, x.ctypes.data, c.size,
+                                          rc_out.ctypes.data, q.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_rcp failed: %d" % rc)
+        return rc_out, q
+
+    def selftest_mag(self, re, im, scalar=1.0):
+        """mifsk_selftest_mag: double arrays re, im -> (sqrt_sumsq(s), sqrt_newton1(s)'s g, its
+        `unsafe` flag, band_mag(re, im, scalar)) with s as band_mag builds it."""
+        re = np.ascontiguousarray(re, np.float64)
+        im = np.ascontiguousarray(im, np.float64)
+        assert re.shape == im.shape and re.ndim == 1
+        root, g = np.empty(re.shape, np.float64), np.empty(re.shape, np.float64)
+        unsafe, mag = np.empty(re.shape, np.uint8), np.empty(re.shape, np.float32)
+        rc = self._lib.mifsk_selftest_mag(self.handle, re.ctypes.data, im.ctypes.data, float(scalar),
+                                          re.size, root.ctypes.data, g.ctypes.data,
+                                          unsafe.ctypes.data, mag.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_mag failed: %d" % rc)
+        return root, g, unsafe, mag
+
+    def selftest_confidence(self, variant, mags, req_mask=0, req_val=0):
+        """mifsk_selftest_confidence: mags[ncases, n_bits, 2] = (mark, space) magnitudes ->
+        (conf, ampl, bits, fell_back) per case; case i runs on lane i % 64 of wave i / 64.
+        variant 0: frame_confidence, 1: frame_confidence_any, 2: frame_confidence_any_staged."""
+        mags = np.ascontiguousarray(mags, np.float32)
+        assert mags.ndim == 3 and mags.shape[2] == 2
+        n = mags.shape[0]
+        conf, ampl = np.empty(n, np.float32), np.empty(n, np.float32)
+        bits, fb = np.empty(n, np.uint64), np.empty(n, np.uint32)
+        rc = self._lib.mifsk_selftest_confidence(self.handle, int(variant), mags.shape[1],
+                                                 int(req_mask), int(req_val), mags.ctypes.data, n,
+                                                 conf.ctypes.data, ampl.ctypes.data,
+                                                 bits.ctypes.data, fb.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_confidence failed: %d" % rc)
+        return conf, ampl, bits, fb
+
     def close(self):
         if self.handle:
             self._lib.mifsk_ctx_destroy(self.handle)

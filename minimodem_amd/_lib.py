@@ -250,6 +250,7 @@ EXPORTS = [
     "mifsk_demod_files", "mifsk_files_count", "mifsk_files_get", "mifsk_files_stats",
     "mifsk_files_free", "mifsk_demod_slab", "mifsk_scan_plan_get",
     "mifsk_demod_slab_ring", "mifsk_ring_floats", "mifsk_selftest_sqrt",
+    "mifsk_selftest_rcp", "mifsk_selftest_mag", "mifsk_selftest_confidence",
     "mifsk_pipeline_create", "mifsk_pipeline_destroy", "mifsk_pipeline_info_get",
     "mifsk_pipeline_outputs_alloc", "mifsk_pipeline_outputs_get", "mifsk_pipeline_submit",
     "mifsk_pipeline_next_ticket", "mifsk_pipeline_wait", "mifsk_pipeline_join",
@@ -431,6 +432,15 @@ def load():
     lib.mifsk_session_pending.argtypes = [C.c_void_p, C.c_int]
     lib.mifsk_selftest_sqrt.restype = C.c_int
     lib.mifsk_selftest_sqrt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.mifsk_selftest_rcp.restype = C.c_int
+    lib.mifsk_selftest_rcp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.mifsk_selftest_mag.restype = C.c_int
+    lib.mifsk_selftest_mag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mifsk_selftest_confidence.restype = C.c_int
+    lib.mifsk_selftest_confidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64,
+                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
     lib.mifsk_time_split_plan_get.restype = C.c_int
     lib.mifsk_time_split_plan_get.argtypes = [C.POINTER(RxConfig), C.c_uint64, C.POINTER(TimeSplit),
                                               C.POINTER(TimeSplitStats)]

@@ -22,7 +22,10 @@ namespace mifsk {
 // corrections -- without the exponent pre-scaling it wraps around it for
 // arguments below 2^-767, which cannot occur here (5 of its 18 instructions).
 // Same instructions, same order: identical results (every parity test compares
-// magnitudes bit for bit).
+// magnitudes bit for bit).  (As a double it is compared per value with the host's correctly
+// rounded sqrt, and sqrt_newton1's distance from it is measured -- at most 35 units of g's last
+// place on an MI355X, where the text below claims 2^8: mifsk_selftest_mag,
+// tests/test_gpu_devmath.py.)
 __device__ __forceinline__ double sqrt_sumsq( double s )
 {
     const double r = __builtin_amdgcn_rsq(s);

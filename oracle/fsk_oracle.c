@@ -161,31 +161,34 @@ ofsk_bit_analyze( ofsk_plan *p, const float *samples, unsigned int bit_nsamples,
 /* frame analysis / confidence: reference src/fsk.c:178-446 (ALGO 6)   */
 /* ------------------------------------------------------------------ */
 
+/* fsk_frame_analyze once the two magnitudes of every bit window are known: the strict `>`
+ * decision of each bit (fsk.c:161-169), the required bits first -- the first mismatch rejects
+ * the frame with confidence 0 and leaves the out-params untouched (fsk.c:199-212) --, then
+ * the sums, class means, divergence and confidence (fsk.c:271-342) and the bits (:439-441).
+ * ofsk_frame_analyze ends in it; tests/test_gpu_devmath.py hands it chosen magnitudes. */
 float
-ofsk_frame_analyze( ofsk_plan *p, const float *samples, float samples_per_bit,
-	int n_bits, const char *expect, unsigned long long *bits_outp, float *ampl_outp )
+ofsk_frame_confidence( const float *mag_mark, const float *mag_space, int n_bits,
+	const char *expect, unsigned long long *bits_outp, float *ampl_outp )
 {
-    unsigned int bit_nsamples = (float)(samples_per_bit + 0.5f);	/* fsk.c:183 */
     unsigned int value[MIFSK_MAX_FRAME_BITS];
     float sig[MIFSK_MAX_FRAME_BITS], noise[MIFSK_MAX_FRAME_BITS];
 
-    /* required bits first; the first mismatch rejects the frame with
-     * confidence 0 and leaves the out-params untouched (fsk.c:199-212) */
-    for ( int k = 0; k < n_bits; k++ ) {
-	if ( expect[k] == 'd' )
-	    continue;
-	unsigned int begin = (float)(samples_per_bit * k + 0.5f);	/* fsk.c:204 */
-	ofsk_bit_analyze(p, samples + begin, bit_nsamples, &value[k], &sig[k], &noise[k]);
-	if ( (unsigned int)(expect[k] - '0') != value[k] )
-	    return 0.0f;
-    }
-    /* then the don't-care bits (fsk.c:246-254) */
-    for ( int k = 0; k < n_bits; k++ ) {
-	if ( expect[k] != 'd' )
-	    continue;
-	unsigned int begin = (float)(samples_per_bit * k + 0.5f);	/* fsk.c:249 */
-	ofsk_bit_analyze(p, samples + begin, bit_nsamples, &value[k], &sig[k], &noise[k]);
-    }
+    for ( int pass = 0; pass < 2; pass++ )	/* required bits, then the don't-care bits (fsk.c:246-254) */
+	for ( int k = 0; k < n_bits; k++ ) {
+	    if ( ( expect[k] == 'd' ) != ( pass == 1 ) )
+		continue;
+	    if ( mag_mark[k] > mag_space[k] ) {			/* fsk.c:161-169 */
+		value[k] = 1;
+		sig[k] = mag_mark[k];
+		noise[k] = mag_space[k];
+	    } else {
+		value[k] = 0;
+		sig[k] = mag_space[k];
+		noise[k] = mag_mark[k];
+	    }
+	    if ( pass == 0 && (unsigned int)(expect[k] - '0') != value[k] )
+		return 0.0f;
+	}
 
     /* fsk.c:271-289: f32 running sums, in bit order */
     float total_sig = 0.0f, total_noise = 0.0f;
@@ -226,6 +229,33 @@ ofsk_frame_analyze( ofsk_plan *p, const float *samples, float samples_per_bit,
 	bits |= (unsigned long long)value[k] << k;
     *bits_outp = bits;
     return confidence;
+}
+
+float
+ofsk_frame_analyze( ofsk_plan *p, const float *samples, float samples_per_bit,
+	int n_bits, const char *expect, unsigned long long *bits_outp, float *ampl_outp )
+{
+    unsigned int bit_nsamples = (float)(samples_per_bit + 0.5f);	/* fsk.c:183 */
+    float mag_mark[MIFSK_MAX_FRAME_BITS], mag_space[MIFSK_MAX_FRAME_BITS];
+
+    /* the windows of the required bits first, as the reference orders them (fsk.c:199-212): a
+     * mismatch ends the frame before the don't-care windows (fsk.c:246-254) are transformed.
+     * (ofsk_frame_confidence makes the same decision from the same two magnitudes: leaving
+     * here only spares the remaining transforms.) */
+    for ( int pass = 0; pass < 2; pass++ )
+	for ( int k = 0; k < n_bits; k++ ) {
+	    if ( ( expect[k] == 'd' ) != ( pass == 1 ) )
+		continue;
+	    unsigned int begin = (float)(samples_per_bit * k + 0.5f);	/* fsk.c:204,249 */
+	    unsigned int value;
+	    float sig, noise;
+	    ofsk_bit_analyze(p, samples + begin, bit_nsamples, &value, &sig, &noise);
+	    mag_mark[k] = value ? sig : noise;
+	    mag_space[k] = value ? noise : sig;
+	    if ( pass == 0 && (unsigned int)(expect[k] - '0') != value )
+		return 0.0f;
+	}
+    return ofsk_frame_confidence(mag_mark, mag_space, n_bits, expect, bits_outp, ampl_outp);
 }
 
 /* ------------------------------------------------------------------ */

@@ -10,6 +10,7 @@
  *   ofsk_plan_new / _destroy        src/fsk.c:33-104
  *   ofsk_bit_analyze                src/fsk.c:107-174
  *   ofsk_frame_analyze              src/fsk.c:178-446 (CONFIDENCE_ALGO 6)
+ *   ofsk_frame_confidence           its tail, from the bit decisions on (:161-169,271-342,439-441)
  *   ofsk_find_frame                 src/fsk.c:449-538
  *   ofsk_detect_carrier             src/fsk.c:543-581
  *   ofsk_set_tones_by_bandshift     src/fsk.c:584-598
@@ -65,6 +66,11 @@ void ofsk_bit_analyze( ofsk_plan *p, const float *samples, unsigned int bit_nsam
 float ofsk_frame_analyze( ofsk_plan *p, const float *samples, float samples_per_bit,
 	int n_bits, const char *expect_bits_string,
 	unsigned long long *bits_outp, float *ampl_outp );
+
+/* the tail of ofsk_frame_analyze, on the per-bit magnitudes themselves (fsk.c:161-169, 199-212,
+ * 271-342, 439-441): returns 0 with the out-params untouched when a required bit is wrong */
+float ofsk_frame_confidence( const float *mag_mark, const float *mag_space, int n_bits,
+	const char *expect_bits_string, unsigned long long *bits_outp, float *ampl_outp );
 
 float ofsk_find_frame( ofsk_plan *p, const float *samples, unsigned int frame_nsamples,
 	unsigned int try_first_sample, unsigned int try_max_nsamples,

@@ -197,6 +197,9 @@ def oracle_lib():
         lib.ofsk_frame_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int,
                                            C.c_char_p, C.POINTER(C.c_ulonglong),
                                            C.POINTER(C.c_float)]
+        lib.ofsk_frame_confidence.restype = C.c_float
+        lib.ofsk_frame_confidence.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_char_p,
+                                              C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)]
         lib.ofsk_bit_analyze.argtypes = [C.c_void_p, C.c_void_p, C.c_uint,
                                          C.POINTER(C.c_uint), C.POINTER(C.c_float),
                                          C.POINTER(C.c_float)]

@@ -4,9 +4,12 @@ double to within a few units in the last place -- the exact quotient of two 24-b
 stays at least 2^-48 (relative) away from every float rounding boundary, the product is within
 2^-51 of it.  A numpy model of that arithmetic (float64 multiply, float32 rounding) over random
 and adversarial operands, with the reciprocal perturbed by up to +-2 ulp (what v_rcp_f64 plus two
-Newton steps can be off by).  The device code itself is pinned by the parity tests: every frame's
-confidence is compared with the oracle's bit for bit."""
+Newton steps can be off by).  That the device's reciprocal does stay within those 2 ulp, and that
+its quotients are the IEEE ones on these same operands, is measured on the device by
+tests/test_gpu_devmath.py (mifsk_selftest_rcp); the operand generators are shared (tests/_divops.py)."""
 import numpy as np
+
+import _divops
 
 
 def _check(x, c):
@@ -29,25 +32,17 @@ def test_random_operands():
     n = 2_000_000
     with np.errstate(all="ignore"):
         # magnitudes as the confidence pass sees them, and the whole float range
-        _check(rng.uniform(0, 2, n), rng.uniform(1e-3, 2, n))
-        bits = rng.integers(0, 0x7F7FFFFF, size=n, dtype=np.uint32)
-        bits2 = rng.integers(0x00800000, 0x7F7FFFFF, size=n, dtype=np.uint32)
-        _check(bits.view(np.float32), bits2.view(np.float32))
+        for x, c in _divops.random_pairs(rng, n):
+            _check(x, c)
 
 
 def test_quotients_next_to_rounding_boundaries():
     """x = q * c for q one step either side of a float midpoint: the hardest quotients there are."""
     rng = np.random.default_rng(2)
     n = 500_000
-    c = rng.integers(0x3F800000, 0x40000000, size=n, dtype=np.uint32).view(np.float32)     # [1, 2)
-    q = rng.integers(0x3F800000, 0x40000000, size=n, dtype=np.uint32).view(np.float32)
-    mid = q.astype(np.float64) + 2.0 ** -24                                                # a midpoint
     with np.errstate(all="ignore"):
-        for eps in (-2.0 ** -47, 2.0 ** -47, -2.0 ** -40, 2.0 ** -40):
-            x = (mid * (1 + eps) * c.astype(np.float64)).astype(np.float32)               # rounded: lands near
+        for x, c in _divops.midpoint_pairs(rng, n):
             _check(x, c)
         # small integers over small integers (the frame length, the class counts)
-        a = rng.integers(1, 1 << 24, size=n).astype(np.float32)
-        b = rng.integers(1, 64, size=n).astype(np.float32)
-        _check(a, b)
-        _check(a * np.float32(1e-7), np.full(n, 11, np.float32))
+        for x, c in _divops.small_integer_pairs(rng, n):
+            _check(x, c)
