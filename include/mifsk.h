@@ -25,6 +25,7 @@
  *   mifsk_gather_*                (none: one process per GPU) decoded bytes to rank 0, RCCL
  *   mifsk_demod_slab[_ring]       the loop over a stream that arrives in pieces  minimodem.c:1144-1174
  *   mifsk_session_*               ... fed from host memory, bookkeeping included
+ *   mifsk_session_feed_ex/_device ... the tails kept on the device; float32, PCM16, device samples
  *   mifsk_demod_long[_batch]      the loop over one long stream, or a few, cut in time across the chip
  *   mifsk_demod_long_batch_s16    ... from PCM16 in device memory (rows gathered straight from it)
  *   mifsk_demod_long_batch_host   ... from host memory, float32 or PCM16
@@ -778,7 +779,8 @@ int mifsk_demod_long_batch_host( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
  * the stream -- in host memory the session owns, valid until the next feed.  Any cut gives,
  * concatenated, the results of one call over the whole streams, bit for bit.
  * flags: MIFSK_IO_RING_EXACT (the reference's buffer semantics across the feeds: `minimodem
- * --rx --file`'s frames digit for digit), MIFSK_IO_ENGINE_*, MIFSK_SESSION_WANT_FRAMES.
+ * --rx --file`'s frames digit for digit), MIFSK_IO_ENGINE_*, MIFSK_SESSION_WANT_FRAMES,
+ * MIFSK_SESSION_RESIDENT (below).
  * One feed at a time per session; sessions on one context are ordered by the caller. */
 typedef struct mifsk_session mifsk_session;
 #define MIFSK_SESSION_WANT_FRAMES	0x1000u	/* the per-frame records too */
@@ -803,6 +805,58 @@ int  mifsk_session_feed( mifsk_session *s, const float *const *samples, const ui
 const mifsk_session_result *mifsk_session_get( const mifsk_session *s, int stream );
 /* samples of stream `stream` the session still holds (fed, not yet passed by the loop) */
 size_t mifsk_session_pending( const mifsk_session *s, int stream );
+
+/* ---- the resident session: tails on the device, PCM16 and device samples ----- */
+
+/* MIFSK_SESSION_RESIDENT (with any other flag of mifsk_session_create) keeps the unconsumed
+ * samples in device memory: two row buffers of nstreams x row_capacity floats, used in turn.  A
+ * feed uploads the new samples and one small per-stream table, in ONE copy, and nothing else --
+ * PCM16 as 16-bit -- or takes the samples from device memory and uploads the table alone; a HIP
+ * kernel moves what the loop has not passed to the front of each row of the other buffer, puts
+ * the new samples behind it (converted, and with the --Xrxnoise term `rxnoise` added, by the
+ * expressions of mifsk_ingest_s16 / mifsk_ingest_rxnoise_f32) and zero-fills up to the feed's
+ * width.  The host keeps integers only.  The buffers grow as DevBuf does (25 % head-room) when a
+ * feed needs more: -ENOMEM when the device has no room (0.5 baud needs 2 x 2.3 M floats per
+ * stream and more).  Results, `pending`, `consumed`: exactly the host-tail session's, whatever
+ * the source.
+ *   mifsk_session_feed       on a resident session: feed_ex(MIFSK_FEED_F32, rxnoise 0).
+ *   mifsk_session_feed_ex    host pointers, one per stream (NULL / 0: nothing new for it), all
+ *                            of one `kind`.
+ *   mifsk_session_feed_device one DEVICE array [nstreams][stride] of `kind` elements (rows may
+ *                            start at any multiple of the element size); nsamples is a HOST
+ *                            array; `producer` is the HIP stream the samples were written on
+ *                            (the session's stream waits for an event recorded on it) or
+ *                            MIFSK_PIPELINE_NO_PRODUCER: they are complete.  Only
+ *                            d_samples[i][0 .. nsamples[i]) is read, until the call returns.
+ * -EINVAL: a session without the flag, an unknown kind, a count without its pointer (d_samples ==
+ * NULL with any count non-zero), a stride smaller than a count, a feed after the final one.
+ * A FAILED FEED leaves the session as it was before the call -- the rows it built are in the
+ * other buffer, and the host's integers change only after the loop has run -- so the caller may
+ * repeat it.  A stream whose loop has FINISHED (--rx-one after its carrier loss, an aborted
+ * loop) holds nothing from then on: later samples for it are ignored, its pending is 0 and its
+ * results are empty; so a live stream's row stays below about two samplebufs plus the piece.
+ * (The host-tail session keeps appending to such a stream's tail.) */
+#define MIFSK_SESSION_RESIDENT	0x2000u	/* the unconsumed tails live in device memory */
+
+#define MIFSK_FEED_F32	0u
+#define MIFSK_FEED_S16	1u		/* PCM16: (float)v / 32768.0f, libsndfile's normalisation */
+
+int mifsk_session_feed_ex( mifsk_session *s, const void *const *samples, const uint32_t *nsamples,
+	unsigned kind, float rxnoise, int final );
+int mifsk_session_feed_device( mifsk_session *s, const void *d_samples, size_t stride,
+	const uint32_t *nsamples, unsigned kind, float rxnoise, int final, void *producer );
+
+/* of either kind of session */
+typedef struct mifsk_session_info {
+    uint32_t	resident;		/* 1: MIFSK_SESSION_RESIDENT                       */
+    uint32_t	feeds;			/* feeds that succeeded                            */
+    uint64_t	row_capacity;		/* elements per stream in each of the two buffers  */
+    uint64_t	device_bytes;		/* what the session holds on the device            */
+    uint64_t	h2d_bytes_last;		/* host-to-device bytes of the last feed, tables included */
+    uint64_t	h2d_bytes_total;
+    uint64_t	reserved[2];
+} mifsk_session_info;
+int mifsk_session_info_get( const mifsk_session *s, mifsk_session_info *info );
 
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 

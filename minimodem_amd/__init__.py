@@ -1366,26 +1366,75 @@ class SlabSession:
 class Session:
     """mifsk_session_*: SlabSession's job behind the C ABI (csrc/mifsk_session.cpp) -- the
     unconsumed tails, origins, loop state, RING cells and output arrays are the library's.
-    feed(new, final) returns one dict per stream of what THIS feed made of it (numpy copies)."""
+    feed(new, final) returns one dict per stream of what THIS feed made of it (numpy copies).
 
-    def __init__(self, ctx, cfg, nstreams, engine=None, ring_exact=False, want_frames=True):
+    resident=True (MIFSK_SESSION_RESIDENT) keeps the tails in device memory: a feed uploads only
+    the new samples.  Such a session takes `new` as a list of numpy float32 or int16 (PCM16)
+    arrays, all of one kind, None for "nothing new" -- or as one CUDA torch.float32 / torch.int16
+    tensor [n, k] whose row i holds stream i's nsamples[i] new samples (default: k for every
+    stream), produced on the current torch stream.  rxnoise is the --Xrxnoise term, added to the
+    new samples on the device."""
+
+    def __init__(self, ctx, cfg, nstreams, engine=None, ring_exact=False, want_frames=True, resident=False):
         self._lib = _lib.load()
         self.n = int(nstreams)
+        self.resident = bool(resident)
         flags = _io_flags(ring_exact, engine) | (_lib.SESSION_WANT_FRAMES if want_frames else 0)
+        flags |= _lib.SESSION_RESIDENT if resident else 0
         h = C.c_void_p()
         rc = self._lib.mifsk_session_create(C.byref(h), ctx.handle, C.byref(cfg), self.n, flags)
         if rc != 0:
             raise RuntimeError("mifsk_session_create failed: %d" % rc)
         self.handle = h
 
-    def feed(self, new, final=False):
-        assert len(new) == self.n
+    def _feed_host(self, new, final):
         keep = [np.ascontiguousarray(x, dtype=np.float32) if x is not None and len(x) else None for x in new]
         ptrs = (C.c_void_p * self.n)(*[k.ctypes.data if k is not None else None for k in keep])
         cnts = (C.c_uint32 * self.n)(*[len(k) if k is not None else 0 for k in keep])
-        rc = self._lib.mifsk_session_feed(self.handle, ptrs, cnts, 1 if final else 0)
+        return self._lib.mifsk_session_feed(self.handle, ptrs, cnts, 1 if final else 0), "mifsk_session_feed"
+
+    def _feed_resident(self, new, final, rxnoise, nsamples):
+        if hasattr(new, "is_cuda"):
+            torch = _torch()
+            if not new.is_cuda or new.dim() != 2 or new.shape[0] != self.n or new.dtype not in (torch.float32, torch.int16):
+                raise ValueError("a resident session takes a CUDA float32 or int16 tensor [nstreams, k]")
+            if new.shape[1] > 1 and new.stride(1) != 1:
+                raise ValueError("the samples of a row must be contiguous")
+            kind = _lib.FEED_S16 if new.dtype == torch.int16 else _lib.FEED_F32
+            k = int(new.shape[1])
+            lens = [k] * self.n if nsamples is None else [int(v) for v in nsamples]
+            if len(lens) != self.n or any(v < 0 or v > k for v in lens):
+                raise ValueError("nsamples: one count per stream, none beyond the tensor's width")
+            cnts = (C.c_uint32 * self.n)(*lens)
+            stride = int(new.stride(0)) if self.n > 1 else k
+            rc = self._lib.mifsk_session_feed_device(
+                self.handle, C.c_void_p(new.data_ptr() if k else None), stride, cnts, kind, C.c_float(rxnoise),
+                1 if final else 0, _stream_ptr(torch, None))
+            return rc, "mifsk_session_feed_device"
+        if nsamples is not None:
+            raise ValueError("nsamples goes with a device tensor")
+        assert len(new) == self.n
+        kinds = {np.asarray(x).dtype for x in new if x is not None and len(x)}
+        if not kinds <= {np.dtype(np.float32), np.dtype(np.int16)} or len(kinds) > 1:
+            raise ValueError("a resident session takes float32 or int16 pieces, all of one kind")
+        dtype = kinds.pop() if kinds else np.dtype(np.float32)
+        keep = [np.ascontiguousarray(x, dtype=dtype) if x is not None and len(x) else None for x in new]
+        ptrs = (C.c_void_p * self.n)(*[k.ctypes.data if k is not None else None for k in keep])
+        cnts = (C.c_uint32 * self.n)(*[len(k) if k is not None else 0 for k in keep])
+        kind = _lib.FEED_S16 if dtype == np.int16 else _lib.FEED_F32
+        rc = self._lib.mifsk_session_feed_ex(self.handle, ptrs, cnts, kind, C.c_float(rxnoise), 1 if final else 0)
+        return rc, "mifsk_session_feed_ex"
+
+    def feed(self, new, final=False, rxnoise=0.0, nsamples=None):
+        if self.resident:
+            rc, what = self._feed_resident(new, final, float(rxnoise), nsamples)
+        else:
+            if rxnoise != 0.0 or nsamples is not None or hasattr(new, "is_cuda"):
+                raise ValueError("rxnoise, nsamples and device tensors need Session(..., resident=True)")
+            assert len(new) == self.n
+            rc, what = self._feed_host(new, final)
         if rc != 0:
-            raise RuntimeError("mifsk_session_feed failed: %d" % rc)
+            raise RuntimeError("%s failed: %d" % (what, rc))
         out = []
         for i in range(self.n):
             r = self._lib.mifsk_session_get(self.handle, i).contents
@@ -1401,6 +1450,14 @@ class Session:
                         "carrier_band": int(r.carrier_band), "consumed": int(r.consumed), "finished": bool(r.finished),
                         "pending": int(self._lib.mifsk_session_pending(self.handle, i))})
         return out
+
+    def info(self):
+        """mifsk_session_info: resident, feeds, row_capacity, device_bytes, h2d_bytes_last / _total"""
+        info = _lib.SessionInfo()
+        rc = self._lib.mifsk_session_info_get(self.handle, C.byref(info))
+        if rc != 0:
+            raise RuntimeError("mifsk_session_info_get failed: %d" % rc)
+        return _struct_dict(info, drop_reserved=True)
 
     def close(self):
         if getattr(self, "handle", None):

@@ -164,7 +164,15 @@ class SessionResult(C.Structure):
                 ("episodes", C.c_void_p), ("consumed", C.c_uint64)]
 
 
+class SessionInfo(C.Structure):
+    _fields_ = [("resident", C.c_uint32), ("feeds", C.c_uint32), ("row_capacity", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("h2d_bytes_last", C.c_uint64),
+                ("h2d_bytes_total", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+
 SESSION_WANT_FRAMES = 0x1000
+SESSION_RESIDENT = 0x2000
+FEED_F32, FEED_S16 = 0, 1
 GATHER_ID_BYTES = 128
 GATHER_LOOPBACK = 1
 WANT_BYTES, WANT_BITS, WANT_FRAMES, WANT_EPISODES = 1, 2, 4, 8
@@ -231,6 +239,7 @@ TIME_SPLIT_REJECT_ALL = 0x10000
 
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
 assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
+assert C.sizeof(SessionInfo) == 56 and SessionInfo.h2d_bytes_last.offset == 24
 
 # every symbol include/*.h declares
 EXPORTS = [
@@ -262,6 +271,7 @@ EXPORTS = [
     "mifsk_time_split_plan_batch_get", "mifsk_demod_long_batch",
     "mifsk_demod_long_batch_s16", "mifsk_demod_long_batch_host", "mifsk_demod_files_long",
     "mifsk_files_time_split",
+    "mifsk_session_feed_ex", "mifsk_session_feed_device", "mifsk_session_info_get",
 ]
 
 _lib = None
@@ -430,6 +440,14 @@ def load():
     lib.mifsk_session_get.argtypes = [C.c_void_p, C.c_int]
     lib.mifsk_session_pending.restype = C.c_size_t
     lib.mifsk_session_pending.argtypes = [C.c_void_p, C.c_int]
+    lib.mifsk_session_feed_ex.restype = C.c_int
+    lib.mifsk_session_feed_ex.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint,
+                                          C.c_float, C.c_int]
+    lib.mifsk_session_feed_device.restype = C.c_int
+    lib.mifsk_session_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint,
+                                              C.c_float, C.c_int, C.c_void_p]
+    lib.mifsk_session_info_get.restype = C.c_int
+    lib.mifsk_session_info_get.argtypes = [C.c_void_p, C.POINTER(SessionInfo)]
     lib.mifsk_selftest_sqrt.restype = C.c_int
     lib.mifsk_selftest_sqrt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.mifsk_selftest_rcp.restype = C.c_int

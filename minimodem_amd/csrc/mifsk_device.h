@@ -385,4 +385,39 @@ inline float rxnoise_term( float factor )
     return ( 0 - 0.5f ) * f;
 }
 
+// A sample as the loop sees it, from what arrives.  THE expressions: every kernel that converts
+// or offsets samples calls these (ingest_s16_kernel, offset_f32_kernel, session_append_kernel,
+// the time split's gather), so that a stream gives the same floats whichever way it comes in.
+//   PCM16: value / 32768 (libsndfile's normalisation, a power of two: exact) + dc
+//   float: x + dc, applied only where --Xrxnoise is given (x + 0.0f would turn -0.0f into +0.0f)
+__device__ inline float sample_from_s16( int v, float dc )
+{
+    return (float)v / 32768.0f + dc;
+}
+
+__device__ inline float sample_from_f32( float x, float dc )
+{
+    return x + dc;
+}
+
+// ---- the resident session's rows (mifsk_ingest.hip) --------
+
+// one record per stream of the table a feed uploads
+struct SessionRow {
+    uint64_t	src_off;	// the new samples start at fresh[src_off] (elements)
+    uint64_t	origin;		// stream index of the destination row's first sample
+    uint32_t	drop;		// samples at the front of the old row that the loop has passed
+    uint32_t	keep;		// samples behind them that stay
+    uint32_t	k;		// new samples
+    uint32_t	reserved;
+};
+
+// new_rows[i][0 .. width) = old_rows[i][drop .. drop + keep) | the k new samples | 0.0, and
+// d_lens[i] = keep + k, d_origin[i] = origin.  `s16`: fresh holds PCM16, else floats.  width and
+// both strides are multiples of 4, both row arrays 16-byte aligned; old_rows may be NULL when no
+// row keeps anything.  `stream` is a hipStream_t.
+int launch_session_append( const float *old_rows, size_t old_stride, float *new_rows, size_t new_stride,
+	uint32_t width, const void *fresh, bool s16, const SessionRow *d_table, uint32_t *d_lens,
+	uint64_t *d_origin, int nstreams, float dc, void *stream );
+
 } // namespace mifsk

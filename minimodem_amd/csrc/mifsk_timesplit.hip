@@ -89,7 +89,7 @@ struct StreamRef {
 // row gathered from PCM16 is bit for bit the row gathered from mifsk_ingest_s16's floats.
 __device__ inline float s16_sample( int v, float dc )
 {
-    return (float)v / 32768.0f + dc;
+    return mifsk::sample_from_s16(v, dc);
 }
 
 __device__ inline float4 s16_pair( int lo, int hi, float dc )
