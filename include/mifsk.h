@@ -200,6 +200,59 @@ int mifsk_selftest_confidence( mifsk_ctx *ctx, int variant, uint32_t n_bits, uin
 	uint64_t req_val, const float *mags, uint64_t ncases, float *conf_out, float *ampl_out,
 	uint64_t *bits_out, uint32_t *fell_back_out );
 
+/* Diagnostics, wave-wide routines (csrc/mifsk_devlib.h) on HOST arrays, synchronous, like the
+ * three above; tests/test_gpu_correlators.py and tests/test_gpu_scans.py compare them with the
+ * oracle's double sums and with a serial float loop.
+ *
+ * _corr: bit windows through ONE of the correlators, the four double accumulators (mark re, im,
+ *   space re, im) of every window returned unrounded.  The twiddle table and the derived kernel
+ *   configuration are the ones mifsk_demod_batch uses for `cfg` (bit length cfg->bit_nsamples,
+ *   bands cfg->b_mark / b_space of cfg->fftsize).  Case i -- the window samples[starts[i] ..
+ *   + bit length) -- runs on lane i % 64 of wave i / 64; every lane of a wave runs the routine,
+ *   lanes beyond the last case on a copy of the wave's first.  `routine`:
+ *     _LDS_FIXED, _LDS_FIXED_HALVES  window of 4 .. 48 (8 .. 48) samples, a multiple of 4, in LDS
+ *     _LDS_STREAM, _LDS_STREAM_LEAN  window of any multiple of 4 samples in LDS, read in whole
+ *                                    groups of 16 samples
+ *     _GLOBAL_STREAM                 any window, read from memory in whole groups of 16
+ *     _GLOBAL_TILED                  any window, through the LDS tile in whole steps of 32; the
+ *                                    instantiation depends on whether a wave has more than 32 cases
+ *     _SLAB_PLAIN                    any window in LDS, at any alignment
+ *     _SKEWED_STREAM                 any window in a slab staged row by row from the lowest start
+ *                                    on, `param` (0 / 1) pad words between the rows
+ *     _SEG_GROUP                     segments of lens[i] <= bit length samples summed in lock step
+ *                                    over the wave's longest, unmasked below its shortest
+ *                                    (`param` 1: masked throughout); esum_out[i] = the float sum
+ *                                    of squares the shared segments' error bound is made from
+ *   `param` is 0 elsewhere; lens and esum_out may be NULL but for _SEG_GROUP.  The LDS routines
+ *   hold all of `samples` in LDS (at most 12288).  -EINVAL, and nothing is launched, for a case
+ *   that breaks its routine's precondition: a start that is no multiple of 4 (the first four
+ *   routines); a window -- for _LDS_STREAM / _LDS_STREAM_LEAN / _GLOBAL_STREAM rounded up to
+ *   whole groups of 16, for _GLOBAL_TILED to whole steps of 32 -- or a segment that does not end
+ *   within nsamples; a bit length the routine does not take; a segment of no or more than a bit
+ *   length's samples.
+ * _scan: the lane scans of the bulk replay, seeded as the receive loops seed them.  Wave w starts
+ *   from state[w] = { track amplitude, peak confidence, confidence total, amplitude total } and
+ *   replays k[w] (1 .. 64) frames of confidence cv[w][l] and amplitude av[w][l]; x_out[w][l] is
+ *   the state after frame l, b_out[w][l] the state before it, both four floats in that order and
+ *   meaningful for l < k[w].  routine 0: replay_scan_asm, 1: replay_scan_soft, 2:
+ *   replay_scan_track (which leaves the peak alone); totals 0: the two totals are left alone.
+ * _wave_max: max_out[w] = wave_max_f32 over v[w][0 .. 63]. */
+#define MIFSK_SELFTEST_CORR_LDS_FIXED		0
+#define MIFSK_SELFTEST_CORR_LDS_FIXED_HALVES	1
+#define MIFSK_SELFTEST_CORR_LDS_STREAM		2
+#define MIFSK_SELFTEST_CORR_LDS_STREAM_LEAN	3
+#define MIFSK_SELFTEST_CORR_GLOBAL_STREAM	4
+#define MIFSK_SELFTEST_CORR_GLOBAL_TILED	5
+#define MIFSK_SELFTEST_CORR_SLAB_PLAIN		6
+#define MIFSK_SELFTEST_CORR_SKEWED_STREAM	7
+#define MIFSK_SELFTEST_CORR_SEG_GROUP		8
+int mifsk_selftest_corr( mifsk_ctx *ctx, const mifsk_rx_config *cfg, int routine, int param,
+	const float *samples, uint32_t nsamples, const uint32_t *starts, const uint32_t *lens,
+	uint32_t ncases, double *acc_out, float *esum_out );
+int mifsk_selftest_scan( mifsk_ctx *ctx, int routine, int totals, const float *state, const float *cv,
+	const float *av, const uint32_t *k, uint32_t nwaves, float *x_out, float *b_out );
+int mifsk_selftest_wave_max( mifsk_ctx *ctx, const float *v, uint32_t nwaves, float *max_out );
+
 /* ---- N independent fsk_find_frame() problems --------------------------- */
 
 typedef struct mifsk_search {

@@ -143,6 +143,59 @@ class Context:
             raise RuntimeError("mifsk_selftest_confidence failed: %d" % rc)
         return conf, ampl, bits, fb
 
+    def selftest_corr(self, cfg, routine, samples, starts, lens=None, param=0):
+        """mifsk_selftest_corr: the windows of cfg.bit_nsamples samples at `starts` of `samples`
+        (for "seg_group": segments of `lens` samples) through one correlator of _lib.CORR_ROUTINES
+        -> (acc[ncases, 4] doubles, the float energy sums of "seg_group" or None); case i runs on
+        lane i % 64 of wave i / 64.  ValueError where the library refuses the cases (-EINVAL: a
+        precondition of the routine does not hold; nothing was launched)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        starts = np.ascontiguousarray(starts, np.uint32)
+        assert samples.ndim == 1 and starts.ndim == 1
+        seg = routine == "seg_group"
+        if seg:
+            lens = np.ascontiguousarray(lens, np.uint32)
+            assert lens.shape == starts.shape
+        acc = np.empty((starts.size, 4), np.float64)
+        esum = np.empty(starts.size, np.float32) if seg else None
+        rc = self._lib.mifsk_selftest_corr(self.handle, C.byref(cfg), _lib.CORR_ROUTINES[routine], int(param),
+                                           samples.ctypes.data, samples.size, starts.ctypes.data,
+                                           lens.ctypes.data if seg else None, starts.size,
+                                           acc.ctypes.data, esum.ctypes.data if seg else None)
+        if rc == -22:
+            raise ValueError("mifsk_selftest_corr refused the cases (-EINVAL)")
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_corr failed: %d" % rc)
+        return acc, esum
+
+    def selftest_scan(self, routine, state, cv, av, k, totals=True):
+        """mifsk_selftest_scan: state[nwaves, 4] = (track, peak, confidence total, amplitude total)
+        before frame 0, cv / av[nwaves, 64], k[nwaves] frames -> (x[nwaves, 64, 4], b[nwaves, 64, 4]):
+        the state after and before every lane's frame.  routine: "asm", "soft" or "track"."""
+        state = np.ascontiguousarray(state, np.float32)
+        cv = np.ascontiguousarray(cv, np.float32)
+        av = np.ascontiguousarray(av, np.float32)
+        k = np.ascontiguousarray(k, np.uint32)
+        n = k.size
+        assert state.shape == (n, 4) and cv.shape == (n, 64) and av.shape == (n, 64)
+        x, b = np.empty((n, 64, 4), np.float32), np.empty((n, 64, 4), np.float32)
+        rc = self._lib.mifsk_selftest_scan(self.handle, _lib.SCAN_ROUTINES[routine], int(bool(totals)),
+                                           state.ctypes.data, cv.ctypes.data, av.ctypes.data, k.ctypes.data, n,
+                                           x.ctypes.data, b.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_scan failed: %d" % rc)
+        return x, b
+
+    def selftest_wave_max(self, v):
+        """mifsk_selftest_wave_max: v[nwaves, 64] -> wave_max_f32 of every wave"""
+        v = np.ascontiguousarray(v, np.float32)
+        assert v.ndim == 2 and v.shape[1] == 64
+        out = np.empty(v.shape[0], np.float32)
+        rc = self._lib.mifsk_selftest_wave_max(self.handle, v.ctypes.data, v.shape[0], out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_wave_max failed: %d" % rc)
+        return out
+
     def close(self):
         if self.handle:
             self._lib.mifsk_ctx_destroy(self.handle)

@@ -179,6 +179,10 @@ WANT_BYTES, WANT_BITS, WANT_FRAMES, WANT_EPISODES = 1, 2, 4, 8
 PIPELINE_NO_PRODUCER = C.c_void_p(-1)
 IO_RING_EXACT = 1
 IO_ENGINE_WORKGROUP = 2
+# mifsk_selftest_corr routines (MIFSK_SELFTEST_CORR_*)
+CORR_ROUTINES = {"lds_fixed": 0, "lds_fixed_halves": 1, "lds_stream": 2, "lds_stream_lean": 3,
+                 "global_stream": 4, "global_tiled": 5, "slab_plain": 6, "skewed_stream": 7, "seg_group": 8}
+SCAN_ROUTINES = {"asm": 0, "soft": 1, "track": 2}
 IO_ENGINE_WAVE = 4
 IO_HOST_S16 = 0x100
 FILES_WANT_FRAMES = 0x1000
@@ -260,6 +264,7 @@ EXPORTS = [
     "mifsk_files_free", "mifsk_demod_slab", "mifsk_scan_plan_get",
     "mifsk_demod_slab_ring", "mifsk_ring_floats", "mifsk_selftest_sqrt",
     "mifsk_selftest_rcp", "mifsk_selftest_mag", "mifsk_selftest_confidence",
+    "mifsk_selftest_corr", "mifsk_selftest_scan", "mifsk_selftest_wave_max",
     "mifsk_pipeline_create", "mifsk_pipeline_destroy", "mifsk_pipeline_info_get",
     "mifsk_pipeline_outputs_alloc", "mifsk_pipeline_outputs_get", "mifsk_pipeline_submit",
     "mifsk_pipeline_next_ticket", "mifsk_pipeline_wait", "mifsk_pipeline_join",
@@ -459,6 +464,14 @@ def load():
     lib.mifsk_selftest_confidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64,
                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+    lib.mifsk_selftest_corr.restype = C.c_int
+    lib.mifsk_selftest_corr.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_int, C.c_int, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.mifsk_selftest_scan.restype = C.c_int
+    lib.mifsk_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.mifsk_selftest_wave_max.restype = C.c_int
+    lib.mifsk_selftest_wave_max.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.mifsk_time_split_plan_get.restype = C.c_int
     lib.mifsk_time_split_plan_get.argtypes = [C.POINTER(RxConfig), C.c_uint64, C.POINTER(TimeSplit),
                                               C.POINTER(TimeSplitStats)]

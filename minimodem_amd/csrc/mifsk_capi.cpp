@@ -160,13 +160,25 @@ extern "C" const char *mifsk_ctx_device_name( const mifsk_ctx *ctx )
     return ctx ? ctx->name : "";
 }
 
+// cos, -sin of an angle as the oracle's tables hold them (ofsk_twiddle, and the spectrum table
+// of ofsk_detect_carrier): its cos(ang) and -sin(ang) are compiled into ONE sincos() call, and the
+// C library's sincos() is not its sin(): at 2 pi 198 / 240, for one, the two sines differ in the
+// last place.  Separate calls made three entries of the Bell-202 table differ from the oracle's by
+// an ulp -- invisible once a sum is rounded to float, but not "the oracle's sums"
+// (tests/test_gpu_correlators.py compares the doubles).
+static inline void cos_msin( double ang, double w[2] )
+{
+    double s, c;
+    ::sincos(ang, &s, &c);
+    w[0] = c;
+    w[1] = -s;
+}
+
 // exp(-2 pi i b n / N): the angle is reduced exactly in integers first
 static inline void twiddle( unsigned b, unsigned n, unsigned fftsize, double w[2] )
 {
     const unsigned long long k = ( (unsigned long long)b * n ) % fftsize;
-    const double ang = 2.0 * M_PI * (double)k / (double)fftsize;
-    w[0] = std::cos(ang);
-    w[1] = -std::sin(ang);
+    cos_msin(2.0 * M_PI * (double)k / (double)fftsize, w);
 }
 
 // The caches are bounded: the legacy API makes a DevCfg per window shape and a twiddle
@@ -305,9 +317,7 @@ static int get_cs( mifsk_ctx *ctx, unsigned N, const double **d_out )
 	}
     std::vector<double> h(2 * (size_t)N);
     for ( unsigned k = 0; k < N; k++ ) {
-	const double ang = 2.0 * M_PI * (double)k / (double)N;
-	h[2 * (size_t)k] = std::cos(ang);
-	h[2 * (size_t)k + 1] = -std::sin(ang);
+	cos_msin(2.0 * M_PI * (double)k / (double)N, &h[2 * (size_t)k]);
     }
     double *d = nullptr;
     if ( hipMalloc(&d, h.size() * sizeof(double)) != hipSuccess )
@@ -384,6 +394,18 @@ static int prepare( mifsk_ctx *ctx, const mifsk_rx_config *cfg, Prepared &p )
 	return rc;
     derive_cfg(ctx, *cfg, p.d);
     return get_devcfg(ctx, p.d, &p.d_cfg, &p.tables);
+}
+
+int mifsk::lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::shared_lock<std::shared_mutex> &gate,
+	DevCfg &d, const double **d_tw )
+{
+    Prepared p;
+    if ( int rc = prepare(ctx, cfg, p) )
+	return rc;
+    gate = std::move(p.gate);
+    d = p.d;
+    *d_tw = p.d_tw;
+    return 0;
 }
 
 // the batch of a demodulating entry point that accepts the flags `accepted`

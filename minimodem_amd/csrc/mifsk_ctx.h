@@ -82,3 +82,11 @@ struct mifsk_ctx {
 
 // -EINVAL for a configuration the kernels cannot take (mifsk_capi.cpp)
 int mifsk_check_cfg( const mifsk_rx_config *cfg );
+
+namespace mifsk {
+// The tables a launching entry point looks up for `cfg` (mifsk_capi.cpp, prepare()): the derived
+// kernel configuration, the context's twiddle table, and the gate that keeps them alive while it
+// is held.  For mifsk_selftest.hip, whose kernels must run on the product's own tables.
+int lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::shared_lock<std::shared_mutex> &gate,
+	DevCfg &d, const double **d_tw );
+}

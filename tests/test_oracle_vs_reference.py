@@ -82,6 +82,36 @@ def test_restatement_equals_reference_program(case, tmp_path):
         assert [O.format_nocarrier(cfg, e) for e in r["episodes"]] == ref_lines
 
 
+# bit lengths the kernels treat differently (tests/test_gpu_bitlengths.py sweeps 3 .. 320 against
+# the restatement): the shortest, an odd one, a tail of 5 samples, Bell-103 tones a bin apart, one
+# past the tile threshold -- at a whole number of samples per bit and at two fractional ones
+ODD_BIT_LENGTHS = [(B, d) for B in (3, 7, 37, 121, 257) for d in (0.0, -0.3, 0.4) if (B, d) != (3, -0.3)]
+
+
+@pytest.mark.parametrize("B,delta", ODD_BIT_LENGTHS, ids=["B%d%+g" % c for c in ODD_BIT_LENGTHS])
+def test_restatement_equals_reference_program_at_odd_bit_lengths(B, delta, tmp_path):
+    """baud = 48000 / (B + delta): the reference program transmits and receives at that rate, the
+    restatement must derive the same bit length and print what the reference prints."""
+    mode = repr(48000.0 / (B + delta))
+    payload = ref_payload("testdata-ascii.txt")[:80]
+    wav = str(tmp_path / "b.wav")
+    O.ref_tx(payload, [mode], wav)
+    out, err = O.ref_rx(wav, [mode])
+    ref_lines = [l for l in err.splitlines() if l.startswith("### NOCARRIER")]
+    sr, x = O.read_wav(wav)
+    cfg = O.oracle_config(mode)
+    assert sr == cfg.sample_rate == 48000 and cfg.bit_nsamples == B
+    for ring in (True, False):
+        r = O.oracle_rx_stream(cfg, x, ring_mode=ring)
+        assert r["bytes"] == out
+        assert [O.format_nocarrier(cfg, e) for e in r["episodes"]] == ref_lines
+    # (the reference itself garbles bits of 3 samples, and of 7 at a fractional rate; at B = 121
+    # its two tones are hardly a bin apart: there only the equality above says anything)
+    assert ref_lines
+    if B >= 37 and B != 121:
+        assert payload in out
+
+
 def test_dc_offset_sweep_tests_40_41(tmp_path):
     """--Xrxnoise adds a DC offset of -factor to every sample (rand()/RAND_MAX is
     an integer division, src/simpleaudio-sndfile.c:64-70); tests 40/41 sweep it."""
