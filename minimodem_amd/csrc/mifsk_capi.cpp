@@ -21,6 +21,7 @@
 #include "mifsk.h"
 #include "mifsk_device.h"
 #include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -76,19 +77,19 @@ extern "C" int mifsk_selftest_sqrt( mifsk_ctx *ctx, uint64_t seed, uint64_t nval
     if ( !ctx || !counts )
 	return -EINVAL;
     HIP_OK(hipSetDevice(ctx->device));
-    unsigned long long *d = nullptr;
-    HIP_OK(hipMalloc(&d, 4 * sizeof(unsigned long long)));
-    int rc = hipMemset(d, 0, 4 * sizeof(unsigned long long)) == hipSuccess ? 0 : -EIO;
+    mifsk::DevMem<unsigned long long> d;
+    if ( d.alloc(4) )
+	return -EIO;
+    int rc = hipMemset(d.p, 0, 4 * sizeof(unsigned long long)) == hipSuccess ? 0 : -EIO;
     const uint32_t per_thread = 4096;
     uint64_t blocks = ( nvalues + 256ull * per_thread - 1 ) / ( 256ull * per_thread );
     if ( blocks < 1 ) blocks = 1;
     if ( blocks > 0x7FFFFFFFull ) blocks = 0x7FFFFFFFull;
     if ( rc == 0 )
-	rc = mifsk::launch_selftest_sqrt(seed, (uint32_t)blocks, per_thread, d, nullptr);
+	rc = mifsk::launch_selftest_sqrt(seed, (uint32_t)blocks, per_thread, d.p, nullptr);
     unsigned long long h[4] = { 0, 0, 0, 0 };
-    if ( rc == 0 && hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess )
+    if ( rc == 0 && hipMemcpy(h, d.p, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess )
 	rc = -EIO;
-    (void)hipFree(d);
     for ( int i = 0; i < 4; i++ )
 	counts[i] = h[i];
     return rc;
@@ -553,16 +554,6 @@ static void wave_args( mifsk::WaveHostArgs &ha, const mifsk_ctx *ctx, const mifs
     ha.chain_ok = !d_state && !ha.ring_exact && !io->d_counters;
 }
 
-// per-call device scratch, allocated and freed in stream order
-struct StreamScratch {
-    hipStream_t	st;
-    void	*p = nullptr;
-    explicit StreamScratch( hipStream_t s ) : st(s) {}
-    StreamScratch( const StreamScratch & ) = delete;
-    ~StreamScratch() { if ( p ) (void)hipFreeAsync(p, st); }
-    bool alloc( size_t bytes ) { return hipMallocAsync(&p, bytes, st) == hipSuccess; }
-};
-
 // One wavefront per stream (mifsk_wave.hip): --auto-carrier and RING addressing
 // need per-call device scratch; it is allocated and freed in stream order (behind a chain's
 // groups too: the caller's stream has joined them when the launcher returns), so
@@ -581,7 +572,7 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const P
 	    ha.d_rot[k] = p.tables.d_rot[k];
 	    ha.rot_stride[k] = p.tables.rot_stride[k];
 	}
-    StreamScratch scratch_tw(st), scratch_ring(st);
+    mifsk::StreamMem scratch_tw(st), scratch_ring(st);
     if ( ha.autodetect ) {
 	// default negative shift, in the reference's float arithmetic (minimodem.c:1203-1206)
 	int b_shift = - (float)( cfg->autodetect_shift + cfg->band_width / 2.0f ) / cfg->band_width;
@@ -598,7 +589,7 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const P
 	ha.nps = cfg->nsamples_per_bit > (float)cfg->fftsize ? (float)cfg->fftsize
 							      : cfg->nsamples_per_bit;
 	ha.b_shift = b_shift;
-	if ( !scratch_tw.alloc(ns * ha.tw_entries * 4 * sizeof(double)) )
+	if ( scratch_tw.alloc(ns * ha.tw_entries * 4 * sizeof(double)) )
 	    return -ENOMEM;
 	ha.d_tw_scratch = (double *)scratch_tw.p;
     }
@@ -607,7 +598,7 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const P
 	// mifsk_demod_slab_ring: the caller's buffer IS the reference's samplebuf between calls
 	ha.d_ring = d_ring_persistent;
 	if ( !ha.d_ring ) {
-	    if ( !scratch_ring.alloc(ns * ha.ring_stride * sizeof(float))
+	    if ( scratch_ring.alloc(ns * ha.ring_stride * sizeof(float))
 		    || hipMemsetAsync(scratch_ring.p, 0, ns * ha.ring_stride * sizeof(float), st) != hipSuccess )
 		return -ENOMEM;
 	    ha.d_ring = (float *)scratch_ring.p;

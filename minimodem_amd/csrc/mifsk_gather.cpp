@@ -25,6 +25,10 @@
 #include <vector>
 
 #include "mifsk.h"
+#include "mifsk_gather_sets.h"
+
+using mifsk::RxSet;
+using mifsk::TxSet;
 
 static_assert(MIFSK_GATHER_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "the id is RCCL's ncclUniqueId");
 
@@ -80,20 +84,6 @@ const Rccl &rccl()
     return r;
 }
 
-// one receive set of the root (or the loopback rank): what every peer sent in one gather
-struct RxSet {
-    std::vector<uint8_t *>	bytes;		// [peer] rows[peer] x cols, dense
-    std::vector<int32_t *>	counts;		// [peer] rows[peer]
-    std::vector<int>		rows;
-    int				cols = 0;
-    bool			filled = false;
-};
-
-struct TxSet {
-    uint8_t	*bytes = nullptr;		// the narrow staging copy
-    size_t	cap = 0;
-};
-
 } // namespace
 
 struct mifsk_gather {
@@ -110,9 +100,6 @@ struct mifsk_gather {
 #define RCCL_OK(call)	do { ncclResult_t e_ = (call); if ( e_ != ncclSuccess ) { \
 	fprintf(stderr, "mifsk: %s failed: %s\n", #call, R.GetErrorString(e_)); \
 	return -EIO; } } while (0)
-#define HIP_OK_(call)	do { hipError_t e_ = (call); if ( e_ != hipSuccess ) { \
-	fprintf(stderr, "mifsk: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-	return -EIO; } } while (0)
 
 extern "C" int mifsk_gather_unique_id( void *id )
 {
@@ -127,26 +114,14 @@ extern "C" int mifsk_gather_unique_id( void *id )
     return 0;
 }
 
-static void free_sets( mifsk_gather *g )
-{
-    for ( RxSet &s : g->rx ) {
-	for ( uint8_t *p : s.bytes ) if ( p ) (void)hipFree(p);
-	for ( int32_t *p : s.counts ) if ( p ) (void)hipFree(p);
-	s = RxSet();
-    }
-    for ( TxSet &t : g->tx ) {
-	if ( t.bytes ) (void)hipFree(t.bytes);
-	t = TxSet();
-    }
-}
-
 extern "C" void mifsk_gather_destroy( mifsk_gather *g )
 {
     if ( !g )
 	return;
     (void)hipSetDevice(g->device);
     (void)hipDeviceSynchronize();		// (a set may still be the target of a receive)
-    free_sets(g);
+    g->rx.clear();
+    g->tx.clear();
     if ( g->comm )
 	(void)rccl().CommDestroy(g->comm);
     delete g;
@@ -207,37 +182,6 @@ extern "C" int mifsk_gather_create( mifsk_gather **out, const void *id, int rank
     return 0;
 }
 
-// room for `rows[p] x cols` from every peer in receive set `s`
-static int fit_rx( mifsk_gather *g, RxSet &s, const int *rows, int rows_all, int cols )
-{
-    const int npeers = g->loopback ? 1 : g->world;
-    bool same = s.cols == cols && (int)s.rows.size() == npeers;
-    for ( int p = 0; same && p < npeers; p++ )
-	same = s.rows[p] == ( rows ? rows[p] : rows_all );
-    if ( same )
-	return 0;
-    // (a set being replaced may still be the target of a receive in flight)
-    HIP_OK_(hipDeviceSynchronize());
-    for ( uint8_t *p : s.bytes ) if ( p ) (void)hipFree(p);
-    for ( int32_t *p : s.counts ) if ( p ) (void)hipFree(p);
-    s = RxSet();
-    s.bytes.assign(npeers, nullptr);
-    s.counts.assign(npeers, nullptr);
-    s.rows.assign(npeers, 0);
-    s.cols = cols;
-    for ( int p = 0; p < npeers; p++ ) {
-	const int r = rows ? rows[p] : rows_all;
-	s.rows[p] = r;
-	if ( !g->loopback && p == g->rank )
-	    continue;				// (the root's own rows stay where they are)
-	const size_t nb = (size_t)r * (size_t)cols;
-	if ( hipMalloc((void **)&s.bytes[p], nb ? nb : 1) != hipSuccess
-		|| hipMalloc((void **)&s.counts[p], ( r ? (size_t)r : 1 ) * sizeof(int32_t)) != hipSuccess )
-	    return -ENOMEM;
-    }
-    return 0;
-}
-
 extern "C" int mifsk_gather_start( mifsk_gather *g, const uint8_t *d_bytes, size_t row_pitch,
 	const int32_t *d_nbytes, int nstreams, int cols, const int *rows, void *stream,
 	uint64_t *ticket )
@@ -256,7 +200,7 @@ extern "C" int mifsk_gather_start( mifsk_gather *g, const uint8_t *d_bytes, size
 	return 0;				// nothing to exchange: the one rank holds everything
     const Rccl &R = rccl();
     hipStream_t st = (hipStream_t)stream;
-    HIP_OK_(hipSetDevice(g->device));
+    HIP_OK(hipSetDevice(g->device));
     const uint32_t slot = (uint32_t)( t % g->slots );
     const bool root = g->rank == 0;
     const bool sends = !root || g->loopback;
@@ -265,20 +209,19 @@ extern "C" int mifsk_gather_start( mifsk_gather *g, const uint8_t *d_bytes, size
     if ( sends && nb && (size_t)cols != row_pitch ) {
 	// only the columns that can hold data travel: a dense copy made on the caller's stream
 	TxSet &tx = g->tx[slot];
-	if ( tx.cap < nb ) {
-	    HIP_OK_(hipDeviceSynchronize());
-	    if ( tx.bytes ) (void)hipFree(tx.bytes);
-	    tx = TxSet();
-	    if ( hipMalloc((void **)&tx.bytes, nb) != hipSuccess )
-		return -ENOMEM;
-	    tx.cap = nb;
+	if ( tx.bytes.cap < nb ) {
+	    HIP_OK(hipDeviceSynchronize());
+	    if ( const int rc = tx.bytes.alloc(nb) )
+		return rc;
 	}
-	HIP_OK_(hipMemcpy2DAsync(tx.bytes, (size_t)cols, d_bytes, row_pitch, (size_t)cols,
+	HIP_OK(hipMemcpy2DAsync(tx.bytes.p, (size_t)cols, d_bytes, row_pitch, (size_t)cols,
 				 (size_t)nstreams, hipMemcpyDeviceToDevice, st));
-	src = tx.bytes;
+	src = tx.bytes.p;
     }
     if ( root ) {
-	const int rc = fit_rx(g, g->rx[slot], g->loopback ? nullptr : rows, nstreams, cols);
+	g->rx[slot].filled = false;		// (until this gather's receives are enqueued)
+	const int rc = mifsk::fit_rx(g->rx[slot], g->loopback ? 1 : g->world, g->loopback ? -1 : g->rank,
+				     g->loopback ? nullptr : rows, nstreams, cols);
 	if ( rc != 0 )
 	    return rc;
     }
@@ -292,11 +235,10 @@ extern "C" int mifsk_gather_start( mifsk_gather *g, const uint8_t *d_bytes, size
 		continue;
 	    const size_t n = (size_t)s.rows[p] * (size_t)cols;
 	    if ( n )
-		e = R.Recv(s.bytes[p], n, ncclUint8, p, g->comm, st);
+		e = R.Recv(s.bytes[p].p, n, ncclUint8, p, g->comm, st);
 	    if ( e == ncclSuccess && s.rows[p] )
-		e = R.Recv(s.counts[p], (size_t)s.rows[p], ncclInt32, p, g->comm, st);
+		e = R.Recv(s.counts[p].p, (size_t)s.rows[p], ncclInt32, p, g->comm, st);
 	}
-	s.filled = true;
     }
     if ( sends && e == ncclSuccess ) {
 	if ( nb )
@@ -310,6 +252,8 @@ extern "C" int mifsk_gather_start( mifsk_gather *g, const uint8_t *d_bytes, size
 		R.GetErrorString(e != ncclSuccess ? e : e2));
 	return -EIO;
     }
+    if ( root )
+	g->rx[slot].filled = true;
     return 0;
 }
 
@@ -327,8 +271,8 @@ extern "C" int mifsk_gather_received( mifsk_gather *g, uint64_t ticket, int peer
     const int npeers = (int)s.rows.size();
     if ( !s.filled || peer < 0 || peer >= npeers || ( !g->loopback && peer == 0 ) )
 	return -EINVAL;
-    if ( d_bytes ) *d_bytes = s.bytes[peer];
-    if ( d_nbytes ) *d_nbytes = s.counts[peer];
+    if ( d_bytes ) *d_bytes = s.bytes[peer].p;
+    if ( d_nbytes ) *d_nbytes = s.counts[peer].p;
     if ( rows ) *rows = s.rows[peer];
     if ( cols ) *cols = s.cols;
     return 0;

@@ -38,6 +38,8 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
+#include "mifsk_outputs.h"
 
 namespace mifsk {
 
@@ -48,10 +50,8 @@ struct HostWork {
     std::mutex	lock;			// one host call at a time per context
     hipStream_t	s_in = nullptr, s_comp = nullptr, s_out = nullptr;
     hipEvent_t	ev_in[2] = { nullptr, nullptr }, ev_comp[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
-    void	*pin[2] = { nullptr, nullptr };	// staging for sources that are not page-locked
-    size_t	pin_cap = 0;
-    void	*pin_n[2] = { nullptr, nullptr };	// per-chunk stream lengths (uint32_t)
-    size_t	pin_n_cap = 0;
+    PinMem<uint8_t>	pin[2];		// staging for sources that are not page-locked
+    PinMem<uint32_t>	pin_n[2];	// per-chunk stream lengths
     bool	ready = false;
 };
 
@@ -63,8 +63,6 @@ void host_work_destroy( HostWork *w )
 	if ( w->ev_in[i] ) (void)hipEventDestroy(w->ev_in[i]);
 	if ( w->ev_comp[i] ) (void)hipEventDestroy(w->ev_comp[i]);
 	if ( w->ev_out[i] ) (void)hipEventDestroy(w->ev_out[i]);
-	if ( w->pin[i] ) (void)hipHostFree(w->pin[i]);
-	if ( w->pin_n[i] ) (void)hipHostFree(w->pin_n[i]);
     }
     if ( w->s_in ) (void)hipStreamDestroy(w->s_in);
     if ( w->s_comp ) (void)hipStreamDestroy(w->s_comp);
@@ -113,28 +111,24 @@ int host_work_init( HostWork *w, bool overlapped )
     return 0;
 }
 
-// both pinned buffers of one kind, `bytes` long at least
-int pin_grow( void *( &buf )[2], size_t &cap, size_t bytes )
+// both pinned buffers of one kind, `n` elements long at least
+template <class T>
+int pin_grow( PinMem<T> ( &buf )[2], size_t n )
 {
-    if ( bytes <= cap )
+    if ( n <= buf[0].cap && n <= buf[1].cap )
 	return 0;
-    for ( void *&p : buf ) {
-	if ( p ) (void)hipHostFree(p);
-	p = nullptr;
-    }
-    cap = 0;
-    for ( void *&p : buf )
-	if ( hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess )
-	    return -ENOMEM;
-    cap = bytes;
-    return 0;
+    buf[0].reset();
+    buf[1].reset();
+    if ( const int rc = buf[0].alloc(n) )
+	return rc;
+    return buf[1].alloc(n);
 }
 
 int pin_reserve( HostWork *w, size_t bytes, size_t nrows )
 {
-    if ( const int rc = pin_grow(w->pin, w->pin_cap, bytes) )
+    if ( const int rc = pin_grow(w->pin, bytes) )
 	return rc;
-    return pin_grow(w->pin_n, w->pin_n_cap, nrows * sizeof(uint32_t));
+    return pin_grow(w->pin_n, nrows);
 }
 
 bool is_pinned( const void *p )
@@ -311,127 +305,16 @@ void host_stats_add( mifsk_host_stats *st, double t_begin, double t_stage, uint6
     st->source_pinned = direct ? 1u : 0u;
 }
 
-// ---- the result arrays of mifsk_demod_io: the one place that lists them ----
-
-enum PerRow { kOne, kFramesCap, kEpisodesCap, kCounters };
-
-struct OutArray {
-    size_t	member;		// where its pointer is in mifsk_demod_io
-    size_t	esz;		// bytes per element
-    PerRow	per;		// elements per row
-};
-
-const OutArray kOutArrays[] = {
-    { offsetof(mifsk_demod_io, d_bytes), sizeof(uint8_t), kFramesCap },
-    { offsetof(mifsk_demod_io, d_nbytes), sizeof(uint32_t), kOne },
-    { offsetof(mifsk_demod_io, d_bits), sizeof(uint64_t), kFramesCap },
-    { offsetof(mifsk_demod_io, d_frames), sizeof(mifsk_frame), kFramesCap },
-    { offsetof(mifsk_demod_io, d_nframes), sizeof(uint32_t), kOne },
-    { offsetof(mifsk_demod_io, d_episodes), sizeof(mifsk_episode), kEpisodesCap },
-    { offsetof(mifsk_demod_io, d_nepisodes), sizeof(uint32_t), kOne },
-    { offsetof(mifsk_demod_io, d_status), sizeof(uint32_t), kOne },
-    { offsetof(mifsk_demod_io, d_counters), sizeof(uint64_t), kCounters },
-    { offsetof(mifsk_demod_io, d_carrier_band), sizeof(int32_t), kOne },
-};
-
-void *out_get( const mifsk_demod_io &io, const OutArray &a )
-{
-    void *p;
-    std::memcpy(&p, (const char *)&io + a.member, sizeof(p));
-    return p;
-}
-
-void out_set( mifsk_demod_io &io, const OutArray &a, void *p )
-{
-    std::memcpy((char *)&io + a.member, &p, sizeof(p));
-}
-
-size_t out_row_bytes( const mifsk_demod_io &io, const OutArray &a )
-{
-    const size_t per = a.per == kFramesCap ? io.frames_cap : a.per == kEpisodesCap ? io.episodes_cap
-		     : a.per == kCounters ? (size_t)MIFSK_NCOUNTERS : 1;
-    return per * a.esz;
-}
-
-void mirror_free( mifsk_demod_io &d )
-{
-    for ( const OutArray &a : kOutArrays ) {
-	if ( void *p = out_get(d, a) )
-	    (void)hipFree(p);
-	out_set(d, a, nullptr);
-    }
-}
-
-// The device mirror of the result arrays `want` for `nrows` rows: a mifsk_demod_io with `want`'s
-// capacities and a device array wherever `want` has an array (everything else 0), which the
-// receive calls take as it is.  `zero`: the arrays are zero-filled, and the fill is done when this
-// returns (before another stream writes into them).  What was allocated is the caller's to
-// mirror_free(), after an error as well.
-int mirror_alloc( const mifsk_demod_io &want, size_t nrows, bool zero, mifsk_demod_io &d )
-{
-    std::memset(&d, 0, sizeof(d));
-    d.frames_cap = want.frames_cap;
-    d.episodes_cap = want.episodes_cap;
-    for ( const OutArray &a : kOutArrays ) {
-	if ( !out_get(want, a) )
-	    continue;
-	const size_t bytes = std::max<size_t>(nrows * out_row_bytes(want, a), 16);
-	void *p = nullptr;
-	if ( hipMalloc(&p, bytes) != hipSuccess )
-	    return -ENOMEM;
-	out_set(d, a, p);
-	if ( zero && hipMemset(p, 0, bytes) != hipSuccess )
-	    return -EIO;
-    }
-    return zero && hipStreamSynchronize(nullptr) != hipSuccess ? -EIO : 0;
-}
-
-// Rows [lo, hi) of the host arrays `ho` from the first hi - lo rows of a mirror, on `st`.  An
-// array that either side lacks is passed over.
-int mirror_copy_out( const mifsk_demod_io &d, const mifsk_demod_io &ho, size_t lo, size_t hi, hipStream_t st,
-	uint64_t *bytes_out )
-{
-    for ( const OutArray &a : kOutArrays ) {
-	void *host = out_get(ho, a), *dev = out_get(d, a);
-	if ( !host || !dev )
-	    continue;
-	const size_t row = out_row_bytes(ho, a), nb = ( hi - lo ) * row;
-	HIP_OK(hipMemcpyAsync((char *)host + lo * row, dev, nb, hipMemcpyDeviceToHost, st));
-	*bytes_out += nb;
-    }
-    return 0;
-}
-
 struct Chunk {
     size_t	lo, hi;		// rows
     size_t	stride;		// elements per device row
 };
 
-struct MirrorGuard {
-    mifsk_demod_io io = {};
-    ~MirrorGuard() { mirror_free(io); }
-};
-
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem() { if ( p ) (void)hipFree(p); }
-    int get( size_t bytes, bool zero )
-    {
-	if ( hipMalloc(&p, bytes ? bytes : 16) != hipSuccess ) {
-	    p = nullptr;
-	    return -ENOMEM;
-	}
-	// (the fill is done before another stream copies into the buffer)
-	return !zero || ( hipMemset(p, 0, bytes ? bytes : 16) == hipSuccess && hipStreamSynchronize(nullptr) == hipSuccess )
-	     ? 0 : -EIO;
-    }
-};
-
 struct Slot {
-    DevMem	in;		// the chunk as it crossed the bus
-    DevMem	x;		// S16 input: the converted samples
-    DevMem	n;		// the chunk's stream lengths
-    MirrorGuard	out;		// the mirror of the host's result arrays
+    DevMem<uint8_t>	in;	// the chunk as it crossed the bus
+    DevMem<float>	x;	// S16 input: the converted samples
+    DevMem<uint32_t>	n;	// the chunk's stream lengths
+    OutMirror		out;	// the mirror of the host's result arrays
 };
 
 // A batch of streams (`s16`: rows are int16_t, else float) through the chunked pipeline the head
@@ -499,10 +382,10 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	back.d_carrier_band = nullptr;
     Slot slots[2];
     for ( Slot &s : slots )
-	if ( ( rc = s.in.get(max_bytes + 64, false) )
-		|| ( s16 && ( rc = s.x.get(( max_floats + 16 ) * sizeof(float), false) ) )
-		|| ( rc = s.n.get(max_rows * sizeof(uint32_t), false) )
-		|| ( rc = mirror_alloc(ho, max_rows, false, s.out.io) ) )
+	if ( ( rc = s.in.alloc(max_bytes + 64) )
+		|| ( s16 && ( rc = s.x.alloc(max_floats + 16) ) )
+		|| ( rc = s.n.alloc(max_rows) )
+		|| ( rc = s.out.alloc(ho, max_rows, false) ) )
 	    return rc;
 
     const double t_alloc = now_s();
@@ -515,7 +398,7 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	const Chunk &c = chunks[ci];
 	if ( !single )
 	    HIP_OK(hipStreamWaitEvent(st_out, w->ev_comp[ci & 1], 0));
-	if ( const int e = mirror_copy_out(slots[ci & 1].out.io, back, c.lo, c.hi, st_out, &bytes_out) )
+	if ( const int e = slots[ci & 1].out.copy_out(back, c.lo, c.hi, st_out, &bytes_out) )
 	    return e;
 	if ( !single )
 	    HIP_OK(hipEventRecord(w->ev_out[ci & 1], st_out));
@@ -526,7 +409,7 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	const Chunk &c = chunks[ci];
 	const int sl = (int)( ci & 1 );
 	Slot &s = slots[sl];
-	uint32_t *const d_n = (uint32_t *)s.n.p;
+	uint32_t *const d_n = s.n.p;
 	const size_t r = c.hi - c.lo;
 	if ( ci >= 2 )
 	    HIP_OK(hipEventSynchronize(w->ev_out[sl]));	// chunk ci - 2 has left this slot
@@ -538,7 +421,7 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	    src_pitch_bytes = src_pitch * esz;
 	} else {
 	    const double t0 = now_s();
-	    unsigned char *dst = (unsigned char *)w->pin[sl];
+	    unsigned char *dst = w->pin[sl].p;
 	    parallel_for(r, nthreads, [&]( size_t i ) {
 		const Row &row = rows[c.lo + i];
 		(void)stage(row, RowFile(row, fault_tag), 0, (size_t)row.n * esz, dst + i * c.stride * esz);
@@ -548,7 +431,7 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	    src_pitch_bytes = c.stride * esz;
 	}
 	for ( size_t i = 0; i < r; i++ )
-	    ( (uint32_t *)w->pin_n[sl] )[i] = (uint32_t)rows[c.lo + i].n;
+	    w->pin_n[sl].p[i] = (uint32_t)rows[c.lo + i].n;
 	// ---- host -> device
 	size_t width = std::min(src_pitch_bytes, c.stride * esz);
 	if ( direct && nrows == 1 ) {
@@ -561,7 +444,7 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	else
 	    HIP_OK(hipMemcpy2DAsync(s.in.p, c.stride * esz, src, src_pitch_bytes, width, r,
 				    hipMemcpyHostToDevice, st_in));
-	HIP_OK(hipMemcpyAsync(d_n, w->pin_n[sl], r * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
+	HIP_OK(hipMemcpyAsync(d_n, w->pin_n[sl].p, r * sizeof(uint32_t), hipMemcpyHostToDevice, st_in));
 	bytes_in += width * r;
 	// ---- convert + receive loop
 	if ( !single ) {
@@ -570,9 +453,9 @@ int run_job( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row> 
 	}
 	const float *d_x = (const float *)s.in.p;
 	if ( s16 ) {
-	    rc = mifsk_ingest_s16(ctx, (const int16_t *)s.in.p, c.stride, (float *)s.x.p, c.stride, d_n, 0,
+	    rc = mifsk_ingest_s16(ctx, (const int16_t *)s.in.p, c.stride, s.x.p, c.stride, d_n, 0,
 				  (int)r, rxnoise, st_comp);
-	    d_x = (const float *)s.x.p;
+	    d_x = s.x.p;
 	} else if ( rxnoise != 0.0f ) {
 	    rc = mifsk_ingest_rxnoise_f32(ctx, (float *)s.in.p, c.stride, d_n, 0, (int)r, rxnoise, st_comp);
 	}
@@ -668,8 +551,8 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row>
     if ( !direct && ( rc = pin_reserve(w, (size_t)std::min<uint64_t>(per, longest) * esz, 0) ) )
 	return rc;
 
-    DevMem d_in;
-    if ( ( rc = d_in.get(M * stride * esz, true) ) )
+    DevMem<uint8_t> d_in;
+    if ( ( rc = d_in.alloc(M * stride * esz, 16, true) ) )
 	return rc;
     const unsigned nthreads = staging_threads();
     const char *fault_tag = read_fault_tag();
@@ -681,7 +564,7 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row>
 	const Row &row = rows[pc.row];
 	const int sl = (int)( k & 1 );
 	const size_t bytes = (size_t)pc.count * esz;
-	char *dst = (char *)d_in.p + ( pc.row * stride + (size_t)pc.first ) * esz;
+	uint8_t *dst = d_in.p + ( pc.row * stride + (size_t)pc.first ) * esz;
 	const void *src;
 	if ( direct ) {
 	    src = (const char *)row.mem + (size_t)pc.first * esz;
@@ -689,7 +572,7 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row>
 	    if ( k >= 2 )
 		HIP_OK(hipEventSynchronize(w->ev_in[sl]));	// piece k - 2 has left this buffer
 	    const double t0 = now_s();
-	    char *pin = (char *)w->pin[sl];
+	    uint8_t *pin = w->pin[sl].p;
 	    const RowFile file(row, fault_tag);		// (opened once per piece, not per block)
 	    parallel_for(( bytes + kBlock - 1 ) / kBlock, nthreads, [&]( size_t b ) {
 		const size_t o = b * kBlock;
@@ -721,8 +604,8 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row>
     want.d_counters = nullptr;
     if ( !( cfg->auto_carrier_threshold > 0.0f ) )
 	want.d_carrier_band = nullptr;
-    MirrorGuard out;
-    if ( ( rc = mirror_alloc(want, M, true, out.io) ) )
+    OutMirror out;
+    if ( ( rc = out.alloc(want, M, true) ) )
 	return rc;
     mifsk_demod_io io = out.io;
     io.nstreams = (int)M;
@@ -733,7 +616,7 @@ int run_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const std::vector<Row>
     if ( rc )
 	return rc;
     // (the call has waited for its stream)
-    if ( ( rc = mirror_copy_out(out.io, ho, 0, M, nullptr, &bytes_out) ) )
+    if ( ( rc = out.copy_out(ho, 0, M, nullptr, &bytes_out) ) )
 	return rc;
     HIP_OK(hipStreamSynchronize(nullptr));
     host_stats_add(hstats, t_begin, t_stage, bytes_in, bytes_out, pieces.size(), M, direct);

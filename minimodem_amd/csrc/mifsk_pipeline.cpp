@@ -25,13 +25,9 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
+#include "mifsk_outputs.h"
 
 namespace {
-
-struct OutSet {
-    mifsk_demod_io	io;		// output fields only
-    std::vector<void *>	blocks;		// what hipMalloc returned
-};
 
 struct Lane {
     mifsk_ctx	*ctx = nullptr;
@@ -40,16 +36,8 @@ struct Lane {
     hipEvent_t	after = nullptr;	// the producer's stream at submit time
     uint64_t	last = 0;		// ticket of that pass
     bool	used = false;
-    OutSet	set;
+    mifsk::OutMirror	set;	// its output arrays (io.nstreams: the batch size they were made for)
 };
-
-void free_set( OutSet &s )
-{
-    for ( void *b : s.blocks )
-	(void)hipFree(b);
-    s.blocks.clear();
-    std::memset(&s.io, 0, sizeof(s.io));
-}
 
 } // namespace
 
@@ -70,7 +58,7 @@ extern "C" void mifsk_pipeline_destroy( mifsk_pipeline *p )
     for ( Lane &l : p->lanes ) {
 	if ( l.stream )
 	    (void)hipStreamSynchronize(l.stream);
-	free_set(l.set);
+	l.set.reset();
 	if ( l.done ) (void)hipEventDestroy(l.done);
 	if ( l.after ) (void)hipEventDestroy(l.after);
 	if ( l.stream ) (void)hipStreamDestroy(l.stream);
@@ -145,46 +133,23 @@ extern "C" int mifsk_pipeline_outputs_alloc( mifsk_pipeline *p, int nstreams, si
     std::lock_guard<std::mutex> g(p->lock);
     if ( hipSetDevice(p->device) != hipSuccess )
 	return -EIO;
+    const mifsk_demod_io ask = mifsk::outputs_want(want, frames_cap, episodes_cap);
     int rc = 0;
     for ( Lane &l : p->lanes ) {
 	if ( l.stream )
 	    (void)hipStreamSynchronize(l.stream);	// nothing may still write the old set
-	free_set(l.set);
-	auto take = [&]( size_t bytes ) -> void * {
-	    void *d = nullptr;
-	    if ( rc != 0 )
-		return nullptr;
-	    if ( hipMalloc(&d, bytes ? bytes : 1) != hipSuccess ) {
-		rc = -ENOMEM;
-		return nullptr;
-	    }
-	    l.set.blocks.push_back(d);
-	    if ( hipMemsetAsync(d, 0, bytes, l.stream) != hipSuccess )
-		rc = -EIO;
-	    return d;
-	};
-	const size_t ns = (size_t)nstreams;
-	mifsk_demod_io &o = l.set.io;
-	o.frames_cap = frames_cap;
-	o.episodes_cap = ( want & MIFSK_WANT_EPISODES ) ? ( episodes_cap ? episodes_cap : 1 ) : 0;
-	o.d_nframes = (uint32_t *)take(ns * sizeof(uint32_t));
-	o.d_nbytes = (uint32_t *)take(ns * sizeof(uint32_t));
-	o.d_status = (uint32_t *)take(ns * sizeof(uint32_t));
-	if ( want & MIFSK_WANT_BYTES )
-	    o.d_bytes = (uint8_t *)take(ns * frames_cap);
-	if ( want & MIFSK_WANT_BITS )
-	    o.d_bits = (uint64_t *)take(ns * frames_cap * sizeof(uint64_t));
-	if ( want & MIFSK_WANT_FRAMES )
-	    o.d_frames = (mifsk_frame *)take(ns * frames_cap * sizeof(mifsk_frame));
-	if ( want & MIFSK_WANT_EPISODES ) {
-	    o.d_episodes = (mifsk_episode *)take(ns * o.episodes_cap * sizeof(mifsk_episode));
-	    o.d_nepisodes = (uint32_t *)take(ns * sizeof(uint32_t));
-	}
-	o.nstreams = nstreams;
+	if ( rc != 0 || ( rc = l.set.alloc(ask, (size_t)nstreams, false) ) != 0 )
+	    continue;
+	// (the zero fill is the lane's own work: in the order of its stream)
+	for ( const mifsk::OutArray &a : mifsk::kOutArrays )
+	    if ( void *d = mifsk::out_get(l.set.io, a) )
+		if ( hipMemsetAsync(d, 0, (size_t)nstreams * mifsk::out_row_bytes(ask, a), l.stream) != hipSuccess )
+		    rc = -EIO;
+	l.set.io.nstreams = nstreams;
     }
     if ( rc != 0 ) {
 	for ( Lane &l : p->lanes )
-	    free_set(l.set);
+	    l.set.reset();
 	p->sets = false;
 	return rc;
     }
@@ -196,17 +161,7 @@ extern "C" int mifsk_pipeline_outputs_get( mifsk_pipeline *p, uint64_t ticket, m
 {
     if ( !p || !io || !p->sets )
 	return -EINVAL;
-    const mifsk_demod_io &o = p->lanes[ticket % p->depth].set.io;
-    io->d_bytes = o.d_bytes;
-    io->d_nbytes = o.d_nbytes;
-    io->d_bits = o.d_bits;
-    io->d_frames = o.d_frames;
-    io->d_nframes = o.d_nframes;
-    io->frames_cap = o.frames_cap;
-    io->d_episodes = o.d_episodes;
-    io->d_nepisodes = o.d_nepisodes;
-    io->episodes_cap = o.episodes_cap;
-    io->d_status = o.d_status;
+    mifsk::outputs_assign(*io, p->lanes[ticket % p->depth].set.io);
     return 0;
 }
 
@@ -229,17 +184,7 @@ extern "C" int mifsk_pipeline_submit( mifsk_pipeline *p, const mifsk_rx_config *
 	// no outputs given: the lane's own set (which must have been made for batches this size)
 	if ( io->nstreams > l.set.io.nstreams )
 	    return -EINVAL;
-	const mifsk_demod_io &o = l.set.io;
-	use.d_bytes = o.d_bytes;
-	use.d_nbytes = o.d_nbytes;
-	use.d_bits = o.d_bits;
-	use.d_frames = o.d_frames;
-	use.d_nframes = o.d_nframes;
-	use.frames_cap = o.frames_cap;
-	use.d_episodes = o.d_episodes;
-	use.d_nepisodes = o.d_nepisodes;
-	use.episodes_cap = o.episodes_cap;
-	use.d_status = o.d_status;
+	mifsk::outputs_assign(use, l.set.io);
     }
     if ( after != MIFSK_PIPELINE_NO_PRODUCER ) {
 	// the batch was produced on the caller's stream: the lane waits for the point it has reached

@@ -18,6 +18,7 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
 #include "mifsk_devlib.h"
 
 namespace mifsk {
@@ -247,12 +248,8 @@ void selftest_wave_max_kernel( const float *__restrict__ v, uint32_t nwaves, flo
 namespace {
 
 // device memory for the length of one call
-struct DevBuf {
-    void	*p = nullptr;
-    DevBuf() {}
-    DevBuf( const DevBuf & ) = delete;
-    ~DevBuf() { if ( p ) (void)hipFree(p); }
-    bool alloc( size_t bytes ) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+struct TestBuf : DevMem<uint8_t> {
+    bool make( size_t bytes ) { return alloc(bytes, 1) == 0; }
     bool put( const void *h, size_t bytes ) { return hipMemcpy(p, h, bytes, hipMemcpyHostToDevice) == hipSuccess; }
     bool get( void *h, size_t bytes ) const { return hipMemcpy(h, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
 };
@@ -269,7 +266,7 @@ inline int finish()
 } // namespace
 } // namespace mifsk
 
-using mifsk::DevBuf;
+using mifsk::TestBuf;
 
 extern "C" int mifsk_selftest_rcp( mifsk_ctx *ctx, const float *c, const float *x, uint64_t n,
 	double *rcp_out, float *quot_out )
@@ -279,9 +276,9 @@ extern "C" int mifsk_selftest_rcp( mifsk_ctx *ctx, const float *c, const float *
     if ( n == 0 )
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf d_c, d_x, d_rc, d_q;
-    if ( !d_c.alloc(n * sizeof(float)) || !d_x.alloc(n * sizeof(float))
-	    || !d_rc.alloc(n * sizeof(double)) || !d_q.alloc(n * sizeof(float)) )
+    TestBuf d_c, d_x, d_rc, d_q;
+    if ( !d_c.make(n * sizeof(float)) || !d_x.make(n * sizeof(float))
+	    || !d_rc.make(n * sizeof(double)) || !d_q.make(n * sizeof(float)) )
 	return -ENOMEM;
     if ( !d_c.put(c, n * sizeof(float)) || !d_x.put(x, n * sizeof(float)) )
 	return -EIO;
@@ -300,9 +297,9 @@ extern "C" int mifsk_selftest_mag( mifsk_ctx *ctx, const double *re, const doubl
     if ( n == 0 )
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf d_re, d_im, d_root, d_g, d_u, d_mag;
-    if ( !d_re.alloc(n * sizeof(double)) || !d_im.alloc(n * sizeof(double)) || !d_root.alloc(n * sizeof(double))
-	    || !d_g.alloc(n * sizeof(double)) || !d_u.alloc(n) || !d_mag.alloc(n * sizeof(float)) )
+    TestBuf d_re, d_im, d_root, d_g, d_u, d_mag;
+    if ( !d_re.make(n * sizeof(double)) || !d_im.make(n * sizeof(double)) || !d_root.make(n * sizeof(double))
+	    || !d_g.make(n * sizeof(double)) || !d_u.make(n) || !d_mag.make(n * sizeof(float)) )
 	return -ENOMEM;
     if ( !d_re.put(re, n * sizeof(double)) || !d_im.put(im, n * sizeof(double)) )
 	return -EIO;
@@ -327,9 +324,9 @@ extern "C" int mifsk_selftest_confidence( mifsk_ctx *ctx, int variant, uint32_t 
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
     const size_t mag_bytes = (size_t)ncases * n_bits * 2 * sizeof(float);
-    DevBuf d_m, d_conf, d_ampl, d_bits, d_fb;
-    if ( !d_m.alloc(mag_bytes) || !d_conf.alloc(ncases * sizeof(float)) || !d_ampl.alloc(ncases * sizeof(float))
-	    || !d_bits.alloc(ncases * sizeof(uint64_t)) || !d_fb.alloc(ncases * sizeof(uint32_t)) )
+    TestBuf d_m, d_conf, d_ampl, d_bits, d_fb;
+    if ( !d_m.make(mag_bytes) || !d_conf.make(ncases * sizeof(float)) || !d_ampl.make(ncases * sizeof(float))
+	    || !d_bits.make(ncases * sizeof(uint64_t)) || !d_fb.make(ncases * sizeof(uint32_t)) )
 	return -ENOMEM;
     if ( !d_m.put(mags, mag_bytes) )
 	return -EIO;
@@ -448,10 +445,10 @@ extern "C" int mifsk_selftest_corr( mifsk_ctx *ctx, const mifsk_rx_config *cfg, 
     std::vector<float> hx(padded, 0.0f);
     for ( uint32_t i = 0; i < nsamples; i++ )
 	hx[i] = samples[i];
-    DevBuf d_cfg, d_x, d_starts, d_lens, d_acc, d_esum;
-    if ( !d_cfg.alloc(sizeof(DevCfg)) || !d_x.alloc(padded * sizeof(float)) || !d_starts.alloc(ncases * sizeof(uint32_t))
-	    || !d_lens.alloc(ncases * sizeof(uint32_t)) || !d_acc.alloc((size_t)ncases * 4 * sizeof(double))
-	    || !d_esum.alloc(ncases * sizeof(float)) )
+    TestBuf d_cfg, d_x, d_starts, d_lens, d_acc, d_esum;
+    if ( !d_cfg.make(sizeof(DevCfg)) || !d_x.make(padded * sizeof(float)) || !d_starts.make(ncases * sizeof(uint32_t))
+	    || !d_lens.make(ncases * sizeof(uint32_t)) || !d_acc.make((size_t)ncases * 4 * sizeof(double))
+	    || !d_esum.make(ncases * sizeof(float)) )
 	return -ENOMEM;
     if ( !d_cfg.put(&d, sizeof(DevCfg)) || !d_x.put(hx.data(), padded * sizeof(float))
 	    || !d_starts.put(starts, ncases * sizeof(uint32_t)) || ( seg && !d_lens.put(lens, ncases * sizeof(uint32_t)) ) )
@@ -520,9 +517,9 @@ extern "C" int mifsk_selftest_scan( mifsk_ctx *ctx, int routine, int totals, con
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
     const size_t lanes = (size_t)nwaves * 64u;
-    DevBuf d_st, d_cv, d_av, d_k, d_x, d_b;
-    if ( !d_st.alloc(nwaves * 4 * sizeof(float)) || !d_cv.alloc(lanes * sizeof(float)) || !d_av.alloc(lanes * sizeof(float))
-	    || !d_k.alloc(nwaves * sizeof(uint32_t)) || !d_x.alloc(lanes * 4 * sizeof(float)) || !d_b.alloc(lanes * 4 * sizeof(float)) )
+    TestBuf d_st, d_cv, d_av, d_k, d_x, d_b;
+    if ( !d_st.make(nwaves * 4 * sizeof(float)) || !d_cv.make(lanes * sizeof(float)) || !d_av.make(lanes * sizeof(float))
+	    || !d_k.make(nwaves * sizeof(uint32_t)) || !d_x.make(lanes * 4 * sizeof(float)) || !d_b.make(lanes * 4 * sizeof(float)) )
 	return -ENOMEM;
     if ( !d_st.put(state, nwaves * 4 * sizeof(float)) || !d_cv.put(cv, lanes * sizeof(float))
 	    || !d_av.put(av, lanes * sizeof(float)) || !d_k.put(k, nwaves * sizeof(uint32_t)) )
@@ -551,8 +548,8 @@ extern "C" int mifsk_selftest_wave_max( mifsk_ctx *ctx, const float *v, uint32_t
     if ( nwaves == 0 )
 	return 0;
     HIP_OK(hipSetDevice(ctx->device));
-    DevBuf d_v, d_m;
-    if ( !d_v.alloc((size_t)nwaves * 64u * sizeof(float)) || !d_m.alloc(nwaves * sizeof(float)) )
+    TestBuf d_v, d_m;
+    if ( !d_v.make((size_t)nwaves * 64u * sizeof(float)) || !d_m.make(nwaves * sizeof(float)) )
 	return -ENOMEM;
     if ( !d_v.put(v, (size_t)nwaves * 64u * sizeof(float)) )
 	return -EIO;

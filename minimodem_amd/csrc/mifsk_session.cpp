@@ -23,54 +23,15 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
 
-namespace {
-
-template <class T>
-struct DevBuf {
-    T		*p = nullptr;
-    size_t	cap = 0;		// elements
-    int fit( size_t n )
-    {
-	if ( n <= cap )
-	    return 0;
-	if ( p ) (void)hipFree(p);
-	p = nullptr;
-	cap = 0;
-	const size_t want = n + n / 4;
-	if ( hipMalloc((void **)&p, want * sizeof(T)) != hipSuccess )
-	    return -ENOMEM;
-	cap = want;
-	return 0;
-    }
-    void drop() { if ( p ) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-template <class T>
-struct PinBuf {
-    T		*p = nullptr;
-    size_t	cap = 0;
-    int fit( size_t n )
-    {
-	if ( n <= cap )
-	    return 0;
-	if ( p ) (void)hipHostFree(p);
-	p = nullptr;
-	cap = 0;
-	const size_t want = n + n / 4;
-	if ( hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault) != hipSuccess )
-	    return -ENOMEM;
-	cap = want;
-	return 0;
-    }
-    void drop() { if ( p ) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
-
-} // namespace
+using mifsk::DevMem;
+using mifsk::PinMem;
 
 struct mifsk_session {
     mifsk_ctx		*ctx = nullptr;
@@ -83,22 +44,22 @@ struct mifsk_session {
     std::vector<std::vector<float>>	tail;
     std::vector<uint64_t>		origin;
     // device: loop state, RING cells, the rows of a feed and its outputs
-    DevBuf<mifsk_stream_state>	d_state;
-    DevBuf<float>		d_ring;
-    DevBuf<float>		d_rows;
-    DevBuf<uint32_t>		d_lens, d_counts;	// counts: nframes | nbytes | nepisodes | status | carrier_band
-    DevBuf<uint64_t>		d_origin, d_bits;
-    DevBuf<uint8_t>		d_bytes;
-    DevBuf<mifsk_frame>		d_frames;
-    DevBuf<mifsk_episode>	d_eps;
+    DevMem<mifsk_stream_state>	d_state;
+    DevMem<float>		d_ring;
+    DevMem<float>		d_rows;
+    DevMem<uint32_t>		d_lens, d_counts;	// counts: nframes | nbytes | nepisodes | status | carrier_band
+    DevMem<uint64_t>		d_origin, d_bits;
+    DevMem<uint8_t>		d_bytes;
+    DevMem<mifsk_frame>		d_frames;
+    DevMem<mifsk_episode>	d_eps;
     // host (page-locked): staging of the rows, the results of the last feed
-    PinBuf<float>		h_rows;
-    PinBuf<uint32_t>		h_lens, h_counts;
-    PinBuf<uint64_t>		h_origin, h_bits;
-    PinBuf<uint8_t>		h_bytes;
-    PinBuf<mifsk_frame>		h_frames;
-    PinBuf<mifsk_episode>	h_eps;
-    PinBuf<mifsk_stream_state>	h_state;
+    PinMem<float>		h_rows;
+    PinMem<uint32_t>		h_lens, h_counts;
+    PinMem<uint64_t>		h_origin, h_bits;
+    PinMem<uint8_t>		h_bytes;
+    PinMem<mifsk_frame>		h_frames;
+    PinMem<mifsk_episode>	h_eps;
+    PinMem<mifsk_stream_state>	h_state;
     size_t			fc = 0, ec = 0;		// capacities of the last feed's arrays
     std::vector<mifsk_session_result>	results;
     // what info_get reports
@@ -111,11 +72,11 @@ struct mifsk_session {
     struct Held { uint32_t len, skip; bool done; };
     bool			resident = false;
     std::vector<Held>		held;
-    float			*rows[2] = { nullptr, nullptr };	// [n][row_cap] each; rows[cur] holds the tails
+    DevMem<float>		rows[2];		// [n][row_cap] each; rows[cur] holds the tails
     size_t			row_cap = 0;
     int				cur = 0;
-    PinBuf<uint8_t>		h_stage;		// a feed's table, then its new pieces
-    DevBuf<uint8_t>		d_stage;
+    PinMem<uint8_t>		h_stage;		// a feed's table, then its new pieces
+    DevMem<uint8_t>		d_stage;
     hipEvent_t			ev_producer = nullptr;	// feed_device: the producer's stream at the call
 };
 
@@ -239,24 +200,18 @@ int run_slab( mifsk_session *s, const float *d_rows, size_t stride, size_t width
 // feed itself when it has synchronised.
 struct GrownRows {
     hipStream_t	st;
-    float	*p[2] = { nullptr, nullptr };
+    DevMem<float>	p[2];
     explicit GrownRows( hipStream_t st_ ) : st(st_) {}
     int alloc( size_t floats )
     {
-	for ( int b = 0; b < 2; b++ )
-	    if ( hipMalloc((void **)&p[b], floats * sizeof(float)) != hipSuccess ) {
-		p[b] = nullptr;
-		return -ENOMEM;
-	    }
-	return 0;
+	if ( const int rc = p[0].alloc(floats) )
+	    return rc;
+	return p[1].alloc(floats);
     }
     ~GrownRows()
     {
-	if ( !p[0] && !p[1] )
-	    return;
-	(void)hipStreamSynchronize(st);
-	for ( int b = 0; b < 2; b++ )
-	    if ( p[b] ) (void)hipFree(p[b]);
+	if ( p[0].p || p[1].p )
+	    (void)hipStreamSynchronize(st);	// (then the members free)
     }
 };
 
@@ -297,11 +252,11 @@ int feed_resident( mifsk_session *s, const void *const *host, const void *d_fres
     GrownRows grown(st);
     size_t new_cap = s->row_cap;
     if ( width > s->row_cap ) {
-	new_cap = ( width + width / 4 + 3 ) & ~(size_t)3;	// (DevBuf::fit's head-room)
+	new_cap = ( width + width / 4 + 3 ) & ~(size_t)3;	// (DevMem::fit's head-room)
 	if ( ( rc = grown.alloc(n * new_cap) ) )
 	    return rc;
     }
-    float *dst = grown.p[0] ? grown.p[0] : s->rows[s->cur ^ 1];
+    float *dst = grown.p[0].p ? grown.p[0].p : s->rows[s->cur ^ 1].p;
 
     mifsk::SessionRow *table = reinterpret_cast<mifsk::SessionRow *>(s->h_stage.p);
     uint8_t *pieces = s->h_stage.p + table_bytes;
@@ -327,7 +282,7 @@ int feed_resident( mifsk_session *s, const void *const *host, const void *d_fres
 	HIP_OK(hipEventRecord(s->ev_producer, (hipStream_t)producer));
 	HIP_OK(hipStreamWaitEvent(st, s->ev_producer, 0));
     }
-    rc = mifsk::launch_session_append(s->rows[s->cur], s->row_cap, dst, new_cap, (uint32_t)width,
+    rc = mifsk::launch_session_append(s->rows[s->cur].p, s->row_cap, dst, new_cap, (uint32_t)width,
 				      device ? d_fresh : (const void *)( s->d_stage.p + table_bytes ),
 				      kind == MIFSK_FEED_S16, reinterpret_cast<const mifsk::SessionRow *>(s->d_stage.p),
 				      s->d_lens.p, s->d_origin.p, s->n, mifsk::rxnoise_term(rxnoise), st);
@@ -338,12 +293,9 @@ int feed_resident( mifsk_session *s, const void *const *host, const void *d_fres
 	return rc;
     }
     // the stream has synchronised: the rows are in the other buffer, of the new pair if it grew
-    if ( grown.p[0] ) {
-	for ( int b = 0; b < 2; b++ ) {
-	    if ( s->rows[b] ) (void)hipFree(s->rows[b]);
-	    s->rows[b] = grown.p[b];
-	    grown.p[b] = nullptr;
-	}
+    if ( grown.p[0].p ) {
+	for ( int b = 0; b < 2; b++ )
+	    s->rows[b] = std::move(grown.p[b]);
 	s->row_cap = new_cap;
 	s->cur = 0;
     } else {
@@ -384,15 +336,8 @@ extern "C" void mifsk_session_destroy( mifsk_session *s )
 	(void)hipStreamSynchronize(s->stream);
 	(void)hipStreamDestroy(s->stream);
     }
-    s->d_state.drop(); s->d_ring.drop(); s->d_rows.drop(); s->d_lens.drop(); s->d_counts.drop();
-    s->d_origin.drop(); s->d_bits.drop(); s->d_bytes.drop(); s->d_frames.drop(); s->d_eps.drop();
-    s->h_rows.drop(); s->h_lens.drop(); s->h_counts.drop(); s->h_origin.drop(); s->h_bits.drop();
-    s->h_bytes.drop(); s->h_frames.drop(); s->h_eps.drop(); s->h_state.drop();
-    s->h_stage.drop(); s->d_stage.drop();
-    for ( int b = 0; b < 2; b++ )
-	if ( s->rows[b] ) (void)hipFree(s->rows[b]);
     if ( s->ev_producer ) (void)hipEventDestroy(s->ev_producer);
-    delete s;
+    delete s;					// (its buffers free themselves)
 }
 
 extern "C" int mifsk_session_create( mifsk_session **out, mifsk_ctx *ctx, const mifsk_rx_config *cfg,

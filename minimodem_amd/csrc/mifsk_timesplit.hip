@@ -30,6 +30,10 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
+#include "mifsk_outputs.h"
+
+using mifsk::StreamMem;
 
 namespace {
 
@@ -609,18 +613,6 @@ int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mif
     return 0;
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    hipStream_t st = nullptr;
-    ~DevBuf() { if ( p ) (void)hipFreeAsync(p, st); }
-};
-
-int alloc( DevBuf &b, size_t bytes, hipStream_t st )
-{
-    b.st = st;
-    return hipMallocAsync(&b.p, bytes ? bytes : 16, st) == hipSuccess ? 0 : -ENOMEM;
-}
-
 unsigned blocks_for( uint64_t stride )
 {
     return (unsigned)std::min<uint64_t>(64, std::max<uint64_t>(1, ( stride / 4 + 255 ) / 256));
@@ -686,10 +678,7 @@ mifsk_demod_io rows_of( mifsk_demod_io b, uint32_t *cnt, int nrows, int lo, int 
     b.d_samples += (size_t)lo * b.stream_stride;
     b.d_nsamples += lo;
     b.nstreams = count;
-    b.d_frames += (size_t)lo * b.frames_cap;
-    if ( b.d_bytes )
-	b.d_bytes += (size_t)lo * b.frames_cap;
-    b.d_episodes += (size_t)lo * b.episodes_cap;
+    mifsk::outputs_advance(b, (size_t)lo);
     b.d_nframes = cnt + lo;
     b.d_nbytes = cnt + nrows + lo;
     b.d_nepisodes = cnt + 2 * nrows + lo;
@@ -793,7 +782,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	// is, and so is a lone row of whole float4s (no allocation, no copy); any other lone row goes
 	// over a padded copy, its stride being its length in whole float4s; PCM16 becomes floats
 	// through mifsk_ingest_s16, as the host pipeline makes them (every row defined up to its stride)
-	DevBuf pad, dn;
+	StreamMem pad(st), dn(st);
 	const bool lone = M == 1;
 	const uint64_t stride = lone ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : src.stride;
 	mifsk_demod_io io = *io_out;
@@ -802,13 +791,13 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 	    std::vector<uint32_t> hn(M);
 	    for ( int m = 0; m < M; m++ )
 		hn[m] = (uint32_t)nsamples[m];
-	    if ( ( rc = alloc(dn, M * sizeof(uint32_t), st) ) )
+	    if ( ( rc = dn.alloc(M * sizeof(uint32_t)) ) )
 		return rc;
 	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
 	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
 	}
 	if ( src.s16 ) {
-	    if ( ( rc = alloc(pad, (size_t)M * stride * sizeof(float), st) ) )
+	    if ( ( rc = pad.alloc((size_t)M * stride * sizeof(float)) ) )
 		return rc;
 	    if ( !src.p )
 		HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
@@ -817,11 +806,11 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
 		return rc;
 	    io.d_samples = (const float *)pad.p;
 	} else if ( lone && nsamples[0] % 4u ) {
-	    if ( ( rc = alloc(pad, stride * sizeof(float), st) ) )
+	    if ( ( rc = pad.alloc(stride * sizeof(float)) ) )
 		return rc;
 	    // (the one row's table, synchronised: it goes out of scope with this block)
 	    const struct { StreamRef s; RowRef r; } one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
-	    if ( ( rc = alloc(dn, sizeof(one), st) ) )
+	    if ( ( rc = dn.alloc(sizeof(one)) ) )
 		return rc;
 	    HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
 	    HIP_OK(hipStreamSynchronize(st));
@@ -853,22 +842,23 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     const uint64_t rstride = ( L + W + 3u ) & ~3ull;
     const size_t fcap = mifsk_max_frames(cfg, L + W);
     const size_t ecap = mifsk_max_episodes(cfg, L + W) + 1;
-    DevBuf rows, X, I, S, Rr, cnt, rcnt, code, mark, rframes, rbytes, reps, pref, ns, streams, rowref, tails;
+    StreamMem rows(st), X(st), I(st), S(st), Rr(st), cnt(st), rcnt(st), code(st), mark(st), rframes(st), rbytes(st),
+	      reps(st), pref(st), ns(st), streams(st), rowref(st), tails(st);
     const size_t stsz = sizeof(mifsk_stream_state);
-    if ( ( rc = alloc(rows, (size_t)R * rstride * sizeof(float), st) )
-	    || ( rc = alloc(X, nrows * stsz, st) ) || ( rc = alloc(I, nrows * stsz, st) )
-	    || ( rc = alloc(S, nrows * stsz, st) ) || ( rc = alloc(Rr, nrows * stsz, st) )
-	    || ( rc = alloc(cnt, 4 * (size_t)nrows * sizeof(uint32_t), st) )
-	    || ( rc = alloc(rcnt, 4 * (size_t)nrows * sizeof(uint32_t), st) )
-	    || ( rc = alloc(code, nrows * sizeof(uint32_t), st) )
-	    || ( rc = alloc(mark, nrows, st) )
-	    || ( rc = alloc(rframes, nrows * fcap * sizeof(mifsk_frame), st) )
-	    || ( io_out->d_bytes && ( rc = alloc(rbytes, nrows * fcap, st) ) )
-	    || ( rc = alloc(reps, nrows * ecap * sizeof(mifsk_episode), st) )
-	    || ( rc = alloc(pref, ( (size_t)nrows + M ) * sizeof(Agg), st) )
-	    || ( rc = alloc(ns, nrows * sizeof(uint32_t), st) )
-	    || ( rc = alloc(streams, M * sizeof(StreamRef), st) )
-	    || ( rc = alloc(rowref, nrows * sizeof(RowRef), st) ) )
+    if ( ( rc = rows.alloc((size_t)R * rstride * sizeof(float)) )
+	    || ( rc = X.alloc(nrows * stsz) ) || ( rc = I.alloc(nrows * stsz) )
+	    || ( rc = S.alloc(nrows * stsz) ) || ( rc = Rr.alloc(nrows * stsz) )
+	    || ( rc = cnt.alloc(4 * (size_t)nrows * sizeof(uint32_t)) )
+	    || ( rc = rcnt.alloc(4 * (size_t)nrows * sizeof(uint32_t)) )
+	    || ( rc = code.alloc(nrows * sizeof(uint32_t)) )
+	    || ( rc = mark.alloc(nrows) )
+	    || ( rc = rframes.alloc(nrows * fcap * sizeof(mifsk_frame)) )
+	    || ( io_out->d_bytes && ( rc = rbytes.alloc(nrows * fcap) ) )
+	    || ( rc = reps.alloc(nrows * ecap * sizeof(mifsk_episode)) )
+	    || ( rc = pref.alloc(( (size_t)nrows + M ) * sizeof(Agg)) )
+	    || ( rc = ns.alloc(nrows * sizeof(uint32_t)) )
+	    || ( rc = streams.alloc(M * sizeof(StreamRef)) )
+	    || ( rc = rowref.alloc(nrows * sizeof(RowRef)) ) )
 	return rc;
     auto *dX = (mifsk_stream_state *)X.p, *dI = (mifsk_stream_state *)I.p;
     auto *dS = (mifsk_stream_state *)S.p, *dR = (mifsk_stream_state *)Rr.p;
@@ -978,7 +968,7 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     HIP_OK(hipMemcpyAsync(dS + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
     if ( live ) {
 	const uint64_t tstride = std::max<uint64_t>(4, ( longest_tail + 3u ) & ~3ull);
-	if ( ( rc = alloc(tails, (size_t)M * tstride * sizeof(float), st) ) )
+	if ( ( rc = tails.alloc((size_t)M * tstride * sizeof(float)) ) )
 	    return rc;
 	HIP_OK(hipMemcpyAsync((uint32_t *)ns.p + R, hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
 	gather_tails(src, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), st, dstreams, (float *)tails.p,

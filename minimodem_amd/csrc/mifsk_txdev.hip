@@ -17,6 +17,7 @@
 
 #include "mifsk.h"
 #include "mifsk_device.h"
+#include "mifsk_hostmem.h"
 #include "mifsk_sinf.h"
 
 namespace mifsk {
@@ -303,12 +304,16 @@ int get_table( unsigned len, float mag, const float **d_f, const short **d_s )
 	sh[i] = (short)lroundf(mag_s * sinf(ang));
 	f[i] = mag * sinf(ang);
     }
-    TxTable t = { len, mag, nullptr, nullptr };
-    if ( hipMalloc(&t.d_f, len * sizeof(float)) != hipSuccess
-	    || hipMalloc(&t.d_s, len * sizeof(short)) != hipSuccess
-	    || hipMemcpy(t.d_f, f.data(), len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess
-	    || hipMemcpy(t.d_s, sh.data(), len * sizeof(short), hipMemcpyHostToDevice) != hipSuccess )
+    // (a table lives as long as the process: what is built here is released into the list, whose
+    // entries nothing frees -- no call into the runtime while the process is being taken down)
+    mifsk::DevMem<float> tf;
+    mifsk::DevMem<short> ts;
+    if ( tf.alloc(len) || ts.alloc(len)
+	    || hipMemcpy(tf.p, f.data(), len * sizeof(float), hipMemcpyHostToDevice) != hipSuccess
+	    || hipMemcpy(ts.p, sh.data(), len * sizeof(short), hipMemcpyHostToDevice) != hipSuccess )
 	return -ENOMEM;
+    g_tables.reserve(g_tables.size() + 1);
+    const TxTable t = { len, mag, tf.release(), ts.release() };
     g_tables.push_back(t);
     *d_f = t.d_f; *d_s = t.d_s;
     return 0;

@@ -66,6 +66,23 @@ def test_loopback_gather_delivers_the_columns_that_were_sent(torch_mod):
     g.close()
 
 
+def test_a_slot_reused_with_another_shape_delivers_the_columns_that_were_sent(torch_mod):
+    """Two slots, four gathers whose shapes change: set 0 is fitted for (8, 16) and met again with the
+    same shape, set 1 is fitted for (24, 40) and replaced by one for (8, 16) -- the sets and the
+    narrow staging copies are freed and made again by their owners (csrc/mifsk_gather_sets.h)."""
+    torch = torch_mod
+    g = M.NativeGatherer(None, 0, 1, slots=2, loopback=True)
+    for k, (rows, cols) in enumerate(((8, 16), (24, 40), (8, 16), (8, 16))):
+        b, nb = _batch(torch, 40 + k, rows, cols + 8)      # (wider than what travels: the staging copy)
+        g.cols = cols
+        assert g.start(b, nb) == []
+        torch.cuda.synchronize()
+        rb, rn = g.received(0)
+        assert rb.shape == (rows, cols) and rn.shape == (rows,)
+        assert torch.equal(rb, b[:, :cols]) and torch.equal(rn, nb)
+    g.close()
+
+
 def test_a_pipeline_pass_and_its_gather_on_the_lanes_stream(torch_mod):
     """bench.py's step: a pass of the library's pipeline, its bytes gathered on the lane's stream
     behind it, several in flight -- what arrives is what a lone launch decodes."""

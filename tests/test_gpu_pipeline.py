@@ -109,3 +109,48 @@ def test_pipelined_passes_equal_serial_launches_on_all_five_workloads(queues, de
     r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0 and b"PIPELINE_OK" in r.stdout, (r.stdout.decode()[-500:], r.stderr.decode()[-3000:])
+
+
+def test_output_sets_made_a_second_time_equal_the_serial_launch():
+    """outputs() twice on one pipeline -- for 8 streams, then for 4 with another frames_cap: every
+    lane's first set is freed by its owner and a new one made (csrc/mifsk_outputs.h OutMirror) --
+    then one pass per lane over 4 short Bell-202 streams: every set holds what a serial launch gives."""
+    import numpy as np
+    import torch
+    import minimodem_amd as M
+
+    ctx = M.Context(0)
+    cfg = M.rx_config("1200")
+    rng = np.random.default_rng(23)
+    rows = [M.synthesize(cfg, rng.integers(32, 127, size=20 + 3 * i, dtype=np.uint8),
+                         leading_silence=int(rng.integers(0, 40))) for i in range(4)]
+    width = (max(len(r) for r in rows) + 3) & ~3
+    host = np.zeros((4, width), np.float32)
+    lens = np.zeros(4, np.int32)
+    for i, r in enumerate(rows):
+        host[i, :len(r)] = r
+        lens[i] = len(r)
+    x, n = torch.from_numpy(host).cuda(), torch.from_numpy(lens).cuda()
+    fc = int(M.max_frames(cfg, width))
+    want = ("bytes", "bits", "frames", "episodes")
+    ref = M.results_to_host(M.demod_batch(ctx, cfg, x, nsamples=n, want=want, frames_cap=fc, episodes_cap=4))
+    assert all(int(ref["nframes"][i]) >= 20 + 3 * i for i in range(4))
+    pipe = M.Pipeline(0, depth=2)
+    pipe.outputs(8, 2 * fc + 5, episodes_cap=8, want=("bytes", "frames"))
+    assert pipe.info()["output_sets"] == pipe.depth
+    pipe.outputs(4, fc, episodes_cap=4, want=want)
+    assert pipe.info()["output_sets"] == pipe.depth
+    tickets = [pipe.submit(cfg, x, nsamples=n) for _ in range(pipe.depth)]
+    pipe.drain()
+    for tk in tickets:
+        r = M.results_to_host(pipe.result(tk))
+        for key in ("nframes", "nbytes", "nepisodes", "status"):
+            assert np.array_equal(r[key], ref[key]), (tk, key)
+        for i in range(4):
+            nf, nb, ne = int(ref["nframes"][i]), int(ref["nbytes"][i]), min(4, int(ref["nepisodes"][i]))
+            assert r["frames"][i, :nf].tobytes() == ref["frames"][i, :nf].tobytes(), (tk, i)
+            assert r["bits"][i, :nf].tobytes() == ref["bits"][i, :nf].tobytes(), (tk, i)
+            assert r["bytes"][i, :nb].tobytes() == ref["bytes"][i, :nb].tobytes(), (tk, i)
+            assert r["episodes"][i, :ne].tobytes() == ref["episodes"][i, :ne].tobytes(), (tk, i)
+    pipe.close()
+    ctx.close()
