@@ -440,28 +440,6 @@ extern "C" int mifsk_find_frame_batch( mifsk_ctx *ctx, const mifsk_rx_config *cf
 					  nproblems, stream);
 }
 
-// Engine.  One wavefront per stream is the general engine (every option,
-// every mode).  Where bit windows are staged through LDS and long enough
-// that correlation, not the per-frame decisions, is the work (linear
-// LATTICE, >= 16 samples per bit: Bell-202, 2400 baud, ...), the workgroup
-// engine's master / worker pipeline overlaps the two and wins at every
-// batch size measured (0.32 vs 0.52 ms at 512 streams, 0.50 vs 0.59 at
-// 1024, 1.64 vs 2.19 at 4096); at 12000 baud (4 samples per bit) the
-// wavefront engine is 4 x faster.  With longer windows and a clean signal it
-// still wins (tools/gpu/eng50.py, 2048 streams: 50 baud 3.0 vs 4.4 ms, 150 baud
-// 1.3 vs 4.1 ms).  Identical results either way.
-static bool use_workgroup_engine( const mifsk_rx_config *cfg, const DevCfg &d, unsigned flags )
-{
-    const bool plain = !( flags & MIFSK_IO_RING_EXACT ) && !( cfg->auto_carrier_threshold > 0.0f );
-    bool workgroup = plain && !( flags & MIFSK_IO_ENGINE_WAVE )
-		  && ( ( flags & MIFSK_IO_ENGINE_WORKGROUP )
-		       || ( d.lat_linear && d.bit_nsamples >= 16u ) );
-    if ( const char *e = mifsk::experiment_env("MIFSK_ENGINE") )	// diagnostic override: "workgroup" / "wave"
-	if ( !( flags & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE ) ) )
-	    workgroup = plain && e[0] == 'w' && e[1] == 'o';
-    return workgroup;
-}
-
 // What a chained launch needs (mifsk_device.h WaveChain), with room for `ns` streams' states.
 // Called with ctx->chain_lock held.
 static int chain_prepare( mifsk_ctx *ctx, size_t ns )
@@ -504,68 +482,48 @@ static int chain_prepare( mifsk_ctx *ctx, size_t ns )
     return 0;
 }
 
-// One launch, or -- where the launcher's plan cuts the batch (ha.chain_ok) -- the chained
-// launches, one chain at a time on the context's streams.
+// what decides a batch's launch plan (mifsk_plan.cpp): the same for a launch and for mifsk_demod_plan
+static mifsk::PlanInputs plan_inputs( const mifsk_ctx *ctx, const mifsk_rx_config *cfg, const DevCfg &d,
+	const mifsk_demod_io &io, const mifsk_stream_state *d_state )
+{
+    return mifsk::PlanInputs{&d, ctx->ncu, io.nstreams, io.nsamples, cfg->samplebuf_size,
+			     io.flags & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE ), ( io.flags & MIFSK_IO_RING_EXACT ) != 0,
+			     cfg->auto_carrier_threshold > 0.0f, d_state != nullptr, io.d_counters != nullptr};
+}
+
+// One launch of the plan or -- where it cuts the batch -- the chained launches, one chain at a
+// time on the context's streams.
 template <class Args>
 static int launch_engine( mifsk_ctx *ctx,
-	int (*launch)( const DevCfg &, const DevCfg *, const double *, const mifsk_demod_io &, const Args &, void *, mifsk::LaunchInfo * ),
-	const Prepared &p, const mifsk_demod_io &io, Args &ha, void *stream )
+	int (*launch)( const mifsk::LaunchPlan &, const DevCfg *, const double *, const mifsk_demod_io &, const Args &, void * ),
+	const mifsk::LaunchPlan &plan, const Prepared &p, const mifsk_demod_io &io, Args &ha, void *stream )
 {
-    if ( ha.chain_ok ) {
-	mifsk::LaunchInfo li;
-	std::memset(&li, 0, sizeof(li));
-	int rc = launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, &li);
-	if ( rc )
-	    return rc;
-	if ( li.chain_groups ) {
-	    std::lock_guard<std::mutex> one(ctx->chain_lock);
-	    rc = chain_prepare(ctx, (size_t)io.nstreams);
-	    if ( rc )
-		return rc;
-	    ha.chain = &ctx->chain;
-	    return launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, nullptr);
-	}
-    }
-    return launch(p.d, p.d_cfg, p.d_tw, io, ha, stream, nullptr);
-}
-
-static void host_args( mifsk::HostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg,
-	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
-{
-    ha.ncu = ctx->ncu;
-    ha.samplebuf_size = cfg->samplebuf_size;
-    ha.d_state = d_state;
-    ha.d_origin = d_origin;
-    ha.final = final;
-}
-
-// what a plan-only call tells the wavefront engine's launcher (the rest decides nothing)
-static void wave_args( mifsk::WaveHostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
-	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
-{
-    host_args(ha, ctx, cfg, d_state, d_origin, final);
-    ha.fftsize = (uint32_t)cfg->fftsize;
-    ha.nbands = cfg->nbands;
-    ha.tw_entries = (uint32_t)mifsk::tw_entries(cfg->bit_nsamples);
-    ha.ring_exact = ( io->flags & MIFSK_IO_RING_EXACT ) != 0;
-    ha.autodetect = cfg->auto_carrier_threshold > 0.0f;
-    // a whole-stream call over a plain batch may be cut into chained launches (the launcher
-    // decides by the batch's shape)
-    ha.chain_ok = !d_state && !ha.ring_exact && !io->d_counters;
+    if ( !plan.chain_groups )
+	return launch(plan, p.d_cfg, p.d_tw, io, ha, stream);
+    std::lock_guard<std::mutex> one(ctx->chain_lock);
+    if ( int rc = chain_prepare(ctx, (size_t)io.nstreams) )
+	return rc;
+    ha.chain = &ctx->chain;
+    return launch(plan, p.d_cfg, p.d_tw, io, ha, stream);
 }
 
 // One wavefront per stream (mifsk_wave.hip): --auto-carrier and RING addressing
 // need per-call device scratch; it is allocated and freed in stream order (behind a chain's
 // groups too: the caller's stream has joined them when the launcher returns), so
 // concurrent calls on different streams never share it.
-static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Prepared &p,
-	const mifsk_demod_io *io, void *stream, mifsk_stream_state *d_state = nullptr,
-	const uint64_t *d_origin = nullptr, bool final = true, float *d_ring_persistent = nullptr )
+static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Prepared &p, const mifsk::LaunchPlan &plan,
+	const mifsk_demod_io *io, void *stream, mifsk_stream_state *d_state, const uint64_t *d_origin, bool final,
+	float *d_ring_persistent )
 {
     hipStream_t st = (hipStream_t)stream;
     const size_t ns = (size_t)io->nstreams;
     mifsk::WaveHostArgs ha = {};
-    wave_args(ha, ctx, cfg, io, d_state, d_origin, final);
+    static_cast<mifsk::HostArgs &>(ha) = mifsk::HostArgs{cfg->samplebuf_size, d_state, d_origin, final, nullptr};
+    ha.fftsize = (uint32_t)cfg->fftsize;
+    ha.nbands = cfg->nbands;
+    ha.tw_entries = (uint32_t)mifsk::tw_entries(cfg->bit_nsamples);
+    ha.ring_exact = ( io->flags & MIFSK_IO_RING_EXACT ) != 0;
+    ha.autodetect = cfg->auto_carrier_threshold > 0.0f;
     // (--auto-carrier retunes per stream: its rotation factors come from the stream's own table)
     if ( !ha.autodetect )
 	for ( int k = 0; k < 5; k++ ) {
@@ -604,30 +562,24 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const P
 	    ha.d_ring = (float *)scratch_ring.p;
 	}
     }
-    return launch_engine(ctx, mifsk::launch_demod_wave, p, *io, ha, stream);
+    return launch_engine(ctx, mifsk::launch_demod_wave, plan, p, *io, ha, stream);
 }
 
-// The workgroup engine: one call over whole streams (maybe cut into chained launches of its
-// resumable instantiation: the launcher decides by the batch's shape) or, with d_state, one
-// slab of streams that arrive in pieces.
-static void workgroup_args( mifsk::HostArgs &ha, const mifsk_ctx *ctx, const mifsk_rx_config *cfg, const mifsk_demod_io *io,
-	mifsk_stream_state *d_state, const uint64_t *d_origin, bool final )
-{
-    host_args(ha, ctx, cfg, d_state, d_origin, final);
-    // (this engine's default is one launch: only MIFSK_CHAIN cuts a batch)
-    ha.chain_ok = !d_state && !io->d_counters && mifsk::experiment_env("MIFSK_CHAIN");
-}
-
-// either engine (the same choice everywhere, the same state record), over whole streams or,
-// with d_state, over streams that arrive in pieces
+// Plan once; the plan names the engine (the same choice everywhere, the same state record).  Over
+// whole streams or, with d_state, over streams that arrive in pieces (d_ring: mifsk_demod_slab_ring's).
 static int demod_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Prepared &p, const mifsk_demod_io *io,
-	void *stream, mifsk_stream_state *d_state = nullptr, const uint64_t *d_origin = nullptr, bool final = true )
+	void *stream, mifsk_stream_state *d_state = nullptr, const uint64_t *d_origin = nullptr, bool final = true,
+	float *d_ring = nullptr )
 {
-    if ( !use_workgroup_engine(cfg, p.d, io->flags) )
-	return demod_batch_wave(ctx, cfg, p, io, stream, d_state, d_origin, final);
-    mifsk::HostArgs ha = {};
-    workgroup_args(ha, ctx, cfg, io, d_state, d_origin, final);
-    return launch_engine(ctx, mifsk::launch_demod_batch, p, *io, ha, stream);
+    if ( io->nstreams <= 0 )
+	return 0;
+    mifsk::LaunchPlan plan;
+    if ( int rc = mifsk::plan_launch(plan_inputs(ctx, cfg, p.d, *io, d_state), plan) )
+	return rc;
+    if ( plan.engine == MIFSK_IO_ENGINE_WAVE )
+	return demod_batch_wave(ctx, cfg, p, plan, io, stream, d_state, d_origin, final, d_ring);
+    mifsk::HostArgs ha = {cfg->samplebuf_size, d_state, d_origin, final, nullptr};
+    return launch_engine(ctx, mifsk::launch_demod_batch, plan, p, *io, ha, stream);
 }
 
 extern "C" int mifsk_demod_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
@@ -639,7 +591,7 @@ extern "C" int mifsk_demod_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
     Prepared p;
     if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    return io->nstreams == 0 ? 0 : demod_batch(ctx, cfg, p, io, stream);
+    return demod_batch(ctx, cfg, p, io, stream);
 }
 
 static_assert(sizeof(mifsk_scan_plan) == sizeof(mifsk::SegPlan), "mifsk_scan_plan mirrors SegPlan");
@@ -666,7 +618,7 @@ extern "C" int mifsk_demod_slab( mifsk_ctx *ctx, const mifsk_rx_config *cfg, con
     Prepared p;
     if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    return io->nstreams == 0 ? 0 : demod_batch(ctx, cfg, p, io, stream, d_state, d_origin, final != 0);
+    return demod_batch(ctx, cfg, p, io, stream, d_state, d_origin, final != 0);
 }
 
 // floats per stream of the buffer mifsk_demod_slab_ring keeps the reference's samplebuf in
@@ -687,11 +639,9 @@ extern "C" int mifsk_demod_slab_ring( mifsk_ctx *ctx, const mifsk_rx_config *cfg
     Prepared p;
     if ( int rc = prepare(ctx, cfg, p) )
 	return rc;
-    if ( io->nstreams == 0 )
-	return 0;
     mifsk_demod_io rio = *io;
     rio.flags |= MIFSK_IO_RING_EXACT;
-    return demod_batch_wave(ctx, cfg, p, &rio, stream, d_state, d_origin, final != 0, d_ring);
+    return demod_batch(ctx, cfg, p, &rio, stream, d_state, d_origin, final != 0, d_ring);
 }
 
 // what mifsk_demod_batch would launch for this configuration and batch size
@@ -713,32 +663,20 @@ extern "C" int mifsk_demod_plan_ex( mifsk_ctx *ctx, const mifsk_rx_config *cfg, 
     io.nstreams = nstreams;
     io.nsamples = nsamples;
     io.flags = flags;
-    mifsk::LaunchInfo li;
-    std::memset(&li, 0, sizeof(li));
-    const bool workgroup = use_workgroup_engine(cfg, d, flags);
-    int rc;
-    if ( workgroup ) {
-	mifsk::HostArgs ha = {};
-	workgroup_args(ha, ctx, cfg, &io, nullptr, nullptr, true);
-	rc = mifsk::launch_demod_batch(d, nullptr, nullptr, io, ha, nullptr, &li);
-    } else {
-	mifsk::WaveHostArgs ha = {};
-	wave_args(ha, ctx, cfg, &io, nullptr, nullptr, true);
-	rc = mifsk::launch_demod_wave(d, nullptr, nullptr, io, ha, nullptr, &li);
-    }
-    if ( rc )
+    mifsk::LaunchPlan plan;
+    if ( int rc = mifsk::plan_launch(plan_inputs(ctx, cfg, d, io, nullptr), plan) )
 	return rc;
     std::memset(out, 0, sizeof(*out));
-    std::snprintf(out->kernel, sizeof(out->kernel), "%s", li.kernel ? li.kernel : "");
-    out->engine = workgroup ? MIFSK_IO_ENGINE_WORKGROUP : MIFSK_IO_ENGINE_WAVE;
-    out->workgroup_size = li.workgroup_size;
-    out->lds_bytes_per_workgroup = li.lds_bytes;
-    out->workgroups_per_cu = mifsk::workgroups_per_cu(li.lds_bytes, li.waves_per_simd, li.workgroup_size);
-    out->lattice_mode = li.lattice_mode;
-    out->frames_per_block = li.frames_per_block;
+    std::snprintf(out->kernel, sizeof(out->kernel), "%s", plan.kernel_name);
+    out->engine = plan.engine;
+    out->workgroup_size = plan.workgroup_size;
+    out->lds_bytes_per_workgroup = plan.lds_bytes;
+    out->workgroups_per_cu = mifsk::workgroups_per_cu(plan.lds_bytes, plan.waves_per_simd, plan.workgroup_size);
+    out->lattice_mode = plan.lattice_mode;
+    out->frames_per_block = plan.frames_per_block;
     out->compute_units = (uint32_t)ctx->ncu;
-    out->chain_groups = li.chain_groups;
-    out->chain_chunks = li.chain_chunks;
+    out->chain_groups = plan.chain_groups;
+    out->chain_chunks = plan.chain_chunks;
     return 0;
 }
 

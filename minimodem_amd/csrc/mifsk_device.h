@@ -1,5 +1,5 @@
 // mifsk_device.h -- types shared by the host glue and the HIP kernels, and what the two
-// engines' launchers share (the slice of a batch, occupancy, the chained launch).
+// engines' launchers share (the launch plan, the slice of a batch, occupancy, the chained launch).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -118,9 +118,10 @@ inline size_t tw_entries( unsigned B )
     return n < 48 ? 48 : n;
 }
 
-// Tuning overrides for experiments (MIFSK_ENGINE, MIFSK_WAVES_PER_CU, MIFSK_SV,
-// MIFSK_LDS_PAD, MIFSK_LAT_ROUNDS, MIFSK_CHAIN): honoured only when MIFSK_EXPERIMENT is set in the
-// environment, so that a stray variable cannot change what production launches.
+// Tuning overrides for experiments (MIFSK_ENGINE, MIFSK_WAVES_PER_CU, MIFSK_SV, MIFSK_LDS_PAD,
+// MIFSK_LAT_ROUNDS, MIFSK_LAT_FMIN, MIFSK_CHAIN: all read by the launch planner, mifsk_plan.cpp):
+// honoured only when MIFSK_EXPERIMENT is set in the environment, so that a stray variable cannot
+// change what production launches.
 inline const char *experiment_env( const char *name )
 {
     return std::getenv("MIFSK_EXPERIMENT") != nullptr ? std::getenv(name) : nullptr;
@@ -131,25 +132,50 @@ int launch_find_frame_batch( const DevCfg &cfg, const DevCfg *d_cfg, const doubl
 	const float *d_samples, const mifsk_search *d_problems,
 	mifsk_search_result *d_results, int nproblems, void *stream );
 
-// what a launcher decided (mifsk_demod_plan): filled instead of launching when
-// the pointer is given
-struct LaunchInfo {
-    const char	*kernel;
-    uint32_t	workgroup_size;
-    uint32_t	lds_bytes;		// dynamic LDS per workgroup
-    uint32_t	lattice_mode;		// LAT_*
-    uint32_t	frames_per_block;	// LATTICE frames scored at once, at most
-    uint32_t	waves_per_simd;		// what the instantiation is compiled for (its VGPR budget)
-    uint32_t	chain_groups, chain_chunks;	// chained launches (WaveChain): groups of streams x time chunks; 0 = one launch
-};
+// ---- what the launch planner (mifsk_plan.cpp) and the kernels agree on ----
+constexpr int P_CAP = 64;	// candidate positions per batch (= one wave of lanes)
+constexpr int W_CAP = 448;	// bit windows per batch (LDS scratch)
+constexpr int STAGE_VEC = 10;	// float4 per thread per staging round
+// the wavefront engine's LDS tile for long windows (mifsk_devlib.h, corr_global_tiled)
+constexpr uint32_t TILE_K = 32u;
+constexpr uint32_t TILE_ROW = TILE_K + 4u;
+constexpr uint32_t TILE_FLOATS = 64u * TILE_ROW;
+constexpr uint32_t kTileMinBit = 256u;			// bit lengths from here on may go through the tile
+// NQ of demod_wave_kernel (mifsk_wave.hip) beside the bit lengths with a resident table
+constexpr int kTiled = -1;
+constexpr int kDirect = -2;
+constexpr size_t kCntBytes = ( MIFSK_NCOUNTERS * sizeof(uint32_t) + 15u ) & ~(size_t)15;	// work counters, first in LDS
+// the workgroup engine's LDS in front of its slab: offsetof(StreamLds, slab) (mifsk_kernels.hip)
+constexpr size_t kWgLdsHeader = 2u * W_CAP * 8u + P_CAP * ( 8u + 4u + 4u + 4u ) + 16u + MIFSK_NCOUNTERS * 4u + 2u * 32u;
 
-// the instantiation a launcher's plan runs: the function and the name mifsk_demod_plan reports,
-// from one table per engine
-struct KernelPick {
-    const void	*fn;
-    const char	*name;
-    uint32_t	waves_per_simd;
-};
+// Every instantiation of demod_wave_kernel<SV, NQ, ST, RA> there is.  The resumable ones (ST)
+// have generic correlators only; mifsk_demod_slab runs them with RA, a chain by --auto-carrier.
+// The name mifsk_demod_plan reports does not spell RA; the waves per SIMD are what the
+// instantiation is compiled for (its __launch_bounds__).
+#define MIFSK_WAVE_KERNELS(X)										\
+    X(10, -1, true, true)	X(10, 0, true, true)	X(10, -2, true, true)				\
+    X(4, 0, true, true)		X(4, -2, true, true)							\
+    X(10, -1, true, false)	X(10, 0, true, false)	X(10, -2, true, false)				\
+    X(4, 0, true, false)	X(4, -2, true, false)							\
+    X(10, -1, false, true)	X(10, -1, false, false)		/* RTTY and slower */			\
+    X(10, 10, false, true)	X(10, 10, false, false)		/* 1200 baud at 48 kHz */		\
+    X(10, 5, false, true)	X(10, 5, false, false)		/* 2400 baud; 1200 baud at 24 kHz */	\
+    X(10, 0, false, true)	X(10, 0, false, false)							\
+    X(10, -2, false, true)	X(10, -2, false, false)							\
+    X(4, 1, false, true)	X(4, 1, false, false)		/* 12000 baud */			\
+    X(4, 0, false, true)	X(4, 0, false, false)							\
+    X(4, -2, false, true)	X(4, -2, false, false)		/* SAME */
+
+// Every instantiation of demod_kernel there is: X(waves per SIMD its registers allow, key: slab,
+// Bell-202, resumable, then the template arguments as the reported name spells them).  ST: the
+// resumable ones (mifsk_demod_slab, chained launches).
+#define MIFSK_WG_KERNELS(X)										\
+    X(4u, false, false, true,  false, 0, 3, true)	/* no slab: e.g. 0.5 baud */			\
+    X(3u, true,  true,  true,  true, 10, 2, true)	/* Bell-202: two workers, resident table */	\
+    X(4u, true,  false, true,  true, 0, 3, true)							\
+    X(3u, true,  true,  false, true, 10, 2)								\
+    X(4u, true,  false, false, true, 0, 3)								\
+    X(4u, false, false, false, false, 0, 3)
 
 constexpr size_t kLdsPerCu = 160 * 1024;
 
@@ -184,22 +210,16 @@ inline mifsk_demod_io io_rows( const mifsk_demod_io &io, size_t lo, int count, s
 }
 
 struct WaveChain;
-// what the host glue hands either engine's launcher besides cfg / io: the loop state of streams
+// what the host glue hands either engine's launcher besides the plan and io: the loop state of streams
 // that arrive in pieces (mifsk_demod_slab) and what a chained launch needs
 struct HostArgs {
-    int		ncu;		// compute units of the device
     uint32_t	samplebuf_size;
     mifsk_stream_state *d_state;	// mifsk_demod_slab: state in / out (nullptr: one call = whole streams)
     const uint64_t *d_origin;
     bool	final;
-    // non-NULL: the launcher may chain (it decides by the batch's shape); the caller holds
-    // whatever serialises the chain's users.  chain_ok: what a plan-only call assumes
+    // what a plan that chains runs on; the caller holds whatever serialises the chain's users
     const WaveChain *chain;
-    bool	chain_ok;
 };
-
-int launch_demod_batch( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only = nullptr );
 
 // ---- one wavefront per stream (mifsk_wave.hip) ---------------------------
 
@@ -226,6 +246,43 @@ struct WaveGeom {
     uint32_t	fftsize, nbands;
     uint32_t	tw_entries;	// samples per per-stream twiddle table
 };
+
+// ---- the launch plan (mifsk_plan.cpp).  What decides a launch: a plan is a pure function of these (and of the experiment knobs above).
+struct PlanInputs {
+    const DevCfg *cfg;
+    int		ncu, nstreams;	// compute units of the device (<= 0: 256); the batch
+    uint32_t	nsamples;	// io.nsamples: the rows' common length (0: per-stream lengths only)
+    uint32_t	samplebuf_size;
+    uint32_t	engine_flags;	// MIFSK_IO_ENGINE_*
+    bool	ring_exact, autodetect;		// MIFSK_IO_RING_EXACT, --auto-carrier
+    bool	has_state, has_counters;	// mifsk_demod_slab's loop state in / out; io.d_counters
+};
+
+// the workgroup engine's geometry: its workers and demod_kernel's geometry arguments
+struct WgGeom {
+    uint32_t	nworkers, slab_cap, lat_frames, lat_rounds, region_floats, region_cap, lat_mode;
+    bool	use_slab;
+};
+
+// Everything either engine's launcher needs to know before it touches the device.
+struct LaunchPlan {
+    uint32_t	engine;			// MIFSK_IO_ENGINE_WAVE or _WORKGROUP
+    uint32_t	kernel;			// index into the engine's list (MIFSK_WAVE_KERNELS / MIFSK_WG_KERNELS)
+    const char	*kernel_name;		// as mifsk_demod_plan reports it
+    uint32_t	waves_per_simd;		// what the instantiation is compiled for (its VGPR budget)
+    uint32_t	workgroup_size, lds_bytes;	// threads and dynamic LDS per workgroup
+    uint32_t	lattice_mode;		// LAT_*
+    uint32_t	frames_per_block;	// LATTICE frames scored at once, at most
+    bool	resumable;		// an instantiation with the state code (mifsk_demod_slab, chains)
+    uint32_t	chain_groups, chain_chunks;	// chained launches (WaveChain): groups of streams x time chunks; 0 = one launch
+    // the wavefront engine: the planned fields of the kernel's geometry (mags_cap .. round_wins;
+    // the launcher fills the run-time ones) and the staging width
+    struct { WaveGeom g; int sv; } wave;
+    WgGeom	wg;
+};
+
+// the engine a batch runs on, and its plan: 0, or -ENOMEM / -EINVAL where nothing fits
+int plan_launch( const PlanInputs &in, LaunchPlan &plan );
 
 // Streams that arrive in pieces (mifsk_demod_slab) and chained launches: what a resumable
 // instantiation of either engine's kernel needs beyond the batch itself.
@@ -273,23 +330,6 @@ struct WaveChain {
     mifsk_stream_state	*d_state;		// [state_cap] the loop's state between chunks
     size_t		state_cap;
 };
-
-// MIFSK_CHAIN = "G,K" (experiments and tests only) cuts any batch that may be chained; then the
-// bounds of a cut: at most kMaxGroups groups, none empty, at least two chunks -- else (0, 0)
-inline void chain_shape( bool allowed, int nstreams, uint32_t &groups, uint32_t &chunks )
-{
-    if ( const char *e = experiment_env("MIFSK_CHAIN") ) {
-	int a = 0, b = 0;
-	if ( allowed && std::sscanf(e, "%d,%d", &a, &b) == 2 ) {
-	    groups = (uint32_t)( a < 0 ? 0 : a );
-	    chunks = (uint32_t)( b < 0 ? 0 : b );
-	}
-    }
-    if ( groups > (uint32_t)WaveChain::kMaxGroups ) groups = (uint32_t)WaveChain::kMaxGroups;
-    if ( groups > (uint32_t)nstreams ) groups = (uint32_t)nstreams;
-    if ( groups < 1u || chunks < 2u )
-	groups = chunks = 0u;
-}
 
 // Enqueue a batch as `groups` x `chunks` launches.  `launch(gio, lo, rs, gs)` enqueues the
 // resumable kernel over the rows `gio` (those from row `lo` of the batch) on the group's stream
@@ -344,6 +384,17 @@ int chain_enqueue( const WaveChain &ch, const mifsk_demod_io &io, uint32_t group
     return launched ? 0 : -5;
 }
 
+// One launch of the plan's kernel over the caller's rows, or -- where the plan cuts the batch -- its
+// chained launches (ha.chain: made by the caller).  `launch(rows, lo, rs, on)` as for chain_enqueue.
+template <class Launch>
+int launch_planned( const LaunchPlan &plan, const HostArgs &ha, const mifsk_demod_io &io, hipStream_t st, Launch launch )
+{
+    if ( plan.chain_groups )
+	return ha.chain ? chain_enqueue(*ha.chain, io, plan.chain_groups, plan.chain_chunks, st, launch) : -22;
+    launch(io, 0u, resume_args(ha.d_state, ha.d_origin, ha.final), st);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
 // what the host glue hands the wavefront engine's launcher besides that
 struct WaveHostArgs : HostArgs {
     bool	ring_exact;
@@ -361,8 +412,10 @@ struct WaveHostArgs : HostArgs {
     uint32_t	rot_stride[5];
 };
 
-int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, const WaveHostArgs &ha, void *stream, LaunchInfo *plan_only = nullptr );
+int launch_demod_wave( const LaunchPlan &plan, const DevCfg *d_cfg, const double *d_tw,
+	const mifsk_demod_io &io, const WaveHostArgs &ha, void *stream );
+int launch_demod_batch( const LaunchPlan &plan, const DevCfg *d_cfg, const double *d_tw,
+	const mifsk_demod_io &io, const HostArgs &ha, void *stream );
 
 int launch_detect_carrier( const float *d_samples, unsigned nsamples,
 	const double *d_cs /* [fftsize][2] */, unsigned fftsize, unsigned nbands,

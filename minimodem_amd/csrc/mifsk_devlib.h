@@ -16,9 +16,6 @@
 
 namespace mifsk {
 
-constexpr int P_CAP = 64;	// candidate positions per batch (= one wave of lanes)
-constexpr int W_CAP = 448;	// bit windows per batch (LDS scratch)
-
 // ---------------------------------------------------------------------------
 // arithmetic shared by every kernel
 // ---------------------------------------------------------------------------
@@ -469,8 +466,6 @@ struct ZigZag {
 	return ( zig && ( i & 1u ) == 0u ) ? first - off : first + off;
     }
 };
-
-constexpr int STAGE_VEC = 10;	// float4 per thread per staging round
 
 // rel / bit_nsamples without a hardware divide: magic = floor(2^32 / B)
 // under-estimates the quotient by at most one
@@ -1219,13 +1214,10 @@ __device__ __forceinline__ void corr_global_stream( const double *__restrict__ t
 // for 4096 RTTY streams), so what counts is how many waves fit: a 9 kB tile, with the
 // shared segments' partial sums aliased onto it, lets twelve waves share a CU's LDS
 // where the 17 kB tile allowed six.
-constexpr uint32_t TILE_K = 32u;
-constexpr uint32_t TILE_ROW = TILE_K + 4u;
-constexpr uint32_t TILE_FLOATS = 64u * TILE_ROW;
+// (TILE_K = 32, TILE_ROW, TILE_FLOATS and kTileMinBit: mifsk_device.h, the launch planner sizes by them)
 constexpr uint32_t TILE_LPW = TILE_K / 4u;		// lanes that fetch one window's step (16 bytes each)
 constexpr uint32_t TILE_WPL = 64u / TILE_LPW;		// windows per load instruction
 constexpr int TILE_GPS = (int)( TILE_K / 16u );		// groups of 16 samples per step
-constexpr uint32_t kTileMinBit = 256u;			// bit lengths from here on may go through the tile
 
 // NLD loads per step: windows 0 .. TILE_WPL NLD - 1.  Straight-line steps: every load
 // and store of a step is unconditional (a conditional load leaves the compiler with

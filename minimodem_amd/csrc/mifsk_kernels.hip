@@ -1856,211 +1856,32 @@ int launch_find_frame_batch( const DevCfg &cfg, const DevCfg *d_cfg, const doubl
     return hip_rc(hipGetLastError());
 }
 
-static constexpr size_t kLdsHeader = offsetof(StreamLds, slab);
+static_assert(kWgLdsHeader == offsetof(StreamLds, slab), "the planner sizes the LDS in front of the slab");
 
-// `nworkers` = 2 asks for the Bell-202 instantiation; kNotBell202 if the
-// configuration does not end up there (the caller then plans with three)
-static constexpr int kNotBell202 = -100000;
+// the functions of MIFSK_WG_KERNELS, in the list's order (LaunchPlan::kernel indexes it)
+#define MIFSK_FN(WAVES_, SLAB_, BELL_, ST_, ...)	reinterpret_cast<const void *>(&demod_kernel<__VA_ARGS__>),
+static const void *const kWgFns[] = { MIFSK_WG_KERNELS(MIFSK_FN) };
+#undef MIFSK_FN
 
-// Every instantiation of demod_kernel there is, with the name mifsk_demod_plan reports for it and
-// the waves per SIMD its registers allow.  ST: the resumable ones (mifsk_demod_slab, chained
-// launches).
-struct WgKernel {
-    bool	use_slab, bell202, st;
-    KernelPick	pick;
-};
-#define MIFSK_WG_KERNEL(WAVES_, ...)										\
-    { reinterpret_cast<const void *>(&demod_kernel<__VA_ARGS__>), "mifsk::demod_kernel<" #__VA_ARGS__ ">", WAVES_ }
-static const WgKernel kWgKernels[] = {
-    { false, false, true,  MIFSK_WG_KERNEL(4u, false, 0, 3, true) },	// no slab: e.g. 0.5 baud
-    { true,  true,  true,  MIFSK_WG_KERNEL(3u, true, 10, 2, true) },	// Bell-202: two workers, resident table
-    { true,  false, true,  MIFSK_WG_KERNEL(4u, true, 0, 3, true) },
-    { true,  true,  false, MIFSK_WG_KERNEL(3u, true, 10, 2) },
-    { true,  false, false, MIFSK_WG_KERNEL(4u, true, 0, 3) },
-    { false, false, false, MIFSK_WG_KERNEL(4u, false, 0, 3) },
-};
-#undef MIFSK_WG_KERNEL
-
-static const KernelPick &wg_kernel( bool use_slab, bool bell202, bool st )
+// (the plan is made: plan_launch, mifsk_plan.cpp)
+int launch_demod_batch( const LaunchPlan &plan, const DevCfg *d_cfg, const double *d_tw,
+	const mifsk_demod_io &io, const HostArgs &ha, void *stream )
 {
-    for ( const WgKernel &k : kWgKernels )
-	if ( k.use_slab == use_slab && k.bell202 == bell202 && k.st == st )
-	    return k.pick;
-    return kWgKernels[0].pick;		// (not reached: Bell-202 always has a slab)
-}
-
-static int launch_with_workers( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only, const uint32_t nworkers )
-{
-    const uint32_t B = cfg.bit_nsamples;
-    const uint32_t lat_lanes = nworkers * 64u;	// bit windows per lattice round
-    const uint32_t block = 64u * ( nworkers + 1u );
-    // samples one search must see at once
-    const uint32_t reach = ( cfg.try_max[0] > cfg.try_max[1] ? cfg.try_max[0] : cfg.try_max[1] )
-			 + cfg.last_reach + 8;
-    auto floats_for = [&]( uint32_t nsamp ) -> size_t {
-	return ( (size_t)nsamp + (size_t)( nsamp / B + 2 ) * cfg.skew + 8 + 3 ) & ~(size_t)3;
-    };
-    // LDS budget: 4 workgroups per CU when the stream count can use them
-    const size_t budget_small = kLdsPerCu / 4 - 64;
-
-    // LATTICE geometry.  A round is as many frames as fill the worker lanes (64 per worker)
-    // with distinct bit windows.  LINEAR workers stage their 64 windows' span in
-    // a private LDS region (fastest; needs bit length, offsets and frame step
-    // in multiples of 4 samples and the span to fit ten 16-byte loads per
-    // lane); otherwise DIRECT workers stream each window from global memory.
-    const uint32_t frames_max = cfg.lat_grid ? ( lat_lanes - 1u ) / ( cfg.n_bits - 1u )
-					     : lat_lanes / cfg.n_bits;
-    uint32_t lat_frames = frames_max > P_CAP ? P_CAP : frames_max;
-    auto wins_in = [&]( uint32_t frames ) -> uint32_t {
-	return cfg.lat_grid ? frames * ( cfg.n_bits - 1u ) + 1u : frames * cfg.n_bits;
-    };
-    // window starts must not decrease in window order (the workers take the
-    // wave's span from its first and last lane)
-    bool ordered = true;
-    for ( uint32_t w = 1; w < lat_frames * cfg.n_bits; w++ ) {
-	const uint32_t a0 = ( ( w - 1 ) / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[( w - 1 ) % cfg.n_bits];
-	const uint32_t a1 = ( w / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[w % cfg.n_bits];
-	ordered = ordered && a1 >= a0;
-    }
-    uint32_t lat_mode = lat_frames ? LAT_DIRECT : LAT_NONE;
-    uint32_t region_cap = 0;
-    size_t region_floats = 0;
-    if ( lat_frames && cfg.lat_linear && ordered ) {
-	// span of the widest wave: 64 windows (or all of them), plus what the
-	// group-wise correlator (corr_lds_stream: whole groups of 16 samples) loads
-	// beyond the last window -- nothing in the Bell-202 instantiation, whose
-	// resident-table correlator reads the window and no more
-	const uint32_t over = ( nworkers == 2u && B == 40u ) ? 0u : ( 16u - B % 16u ) % 16u;
-	uint32_t span = 0;
-	if ( cfg.lat_grid ) {
-	    const uint32_t nwin = wins_in(lat_frames);
-	    span = ( nwin < 64u ? nwin : 64u ) * B + over;
-	} else {
-	    const uint32_t nwin = lat_frames * cfg.n_bits;
-	    for ( uint32_t w0 = 0; w0 < nwin; w0 += 64 ) {
-		const uint32_t wl = w0 + 63 < nwin ? w0 + 63 : nwin - 1;
-		const uint32_t lo = ( w0 / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[w0 % cfg.n_bits];
-		const uint32_t hi = ( wl / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[wl % cfg.n_bits] + B;
-		span = hi - lo > span ? hi - lo : span;
-	    }
-	    span += over;
-	}
-	region_cap = ( span + 3 ) & ~3u;
-	region_floats = floats_for(region_cap);
-	if ( region_cap <= 64u * STAGE_VEC * 4u
-		&& kLdsHeader + nworkers * region_floats * 4 <= budget_small
-		&& nworkers * region_floats >= floats_for(reach + 4) )
-	    lat_mode = LAT_LINEAR;
-    }
-
-    // the master scores `lat_rounds` rounds at once: halves the per-frame cost
-    // of everything that is paid per batch -- the confidence pass, the barrier,
-    // the command hand-off
-    uint32_t lat_rounds = 1;
-    if ( lat_frames ) {
-	lat_rounds = 2;
-	if ( const char *e = experiment_env("MIFSK_LAT_ROUNDS") )	// experiments only
-	    lat_rounds = (uint32_t)std::atoi(e) < 1u ? 1u : (uint32_t)std::atoi(e);
-	while ( lat_rounds > 1 && ( lat_frames * lat_rounds > P_CAP
-				    || wins_in(lat_frames) * lat_rounds > W_CAP ) )
-	    lat_rounds--;
-    }
-
-    uint32_t slab_cap = 0;
-    size_t slab_floats = 0;
-    bool use_slab = true;
-    if ( lat_mode == LAT_LINEAR ) {
-	slab_floats = nworkers * region_floats;
-	// samples the whole slab holds in SCAN mode
-	size_t ns = slab_floats * B / ( B + cfg.skew );
-	ns = ns > 16 ? ns - 16 : 0;
-	slab_cap = (uint32_t)( ns & ~(size_t)3 );
-    } else {
-	// no regions: the slab serves SCAN only; take what one search needs
-	region_cap = 0;
-	region_floats = 0;
-	const size_t need = kLdsHeader + floats_for(reach + 4) * 4;
-	if ( need <= kLdsPerCu - 1024 ) {
-	    slab_cap = ( reach + 4 + 3 ) & ~3u;
-	    slab_floats = floats_for(slab_cap);
-	} else {
-	    use_slab = false;	// e.g. 0.5 baud: windows of 96000 samples
-	    lat_mode = LAT_NONE;
-	    lat_frames = 0;
-	}
-    }
-
-    const bool bell202 = nworkers == 2u && use_slab && lat_mode == LAT_LINEAR && B == 40u;
-    if ( nworkers == 2u && !bell202 )
-	return kNotBell202;
-    const size_t lds_all = use_slab ? kLdsHeader + slab_floats * 4 : kLdsHeader + 16;
-    // Chained launches (as in launch_demod_wave): the batch cut into G groups of
-    // streams x K time chunks, each (group, chunk) its own grid of the RESUMABLE instantiation on
-    // the group's stream.  The mechanism is the wavefront engine's and gives the single launch's
-    // results bit for bit (tests/test_gpu_chain.py) -- but this engine's library default is ONE
-    // launch at every batch size: its streams are short chains (0.45 ms for 10 s of Bell-202), the
-    // dispatcher refills a finished workgroup's slot with the next stream anyway, and every chunk
-    // restarts with a search and a pipeline fill.  Measured (tools/gpu/wg_chain_sizes.py,
-    // profiles/r04_history.md): 1536 / 3000 / 5000 streams 0.825 / 1.43 / 2.16 ms in one launch,
-    // 0.84-0.90 / 1.43-1.52 / 2.24-2.38 chained (2x2 ... 3x3).  MIFSK_CHAIN forces a cut
-    // (experiments and tests).
-    uint32_t chain_g = 0, chain_k = 0;
-    chain_shape(( plan_only ? ha.chain_ok : ha.chain != nullptr ) && !ha.d_state && !io.d_counters && io.nstreams > 0,
-		io.nstreams, chain_g, chain_k);
-    // (the cut is made by io.nsamples: with per-stream lengths only -- io.nsamples == 0 -- a
-    // limit of 0 would mean "all samples" to every chunk but the last; such a batch is not cut)
-    if ( io.nsamples == 0u )
-	chain_g = chain_k = 0u;
-    const KernelPick &kernel = wg_kernel(use_slab, bell202, ha.d_state || chain_g);
-    if ( plan_only ) {
-	plan_only->kernel = kernel.name;
-	plan_only->workgroup_size = block;
-	plan_only->lds_bytes = (uint32_t)lds_all;
-	plan_only->lattice_mode = lat_mode;
-	plan_only->frames_per_block = lat_frames * lat_rounds;
-	plan_only->waves_per_simd = kernel.waves_per_simd;
-	plan_only->chain_groups = chain_g;
-	plan_only->chain_chunks = chain_k;
-	return 0;
-    }
+    const void *fn = kWgFns[plan.kernel];
     // (the plain instantiations ignore all of it)
     WgResume rs;
     std::memset(&rs, 0, sizeof(rs));
-    static_cast<ResumeArgs &>(rs) = resume_args(ha.d_state, ha.d_origin, ha.final);
     rs.bufsize = ha.samplebuf_size;
-    if ( hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_all) != hipSuccess )
+    if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes) != hipSuccess )
 	return -5;
-    uint32_t a_slab_cap = use_slab ? slab_cap : 0u, a_lat_frames = use_slab ? lat_frames : 0u;
-    uint32_t a_lat_rounds = use_slab ? lat_rounds : 1u, a_region_floats = use_slab ? (uint32_t)region_floats : 0u;
-    uint32_t a_region_cap = use_slab ? region_cap : 0u, a_lat_mode = use_slab ? lat_mode : (uint32_t)LAT_NONE;
-    auto launch = [&]( const mifsk_demod_io &rows, hipStream_t on ) {
-	void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&a_slab_cap, (void *)&a_lat_frames,
-			  (void *)&a_lat_rounds, (void *)&a_region_floats, (void *)&a_region_cap, (void *)&a_lat_mode, (void *)&rs };
-	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(block), kargs, lds_all, on);
-    };
-    if ( chain_g ) {
-	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
-		[&]( const mifsk_demod_io &rows, uint32_t, const ResumeArgs &chunk, hipStream_t gs ) {
-		    static_cast<ResumeArgs &>(rs) = chunk;
-		    launch(rows, gs);
-		});
-    }
-    launch(io, (hipStream_t)stream);
-    return hip_rc(hipGetLastError());
-}
-
-int launch_demod_batch( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, const HostArgs &ha, void *stream, LaunchInfo *plan_only )
-{
-    if ( io.nstreams <= 0 && !plan_only )
-	return 0;
-    if ( cfg.lat_linear && cfg.bit_nsamples == 40u ) {
-	const int rc = launch_with_workers(cfg, d_cfg, d_tw, io, ha, stream, plan_only, 2u);
-	if ( rc != kNotBell202 )
-	    return rc;
-    }
-    return launch_with_workers(cfg, d_cfg, d_tw, io, ha, stream, plan_only, 3u);
+    auto g = plan.wg;
+    return launch_planned(plan, ha, io, (hipStream_t)stream,
+	    [&]( const mifsk_demod_io &rows, uint32_t, const ResumeArgs &chunk, hipStream_t on ) {
+		static_cast<ResumeArgs &>(rs) = chunk;
+		void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&g.slab_cap, (void *)&g.lat_frames,
+				  (void *)&g.lat_rounds, (void *)&g.region_floats, (void *)&g.region_cap, (void *)&g.lat_mode, (void *)&rs };
+		(void)hipLaunchKernel(fn, dim3((unsigned)rows.nstreams), dim3(plan.workgroup_size), kargs, plan.lds_bytes, on);
+	    });
 }
 
 int launch_detect_carrier( const float *d_samples, unsigned nsamples,

@@ -1,6 +1,6 @@
-// mifsk_plan.cpp -- the host-side planner: what the kernels read of a receive configuration
-// (DevCfg, mifsk_device.h), derived once per configuration and cached by the context.  Plain
-// C++: nothing here touches the device.
+// mifsk_plan.cpp -- the host-side planner: what the kernels read of a receive configuration (DevCfg,
+// mifsk_device.h; cached by the context) and the launch plan of a batch (LaunchPlan: engine, kernel,
+// LDS geometry, chain cut).  Plain C++: nothing here touches the device; every experiment knob is read here.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -450,6 +450,510 @@ void fill_devcfg( DevCfg &d, const mifsk_rx_config &c )
 	    }
 	}
     }
+}
+
+// ---- the launch plan of a batch: a pure function of PlanInputs and the experiment knobs ----
+
+// Engine.  One wavefront per stream is the general engine (every option,
+// every mode).  Where bit windows are staged through LDS and long enough
+// that correlation, not the per-frame decisions, is the work (linear
+// LATTICE, >= 16 samples per bit: Bell-202, 2400 baud, ...), the workgroup
+// engine's master / worker pipeline overlaps the two and wins at every
+// batch size measured (0.32 vs 0.52 ms at 512 streams, 0.50 vs 0.59 at
+// 1024, 1.64 vs 2.19 at 4096); at 12000 baud (4 samples per bit) the
+// wavefront engine is 4 x faster.  With longer windows and a clean signal it
+// still wins (tools/gpu/eng50.py, 2048 streams: 50 baud 3.0 vs 4.4 ms, 150 baud
+// 1.3 vs 4.1 ms).  Identical results either way.  (The workgroup engine has neither RING
+// addressing nor the in-loop --auto-carrier.)
+static bool use_workgroup_engine( const PlanInputs &in )
+{
+    const DevCfg &d = *in.cfg;
+    const bool plain = !in.ring_exact && !in.autodetect;
+    bool workgroup = plain && !( in.engine_flags & MIFSK_IO_ENGINE_WAVE )
+		  && ( ( in.engine_flags & MIFSK_IO_ENGINE_WORKGROUP )
+		       || ( d.lat_linear && d.bit_nsamples >= 16u ) );
+    if ( const char *e = experiment_env("MIFSK_ENGINE") )	// diagnostic override: "workgroup" / "wave"
+	if ( !( in.engine_flags & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE ) ) )
+	    workgroup = plain && e[0] == 'w' && e[1] == 'o';
+    return workgroup;
+}
+
+namespace {
+
+// ---- what the two engines' plans share -------------------------------------
+
+// samples one search must see at once (+ slack for the chunked correlator)
+uint32_t search_reach( const DevCfg &cfg )
+{
+    return ( cfg.try_max[0] > cfg.try_max[1] ? cfg.try_max[0] : cfg.try_max[1] ) + cfg.last_reach + 8u;
+}
+
+// floats of a skewed slab of `nsamp` samples (DevCfg::skew: a pad word per bit row)
+size_t skewed_floats( const DevCfg &cfg, uint32_t nsamp )
+{
+    return ( (size_t)nsamp + (size_t)( nsamp / cfg.bit_nsamples + 2 ) * cfg.skew + 8 + 3 ) & ~(size_t)3;
+}
+
+// samples a skewed slab of `floats` floats holds in SCAN mode
+uint32_t skewed_samples( const DevCfg &cfg, size_t floats )
+{
+    size_t ns = floats * cfg.bit_nsamples / ( cfg.bit_nsamples + cfg.skew );
+    ns = ns > 16 ? ns - 16 : 0;
+    return (uint32_t)( ns & ~(size_t)3 );
+}
+
+// distinct bit windows of the first F frames of a LATTICE block (on the grid the last window of
+// a frame is the first of the next)
+uint32_t block_wins( const DevCfg &cfg, uint32_t F )
+{
+    return cfg.lat_grid ? F * ( cfg.n_bits - 1u ) + 1u : F * cfg.n_bits;
+}
+
+// where window w of a block starts, relative to the block's first: windows numbered frame by
+// frame, or -- `grid` -- along the one grid of bit lengths the frames share
+uint32_t win_rel( const DevCfg &cfg, uint32_t w, bool grid )
+{
+    return grid ? w * cfg.bit_nsamples
+		: ( w / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[w % cfg.n_bits];
+}
+
+// window starts do not decrease in window order (a wave takes its span from its first and last lane)
+bool starts_ordered( const DevCfg &cfg, uint32_t nwin, bool grid )
+{
+    bool ordered = true;
+    for ( uint32_t w = 1; w < nwin; w++ )
+	ordered = ordered && win_rel(cfg, w, grid) >= win_rel(cfg, w - 1, grid);
+    return ordered;
+}
+
+// MIFSK_CHAIN = "G,K" (experiments and tests only) cuts any batch that may be chained; then the
+// bounds of a cut: at most kMaxGroups groups, none empty, at least two chunks -- else (0, 0)
+void chain_shape( bool allowed, int nstreams, uint32_t &groups, uint32_t &chunks )
+{
+    if ( const char *e = experiment_env("MIFSK_CHAIN") ) {
+	int a = 0, b = 0;
+	if ( allowed && std::sscanf(e, "%d,%d", &a, &b) == 2 ) {
+	    groups = (uint32_t)( a < 0 ? 0 : a );
+	    chunks = (uint32_t)( b < 0 ? 0 : b );
+	}
+    }
+    if ( groups > (uint32_t)WaveChain::kMaxGroups ) groups = (uint32_t)WaveChain::kMaxGroups;
+    if ( groups > (uint32_t)nstreams ) groups = (uint32_t)nstreams;
+    if ( groups < 1u || chunks < 2u )
+	groups = chunks = 0u;
+}
+
+// ---- one wavefront per stream: occupancy and LDS geometry per configuration ----
+
+// Geometry for a staging width `sv` within `budget` bytes of LDS per wave (plan.wave, plan.lds_bytes);
+// false when it does not fit.
+bool wave_fit( const PlanInputs &in, int sv, size_t budget, LaunchPlan &plan, bool want_tile = false )
+{
+    const DevCfg &cfg = *in.cfg;
+    const uint32_t B = cfg.bit_nsamples, nb = cfg.n_bits;
+    WaveGeom g;
+    std::memset(&g, 0, sizeof(g));
+    const uint32_t round_floats = 64u * (uint32_t)sv * 4u;
+
+    // The bulk path accepts a frame without looking at samples_nvalid: sound
+    // when half the reference's buffer (what is always valid away from the end
+    // of the stream) covers everything a carrier-held search reads and the
+    // largest advance.
+    const uint32_t half = in.samplebuf_size / 2u;
+    const bool lattice_sound = !in.ring_exact
+	&& half >= cfg.try_max[1] + cfg.last_reach
+	&& half >= cfg.expect_nsamples + cfg.try_max[1]
+	&& half > cfg.try_max[1] + cfg.frame_nsamples;
+    g.lat_mode = lattice_sound ? LAT_DIRECT : LAT_NONE;
+    g.lat_fmax = 64u;
+    {
+	uint32_t fmin = cfg.lat_grid ? 63u / ( nb - 1u ) : 64u / nb;	// one pass of lanes
+	if ( fmin < 2u ) fmin = 2u;
+	g.lat_fmin = fmin;
+    }
+    // LINEAR: window starts non-decreasing in window order and a round's span
+    // within one staging pass
+    if ( g.lat_mode != LAT_NONE && cfg.lat_linear ) {
+	const uint32_t wtot = block_wins(cfg, 64u);
+	const bool ordered = starts_ordered(cfg, wtot, cfg.lat_grid != 0u);
+	uint32_t rw = 0;
+	for ( uint32_t cand = 64u; ordered && cand <= 1024u; cand += 64u ) {
+	    bool fits = true;
+	    for ( uint32_t w0 = 0; w0 < wtot && fits; w0 += cand ) {
+		const uint32_t w1 = w0 + cand < wtot ? w0 + cand : wtot;
+		fits = win_rel(cfg, w1 - 1, cfg.lat_grid != 0u) + B - win_rel(cfg, w0, cfg.lat_grid != 0u) <= round_floats;
+	    }
+	    if ( !fits )
+		break;
+	    rw = cand;
+	}
+	if ( rw ) {
+	    g.lat_mode = LAT_LINEAR;
+	    g.round_wins = rw;
+	}
+    }
+
+    const uint32_t slab_cap = ( search_reach(cfg) + 4u + 3u ) & ~3u;
+    size_t scan_floats = skewed_floats(cfg, slab_cap);
+    const size_t region_floats = g.lat_mode == LAT_LINEAR ? round_floats + 16u : 0u;
+    if ( want_tile )
+	scan_floats = 0;		// the tile instead of a slab
+
+    for (;;) {
+	// a SCAN chunk scores mags_cap / n_bits candidates at once: room for a
+	// whole fine scan (<= 2 * 8 candidates) where it fits
+	uint32_t mcap = g.lat_mode != LAT_NONE ? block_wins(cfg, g.lat_fmax) : 0u;
+	if ( mcap < 16u * nb ) mcap = 16u * nb;
+	g.mags_cap = ( mcap + 1u ) & ~1u;
+	size_t sf = scan_floats > region_floats ? scan_floats : region_floats;
+	// no SCAN slab: long windows go through a tile instead (corr_global_tiled)
+	g.tiled = ( scan_floats == 0 && want_tile && !in.ring_exact && B >= TILE_K ) ? 1u : 0u;
+	if ( g.tiled ) {
+	    if ( g.lat_mode == LAT_LINEAR )
+		g.lat_mode = LAT_DIRECT;	// (that instantiation has no staged rounds)
+	    sf = TILE_FLOATS;
+	    bool any = false;
+	    for ( int i = 0; i < 4; i++ )
+		any = any || cfg.seg[i].valid;
+	    if ( any )			// shared segments: the carrier-held scans' plan words, the list of
+		sf += 2u * ( 2u * SEG_MAX + SEG_MAX / 4u ) + 64u;	// windows to sum again (the partial sums lie on the tile)
+	}
+	const size_t total = kCntBytes + (size_t)g.mags_cap * 2u * sizeof(float) + sf * 4u + 16u;
+	if ( total <= budget ) {
+	    g.slab_floats = (uint32_t)sf;
+	    g.slab_cap = 0;
+	    if ( scan_floats ) {
+		// the skewed slab may use the whole region
+		g.slab_cap = skewed_samples(cfg, sf);
+		if ( g.slab_cap < slab_cap )
+		    g.slab_cap = slab_cap;
+	    }
+	    // DIRECT blocks of short windows (SAME) stream every lane's window from global memory,
+	    // and the frames behind a refinement are read AGAIN by the block after it -- on a signal
+	    // that is refined every fifth frame (SAME's 8-bit frames without start / stop bits) a
+	    // block of a full pass of lanes (8 frames) throws three of them away: 2.3 x the
+	    // algorithmic bytes moved, at 4.6 TB/s of fabric traffic.  A pass of lanes costs the
+	    // same half full, so after a break the next block is as long as the lattice held last
+	    // time, down to four frames (same-box: 7.46 -> 7.07 ms; 3, 5, 6: 7.23, 7.27, 7.21).
+	    if ( g.lat_mode == LAT_DIRECT && !g.tiled && g.lat_fmin > 4u )
+		g.lat_fmin = 4u;
+	    if ( const char *e = experiment_env("MIFSK_LAT_FMIN") )	// experiments only
+		if ( std::atoi(e) >= 1 )
+		    g.lat_fmin = (uint32_t)std::atoi(e);
+	    plan.wave.g = g;
+	    plan.wave.sv = sv;
+	    plan.lds_bytes = (uint32_t)total;
+	    return true;
+	}
+	if ( g.lat_mode != LAT_NONE && g.lat_fmax / 2u >= g.lat_fmin && g.lat_fmax > 8u ) {
+	    g.lat_fmax /= 2u;			// shorter blocks: fewer magnitude slots
+	    continue;
+	}
+	if ( scan_floats > region_floats ) {
+	    scan_floats = 0;			// SCAN streams its windows from global memory
+	    continue;
+	}
+	return false;
+    }
+}
+
+struct WaveKernelRow {
+    int		sv, nq;
+    bool	st, ra;
+    const char	*name;
+    uint32_t	waves_per_simd;
+};
+#define MIFSK_ROW(SV_, NQ_, ST_, RA_)										\
+    { SV_, NQ_, ST_, RA_,											\
+      ST_ ? "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ", true>" : "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ">",	\
+      NQ_ == kTiled || SV_ >= 10 ? 2u : 4u },
+const WaveKernelRow kWaveKernels[] = { MIFSK_WAVE_KERNELS(MIFSK_ROW) };
+#undef MIFSK_ROW
+
+// The instantiation a fit runs (its index in the list; -1: a staging width no instantiation
+// has).  `nq`: the resident-table correlator of the bit length, where there is one (0: the
+// generic correlators); `st`: resumable; `ra`: with RING addressing and --auto-carrier.
+int wave_kernel( const LaunchPlan &plan, uint32_t nq, bool st, bool ra )
+{
+    const WaveGeom &g = plan.wave.g;
+    const int sv = g.tiled ? 10 : plan.wave.sv;
+    int want = g.tiled ? kTiled : g.lat_mode == LAT_LINEAR ? 0 : kDirect;
+    if ( !st && !g.tiled && ( sv == 10 ? nq == 10u || nq == 5u : nq == 1u ) )
+	want = (int)nq;
+    for ( int i = 0; i < (int)( sizeof(kWaveKernels) / sizeof(kWaveKernels[0]) ); i++ )
+	if ( kWaveKernels[i].sv == sv && kWaveKernels[i].nq == want && kWaveKernels[i].st == st && kWaveKernels[i].ra == ra )
+	    return i;
+    return -1;
+}
+
+int plan_wave( const PlanInputs &in, LaunchPlan &plan )
+{
+    const DevCfg &cfg = *in.cfg;
+    const int ncu = in.ncu > 0 ? in.ncu : 256;
+    // Waves per CU the batch can use (a wave is a workgroup): at least one per
+    // SIMD, at most 16 (4 per SIMD at <= 128 VGPRs).  Each gets that share of
+    // the CU's LDS; prefer the widest staging that fits, then fewer waves.
+    uint32_t want = ( (uint32_t)in.nstreams + (uint32_t)ncu - 1u ) / (uint32_t)ncu;
+    if ( want < 4u ) want = 4u;
+    if ( want > 16u ) want = 16u;
+    int force_sv = 0;
+    if ( const char *e = experiment_env("MIFSK_WAVES_PER_CU") )	// experiments only
+	want = (uint32_t)std::atoi(e) < 1u ? 1u : (uint32_t)std::atoi(e);
+    if ( const char *e = experiment_env("MIFSK_SV") )
+	force_sv = std::atoi(e);
+    const WaveGeom &g = plan.wave.g;
+    bool ok = false;
+    // Long windows are better read through the tile at two waves per SIMD than
+    // from a slab that leaves one wave per SIMD (tools/ubench/longwin.hip: 17 ms
+    // against 45): a slab only while it fits 8 waves per CU then
+    const bool tile_ok = !in.ring_exact && cfg.bit_nsamples >= kTileMinBit && force_sv != 4;
+    const uint32_t wmin = tile_ok ? 8u : 4u;
+    for ( uint32_t wpc = want; wpc >= wmin && !ok; wpc -= ( wpc > 8u ? 4u : ( wpc > 4u ? 2u : 1u ) ) ) {
+	const size_t budget = ( kLdsPerCu / wpc ) & ~(size_t)255;
+	// The wide-staging instantiation is compiled for two waves per SIMD (256
+	// VGPRs): worth it where rounds are staged through LDS (linear LATTICE) or
+	// where no more than 8 waves per CU are wanted anyway
+	const bool wide = force_sv ? force_sv == 10 : ( wpc <= 8u || cfg.lat_linear );
+	ok = wide && wave_fit(in, 10, budget, plan) && g.slab_cap != 0u
+		  && ( g.lat_mode == LAT_LINEAR || wpc <= 8u || force_sv == 10 );
+	if ( !ok )
+	    ok = wave_fit(in, 4, budget, plan) && g.slab_cap != 0u;
+	if ( wpc == 4u )
+	    break;
+    }
+    if ( !ok && force_sv != 4 ) {
+	// nothing keeps the SCAN slab in LDS (RTTY: 1056-sample windows, a 40 kB
+	// span; 0.5 baud: 96000-sample windows): the windows come from global
+	// memory through the tile (with the shared segments' plan words 12.9 kB), two waves per
+	// SIMD: compiled for three (168 VGPRs) the instantiation spilled 44 VGPRs to scratch and
+	// ran 4096 RTTY streams in 10.8 ms at 8 waves per CU; with 191 VGPRs and nothing spilled
+	// the same 8 waves per CU take 9.3 ms (profiles/r03_history.md)
+	for ( uint32_t wpc = want < 8u ? want : 8u; wpc >= 4u && !ok; wpc-- ) {
+	    const size_t budget = ( kLdsPerCu / wpc ) & ~(size_t)255;
+	    ok = wave_fit(in, 10, budget, plan, true) && g.tiled;
+	}
+    }
+    if ( !ok ) {
+	// ... or straight into registers, a window per lane
+	const size_t budget = ( kLdsPerCu / want ) & ~(size_t)255;
+	ok = wave_fit(in, 4, budget, plan);
+	if ( !ok )
+	    return -12;
+    }
+    const bool lin = g.lat_mode == LAT_LINEAR;
+    // the resident-table correlator of the bit lengths that have one (linear LATTICE only)
+    const uint32_t nq = ( lin && cfg.bit_nsamples % 4u == 0u ) ? cfg.bit_nsamples / 4u : 0u;
+    // (RING addressing and --auto-carrier have their own instantiations: the plain ones carry
+    // neither that code nor the registers it keeps alive; mifsk_demod_slab's all do)
+    const bool ra = in.has_state || in.ring_exact || in.autodetect;
+    // Chained launches (WaveChain, mifsk_device.h): where the plain instantiation is one of the
+    // resumable ones, the batch is more than the chip holds at once and the streams are long
+    // enough to cut (a chunk's last samplebuf waits for the next chunk: at least 8 per chunk).
+    uint32_t &chain_g = plan.chain_groups, &chain_k = plan.chain_chunks;
+    {
+	const int plain = wave_kernel(plan, nq, false, ra);
+	if ( plain < 0 )
+	    return -22;
+	const bool st_kernel = plain == wave_kernel(plan, 0u, false, ra);
+	const uint64_t slots = (uint64_t)workgroups_per_cu(plan.lds_bytes, kWaveKernels[plain].waves_per_simd, 64u) * (uint64_t)ncu;
+	const bool allowed = st_kernel && !in.has_state && !in.ring_exact && !in.has_counters && in.nstreams > 0;
+	if ( allowed && (uint64_t)in.nstreams > slots && in.samplebuf_size > 0u ) {
+	    chain_g = 2u;
+	    chain_k = in.nsamples / ( 8u * in.samplebuf_size );
+	    if ( chain_k > 8u ) chain_k = 8u;
+	}
+	chain_shape(allowed, in.nstreams, chain_g, chain_k);
+    }
+    // (mifsk_demod_slab and the chained launches: the instantiations with the state code)
+    plan.resumable = in.has_state || chain_g;
+    const int index = wave_kernel(plan, nq, plan.resumable, ra);
+    if ( index < 0 )
+	return -22;
+    plan.engine = MIFSK_IO_ENGINE_WAVE;
+    plan.kernel = (uint32_t)index;
+    plan.kernel_name = kWaveKernels[index].name;
+    plan.waves_per_simd = kWaveKernels[index].waves_per_simd;
+    // Whole rounds.  A batch of more streams than waves fit runs in rounds, and a last round
+    // that is a fraction of one leaves the chip mostly idle while its chains finish (4096 RTTY
+    // streams at 12 waves per CU are 1.33 rounds: measured 13.8 ms against 13.3 at 8-10).  Among
+    // the occupancies this plan allows (down to two thirds of the most) take the one that wastes
+    // the fewest wave slots over the whole batch, the higher one on a tie; the kernel is limited
+    // to it by its LDS allocation.  (Not for chained launches: their slots are refilled as they
+    // come free.)
+    {
+	const uint32_t most = workgroups_per_cu(plan.lds_bytes, plan.waves_per_simd, 64u);
+	const uint32_t per_cu = ( (uint32_t)( in.nstreams > 0 ? in.nstreams : 0 ) + (uint32_t)ncu - 1u ) / (uint32_t)ncu;
+	if ( most >= 3u && per_cu > most && !chain_g ) {
+	    uint32_t best = most, best_waste = 0xFFFFFFFFu;
+	    for ( uint32_t w = most; 3u * w >= 2u * most; w-- ) {
+		const uint32_t waste = ( per_cu + w - 1u ) / w * w - per_cu;
+		if ( waste < best_waste ) {
+		    best_waste = waste;
+		    best = w;
+		}
+	    }
+	    if ( best < most ) {
+		const size_t pad = ( kLdsPerCu / best ) & ~(size_t)255;	// exactly `best` of these fit a CU
+		if ( pad > plan.lds_bytes && kLdsPerCu / pad == best )
+		    plan.lds_bytes = (uint32_t)pad;
+	    }
+	}
+    }
+    if ( const char *e = experiment_env("MIFSK_LDS_PAD") )	// experiments only: limit occupancy
+	if ( (size_t)std::atoi(e) > plan.lds_bytes )
+	    plan.lds_bytes = (uint32_t)std::atoi(e);
+    plan.workgroup_size = 64u;
+    plan.lattice_mode = g.lat_mode;
+    plan.frames_per_block = g.lat_mode != LAT_NONE ? g.lat_fmax : 0u;
+    return 0;
+}
+
+// ---- one workgroup per stream: a master wave and its workers ----------------
+
+struct WgKernelRow {
+    bool	use_slab, bell202, st;
+    const char	*name;
+    uint32_t	waves_per_simd;
+};
+#define MIFSK_ROW(WAVES_, SLAB_, BELL_, ST_, ...)	{ SLAB_, BELL_, ST_, "mifsk::demod_kernel<" #__VA_ARGS__ ">", WAVES_ },
+const WgKernelRow kWgKernels[] = { MIFSK_WG_KERNELS(MIFSK_ROW) };
+#undef MIFSK_ROW
+
+// LDS geometry with `nworkers` workers: the kernel's arguments and its dynamic LDS
+size_t wg_fit( const DevCfg &cfg, uint32_t nworkers, WgGeom &g )
+{
+    const uint32_t B = cfg.bit_nsamples;
+    const uint32_t lat_lanes = nworkers * 64u;	// bit windows per lattice round
+    const uint32_t reach = search_reach(cfg);
+    // LDS budget: 4 workgroups per CU when the stream count can use them
+    const size_t budget_small = kLdsPerCu / 4 - 64;
+
+    // LATTICE geometry.  A round is as many frames as fill the worker lanes (64 per worker)
+    // with distinct bit windows.  LINEAR workers stage their 64 windows' span in
+    // a private LDS region (fastest; needs bit length, offsets and frame step
+    // in multiples of 4 samples and the span to fit ten 16-byte loads per
+    // lane); otherwise DIRECT workers stream each window from global memory.
+    const uint32_t frames_max = cfg.lat_grid ? ( lat_lanes - 1u ) / ( cfg.n_bits - 1u )
+					     : lat_lanes / cfg.n_bits;
+    g.nworkers = nworkers;
+    g.lat_frames = frames_max > P_CAP ? P_CAP : frames_max;
+    g.lat_mode = g.lat_frames ? LAT_DIRECT : LAT_NONE;
+    g.region_cap = g.region_floats = 0;
+    if ( g.lat_frames && cfg.lat_linear && starts_ordered(cfg, g.lat_frames * cfg.n_bits, false) ) {
+	// span of the widest wave: 64 windows (or all of them), plus what the
+	// group-wise correlator (corr_lds_stream: whole groups of 16 samples) loads
+	// beyond the last window -- nothing in the Bell-202 instantiation, whose
+	// resident-table correlator reads the window and no more
+	const uint32_t over = ( nworkers == 2u && B == 40u ) ? 0u : ( 16u - B % 16u ) % 16u;
+	uint32_t span = 0;
+	if ( cfg.lat_grid ) {
+	    const uint32_t nwin = block_wins(cfg, g.lat_frames);
+	    span = ( nwin < 64u ? nwin : 64u ) * B + over;
+	} else {
+	    const uint32_t nwin = g.lat_frames * cfg.n_bits;
+	    for ( uint32_t w0 = 0; w0 < nwin; w0 += 64 ) {
+		const uint32_t wl = w0 + 63 < nwin ? w0 + 63 : nwin - 1;
+		const uint32_t len = win_rel(cfg, wl, false) + B - win_rel(cfg, w0, false);
+		span = len > span ? len : span;
+	    }
+	    span += over;
+	}
+	g.region_cap = ( span + 3 ) & ~3u;
+	g.region_floats = (uint32_t)skewed_floats(cfg, g.region_cap);
+	if ( g.region_cap <= 64u * STAGE_VEC * 4u
+		&& kWgLdsHeader + (size_t)nworkers * g.region_floats * 4 <= budget_small
+		&& (size_t)nworkers * g.region_floats >= skewed_floats(cfg, reach + 4) )
+	    g.lat_mode = LAT_LINEAR;
+    }
+
+    // the master scores `g.lat_rounds` rounds at once: halves the per-frame cost
+    // of everything that is paid per batch -- the confidence pass, the barrier,
+    // the command hand-off
+    g.lat_rounds = 1;
+    if ( g.lat_frames ) {
+	g.lat_rounds = 2;
+	if ( const char *e = experiment_env("MIFSK_LAT_ROUNDS") )	// experiments only
+	    g.lat_rounds = (uint32_t)std::atoi(e) < 1u ? 1u : (uint32_t)std::atoi(e);
+	while ( g.lat_rounds > 1 && ( g.lat_frames * g.lat_rounds > P_CAP
+				    || block_wins(cfg, g.lat_frames) * g.lat_rounds > W_CAP ) )
+	    g.lat_rounds--;
+    }
+
+    g.slab_cap = 0;
+    size_t slab_floats = 0;
+    g.use_slab = true;
+    if ( g.lat_mode == LAT_LINEAR ) {
+	slab_floats = (size_t)nworkers * g.region_floats;
+	g.slab_cap = skewed_samples(cfg, slab_floats);
+    } else {
+	// no regions: the slab serves SCAN only; take what one search needs
+	g.region_cap = 0;
+	g.region_floats = 0;
+	if ( kWgLdsHeader + skewed_floats(cfg, reach + 4) * 4 <= kLdsPerCu - 1024 ) {
+	    g.slab_cap = ( reach + 4 + 3 ) & ~3u;
+	    slab_floats = skewed_floats(cfg, g.slab_cap);
+	} else {
+	    g.use_slab = false;	// e.g. 0.5 baud: windows of 96000 samples; no lattice either
+	    g.lat_mode = LAT_NONE;
+	    g.lat_frames = 0;
+	    g.lat_rounds = 1;
+	}
+    }
+    return g.use_slab ? kWgLdsHeader + slab_floats * 4 : kWgLdsHeader + 16;
+}
+
+int plan_workgroup( const PlanInputs &in, LaunchPlan &plan )
+{
+    const DevCfg &cfg = *in.cfg;
+    // Bell-202 (40 samples per bit, linear): two workers and the resident table, where that
+    // geometry keeps the linear lattice; three workers otherwise
+    WgGeom &g = plan.wg;
+    size_t lds_all = 0;
+    bool bell202 = false;
+    if ( cfg.lat_linear && cfg.bit_nsamples == 40u ) {
+	lds_all = wg_fit(cfg, 2u, g);
+	bell202 = g.use_slab && g.lat_mode == LAT_LINEAR;
+    }
+    if ( !bell202 )
+	lds_all = wg_fit(cfg, 3u, g);
+    // Chained launches (as in plan_wave): the batch cut into G groups of
+    // streams x K time chunks, each (group, chunk) its own grid of the RESUMABLE instantiation on
+    // the group's stream.  The mechanism is the wavefront engine's and gives the single launch's
+    // results bit for bit (tests/test_gpu_chain.py) -- but this engine's library default is ONE
+    // launch at every batch size: its streams are short chains (0.45 ms for 10 s of Bell-202), the
+    // dispatcher refills a finished workgroup's slot with the next stream anyway, and every chunk
+    // restarts with a search and a pipeline fill.  Measured (tools/gpu/wg_chain_sizes.py,
+    // profiles/r04_history.md): 1536 / 3000 / 5000 streams 0.825 / 1.43 / 2.16 ms in one launch,
+    // 0.84-0.90 / 1.43-1.52 / 2.24-2.38 chained (2x2 ... 3x3).  MIFSK_CHAIN forces a cut
+    // (experiments and tests).
+    uint32_t &chain_g = plan.chain_groups, &chain_k = plan.chain_chunks;
+    chain_shape(!in.has_state && !in.has_counters && in.nstreams > 0, in.nstreams, chain_g, chain_k);
+    // (the cut is made by io.nsamples: with per-stream lengths only -- io.nsamples == 0 -- a
+    // limit of 0 would mean "all samples" to every chunk but the last; such a batch is not cut)
+    if ( in.nsamples == 0u )
+	chain_g = chain_k = 0u;
+    plan.resumable = in.has_state || chain_g;
+    int index = 0;		// (always found: Bell-202 has a slab)
+    while ( index + 1 < (int)( sizeof(kWgKernels) / sizeof(kWgKernels[0]) )
+	    && !( kWgKernels[index].use_slab == g.use_slab && kWgKernels[index].bell202 == bell202 && kWgKernels[index].st == plan.resumable ) )
+	index++;
+    plan.engine = MIFSK_IO_ENGINE_WORKGROUP;
+    plan.kernel = (uint32_t)index;
+    plan.kernel_name = kWgKernels[index].name;
+    plan.waves_per_simd = kWgKernels[index].waves_per_simd;
+    plan.workgroup_size = 64u * ( g.nworkers + 1u );
+    plan.lds_bytes = (uint32_t)lds_all;
+    plan.lattice_mode = g.lat_mode;
+    plan.frames_per_block = g.lat_frames * g.lat_rounds;
+    return 0;
+}
+
+} // namespace
+
+int plan_launch( const PlanInputs &in, LaunchPlan &plan )
+{
+    std::memset(&plan, 0, sizeof(plan));
+    return use_workgroup_engine(in) ? plan_workgroup(in, plan) : plan_wave(in, plan);
 }
 
 } // namespace mifsk

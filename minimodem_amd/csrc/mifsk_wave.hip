@@ -158,9 +158,7 @@ __device__ __forceinline__ void wave_build_table( double *tw_own, const double *
 // LATTICE); 0 = any bit length, linear LATTICE; kDirect = any bit length, the lattice's
 // windows streamed per lane from global memory (or no lattice): no staging rounds, no round
 // prefetch registers; kTiled = the instantiation for long windows read from global memory
-// through the LDS tile (no linear LATTICE in it either)
-constexpr int kTiled = -1;
-constexpr int kDirect = -2;
+// through the LDS tile (no linear LATTICE in it either).  (kTiled, kDirect: mifsk_device.h)
 
 template <int SV, int NQ>
 struct Wave {
@@ -1163,7 +1161,7 @@ __device__ __forceinline__ uint64_t lane_gather64( uint64_t v, uint32_t src )
 }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char mifsk_wave_smem[];
-constexpr size_t kCntBytes = ( MIFSK_NCOUNTERS * sizeof(uint32_t) + 15u ) & ~(size_t)15;	// work counters, first in LDS
+// (kCntBytes of work counters come first in LDS: mifsk_device.h)
 
 // (the wide-staging instantiation runs where a wave has >= 10 KiB of LDS to
 // itself, i.e. at most 2-3 waves per SIMD: it may use 256 VGPRs)
@@ -1799,323 +1797,19 @@ void demod_wave_kernel( const DevCfg *__restrict__ cfgp, const double *__restric
 }
 
 // ---------------------------------------------------------------------------
-// launcher: occupancy and LDS geometry per configuration
+// launcher: the plan is made (plan_launch, mifsk_plan.cpp); what is left is the kernel's
+// run-time arguments and the launch.  The functions of MIFSK_WAVE_KERNELS, in the list's order
+// (LaunchPlan::kernel indexes it):
 // ---------------------------------------------------------------------------
+#define MIFSK_FN(SV_, NQ_, ST_, RA_)	reinterpret_cast<const void *>(&demod_wave_kernel<SV_, NQ_, ST_, RA_>),
+static const void *const kWaveFns[] = { MIFSK_WAVE_KERNELS(MIFSK_FN) };
+#undef MIFSK_FN
 
-namespace {
-
-struct Plan {
-    WaveGeom	g;
-    int		sv;		// staging width of the kernel instantiation
-    size_t	lds_bytes;
-};
-
-// windows of the first F frames of a block
-inline uint32_t wins_of( const DevCfg &cfg, uint32_t F )
+int launch_demod_wave( const LaunchPlan &plan, const DevCfg *d_cfg, const double *d_tw,
+	const mifsk_demod_io &io, const WaveHostArgs &ha, void *stream )
 {
-    return cfg.lat_grid ? F * ( cfg.n_bits - 1u ) + 1u : F * cfg.n_bits;
-}
-inline uint32_t rel_of( const DevCfg &cfg, uint32_t w )
-{
-    return cfg.lat_grid ? w * cfg.bit_nsamples
-			: ( w / cfg.n_bits ) * cfg.lock_advance + cfg.bit_offset[w % cfg.n_bits];
-}
-
-// Geometry for a staging width `sv` within `budget` bytes of LDS per wave;
-// false when it does not fit.
-bool plan_for( const DevCfg &cfg, const WaveHostArgs &ha, int sv, size_t budget, Plan &out,
-	       bool want_tile = false )
-{
-    const uint32_t B = cfg.bit_nsamples, nb = cfg.n_bits;
-    WaveGeom g;
-    std::memset(&g, 0, sizeof(g));
-    const uint32_t round_floats = 64u * (uint32_t)sv * 4u;
-
-    // The bulk path accepts a frame without looking at samples_nvalid: sound
-    // when half the reference's buffer (what is always valid away from the end
-    // of the stream) covers everything a carrier-held search reads and the
-    // largest advance.
-    const uint32_t half = ha.samplebuf_size / 2u;
-    const bool lattice_sound = !ha.ring_exact
-	&& half >= cfg.try_max[1] + cfg.last_reach
-	&& half >= cfg.expect_nsamples + cfg.try_max[1]
-	&& half > cfg.try_max[1] + cfg.frame_nsamples;
-    g.lat_mode = lattice_sound ? LAT_DIRECT : LAT_NONE;
-    g.lat_fmax = 64u;
-    {
-	uint32_t fmin = cfg.lat_grid ? 63u / ( nb - 1u ) : 64u / nb;	// one pass of lanes
-	if ( fmin < 2u ) fmin = 2u;
-	g.lat_fmin = fmin;
-    }
-    // LINEAR: window starts non-decreasing in window order and a round's span
-    // within one staging pass
-    if ( g.lat_mode != LAT_NONE && cfg.lat_linear ) {
-	bool ordered = true;
-	const uint32_t wtot = wins_of(cfg, 64u);
-	for ( uint32_t w = 1; w < wtot; w++ )
-	    ordered = ordered && rel_of(cfg, w) >= rel_of(cfg, w - 1);
-	uint32_t rw = 0;
-	for ( uint32_t cand = 64u; ordered && cand <= 1024u; cand += 64u ) {
-	    bool fits = true;
-	    for ( uint32_t w0 = 0; w0 < wtot && fits; w0 += cand ) {
-		const uint32_t w1 = w0 + cand < wtot ? w0 + cand : wtot;
-		fits = rel_of(cfg, w1 - 1) + B - rel_of(cfg, w0) <= round_floats;
-	    }
-	    if ( !fits )
-		break;
-	    rw = cand;
-	}
-	if ( rw ) {
-	    g.lat_mode = LAT_LINEAR;
-	    g.round_wins = rw;
-	}
-    }
-
-    // samples one search must see at once (+ slack for the chunked correlator)
-    const uint32_t reach = ( cfg.try_max[0] > cfg.try_max[1] ? cfg.try_max[0] : cfg.try_max[1] )
-			 + cfg.last_reach + 8u;
-    auto skewed_floats = [&]( uint32_t nsamp ) -> size_t {
-	return ( (size_t)nsamp + (size_t)( nsamp / B + 2 ) * cfg.skew + 8 + 3 ) & ~(size_t)3;
-    };
-    uint32_t slab_cap = ( reach + 4u + 3u ) & ~3u;
-    size_t scan_floats = skewed_floats(slab_cap);
-    const size_t region_floats = g.lat_mode == LAT_LINEAR ? round_floats + 16u : 0u;
-    if ( want_tile )
-	scan_floats = 0;		// the tile instead of a slab
-
-    for (;;) {
-	// a SCAN chunk scores mags_cap / n_bits candidates at once: room for a
-	// whole fine scan (<= 2 * 8 candidates) where it fits
-	uint32_t mcap = g.lat_mode != LAT_NONE ? wins_of(cfg, g.lat_fmax) : 0u;
-	if ( mcap < 16u * nb ) mcap = 16u * nb;
-	g.mags_cap = ( mcap + 1u ) & ~1u;
-	size_t sf = scan_floats > region_floats ? scan_floats : region_floats;
-	// no SCAN slab: long windows go through a tile instead (corr_global_tiled)
-	g.tiled = ( scan_floats == 0 && want_tile && !ha.ring_exact && B >= TILE_K ) ? 1u : 0u;
-	if ( g.tiled ) {
-	    if ( g.lat_mode == LAT_LINEAR )
-		g.lat_mode = LAT_DIRECT;	// (that instantiation has no staged rounds)
-	    sf = TILE_FLOATS;
-	    bool any = false;
-	    for ( int i = 0; i < 4; i++ )
-		any = any || cfg.seg[i].valid;
-	    if ( any )			// shared segments: the carrier-held scans' plan words, the list of
-		sf += 2u * ( 2u * SEG_MAX + SEG_MAX / 4u ) + 64u;	// windows to sum again (the partial sums lie on the tile)
-	}
-	const size_t total = kCntBytes + (size_t)g.mags_cap * sizeof(float2) + sf * 4u + 16u;
-	if ( total <= budget ) {
-	    g.slab_floats = (uint32_t)sf;
-	    g.slab_cap = 0;
-	    if ( scan_floats ) {
-		// the skewed slab may use the whole region
-		size_t ns = sf * B / ( B + cfg.skew );
-		ns = ns > 16 ? ns - 16 : 0;
-		g.slab_cap = (uint32_t)( ns & ~(size_t)3 );
-		if ( g.slab_cap < slab_cap )
-		    g.slab_cap = slab_cap;
-	    }
-	    // DIRECT blocks of short windows (SAME) stream every lane's window from global memory,
-	    // and the frames behind a refinement are read AGAIN by the block after it -- on a signal
-	    // that is refined every fifth frame (SAME's 8-bit frames without start / stop bits) a
-	    // block of a full pass of lanes (8 frames) throws three of them away: 2.3 x the
-	    // algorithmic bytes moved, at 4.6 TB/s of fabric traffic.  A pass of lanes costs the
-	    // same half full, so after a break the next block is as long as the lattice held last
-	    // time, down to four frames (same-box: 7.46 -> 7.07 ms; 3, 5, 6: 7.23, 7.27, 7.21).
-	    if ( g.lat_mode == LAT_DIRECT && !g.tiled && g.lat_fmin > 4u )
-		g.lat_fmin = 4u;
-	    if ( const char *e = experiment_env("MIFSK_LAT_FMIN") )	// experiments only
-		if ( std::atoi(e) >= 1 )
-		    g.lat_fmin = (uint32_t)std::atoi(e);
-	    out.g = g;
-	    out.sv = sv;
-	    out.lds_bytes = total;
-	    return true;
-	}
-	if ( g.lat_mode != LAT_NONE && g.lat_fmax / 2u >= g.lat_fmin && g.lat_fmax > 8u ) {
-	    g.lat_fmax /= 2u;			// shorter blocks: fewer magnitude slots
-	    continue;
-	}
-	if ( scan_floats > region_floats ) {
-	    scan_floats = 0;			// SCAN streams its windows from global memory
-	    continue;
-	}
-	return false;
-    }
-}
-
-// Every instantiation of demod_wave_kernel there is, with the name mifsk_demod_plan reports for
-// it (which does not spell RA) and the waves per SIMD it is compiled for (its __launch_bounds__).
-// The resumable ones (ST) have generic correlators only; mifsk_demod_slab runs them with RA, a
-// chain by --auto-carrier.
-static_assert(kTiled == -1 && kDirect == -2, "the rows below spell them out");
-struct WaveKernel {
-    int		sv, nq;
-    bool	st, ra;
-    KernelPick	pick;
-};
-#define MIFSK_WAVE_KERNEL(SV_, NQ_, ST_, RA_)									\
-    { SV_, NQ_, ST_, RA_,											\
-      { reinterpret_cast<const void *>(&demod_wave_kernel<SV_, NQ_, ST_, RA_>),				\
-	ST_ ? "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ", true>" : "mifsk::demod_wave_kernel<" #SV_ ", " #NQ_ ">",	\
-	NQ_ == kTiled || SV_ >= 10 ? 2u : 4u } }
-const WaveKernel kWaveKernels[] = {
-    MIFSK_WAVE_KERNEL(10, -1, true, true),	MIFSK_WAVE_KERNEL(10, 0, true, true),	MIFSK_WAVE_KERNEL(10, -2, true, true),
-    MIFSK_WAVE_KERNEL(4, 0, true, true),	MIFSK_WAVE_KERNEL(4, -2, true, true),
-    MIFSK_WAVE_KERNEL(10, -1, true, false),	MIFSK_WAVE_KERNEL(10, 0, true, false),	MIFSK_WAVE_KERNEL(10, -2, true, false),
-    MIFSK_WAVE_KERNEL(4, 0, true, false),	MIFSK_WAVE_KERNEL(4, -2, true, false),
-    MIFSK_WAVE_KERNEL(10, -1, false, true),	MIFSK_WAVE_KERNEL(10, -1, false, false),	// RTTY and slower
-    MIFSK_WAVE_KERNEL(10, 10, false, true),	MIFSK_WAVE_KERNEL(10, 10, false, false),	// 1200 baud at 48 kHz
-    MIFSK_WAVE_KERNEL(10, 5, false, true),	MIFSK_WAVE_KERNEL(10, 5, false, false),		// 2400 baud; 1200 baud at 24 kHz
-    MIFSK_WAVE_KERNEL(10, 0, false, true),	MIFSK_WAVE_KERNEL(10, 0, false, false),
-    MIFSK_WAVE_KERNEL(10, -2, false, true),	MIFSK_WAVE_KERNEL(10, -2, false, false),
-    MIFSK_WAVE_KERNEL(4, 1, false, true),	MIFSK_WAVE_KERNEL(4, 1, false, false),		// 12000 baud
-    MIFSK_WAVE_KERNEL(4, 0, false, true),	MIFSK_WAVE_KERNEL(4, 0, false, false),
-    MIFSK_WAVE_KERNEL(4, -2, false, true),	MIFSK_WAVE_KERNEL(4, -2, false, false),		// SAME
-};
-#undef MIFSK_WAVE_KERNEL
-
-// The instantiation a plan runs.  `nq`: the resident-table correlator of the bit length, where
-// there is one (0: the generic correlators); `st`: resumable; `ra`: with RING addressing and
-// --auto-carrier.
-const KernelPick *wave_kernel( const Plan &plan, uint32_t nq, bool st, bool ra )
-{
-    const int sv = plan.g.tiled ? 10 : plan.sv;
-    int want = plan.g.tiled ? kTiled : plan.g.lat_mode == LAT_LINEAR ? 0 : kDirect;
-    if ( !st && !plan.g.tiled && ( sv == 10 ? nq == 10u || nq == 5u : nq == 1u ) )
-	want = (int)nq;
-    for ( const WaveKernel &k : kWaveKernels )
-	if ( k.sv == sv && k.nq == want && k.st == st && k.ra == ra )
-	    return &k.pick;
-    return nullptr;		// (a staging width no instantiation has)
-}
-
-} // namespace
-
-int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_tw,
-	const mifsk_demod_io &io, const WaveHostArgs &ha, void *stream, LaunchInfo *plan_only )
-{
-    if ( io.nstreams <= 0 && !plan_only )
-	return 0;
-    const int ncu = ha.ncu > 0 ? ha.ncu : 256;
-    // Waves per CU the batch can use (a wave is a workgroup): at least one per
-    // SIMD, at most 16 (4 per SIMD at <= 128 VGPRs).  Each gets that share of
-    // the CU's LDS; prefer the widest staging that fits, then fewer waves.
-    uint32_t want = ( (uint32_t)io.nstreams + (uint32_t)ncu - 1u ) / (uint32_t)ncu;
-    if ( want < 4u ) want = 4u;
-    if ( want > 16u ) want = 16u;
-    int force_sv = 0;
-    if ( const char *e = experiment_env("MIFSK_WAVES_PER_CU") )	// experiments only
-	want = (uint32_t)std::atoi(e) < 1u ? 1u : (uint32_t)std::atoi(e);
-    if ( const char *e = experiment_env("MIFSK_SV") )
-	force_sv = std::atoi(e);
-    Plan plan;
-    bool ok = false;
-    // Long windows are better read through the tile at two waves per SIMD than
-    // from a slab that leaves one wave per SIMD (tools/ubench/longwin.hip: 17 ms
-    // against 45): a slab only while it fits 8 waves per CU then
-    const bool tile_ok = !ha.ring_exact && cfg.bit_nsamples >= kTileMinBit && force_sv != 4;
-    const uint32_t wmin = tile_ok ? 8u : 4u;
-    for ( uint32_t wpc = want; wpc >= wmin && !ok; wpc -= ( wpc > 8u ? 4u : ( wpc > 4u ? 2u : 1u ) ) ) {
-	const size_t budget = ( kLdsPerCu / wpc ) & ~(size_t)255;
-	// The wide-staging instantiation is compiled for two waves per SIMD (256
-	// VGPRs): worth it where rounds are staged through LDS (linear LATTICE) or
-	// where no more than 8 waves per CU are wanted anyway
-	const bool wide = force_sv ? force_sv == 10 : ( wpc <= 8u || cfg.lat_linear );
-	ok = wide && plan_for(cfg, ha, 10, budget, plan) && plan.g.slab_cap != 0u
-		  && ( plan.g.lat_mode == LAT_LINEAR || wpc <= 8u || force_sv == 10 );
-	if ( !ok )
-	    ok = plan_for(cfg, ha, 4, budget, plan) && plan.g.slab_cap != 0u;
-	if ( wpc == 4u )
-	    break;
-    }
-    if ( !ok && force_sv != 4 ) {
-	// nothing keeps the SCAN slab in LDS (RTTY: 1056-sample windows, a 40 kB
-	// span; 0.5 baud: 96000-sample windows): the windows come from global
-	// memory through the tile (with the shared segments' plan words 12.9 kB), two waves per
-	// SIMD: compiled for three (168 VGPRs) the instantiation spilled 44 VGPRs to scratch and
-	// ran 4096 RTTY streams in 10.8 ms at 8 waves per CU; with 191 VGPRs and nothing spilled
-	// the same 8 waves per CU take 9.3 ms (profiles/r03_history.md)
-	for ( uint32_t wpc = want < 8u ? want : 8u; wpc >= 4u && !ok; wpc-- ) {
-	    const size_t budget = ( kLdsPerCu / wpc ) & ~(size_t)255;
-	    ok = plan_for(cfg, ha, 10, budget, plan, true) && plan.g.tiled;
-	}
-    }
-    if ( !ok ) {
-	// ... or straight into registers, a window per lane
-	const size_t budget = ( kLdsPerCu / want ) & ~(size_t)255;
-	ok = plan_for(cfg, ha, 4, budget, plan);
-	if ( !ok )
-	    return -12;
-    }
-    const bool lin = plan.g.lat_mode == LAT_LINEAR;
-    // the resident-table correlator of the bit lengths that have one (linear LATTICE only)
-    const uint32_t nq = ( lin && cfg.bit_nsamples % 4u == 0u ) ? cfg.bit_nsamples / 4u : 0u;
-    // (RING addressing and --auto-carrier have their own instantiations: the plain ones carry
-    // neither that code nor the registers it keeps alive; mifsk_demod_slab's all do)
-    const bool ra = ha.d_state || ha.ring_exact || ha.autodetect;
-    // Chained launches (WaveChain, mifsk_device.h): where the plain instantiation is one of the
-    // resumable ones, the batch is more than the chip holds at once and the streams are long
-    // enough to cut (a chunk's last samplebuf waits for the next chunk: at least 8 per chunk).
-    uint32_t chain_g = 0, chain_k = 0;
-    {
-	const KernelPick *plain = wave_kernel(plan, nq, false, ra);
-	if ( !plain )
-	    return -22;
-	const bool st_kernel = plain == wave_kernel(plan, 0u, false, ra);
-	const uint64_t slots = (uint64_t)workgroups_per_cu(plan.lds_bytes, plain->waves_per_simd, 64u) * (uint64_t)ncu;
-	const bool allowed = ( plan_only ? ha.chain_ok : ha.chain != nullptr ) && st_kernel && !ha.d_state
-			  && !ha.ring_exact && !io.d_counters && io.nstreams > 0;
-	if ( allowed && (uint64_t)io.nstreams > slots && ha.samplebuf_size > 0u ) {
-	    chain_g = 2u;
-	    chain_k = io.nsamples / ( 8u * ha.samplebuf_size );
-	    if ( chain_k > 8u ) chain_k = 8u;
-	}
-	chain_shape(allowed, io.nstreams, chain_g, chain_k);
-    }
-    // (mifsk_demod_slab and the chained launches: the instantiations with the state code)
-    const bool resumable = ha.d_state || chain_g;
-    const KernelPick &kernel = *wave_kernel(plan, nq, resumable, ra);
-    // Whole rounds.  A batch of more streams than waves fit runs in rounds, and a last round
-    // that is a fraction of one leaves the chip mostly idle while its chains finish (4096 RTTY
-    // streams at 12 waves per CU are 1.33 rounds: measured 13.8 ms against 13.3 at 8-10).  Among
-    // the occupancies this plan allows (down to two thirds of the most) take the one that wastes
-    // the fewest wave slots over the whole batch, the higher one on a tie; the kernel is limited
-    // to it by its LDS allocation.  (Not for chained launches: their slots are refilled as they
-    // come free.)
-    {
-	const uint32_t most = workgroups_per_cu(plan.lds_bytes, kernel.waves_per_simd, 64u);
-	const uint32_t per_cu = ( (uint32_t)( io.nstreams > 0 ? io.nstreams : 0 ) + (uint32_t)ncu - 1u ) / (uint32_t)ncu;
-	if ( most >= 3u && per_cu > most && !chain_g ) {
-	    uint32_t best = most, best_waste = 0xFFFFFFFFu;
-	    for ( uint32_t w = most; 3u * w >= 2u * most; w-- ) {
-		const uint32_t waste = ( per_cu + w - 1u ) / w * w - per_cu;
-		if ( waste < best_waste ) {
-		    best_waste = waste;
-		    best = w;
-		}
-	    }
-	    if ( best < most ) {
-		const size_t pad = ( kLdsPerCu / best ) & ~(size_t)255;	// exactly `best` of these fit a CU
-		if ( pad > plan.lds_bytes && kLdsPerCu / pad == best )
-		    plan.lds_bytes = pad;
-	    }
-	}
-    }
-    if ( const char *e = experiment_env("MIFSK_LDS_PAD") )	// experiments only: limit occupancy
-	if ( (size_t)std::atoi(e) > plan.lds_bytes )
-	    plan.lds_bytes = (size_t)std::atoi(e);
-    WaveGeom &g = plan.g;
-    if ( plan_only ) {
-	plan_only->kernel = kernel.name;
-	plan_only->workgroup_size = 64;
-	plan_only->lds_bytes = (uint32_t)plan.lds_bytes;
-	plan_only->lattice_mode = g.lat_mode;
-	plan_only->frames_per_block = g.lat_mode != LAT_NONE ? g.lat_fmax : 0u;
-	plan_only->waves_per_simd = kernel.waves_per_simd;
-	plan_only->chain_groups = chain_g;
-	plan_only->chain_chunks = chain_k;
-	return 0;
-    }
+    const void *fn = kWaveFns[plan.kernel];
+    WaveGeom g = plan.wave.g;
     g.bufsize = ha.samplebuf_size;
     g.ring_exact = ha.ring_exact ? 1u : 0u;
     g.ring_stride = ha.ring_stride;
@@ -2130,28 +1824,20 @@ int launch_demod_wave( const DevCfg &cfg, const DevCfg *d_cfg, const double *d_t
     au.d_cs = ha.d_cs;
     au.d_tw_scratch = ha.d_tw_scratch;
     au.d_ring = ha.d_ring;
-    au.rs = resume_args(ha.d_state, ha.d_origin, ha.final);
     for ( int k = 0; k < 5; k++ ) {
 	au.d_rot[k] = ha.d_rot[k];
 	au.rot_stride[k] = ha.rot_stride[k];
     }
-    if ( hipFuncSetAttribute(kernel.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes) != hipSuccess )
+    if ( hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes) != hipSuccess )
 	return -5;
-    auto launch = [&]( const mifsk_demod_io &rows, hipStream_t on ) {
-	void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&g, (void *)&au };
-	(void)hipLaunchKernel(kernel.fn, dim3((unsigned)rows.nstreams), dim3(64), kargs, plan.lds_bytes, on);
-    };
-    if ( chain_g ) {
-	return chain_enqueue(*ha.chain, io, chain_g, chain_k, (hipStream_t)stream,
-		[&]( const mifsk_demod_io &rows, uint32_t lo, const ResumeArgs &rs, hipStream_t gs ) {
-		    au.rs = rs;
-		    if ( ha.d_tw_scratch )		// (--auto-carrier: the group's streams' own tables)
-			au.d_tw_scratch = ha.d_tw_scratch + (size_t)lo * g.tw_entries * 4u;
-		    launch(rows, gs);
-		});
-    }
-    launch(io, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_planned(plan, ha, io, (hipStream_t)stream,
+	    [&]( const mifsk_demod_io &rows, uint32_t lo, const ResumeArgs &rs, hipStream_t on ) {
+		au.rs = rs;
+		if ( ha.d_tw_scratch )		// (--auto-carrier: the rows' streams' own tables)
+		    au.d_tw_scratch = ha.d_tw_scratch + (size_t)lo * g.tw_entries * 4u;
+		void *kargs[] = { (void *)&d_cfg, (void *)&d_tw, (void *)&rows, (void *)&g, (void *)&au };
+		(void)hipLaunchKernel(fn, dim3((unsigned)rows.nstreams), dim3(64), kargs, plan.lds_bytes, on);
+	    });
 }
 
 } // namespace mifsk

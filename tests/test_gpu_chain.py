@@ -182,3 +182,33 @@ def test_which_batches_are_cut(gpu):
     assert M.demod_plan(ctx, rtty, 4096, nsamples=n, ring_exact=True)["chain_groups"] == 0
     # (12000 baud runs demod_wave_kernel<4, 1>: the resumable instantiations are the generic ones)
     assert M.demod_plan(ctx, M.rx_config("12000"), 8192, nsamples=96000)["chain_groups"] == 0
+
+
+NAMED_MODES = ["1200", "300", "rtty", "tdd", "same", "12000", "2400", "uic-train", "uic-ground", "callerid", "V.21", "50"]
+
+
+def test_the_context_plans_what_the_host_only_planner_plans(gpu, tmp_path):
+    """mifsk_demod_plan_ex on a device's context against tools/launch_plans.cpp (the planner alone,
+    tests/test_launch_plans.py) at that context's compute units: the glue hands the planner the
+    inputs the tool hands it.  No kernel is launched."""
+    import test_launch_plans as L
+    M, torch, ctx = gpu
+    ncu = M.demod_plan(ctx, M.rx_config("1200"), 1)["compute_units"]
+    exe = L.build_tool(tmp_path, sanitize=False)         # (the sanitized sweep is the CPU test's)
+    tool = dict(L.parse(line) for line in L.run_tool(exe, "--ncu", ncu, "--named", sanitize=False)[0])
+    nsamples = 1440000
+    compared = chained = 0
+    for mode in NAMED_MODES:
+        cfg = M.rx_config(mode)
+        for n in (1, 1024, 4096):
+            for variant, ring, engine in (("plain/lib", False, None), ("ring/lib", True, None),
+                                          ("plain/wave", False, "wave"), ("plain/workgroup", False, "workgroup")):
+                p = M.demod_plan(ctx, cfg, n, ring_exact=ring, engine=engine, nsamples=nsamples)
+                t = tool["%s n=%d ns=%d %s" % (mode, n, nsamples, variant)]
+                got = (p["engine"], p["kernel"], p["workgroup_size"], p["lds_bytes_per_workgroup"], p["lattice_mode"],
+                       p["frames_per_block"], "%dx%d" % (p["chain_groups"], p["chain_chunks"]))
+                want = (t["engine"], t["kernel"], int(t["wg"]), int(t["lds"]), int(t["lat"]), int(t["fpb"]), t["chain"])
+                assert got == want, (mode, n, variant)
+                compared += 1
+                chained += p["chain_groups"] != 0
+    assert compared == 12 * 3 * 4 and chained > 0
