@@ -950,7 +950,12 @@ __device__ __forceinline__ void master_loop( const DevCfg &cfg, const double *__
 	// order from the scored (confidence, amplitude) pairs; the first frame
 	// that fails any of them falls through to the general path below.
 	// ------------------------------------------------------------------
-	if ( carrier && advance && ( ST ? ( base <= N_lat && advance <= N_lat - base ) : advance <= N - base ) ) {
+	// (ST: the step onto the lattice is the reference's `advance <= samples_nvalid` too, minimodem.c:1150 --
+	// behind a frame found late in its search it may exceed what is valid where the stop bits make a frame
+	// as long as half the buffer; the general path below ends the loop then.  The lattice's own steps
+	// never do: the planner keeps lock_advance within half a buffer.)
+	if ( carrier && advance && ( ST ? ( base <= N_lat && advance <= N_lat - base && advance <= rp - base )
+					: advance <= N - base ) ) {
 	    const uint32_t t_bulk = MIFSK_CLOCK();
 	    const uint32_t first = h_first1;
 	    const uint32_t nb = base + advance;		// cursor of the next iteration

@@ -464,11 +464,14 @@ void fill_devcfg( DevCfg &d, const mifsk_rx_config &c )
 // wavefront engine is 4 x faster.  With longer windows and a clean signal it
 // still wins (tools/gpu/eng50.py, 2048 streams: 50 baud 3.0 vs 4.4 ms, 150 baud
 // 1.3 vs 4.1 ms).  Identical results either way.  (The workgroup engine has neither RING
-// addressing nor the in-loop --auto-carrier.)
+// addressing nor the in-loop --auto-carrier, and accepts lattice frames without the reference's
+// `advance <= samples_nvalid`: not where the lattice's own step exceeds half the reference's buffer,
+// 4 and more stop bits.)
 static bool use_workgroup_engine( const PlanInputs &in )
 {
     const DevCfg &d = *in.cfg;
-    const bool plain = !in.ring_exact && !in.autodetect;
+    const bool plain = !in.ring_exact && !in.autodetect
+		    && ( in.samplebuf_size == 0u || d.lock_advance <= in.samplebuf_size / 2u );
     bool workgroup = plain && !( in.engine_flags & MIFSK_IO_ENGINE_WAVE )
 		  && ( ( in.engine_flags & MIFSK_IO_ENGINE_WORKGROUP )
 		       || ( d.lat_linear && d.bit_nsamples >= 16u ) );
@@ -932,7 +935,17 @@ int plan_workgroup( const PlanInputs &in, LaunchPlan &plan )
     // limit of 0 would mean "all samples" to every chunk but the last; such a batch is not cut)
     if ( in.nsamples == 0u )
 	chain_g = chain_k = 0u;
-    plan.resumable = in.has_state || chain_g;
+    // The plain instantiations take `advance <= N - base` for the reference's `advance <= samples_nvalid`
+    // (minimodem.c:1150-1152, where its loop ENDS otherwise): the same thing while no advance exceeds half
+    // the reference's buffer, which is what is valid of it away from the end of the stream.  The buffer is
+    // sized without the stop bits (minimodem.c:1056-1060): with 3 of them a frame is as long as that half,
+    // and the advance behind a frame found late in its search longer -- the reference stops decoding there,
+    // in mid stream.  Such configurations run the resumable instantiation, which carries the file position
+    // and does the reference's buffer arithmetic statement for statement, here without a state record.
+    const uint32_t reach = cfg.try_max[0] > cfg.try_max[1] ? cfg.try_max[0] : cfg.try_max[1];
+    const bool flat_sound = in.samplebuf_size == 0u
+			 || reach + cfg.frame_nsamples - cfg.overscan <= in.samplebuf_size / 2u;
+    plan.resumable = in.has_state || chain_g || !flat_sound;
     int index = 0;		// (always found: Bell-202 has a slab)
     while ( index + 1 < (int)( sizeof(kWgKernels) / sizeof(kWgKernels[0]) )
 	    && !( kWgKernels[index].use_slab == g.use_slab && kWgKernels[index].bell202 == bell202 && kWgKernels[index].st == plan.resumable ) )

@@ -4,7 +4,8 @@ and the CU count (plan_launch in minimodem_amd/csrc/mifsk_plan.cpp), so tools/la
 the planner alone -- mifsk_plan.cpp and mifsk_config.cpp, nothing else linked or loaded -- under
 the address and undefined-behaviour sanitizers over
 
-  the 953 configurations of test_gpu_bitlengths.py and twelve named modes
+  the 953 configurations of test_gpu_bitlengths.py, twelve named modes and the 6 x 187 frame shapes
+  of test_gpu_frameshapes.py (1 .. 64 bit windows a frame; labels like 240/raw43, 1200/7-13-1.5)
   x nstreams 1, 5, 256, 1024, 3000, 4096, 8192, 65536  x nsamples 0, 96000, 1440000  at 256 CUs
   x {plain, RING, --auto-carrier, with loop state, with counters}
   x {library's choice, forced wavefront engine, forced workgroup engine where it is accepted}
@@ -23,10 +24,13 @@ import subprocess
 
 import pytest
 
+import _shapes as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROCM_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "launch_plans.txt")
-CASES = (953 + 2 * 12) * 8 * 3 * 13     # 13: the variants x engines that are accepted
+SHAPED = len(S.RATES) * len(S.SHAPES)   # the frame-shape leg: 6 x 187
+CASES = (953 + 2 * 12 + SHAPED) * 8 * 3 * 13     # 13: the variants x engines that are accepted
 
 
 # (the sanitizers' runtimes in the program: nothing to load first)
@@ -76,7 +80,10 @@ def test_every_plan_is_the_recorded_one_and_keeps_the_invariants(tool):
     assert m and int(m.group(1)) == CASES and int(m.group(3)) > 0, err[-2000:]
     with open(FIXTURE) as f:
         want = f.read().splitlines()
-    assert sum(" digest=" in w for w in want) == 2 * 12 + 953 and all(w.endswith(" lines=312") for w in want if " digest=" in w)
+    assert sum(" digest=" in w for w in want) == 2 * 12 + 953 + SHAPED and all(w.endswith(" lines=312") for w in want if " digest=" in w)
+    # no frame shape is refused: every configuration of the shape sweep has its digest line
+    shaped = [label for rate in S.RATE_IDS for label, _mode, _kw, _seed in S.configs(rate)]
+    assert [g.split(" digest=")[0] for g in lines if " digest=" in g][-SHAPED:] == shaped
     if lines == want:
         return
     recorded = dict(w.split(" digest=") for w in want if " digest=" in w)

@@ -9,6 +9,7 @@ import pytest
 
 import _golden as G
 import _oracle as O
+import _shapes as S
 
 pytestmark = pytest.mark.skipif(not O.have_ref(), reason="needs oracle/_ref (the reference built from its sources)")
 REFDATA = np.load(os.path.join(G.GOLDEN_DIR, "refdata.npz"))
@@ -162,3 +163,63 @@ def test_find_frame_against_reference_fsk_c():
                 assert oa == pytest.approx(ra, rel=1e-5, abs=1e-6)
         rl.fsk_plan_destroy(rp)
         ol.ofsk_plan_destroy(op)
+
+
+# frame shapes the named modes do not have (tests/test_gpu_frameshapes.py sweeps 187 of them against
+# the restatement): (shape, further options, the reference's command line for them)
+_RAW = lambda n: (dict(binary_raw_nbits=n), {}, ["--binary-raw", str(n)])                               # noqa: E731
+
+
+def _framed(d, s, p, opts=None, args=()):
+    kw = dict(n_data_bits=d, nstartbits=s, nstopbits=float(p))
+    return kw, dict(opts or {}), ["-%d" % d, "--startbits", str(s), "--stopbits", "%g" % p] + list(args)
+
+
+REF_SHAPES = [_RAW(1), _RAW(9), _RAW(33), _RAW(64),
+              _framed(5, 0, 0, dict(baudot=1)),                 # (-5 selects the Baudot decoder)
+              _framed(7, 2, 1.5), _framed(8, 20, 2), _framed(8, 1, 0.5),
+              _framed(8, 13, 1, dict(invert_start_stop=1), ["--invert-start-stop"]),
+              _framed(7, 1, 1, dict(msb_first=1), ["--msb-first"])]
+
+
+@pytest.mark.parametrize("rate", ["1200", "b300.4"])
+@pytest.mark.parametrize("shape", REF_SHAPES, ids=[S.option_label(kw, o) if o else S.shape_label(kw) for kw, o, _a in REF_SHAPES])
+def test_restatement_equals_reference_program_at_other_frame_shapes(shape, rate, tmp_path):
+    """1 .. 64 bit windows a frame at 40 and 300 samples per bit: the sigma = 0.03 stream of
+    _shapes.py's keyer as a float WAV through the reference program with --startbits / --stopbits /
+    -5 -7 -8 / --binary-raw N.  The restatement's episodes must print the reference's NOCARRIER
+    lines, its bytes must be the reference's stdout where the decoder is ASCII, and for the other
+    decoders (--binary-raw's lines of 0 and 1, -5's Baudot) the product's host post-pass over the
+    restatement's frames must print that stdout.
+
+    Twice: the stream as keyed, in ring mode -- it ends with its last bit, and a frame that
+    reaches past the end reads the reference's stale buffer cells, which is what ring mode is
+    (at raw 1 and 300 samples per bit the last frame's confidence is 4.04 there and 5.21 over
+    flat mode's zeros) -- and behind a buffer's length of silence, as the reference's own
+    transmissions end, in ring and flat mode.
+
+    --binary-raw 64: NOCARRIER lines only.  The reference's bit_window() shifts 1ULL by 64 for
+    its mask, which C leaves undefined; the build under oracle/_ref prints 64 zeros a frame.
+    The restatement and the product do what its `// handle bits==64` comment says."""
+    import minimodem_amd as M
+    kw, opts, args = shape
+    ri = S.RATE_IDS.index(rate)
+    mode = S.RATES[ri][1]
+    allkw = dict(kw, **opts)
+    cfg, mcfg = O.oracle_config(mode, **allkw), M.rx_config(mode, **allkw)
+    keyed = S.make_streams(mcfg, [S.SEED, ri, 2000 + REF_SHAPES.index(shape)])[1][1]
+    wav = str(tmp_path / "s.wav")
+    for x, rings in ((keyed, (True,)), (np.concatenate([keyed, np.zeros(int(cfg.samplebuf_size), np.float32)]), (True, False))):
+        O.write_wav(wav, x, int(cfg.sample_rate), s16=False)
+        out, err = O.ref_rx(wav, [mode] + args)
+        ref_lines = [l for l in err.splitlines() if l.startswith("### NOCARRIER")]
+        assert ref_lines
+        for ring in rings:
+            r = O.oracle_rx_stream(cfg, x, ring_mode=ring)
+            assert len(r["frames"]) >= 3
+            assert [O.format_nocarrier(cfg, e) for e in r["episodes"]] == ref_lines
+            if cfg.decoder == 0:
+                assert r["bytes"] == out
+            if kw.get("binary_raw_nbits") != 64:
+                text, _err = M.stream_text(mcfg, r["frames"]["bits"], r["episodes"], quiet=True)
+                assert text == out

@@ -1,7 +1,8 @@
 // launch_plans.cpp -- every launch plan of libmifsk.so without a device: the planner of
 // minimodem_amd/csrc/mifsk_plan.cpp (plan_launch) over every bit length 3..320 at three rates,
-// the named modes, eight batch sizes, three row lengths and every variant of a call, one line
-// per case with every field of the plan, and the invariants of a plan checked on each.
+// the named modes, the 187 frame shapes of tests/_shapes.py (1 .. 64 bit windows a frame) at six
+// rates, eight batch sizes, three row lengths and every variant of a call, one line per case with
+// every field of the plan, and the invariants of a plan checked on each.
 //
 //   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iminimodem_amd/csrc
 //       -fsanitize=address,undefined -o launch_plans tools/launch_plans.cpp
@@ -14,6 +15,9 @@
 //   launch_plans [--ncu N] --named            the named modes' lines in full (no forced-chain leg)
 //   launch_plans [--ncu N] --only LABEL       one configuration's lines (LABEL as in its digest line)
 //   launch_plans [--ncu N] --one MODE NSTREAMS NSAMPLES VARIANT FORCE     one case
+//
+// A frame shape's LABEL / MODE is RATE/SHAPE: 240/raw43 (--binary-raw 43 at 240 baud), 1200/7-13-1.5
+// (7 data bits, 13 start bits, 1.5 stop bits), b40.4/8-1-1 (40.4 samples per bit at 48 kHz).
 //
 // The summary goes to stderr: "launch_plans: N cases, M distinct plans, K chained, 0 violations";
 // exit status 1 with a violation.  (tests/test_launch_plans.py)
@@ -39,6 +43,19 @@ static const uint32_t kSamples[] = { 0u, 96000u, 1440000u };
 static const char *const kVariants[] = { "plain", "ring", "auto", "state", "counters" };
 static const char *const kForces[] = { "lib", "wave", "workgroup" };
 static const double kDeltas[] = { 0.0, -0.3, 0.4 };
+// the frame-shape leg's rates (tests/_shapes.py): a baud rate, or the samples per bit at 48 kHz
+static const struct { const char *label; double baud, spb; } kShapeRates[] = {
+    { "1200", 1200.0, 0.0 }, { "b40.4", 0.0, 40.4 }, { "12000", 12000.0, 0.0 },
+    { "240", 240.0, 0.0 }, { "b300.4", 0.0, 300.4 }, { "45.45", 45.45, 0.0 } };
+static const int kShapeData[] = { 5, 7, 8 };
+static const int kShapeStart[] = { 0, 1, 2, 3, 7, 13, 20 };
+static const float kShapeStop[] = { 0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f };
+
+// a frame shape: --binary-raw N, or data bits - start bits - stop bits
+struct Shape {
+    int		raw, n_data, nstart;
+    float	nstop;
+};
 
 static int g_ncu = 256;
 static long g_cases = 0, g_chained = 0, g_violations = 0;
@@ -50,11 +67,53 @@ struct Config {
     DevCfg		d, d_auto;
 };
 
-static bool make_config( Config &c, const char *label, const char *mode )
+static std::string shape_label( const Shape &s )
+{
+    char b[48];
+    if ( s.raw )
+	std::snprintf(b, sizeof(b), "raw%d", s.raw);
+    else
+	std::snprintf(b, sizeof(b), "%d-%d-%g", s.n_data, s.nstart, (double)s.nstop);
+    return b;
+}
+
+// "RATE/SHAPE" -> the rate's baudmode string and the shape; false: not such a label
+static bool parse_shape_label( const char *label, std::string &mode, Shape &s )
+{
+    const char *slash = std::strchr(label, '/');
+    if ( !slash )
+	return false;
+    const std::string rate(label, slash);
+    mode.clear();
+    for ( const auto &r : kShapeRates )
+	if ( rate == r.label ) {
+	    char b[64];
+	    if ( r.spb != 0.0 )
+		std::snprintf(b, sizeof(b), "%.17g", 48000.0 / r.spb);
+	    else
+		std::snprintf(b, sizeof(b), "%s", r.label);
+	    mode = b;
+	}
+    s = Shape{0, 0, 0, 0.0f};
+    if ( mode.empty() )
+	return false;
+    if ( std::sscanf(slash + 1, "raw%d", &s.raw) == 1 )
+	return s.raw > 0 && shape_label(s) == slash + 1;
+    return std::sscanf(slash + 1, "%d-%d-%f", &s.n_data, &s.nstart, &s.nstop) == 3 && shape_label(s) == slash + 1;
+}
+
+static bool make_config( Config &c, const char *label, const char *mode, const Shape *shape = nullptr )
 {
     mifsk_modem_args a;
     mifsk_modem_args_default(&a);
     a.baudmode = mode;
+    if ( shape && shape->raw )
+	a.binary_raw_nbits = shape->raw;
+    else if ( shape ) {
+	a.n_data_bits = shape->n_data;
+	a.nstartbits = shape->nstart;
+	a.nstopbits = shape->nstop;
+    }
     if ( mifsk_rx_config_init(&c.cfg, &a) )
 	return false;
     a.auto_carrier_threshold = 0.001f;
@@ -89,7 +148,13 @@ static void check( const PlanInputs &in, const LaunchPlan &p, const char *line )
 	INVARIANT(g.mags_cap % 2u == 0u && g.mags_cap >= 16u * d.n_bits);
 	INVARIANT(g.lat_fmin <= g.lat_fmax && g.lat_fmax <= 64u);
 	INVARIANT(g.lat_mode != (uint32_t)LAT_LINEAR || ( g.round_wins != 0u && g.round_wins % 64u == 0u ));
-	INVARIANT(!g.tiled || ( d.bit_nsamples >= 256u && !in.ring_exact ));
+	// The tile serves any bit length of at least one step: corr_global_tiled takes whole steps of TILE_K
+	// samples, then whole groups of 16, then the tail, whatever B is, and the shared segments are planned
+	// per configuration (none below kTileMinBit).  kTileMinBit is where the planner PREFERS the tile to a
+	// slab; below it the tile is what is left when no SCAN slab fits a wave's share of LDS -- 200 samples
+	// per bit with 43 and more windows a frame, 160 with 52 and more -- and tests/test_gpu_frameshapes.py
+	// runs those plans against the oracle (240 baud, --binary-raw 43 .. 64).
+	INVARIANT(!g.tiled || ( d.bit_nsamples >= TILE_K && !in.ring_exact ));
 	INVARIANT(g.slab_cap == 0u || g.slab_cap >= reach);
 	// (the kernel's LDS: counters, magnitudes, slab)
 	INVARIANT(p.lds_bytes >= kCntBytes + g.mags_cap * 8u + g.slab_floats * 4u);
@@ -217,17 +282,20 @@ int main( int argc, char **argv )
 	for ( int k = 0; k < 5; k++ ) if ( !std::strcmp(one[3], kVariants[k]) ) v = k;
 	for ( int k = 0; k < 3; k++ ) if ( !std::strcmp(one[4], kForces[k]) ) f = k;
 	std::string line;
-	if ( v < 0 || f < 0 || !make_config(c, one[0], one[0])
+	std::string mode = one[0];
+	Shape shape;
+	const bool shaped = parse_shape_label(one[0], mode, shape);
+	if ( v < 0 || f < 0 || !make_config(c, one[0], mode.c_str(), shaped ? &shape : nullptr)
 		|| !one_case(c, std::atoi(one[1]), (uint32_t)std::strtoul(one[2], nullptr, 10), v, f, line) )
 	    return 2;
 	std::printf("%s\n", line.c_str());
 	return g_violations ? 1 : 0;
     }
     // a configuration's cases, unless another one is asked for; false: mifsk_rx_config_init refuses it
-    auto visit = [&]( const std::string &label, const char *mode, bool in_full, bool plans ) -> bool {
+    auto visit = [&]( const std::string &label, const char *mode, bool in_full, bool plans, const Shape *shape = nullptr ) -> bool {
 	if ( only && label != only )
 	    return true;
-	if ( !make_config(c, label.c_str(), mode) )
+	if ( !make_config(c, label.c_str(), mode, shape) )
 	    return false;
 	all_cases(c, in_full || only, plans);
 	return true;
@@ -261,6 +329,27 @@ int main( int argc, char **argv )
     if ( !named_only && !only && refused != 1 ) {
 	g_violations++;
 	std::fprintf(stderr, "VIOLATION %ld configurations refused\n", refused);
+    }
+    // the frame-shape leg: every number of bit windows a frame may have, at the six rates
+    if ( !named_only ) {
+	std::vector<Shape> shapes;
+	for ( int n = 1; n <= 64; n++ )
+	    shapes.push_back(Shape{n, 0, 0, 0.0f});
+	for ( int nd : kShapeData )
+	    for ( int st : kShapeStart )
+		for ( float sp : kShapeStop )
+		    if ( !( st == 0 && sp == 3.0f ) )
+			shapes.push_back(Shape{0, nd, st, sp});
+	for ( const auto &r : kShapeRates )
+	    for ( const Shape &sh : shapes ) {
+		const std::string label = std::string(r.label) + "/" + shape_label(sh);
+		std::string mode;
+		Shape parsed;
+		if ( !parse_shape_label(label.c_str(), mode, parsed) || !visit(label, mode.c_str(), full, false, &sh) ) {
+		    g_violations++;
+		    std::fprintf(stderr, "VIOLATION %s: refused\n", label.c_str());
+		}
+	    }
     }
     std::fprintf(stderr, "launch_plans: %ld cases, %zu distinct plans, %ld chained, %ld violations\n",
 		 g_cases, g_distinct.size(), g_chained, g_violations);
