@@ -33,6 +33,7 @@
  *   mifsk_demod_files             --rx --file, N files   simpleaudio-sndfile.c:42-74,
  *                                                        minimodem.c:1014-1032
  *   mifsk_demod_files_long        ... long recordings: every group cut in time across the chip
+ *   mifsk_frame_softbits          fsk_bit_analyze on every bit window of the frames found  fsk.c:107-169
  */
 #ifndef MIFSK_H
 #define MIFSK_H
@@ -910,6 +911,57 @@ typedef struct mifsk_session_info {
     uint64_t	reserved[2];
 } mifsk_session_info;
 int mifsk_session_info_get( const mifsk_session *s, mifsk_session_info *info );
+
+/* ---- soft bits: the band magnitudes of every bit of every decoded frame -------- */
+
+/* A second pass over frames a receive entry has written: what the loop makes `bits`, `confidence`
+ * and `amplitude` of and then drops.  For stream s, frame j < min(d_nframes[s], frames_cap) and
+ * bit k < cfg->expect_n_bits the window is x[a .. a + cfg->bit_nsamples) with
+ * a = d_frames[s][j].start - d_origin[s] + cfg->bit_offset[k], where x[i] is the row's sample for
+ * i < min(nsamples[s], stream_stride) and 0.0 beyond, whatever the memory holds there (flat
+ * addressing).  d_mag[s][j][k] receives the two floats fsk_bit_analyze makes of that window
+ * (fsk.c:107-169: the double sums in index order, hypotf, 2.0f / bit_nsamples) -- mark, then space;
+ * bit k of d_rawbits[s][j] is mark > space (strict; a NaN gives 0), in time order, start and stop
+ * bits included: the loop's shift, window and bit reversal have not been applied.  With an
+ * all-'d' expect string fsk_frame_analyze's confidence pass over d_mag[s][j] gives the frame's
+ * amplitude; with cfg->expect_data it gives its confidence, unless the frame is
+ * MIFSK_FRAME_REFINED: that one keeps its coarse scan's confidence beside the fine scan's start
+ * (minimodem.c:1357-1389), so the pass gives at least the frame's.
+ *   A frame whose windows lie partly or wholly beyond the row's end -- an absurd start included
+ * -- sees zeros there.  A frame with start < d_origin[s] refers to samples the caller no longer
+ * holds: all its magnitudes are -1.0f and its rawbits 0.  Entries j >= d_nframes[s] are left
+ * untouched.  PCM16 samples are (float)v / 32768.0f plus the --Xrxnoise term, mifsk_ingest_s16's
+ * expression: the result is bit for bit that of mifsk_ingest_s16 and the float call.
+ *   d_frames is caller data: whatever it holds, nothing outside nstreams * stream_stride elements
+ * of d_samples is read and nothing outside the two output arrays is written.
+ *   Frames of a MIFSK_IO_RING_EXACT call can be passed; they get the FLAT answer (where the loop
+ * saw stale cells behind the stream's end, this pass sees zeros).
+ *   Checked in this order, before any HIP call: -EINVAL for a NULL ctx, cfg, io, d_samples,
+ * d_frames, d_nframes or d_mag; for nstreams <= 0 or frames_cap == 0; for an unknown kind, or
+ * rxnoise != 0 with MIFSK_FEED_F32; for a base that is not 16-byte aligned or a stride that is no
+ * multiple of 4 (float32) or 8 (PCM16); what mifsk_check_cfg says of cfg; -ENOTSUP for
+ * cfg->auto_carrier_threshold > 0 -- with --auto-carrier a frame's bands are its episode's
+ * (mifsk_episode.b_mark), and a table of bands per episode is a follow-up; -EINVAL for
+ * frames_cap * cfg->expect_n_bits above 2^32 - 65 (a stream's cases are counted in 32 bits).
+ * Asynchronous on `stream`; the context's tables are looked up as mifsk_demod_batch does. */
+typedef struct mifsk_softbits_io {
+    const void		*d_samples;	/* nstreams rows: float32, or PCM16 (kind)             */
+    size_t		stream_stride;	/* elements between rows (16-byte aligned rows)        */
+    const uint32_t	*d_nsamples;	/* per stream; NULL -> all = nsamples                  */
+    uint32_t		nsamples;
+    int			nstreams;
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16                     */
+    float		rxnoise;	/* S16 only: mifsk_ingest_s16's term; F32: must be 0   */
+    const uint64_t	*d_origin;	/* stream index of each row's sample 0; NULL -> 0      */
+    const mifsk_frame	*d_frames;	/* [nstreams][frames_cap], as the receive entries write */
+    const uint32_t	*d_nframes;	/* [nstreams]; more than frames_cap is clamped         */
+    size_t		frames_cap;
+    float		*d_mag;		/* [nstreams][frames_cap][expect_n_bits][2]: mark, space */
+    uint64_t		*d_rawbits;	/* [nstreams][frames_cap] or NULL: bit k = mark > space */
+} mifsk_softbits_io;
+
+int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const mifsk_softbits_io *io, void *stream );
 
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import ModemArgs, RxConfig  # noqa: F401
 
-__all__ = ["build", "rx_config", "Context", "demod_batch", "find_frame_batch",
+__all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
            "gather_bytes", "shard_range"]
 
@@ -376,6 +376,69 @@ def demod_batch(ctx, cfg, samples, nsamples=None, want=("bytes", "episodes"),
     if rc != 0:
         raise RuntimeError("mifsk_demod_batch failed: %d" % rc)
     return out
+
+
+def frame_softbits(ctx, cfg, samples, out, nsamples=None, origin=None, rxnoise=0.0, stream=None, rawbits=True):
+    """mifsk_frame_softbits: the mark and space magnitudes of every bit window of the frames in
+    `out` -- a result dict of demod_batch / demod_long[_batch] made with "frames" in `want`.
+
+    samples : torch.float32 or torch.int16 (PCM16) CUDA tensor [nstreams, stride] (stride % 4 == 0,
+              % 8 == 0 for PCM16), or 1-D for one stream; the rows the frames were decoded from, or
+              rows that start at `origin` in them
+    nsamples: optional torch.int32/uint32 CUDA tensor [nstreams]; default: the rows' width
+    origin  : optional torch.int64 CUDA tensor [nstreams], the stream index of each row's sample 0;
+              frames that start before it get magnitudes of -1
+    rxnoise : the --Xrxnoise factor, PCM16 only (mifsk_ingest_s16's term)
+    Returns {"mag": float32 [nstreams, frames_cap, expect_n_bits, 2] (mark, space), "rawbits": int64
+    [nstreams, frames_cap] (bit k = mark > space of bit window k; absent with rawbits=False)},
+    allocated on the launch stream; entries at or beyond a stream's frame count are 0.  No
+    synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
+    if samples.dim() == 1:
+        samples = samples[None, :]
+    assert samples.dim() == 2 and samples.stride(1) == 1
+    s16 = samples.dtype == torch.int16
+    vec = 8 if s16 else 4
+    nstreams, width = samples.shape
+    _check_nsamples(torch, nsamples, nstreams)
+    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d samples" % vec
+    frames, nframes = out["frames"], out["nframes"]
+    assert frames.is_cuda and frames.is_contiguous() and frames.dim() == 3 and frames.shape[0] == nstreams \
+        and frames.shape[2] == FRAME_DTYPE.itemsize, "out must hold the frames of these streams"
+    assert nframes.is_cuda and nframes.is_contiguous() and nframes.shape == (nstreams,)
+    if origin is not None:
+        assert origin.is_cuda and origin.dtype == torch.int64 and origin.is_contiguous() \
+            and origin.shape == (nstreams,)
+    frames_cap = int(frames.shape[1])
+    with _on(torch, stream):
+        res = {"mag": torch.zeros((nstreams, frames_cap, int(cfg.expect_n_bits), 2), dtype=torch.float32,
+                                  device=samples.device)}
+        if rawbits:
+            res["rawbits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=samples.device)
+    if stream is not None:
+        cur = torch.cuda.current_stream()       # (see _torch_outputs)
+        for t in res.values():
+            t.record_stream(cur)
+    io = _lib.SoftbitsIO()
+    io.d_samples = samples.data_ptr()
+    io.stream_stride = samples.stride(0) if nstreams > 1 else int(width)
+    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
+    io.nsamples = int(width)
+    io.nstreams = nstreams
+    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    io.rxnoise = float(rxnoise)
+    io.d_origin = origin.data_ptr() if origin is not None else None
+    io.d_frames = frames.data_ptr()
+    io.d_nframes = nframes.data_ptr()
+    io.frames_cap = frames_cap
+    io.d_mag = res["mag"].data_ptr()
+    io.d_rawbits = res["rawbits"].data_ptr() if rawbits else None
+    rc = lib.mifsk_frame_softbits(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_frame_softbits failed: %d" % rc)
+    return res
 
 
 def demod_plan(ctx, cfg, nstreams, ring_exact=False, engine=None, nsamples=None):

@@ -241,6 +241,14 @@ class TimeSplitStats(C.Structure):
 
 TIME_SPLIT_REJECT_ALL = 0x10000
 
+
+class SoftbitsIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("rxnoise", C.c_float),
+                ("d_origin", C.c_void_p), ("d_frames", C.c_void_p), ("d_nframes", C.c_void_p),
+                ("frames_cap", C.c_size_t), ("d_mag", C.c_void_p), ("d_rawbits", C.c_void_p)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
 assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
 assert C.sizeof(SessionInfo) == 56 and SessionInfo.h2d_bytes_last.offset == 24
@@ -277,6 +285,7 @@ EXPORTS = [
     "mifsk_demod_long_batch_s16", "mifsk_demod_long_batch_host", "mifsk_demod_files_long",
     "mifsk_files_time_split",
     "mifsk_session_feed_ex", "mifsk_session_feed_device", "mifsk_session_info_get",
+    "mifsk_frame_softbits",
 ]
 
 _lib = None
@@ -500,5 +509,7 @@ def load():
                                            C.c_float, C.c_uint, C.POINTER(TimeSplit), C.POINTER(C.c_void_p)]
     lib.mifsk_files_time_split.restype = C.POINTER(TimeSplitStats)
     lib.mifsk_files_time_split.argtypes = [C.c_void_p, C.c_int]
+    lib.mifsk_frame_softbits.restype = C.c_int
+    lib.mifsk_frame_softbits.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(SoftbitsIO), C.c_void_p]
     _lib = lib
     return lib

@@ -67,6 +67,7 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_file_result);
     MIFSK_SIZEOF(mifsk_time_split);
     MIFSK_SIZEOF(mifsk_time_split_stats);
+    MIFSK_SIZEOF(mifsk_softbits_io);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;
@@ -398,7 +399,7 @@ static int prepare( mifsk_ctx *ctx, const mifsk_rx_config *cfg, Prepared &p )
 }
 
 int mifsk::lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::shared_lock<std::shared_mutex> &gate,
-	DevCfg &d, const double **d_tw )
+	DevCfg &d, const double **d_tw, const DevCfg **d_cfg )
 {
     Prepared p;
     if ( int rc = prepare(ctx, cfg, p) )
@@ -406,6 +407,8 @@ int mifsk::lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::share
     gate = std::move(p.gate);
     d = p.d;
     *d_tw = p.d_tw;
+    if ( d_cfg )
+	*d_cfg = p.d_cfg;
     return 0;
 }
 

@@ -86,7 +86,8 @@ int mifsk_check_cfg( const mifsk_rx_config *cfg );
 namespace mifsk {
 // The tables a launching entry point looks up for `cfg` (mifsk_capi.cpp, prepare()): the derived
 // kernel configuration, the context's twiddle table, and the gate that keeps them alive while it
-// is held.  For mifsk_selftest.hip, whose kernels must run on the product's own tables.
+// is held.  For mifsk_selftest.hip and mifsk_softbits.hip, whose kernels must run on the product's
+// own tables.  d_cfg (may be NULL): the context's device copy of `d`.
 int lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::shared_lock<std::shared_mutex> &gate,
-	DevCfg &d, const double **d_tw );
+	DevCfg &d, const double **d_tw, const DevCfg **d_cfg = nullptr );
 }
