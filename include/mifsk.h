@@ -34,6 +34,7 @@
  *                                                        minimodem.c:1014-1032
  *   mifsk_demod_files_long        ... long recordings: every group cut in time across the chip
  *   mifsk_frame_softbits          fsk_bit_analyze on every bit window of the frames found  fsk.c:107-169
+ *   mifsk_detect_carrier_batch    fsk_detect_carrier     fsk.c:543-581 (windows of every stream)
  */
 #ifndef MIFSK_H
 #define MIFSK_H
@@ -962,6 +963,71 @@ typedef struct mifsk_softbits_io {
 
 int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
 	const mifsk_softbits_io *io, void *stream );
+
+/* ---- a batch of fsk_detect_carrier() problems ------------------------------------ */
+
+/* fsk_detect_carrier (fsk.c:543-581) on windows of every stream of a batch: "where is there a
+ * tone, and in which band?" -- the question that comes before any decoding.  Window w of stream s
+ * is x[a .. a + window) with a = first + w * hop (64 bits), where x is the row as
+ * mifsk_frame_softbits defines it: valid length min(nsamples[s], stream_stride), PCM16 as
+ * (float)v / 32768.0f plus the --Xrxnoise term (mifsk_ingest_s16's expression).  A window that
+ * ends inside the valid length is evaluated; any other (the reference never calls the function on
+ * a partial window, minimodem.c:1179-1190) gets d_band = MIFSK_CARRIER_NO_WINDOW and d_mag = 0, and
+ * its spectrum row is left untouched.
+ *   An evaluated window's d_band is the reference's return value: the band b in 1 .. nbands-1 with
+ * the largest magnitude among those for which `mag < threshold` is false, the lowest such band on
+ * a tie (the first strict maximum), never one whose magnitude is NaN, MIFSK_CARRIER_NONE if there
+ * is none; d_mag is that band's magnitude (0.0f with NONE); d_spectrum[s][w][b] the magnitude of
+ * every band b in 0 .. nbands-1.  The sums are the reference's as the oracle restates them: re, im
+ * from 0.0, n ascending, re = fma((double)x[n], cos, re), im = fma((double)x[n], -sin, im) of the
+ * angle 2 pi ((b n) mod fftsize) / fftsize from the context's spectrum table, then hypotf of the
+ * two floats times 1.0f / ((float)window / 2.0f).
+ *   Checked in this order, before any HIP call: -EINVAL for a NULL ctx, cfg, io, d_samples or
+ * d_band; for nstreams <= 0 or nwindows == 0; for an unknown kind, or rxnoise != 0 with
+ * MIFSK_FEED_F32; for a base that is not 16-byte aligned or a stride that is no multiple of 4
+ * (float32) or 8 (PCM16); what mifsk_check_cfg says of cfg, and cfg->nbands < 2; for a window
+ * above cfg->fftsize (asserted at fsk.c:547) or a default window of 0; for cfg->nbands * window
+ * above 2^32 - 1 (b * n is reduced in 32 bits on the device); for nwindows * cfg->nbands above
+ * 2^32 - 1 when d_spectrum is given.  Any threshold is accepted (the two comparisons decide), and
+ * cfg->auto_carrier_threshold is not looked at.  Asynchronous on `stream`; the context's tables
+ * are looked up as mifsk_frame_softbits does.  Whatever the arguments hold, nothing outside
+ * nstreams * stream_stride elements of d_samples is read and nothing outside the three output
+ * arrays is written. */
+#define MIFSK_CARRIER_NONE       (-1)   /* no band reached the threshold (the reference's -1) */
+#define MIFSK_CARRIER_NO_WINDOW  (-2)   /* the window does not lie wholly inside the row      */
+
+typedef struct mifsk_carrier_io {
+    const void		*d_samples;	/* nstreams rows: float32, or PCM16 (kind)             */
+    size_t		stream_stride;	/* elements between rows (16-byte aligned rows)        */
+    const uint32_t	*d_nsamples;	/* per stream; NULL -> all = nsamples                  */
+    uint32_t		nsamples;
+    int			nstreams;
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16                     */
+    float		rxnoise;	/* S16 only: mifsk_ingest_s16's term; F32: must be 0   */
+    uint64_t		first;		/* start of window 0 in every row                      */
+    uint32_t		window;		/* samples per window, 1 .. cfg->fftsize; 0 -> what
+					   --auto-carrier uses: (unsigned)min(cfg->nsamples_per_bit,
+					   (float)cfg->fftsize)  (minimodem.c:1179-1190)       */
+    uint32_t		hop;		/* samples between window starts; 0 -> window          */
+    uint32_t		nwindows;	/* windows per stream the outputs have room for        */
+    float		threshold;	/* min_mag_threshold (fsk.c:570)                       */
+    int32_t		*d_band;	/* [nstreams][nwindows]                                */
+    float		*d_mag;		/* [nstreams][nwindows] or NULL                        */
+    float		*d_spectrum;	/* [nstreams][nwindows][cfg->nbands] or NULL           */
+} mifsk_carrier_io;			/* 88 bytes */
+
+int mifsk_detect_carrier_batch( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
+	const mifsk_carrier_io *io, void *stream );
+/* host only: how many whole windows a row of nsamples holds -- 0 when first + window > nsamples,
+ * else (nsamples - first - window) / hop + 1; hop == 0 means window */
+uint64_t mifsk_carrier_windows( uint64_t nsamples, uint64_t first, uint32_t window, uint32_t hop );
+/* host only: the tone pair --auto-carrier tunes to when it detects `band` (minimodem.c:1203-1219):
+ * b_mark = band, b_space = band + b_shift, the frequencies band * cfg->band_width as
+ * fsk_set_tones_by_bandshift makes them (outputs may be NULL).  -EINVAL for a NULL cfg, band < 1,
+ * band >= nbands or b_shift == 0; -ERANGE when the space band falls outside 1 .. nbands-1, the
+ * case in which the loop drops the detection. */
+int mifsk_carrier_tones( const mifsk_rx_config *cfg, int band, unsigned *b_mark, unsigned *b_space,
+	float *mark_f, float *space_f );
 
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 

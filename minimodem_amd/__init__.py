@@ -19,7 +19,7 @@ from ._lib import ModemArgs, RxConfig  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
-           "gather_bytes", "shard_range"]
+           "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -439,6 +439,103 @@ def frame_softbits(ctx, cfg, samples, out, nsamples=None, origin=None, rxnoise=0
     if rc != 0:
         raise RuntimeError("mifsk_frame_softbits failed: %d" % rc)
     return res
+
+
+def carrier_windows(nsamples, window, hop=0, first=0):
+    """mifsk_carrier_windows: how many whole windows of `window` samples, `hop` apart (0: window) from
+    `first` on, a row of `nsamples` samples holds."""
+    return int(_lib.load().mifsk_carrier_windows(int(nsamples), int(first), int(window), int(hop)))
+
+
+def carrier_tones(cfg, band):
+    """mifsk_carrier_tones: the tone pair --auto-carrier tunes to when it detects `band` ->
+    {"b_mark", "b_space", "mark_f", "space_f"}.  ValueError for a band outside 1 .. nbands-1 or a
+    configuration without a shift, IndexError where the space band falls outside 1 .. nbands-1 (the
+    receive loop drops such a detection)."""
+    bm, bs, fm, fs = C.c_uint(0), C.c_uint(0), C.c_float(0), C.c_float(0)
+    rc = _lib.load().mifsk_carrier_tones(C.byref(cfg), int(band), C.byref(bm), C.byref(bs), C.byref(fm), C.byref(fs))
+    if rc == -34:
+        raise IndexError("band %d: the space band falls outside 1 .. %d" % (band, cfg.nbands - 1))
+    if rc != 0:
+        raise ValueError("mifsk_carrier_tones failed: %d" % rc)
+    return {"b_mark": bm.value, "b_space": bs.value, "mark_f": fm.value, "space_f": fs.value}
+
+
+def carrier_window_default(cfg):
+    """The window --auto-carrier scans with: (unsigned)min(nsamples_per_bit, fftsize)
+    (minimodem.c:1179-1190)."""
+    return int(min(np.float32(cfg.nsamples_per_bit), np.float32(cfg.fftsize)))
+
+
+def carrier_survey(ctx, cfg, samples, nsamples=None, window=None, hop=None, first=0, nwindows=None,
+                   threshold=0.001, spectrum=False, rxnoise=0.0, stream=None, out=None):
+    """mifsk_detect_carrier_batch: fsk_detect_carrier on every window of every stream.
+
+    samples : torch.float32 or torch.int16 (PCM16) CUDA tensor [nstreams, stride] (stride % 4 == 0,
+              % 8 == 0 for PCM16), or 1-D for one stream
+    nsamples: optional torch.int32/uint32 CUDA tensor [nstreams]; default: the rows' width
+    window  : samples per window (None: what --auto-carrier uses); hop: samples between window starts
+              (None: window); first: start of window 0 in every row
+    nwindows: windows per stream (None: carrier_windows of the rows' width)
+    threshold: min_mag_threshold; spectrum: also return every band's magnitude
+    rxnoise : the --Xrxnoise factor, PCM16 only
+    out     : a dict a former call with the same shapes returned, to reuse its tensors
+    Returns {"band": int32 [nstreams, nwindows] (the band, -1 = none reached the threshold, -2 = the
+    window does not lie wholly inside the row), "mag": float32 [nstreams, nwindows], "spectrum":
+    float32 [nstreams, nwindows, nbands] with spectrum=True, "window", "hop"}, allocated on the launch
+    stream.  No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
+    if samples.dim() == 1:
+        samples = samples[None, :]
+    assert samples.dim() == 2 and samples.stride(1) == 1
+    s16 = samples.dtype == torch.int16
+    vec = 8 if s16 else 4
+    nstreams, width = samples.shape
+    _check_nsamples(torch, nsamples, nstreams)
+    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d samples" % vec
+    window = carrier_window_default(cfg) if window is None else int(window)
+    hop = window if not hop else int(hop)
+    if nwindows is None:
+        nwindows = max(1, carrier_windows(width, window, hop, first))
+    nwindows = int(nwindows)
+    if out is None:
+        with _on(torch, stream):
+            out = {"band": torch.full((nstreams, nwindows), _lib.CARRIER_NO_WINDOW, dtype=torch.int32,
+                                      device=samples.device),
+                   "mag": torch.zeros((nstreams, nwindows), dtype=torch.float32, device=samples.device)}
+            if spectrum:
+                out["spectrum"] = torch.zeros((nstreams, nwindows, int(cfg.nbands)), dtype=torch.float32,
+                                              device=samples.device)
+        if stream is not None:
+            cur = torch.cuda.current_stream()       # (see _torch_outputs)
+            for t in out.values():
+                t.record_stream(cur)
+    else:
+        assert out["band"].shape == (nstreams, nwindows) and out["band"].is_contiguous()
+        assert (not spectrum) or out["spectrum"].shape == (nstreams, nwindows, int(cfg.nbands))
+    io = _lib.CarrierIO()
+    io.d_samples = samples.data_ptr()
+    io.stream_stride = samples.stride(0) if nstreams > 1 else int(width)
+    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
+    io.nsamples = int(width)
+    io.nstreams = nstreams
+    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    io.rxnoise = float(rxnoise)
+    io.first = int(first)
+    io.window = window
+    io.hop = hop
+    io.nwindows = nwindows
+    io.threshold = float(threshold)
+    io.d_band = out["band"].data_ptr()
+    io.d_mag = out["mag"].data_ptr()
+    io.d_spectrum = out["spectrum"].data_ptr() if spectrum else None
+    rc = lib.mifsk_detect_carrier_batch(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_detect_carrier_batch failed: %d" % rc)
+    out["window"], out["hop"] = window, hop
+    return out
 
 
 def demod_plan(ctx, cfg, nstreams, ring_exact=False, engine=None, nsamples=None):

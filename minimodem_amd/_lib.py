@@ -249,7 +249,19 @@ class SoftbitsIO(C.Structure):
                 ("frames_cap", C.c_size_t), ("d_mag", C.c_void_p), ("d_rawbits", C.c_void_p)]
 
 
+CARRIER_NONE, CARRIER_NO_WINDOW = -1, -2
+
+
+class CarrierIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("rxnoise", C.c_float),
+                ("first", C.c_uint64), ("window", C.c_uint32), ("hop", C.c_uint32), ("nwindows", C.c_uint32),
+                ("threshold", C.c_float), ("d_band", C.c_void_p), ("d_mag", C.c_void_p),
+                ("d_spectrum", C.c_void_p)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
+assert C.sizeof(CarrierIO) == 88 and CarrierIO.first.offset == 40 and CarrierIO.d_band.offset == 64
 assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
 assert C.sizeof(SessionInfo) == 56 and SessionInfo.h2d_bytes_last.offset == 24
 
@@ -286,6 +298,7 @@ EXPORTS = [
     "mifsk_files_time_split",
     "mifsk_session_feed_ex", "mifsk_session_feed_device", "mifsk_session_info_get",
     "mifsk_frame_softbits",
+    "mifsk_detect_carrier_batch", "mifsk_carrier_windows", "mifsk_carrier_tones",
 ]
 
 _lib = None
@@ -511,5 +524,12 @@ def load():
     lib.mifsk_files_time_split.argtypes = [C.c_void_p, C.c_int]
     lib.mifsk_frame_softbits.restype = C.c_int
     lib.mifsk_frame_softbits.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(SoftbitsIO), C.c_void_p]
+    lib.mifsk_detect_carrier_batch.restype = C.c_int
+    lib.mifsk_detect_carrier_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(CarrierIO), C.c_void_p]
+    lib.mifsk_carrier_windows.restype = C.c_uint64
+    lib.mifsk_carrier_windows.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.mifsk_carrier_tones.restype = C.c_int
+    lib.mifsk_carrier_tones.argtypes = [C.POINTER(RxConfig), C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = lib
     return lib

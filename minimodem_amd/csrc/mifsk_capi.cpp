@@ -68,6 +68,7 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_time_split);
     MIFSK_SIZEOF(mifsk_time_split_stats);
     MIFSK_SIZEOF(mifsk_softbits_io);
+    MIFSK_SIZEOF(mifsk_carrier_io);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;
@@ -309,7 +310,7 @@ static int get_devcfg( mifsk_ctx *ctx, const DevCfg &d, const DevCfg **d_out, Cf
 
 // cos / -sin of 2 pi k / N for k < N (the spectrum table of fsk_detect_carrier), one per
 // FFT size seen; like the other tables it is only ever freed by cache_gc()
-static int get_cs( mifsk_ctx *ctx, unsigned N, const double **d_out )
+int mifsk::get_cs( mifsk_ctx *ctx, unsigned N, const double **d_out )
 {
     std::lock_guard<std::mutex> g(ctx->lock);
     for ( const TwEntry &e : ctx->tables )
@@ -543,7 +544,7 @@ static int demod_batch_wave( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const P
 	    return -EINVAL;			// assert in fsk_set_tones_by_bandshift (fsk.c:587)
 	if ( (unsigned long long)cfg->nbands * cfg->bit_nsamples > 0xFFFFFFFFull )
 	    return -EINVAL;			// (band * n is reduced in 32 bits on the device)
-	int rc = get_cs(ctx, (unsigned)cfg->fftsize, &ha.d_cs);
+	int rc = mifsk::get_cs(ctx, (unsigned)cfg->fftsize, &ha.d_cs);
 	if ( rc )
 	    return rc;
 	ha.auto_threshold = cfg->auto_carrier_threshold;
@@ -905,7 +906,7 @@ extern "C" int fsk_detect_carrier( fsk_plan *p, float *samples, unsigned int nsa
     cache_gc(ctx);
     std::shared_lock<std::shared_mutex> gate(ctx->gate);	// lookup .. enqueue
     const double *d_cs = nullptr;
-    if ( get_cs(ctx, N, &d_cs) )
+    if ( mifsk::get_cs(ctx, N, &d_cs) )
 	return -1;
     if ( legacy_reserve(lp, nsamples) )
 	return -1;

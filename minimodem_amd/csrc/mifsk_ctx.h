@@ -90,4 +90,8 @@ namespace mifsk {
 // own tables.  d_cfg (may be NULL): the context's device copy of `d`.
 int lookup_tables( mifsk_ctx *ctx, const mifsk_rx_config *cfg, std::shared_lock<std::shared_mutex> &gate,
 	DevCfg &d, const double **d_tw, const DevCfg **d_cfg = nullptr );
+// The context's spectrum table for FFT size N (mifsk_capi.cpp): cos, -sin of 2 pi k / N for k < N,
+// [N][2] doubles in device memory.  Called with the gate held (it is freed only by the collector).
+// For mifsk_carrier.hip.
+int get_cs( mifsk_ctx *ctx, unsigned N, const double **d_out );
 }
