@@ -1029,6 +1029,90 @@ uint64_t mifsk_carrier_windows( uint64_t nsamples, uint64_t first, uint32_t wind
 int mifsk_carrier_tones( const mifsk_rx_config *cfg, int band, unsigned *b_mark, unsigned *b_space,
 	float *mark_f, float *space_f );
 
+/* ---- channelizer: every carrier of a recording as a row the receive entries take ---- */
+
+/* Mix -> low-pass -> decimate -> move to one output tone, for nchannels centres of every row of a
+ * batch: what acts on the survey's answer when a recording holds more than one signal.  A row x
+ * of valid length N = min(nsamples[s], stream_stride) ELEMENTS is real float32, real PCM16, or --
+ * MIFSK_CHANNEL_COMPLEX -- interleaved I, Q of either (an element is then one complex sample);
+ * PCM16 scalars are (float)v / 32768.0f, mifsk_ingest_s16's expression without the --Xrxnoise
+ * term; every scalar is widened to double.
+ *   With P = phase_steps, T = ntaps, h = taps, D = decim, q = centres[k] reduced to [0, P) (a
+ * centre is in steps of fs_in / P Hz, negative allowed), r = out_centre likewise, the tables are
+ * made on the host in double with the C library (every product rounded once, integers in 64 bits):
+ *   G[k][t] = ( (double)h[t] * c, -((double)h[t] * s) ),  (s, c) = sincos(2 pi ((q t) mod P) / P)
+ *   W[p]    = ( cos, sin ) of 2 pi p / P,  p < P
+ * Output m of a row exists when m D + T <= N (whole windows only: mifsk_carrier_windows(N, 0, T,
+ * D) of them).  re = im = 0.0, then for t ascending from 0 with n = m D + t:
+ *   real x:     re = fma(x[n], G.re, re);   im = fma(x[n], G.im, im)
+ *   xr + j xi:  re = fma(xr, G.re, re);  re = fma(-xi, G.im, re);
+ *               im = fma(xr, G.im, im);  im = fma(xi, G.re, im)
+ * and with p = (((r - q) mod P) * ((m D) mod P)) mod P, (C, S) = W[p]:
+ *   out[m] = (float) fma(re, C, -(im * S))
+ * the real part of the filtered, down-mixed signal moved up to r fs_in / P Hz, at fs_in / D samples
+ * per second.  Gain is the taps' business (a real input wants taps that sum to 2); NaN and Inf
+ * propagate as the arithmetic says.
+ *   mifsk_channel_plan_create checks, in this order and before any HIP call: -EINVAL for a NULL
+ * ctx, params or out; for a kind that is neither MIFSK_FEED_F32 nor MIFSK_FEED_S16, or flags beyond
+ * MIFSK_CHANNEL_COMPLEX; for phase_steps outside 1 .. 2^20; for ntaps outside 1 .. 4096 or NULL
+ * taps; for decim outside 1 .. 65535; for nchannels outside 1 .. 4096 or NULL centres; for
+ * nchannels * ntaps above 2^22; for a centre with |centre| >= phase_steps.  Then it builds G and W
+ * and uploads them once (-ENOMEM, -EIO).  The plan belongs to ctx's device and must be destroyed
+ * before the context; it may be used from several threads and streams at once (it is read only).
+ * mifsk_channel_plan_destroy SYNCHRONISES THE DEVICE (hipDeviceSynchronize: every stream) before
+ * it frees the tables, so a launch still in flight never reads freed memory; keep plans for as
+ * long as their parameters are in use rather than making one per call.
+ *   mifsk_channelize_batch writes row s * nchannels + k of d_rows: out[m] for m < min(M_s,
+ * nout_cap), 0.0f from there to out_stride, and that count into d_nout[s * nchannels + k] -- what
+ * mifsk_demod_batch takes as d_samples and d_nsamples.  It checks, in this order and before any
+ * HIP call: -EINVAL for a NULL plan, io, d_samples, d_rows or d_nout; for nstreams <= 0; for an
+ * input base that is not 16-byte aligned or a stream_stride that is not a whole number of 16-byte
+ * vectors (4 real floats, 8 real PCM16, 2 complex floats, 4 complex PCM16); for an output base
+ * that is not 16-byte aligned, out_stride == 0, out_stride % 4 != 0 or out_stride above 2^32 - 4;
+ * for nout_cap > out_stride; for nstreams * nchannels above 2^31 - 1.  Asynchronous on `stream`;
+ * it allocates nothing and synchronises nothing.  Whatever the arguments hold, nothing outside
+ * nstreams * stream_stride input elements is read and nothing outside the two output arrays is
+ * written. */
+#define MIFSK_CHANNEL_COMPLEX	1u	/* rows are interleaved I, Q */
+
+typedef struct mifsk_channel_params {
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16 (the scalars)        */
+    uint32_t		flags;		/* MIFSK_CHANNEL_COMPLEX                                */
+    uint32_t		phase_steps;	/* P: 1 .. 2^20                                         */
+    uint32_t		ntaps;		/* T: 1 .. 4096                                         */
+    const float		*taps;		/* [ntaps], host                                        */
+    uint32_t		decim;		/* D: 1 .. 65535                                        */
+    uint32_t		nchannels;	/* K: 1 .. 4096, K * T <= 2^22                          */
+    const int32_t	*centres;	/* [nchannels], host; |centre| < P, in steps of fs_in/P */
+    int32_t		out_centre;	/* r, same unit                                         */
+} mifsk_channel_params;			/* 48 bytes */
+
+typedef struct mifsk_channel_plan mifsk_channel_plan;
+
+typedef struct mifsk_channel_io {
+    const void		*d_samples;	/* nstreams rows of the plan's kind                     */
+    size_t		stream_stride;	/* elements between rows (16-byte aligned rows)         */
+    const uint32_t	*d_nsamples;	/* elements per stream; NULL -> all = nsamples          */
+    uint32_t		nsamples;
+    int			nstreams;
+    float		*d_rows;	/* [nstreams * nchannels][out_stride]                   */
+    size_t		out_stride;	/* floats between output rows, % 4 == 0                 */
+    uint32_t		nout_cap;	/* outputs per row at most, <= out_stride               */
+    uint32_t		*d_nout;	/* [nstreams * nchannels]                               */
+} mifsk_channel_io;			/* 64 bytes */
+
+int  mifsk_channel_plan_create( mifsk_ctx *ctx, const mifsk_channel_params *params, mifsk_channel_plan **out );
+void mifsk_channel_plan_destroy( mifsk_channel_plan *plan );
+int  mifsk_channelize_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream );
+/* host only, no context: channel k's G as the plan makes it, [ntaps][2] doubles.  -EINVAL for what
+ * mifsk_channel_plan_create refuses of params, for k >= nchannels or a NULL g_out. */
+int  mifsk_channel_table( const mifsk_channel_params *params, uint32_t k, double *g_out );
+/* host only: ntaps Hamming-windowed sinc taps, 2 fc/fs sinc(2 fc/fs (t - (T-1)/2)) (0.54 - 0.46
+ * cos(2 pi t / (T-1))) in double, scaled so that they sum to `gain`, each rounded to float once;
+ * ntaps == 1 gives {gain}.  -EINVAL for ntaps outside 1 .. 4096, a NULL out, or a cutoff or rate
+ * that is not positive and finite. */
+int  mifsk_channel_taps( uint32_t ntaps, double cutoff_hz, double sample_rate, double gain, float *out );
+
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 
 /* Streams are independent: device k of `world` owns the contiguous, balanced

@@ -19,7 +19,8 @@ from ._lib import ModemArgs, RxConfig  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
-           "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones"]
+           "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones",
+           "channel_taps", "ChannelPlan", "channelize"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -535,6 +536,139 @@ def carrier_survey(ctx, cfg, samples, nsamples=None, window=None, hop=None, firs
     if rc != 0:
         raise RuntimeError("mifsk_detect_carrier_batch failed: %d" % rc)
     out["window"], out["hop"] = window, hop
+    return out
+
+
+def channel_taps(ntaps, cutoff, sample_rate, gain=1.0):
+    """mifsk_channel_taps: `ntaps` Hamming-windowed sinc taps with a cutoff of `cutoff` Hz at
+    `sample_rate`, scaled to sum to `gain`, as a float32 numpy array (a real input wants gain 2)."""
+    out = np.empty(int(ntaps), np.float32)
+    rc = _lib.load().mifsk_channel_taps(int(ntaps), float(cutoff), float(sample_rate), float(gain), out.ctypes.data)
+    if rc != 0:
+        raise ValueError("mifsk_channel_taps failed: %d" % rc)
+    return out
+
+
+def _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16):
+    """(mifsk_channel_params, the arrays it points to)"""
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    centres = np.ascontiguousarray(centres, np.int32).reshape(-1)
+    p = _lib.ChannelParams()
+    p.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    p.flags = _lib.CHANNEL_COMPLEX if complex_input else 0
+    p.phase_steps, p.ntaps, p.taps = int(phase_steps), taps.size, taps.ctypes.data
+    p.decim, p.nchannels, p.centres = int(decim), centres.size, centres.ctypes.data
+    p.out_centre = int(out_centre)
+    return p, (taps, centres)
+
+
+def channel_table(taps, centres, k, phase_steps):
+    """mifsk_channel_table: channel k's G as a plan makes it, float64 [ntaps, 2] (host only)."""
+    p, _keep = _channel_params(taps, 1, centres, 0, phase_steps, False, False)
+    g = np.empty((p.ntaps, 2), np.float64)
+    rc = _lib.load().mifsk_channel_table(C.byref(p), int(k), g.ctypes.data)
+    if rc != 0:
+        raise ValueError("mifsk_channel_table failed: %d" % rc)
+    return g
+
+
+class ChannelPlan:
+    """mifsk_channel_plan: the tables of a channelizer on ctx's device.
+
+    taps       : float32 filter taps (channel_taps), 1 .. 4096
+    decim      : output m is the window that starts at input element m * decim
+    centres    : the channels' centres in steps of fs_in / phase_steps Hz, negative allowed
+    out_centre : where every channel is moved to, same unit (real rows out)
+    complex_input: rows are interleaved I, Q; s16: the scalars are PCM16"""
+
+    def __init__(self, ctx, taps, decim, centres, out_centre, phase_steps, complex_input=False, s16=False):
+        self._lib = _lib.load()
+        p, _keep = _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16)
+        h = C.c_void_p()
+        rc = self._lib.mifsk_channel_plan_create(ctx.handle, C.byref(p), C.byref(h))
+        if rc != 0:
+            raise (ValueError if rc == -22 else RuntimeError)("mifsk_channel_plan_create failed: %d" % rc)
+        self.handle = h
+        self.ctx = ctx                      # the plan must not outlive its context
+        self.ntaps, self.decim, self.nchannels = p.ntaps, p.decim, p.nchannels
+        self.complex_input, self.s16 = bool(complex_input), bool(s16)
+
+    def close(self):
+        if self.handle:
+            self._lib.mifsk_channel_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
+    """mifsk_channelize_batch: every channel of every row as a row demod_batch takes.
+
+    samples : CUDA tensor [nstreams, stride] (or 1-D for one stream) of the plan's kind: float32 or
+              int16 (PCM16) for real rows; for complex rows complex64, or float32 / int16 with a last
+              dimension of 2 (I, Q).  Rows are 16-byte aligned and a whole number of 16-byte vectors apart.
+    nsamples: optional torch.int32/uint32 CUDA tensor [nstreams] of elements; default: the rows' width
+    nout_cap: outputs per row at most (None: what a full row gives, at least 4, rounded up to 4)
+    out     : a dict a former call with the same shapes returned, to reuse its tensors
+    Returns {"rows": float32 [nstreams * nchannels, out_stride], "nsamples": int32 [nstreams * nchannels]}:
+    row s * nchannels + k is channel k of stream s, zero behind its count.  Allocated on the launch
+    stream.  No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda
+    if plan.complex_input:
+        if samples.dtype == torch.complex64:
+            samples = torch.view_as_real(samples)
+        assert samples.shape[-1] == 2 and samples.stride(-1) == 1, "complex rows are interleaved I, Q"
+        if samples.dim() == 2:
+            samples = samples[None]
+        assert samples.dim() == 3 and samples.stride(1) == 2
+        nstreams, width = samples.shape[0], samples.shape[1]
+        row_stride = samples.stride(0) // 2 if nstreams > 1 else int(width)
+        assert nstreams == 1 or samples.stride(0) % 2 == 0
+    else:
+        if samples.dim() == 1:
+            samples = samples[None, :]
+        assert samples.dim() == 2 and samples.stride(1) == 1
+        nstreams, width = samples.shape
+        row_stride = samples.stride(0) if nstreams > 1 else int(width)
+    assert samples.dtype == (torch.int16 if plan.s16 else torch.float32), "the rows are not of the plan's kind"
+    vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_input else 1))
+    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d elements" % vec
+    _check_nsamples(torch, nsamples, nstreams)
+    nrows = nstreams * plan.nchannels
+    if out is None:
+        full = carrier_windows(width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap)
+        out_stride = max(4, (full + 3) // 4 * 4)
+        with _on(torch, stream):
+            out = {"rows": torch.empty((nrows, out_stride), dtype=torch.float32, device=samples.device),
+                   "nsamples": torch.empty((nrows,), dtype=torch.int32, device=samples.device)}
+        if stream is not None:
+            cur = torch.cuda.current_stream()       # (see _torch_outputs)
+            for t in out.values():
+                t.record_stream(cur)
+    else:
+        assert out["rows"].dim() == 2 and out["rows"].shape[0] == nrows and out["rows"].is_contiguous()
+        assert out["rows"].dtype == torch.float32 and out["nsamples"].shape == (nrows,)
+        assert out["nsamples"].dtype == torch.int32 and out["nsamples"].is_contiguous()
+    out_stride = out["rows"].shape[1]
+    io = _lib.ChannelIO()
+    io.d_samples = samples.data_ptr()
+    io.stream_stride = row_stride
+    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
+    io.nsamples = int(width)
+    io.nstreams = nstreams
+    io.d_rows = out["rows"].data_ptr()
+    io.out_stride = out_stride
+    io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
+    io.d_nout = out["nsamples"].data_ptr()
+    rc = lib.mifsk_channelize_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_channelize_batch failed: %d" % rc)
     return out
 
 

@@ -260,7 +260,24 @@ class CarrierIO(C.Structure):
                 ("d_spectrum", C.c_void_p)]
 
 
+CHANNEL_COMPLEX = 1
+
+
+class ChannelParams(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("phase_steps", C.c_uint32), ("ntaps", C.c_uint32),
+                ("taps", C.c_void_p), ("decim", C.c_uint32), ("nchannels", C.c_uint32), ("centres", C.c_void_p),
+                ("out_centre", C.c_int32)]
+
+
+class ChannelIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("d_rows", C.c_void_p),
+                ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
+assert C.sizeof(ChannelParams) == 48 and ChannelParams.centres.offset == 32
+assert C.sizeof(ChannelIO) == 64 and ChannelIO.d_rows.offset == 32 and ChannelIO.d_nout.offset == 56
 assert C.sizeof(CarrierIO) == 88 and CarrierIO.first.offset == 40 and CarrierIO.d_band.offset == 64
 assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
 assert C.sizeof(SessionInfo) == 56 and SessionInfo.h2d_bytes_last.offset == 24
@@ -299,6 +316,8 @@ EXPORTS = [
     "mifsk_session_feed_ex", "mifsk_session_feed_device", "mifsk_session_info_get",
     "mifsk_frame_softbits",
     "mifsk_detect_carrier_batch", "mifsk_carrier_windows", "mifsk_carrier_tones",
+    "mifsk_channel_plan_create", "mifsk_channel_plan_destroy", "mifsk_channelize_batch",
+    "mifsk_channel_table", "mifsk_channel_taps",
 ]
 
 _lib = None
@@ -531,5 +550,15 @@ def load():
     lib.mifsk_carrier_tones.restype = C.c_int
     lib.mifsk_carrier_tones.argtypes = [C.POINTER(RxConfig), C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
                                         C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.mifsk_channel_plan_create.restype = C.c_int
+    lib.mifsk_channel_plan_create.argtypes = [C.c_void_p, C.POINTER(ChannelParams), C.POINTER(C.c_void_p)]
+    lib.mifsk_channel_plan_destroy.restype = None
+    lib.mifsk_channel_plan_destroy.argtypes = [C.c_void_p]
+    lib.mifsk_channelize_batch.restype = C.c_int
+    lib.mifsk_channelize_batch.argtypes = [C.c_void_p, C.POINTER(ChannelIO), C.c_void_p]
+    lib.mifsk_channel_table.restype = C.c_int
+    lib.mifsk_channel_table.argtypes = [C.POINTER(ChannelParams), C.c_uint32, C.c_void_p]
+    lib.mifsk_channel_taps.restype = C.c_int
+    lib.mifsk_channel_taps.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p]
     _lib = lib
     return lib

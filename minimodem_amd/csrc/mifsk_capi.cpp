@@ -69,6 +69,8 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_time_split_stats);
     MIFSK_SIZEOF(mifsk_softbits_io);
     MIFSK_SIZEOF(mifsk_carrier_io);
+    MIFSK_SIZEOF(mifsk_channel_params);
+    MIFSK_SIZEOF(mifsk_channel_io);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;

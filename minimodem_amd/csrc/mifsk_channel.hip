@@ -1,0 +1,471 @@
+// mifsk_channel.hip -- the channelizer (include/mifsk.h): mifsk_channel_plan_create / _destroy,
+// mifsk_channelize_batch, and the host helpers mifsk_channel_table and mifsk_channel_taps.
+//
+// One output sample is a window sum of carrier_survey_kernel's kind -- the complex sum kept, the
+// rectangle replaced by a filter's taps, then rotated to the output tone -- so the kernel is laid
+// out the same way around what feeds the FP64 pipe:
+//   * a lane owns NC channels (c, c + cw) and kChO outputs: 2 * NC * kChO independent accumulator
+//     chains.  G[k][t] does not depend on the output: ONE table read per channel and tap feeds
+//     2 * kChO FMAs (4 * kChO with complex rows); a sample is the same for every channel: ONE
+//     read per output and tap feeds 2 * NC (4 * NC) FMAs.
+//   * the 64 lanes of a wave are cw channel lanes x 64 / cw groups of outputs, cw the power of two
+//     that holds the channels (at most 64): three channels keep 64 lanes busy.  The four waves of
+//     a workgroup take further groups of outputs of the same channels, channel blocks beyond
+//     64 * NC are workgroups of their own (grid z).  A lane's outputs are NOG apart (NOG: the
+//     workgroup's groups of outputs), so lanes of neighbouring groups read neighbouring samples
+//     and, with few channel lanes, write neighbouring outputs; with 64 channel lanes every lane
+//     of a wave stores to a row of its own (one store per T taps of work).
+//   * G is uploaded transposed ([t][k]) and staged into LDS in tiles of tt taps as [t][NC][cw]:
+//     the lanes of a wave read consecutive 16-byte entries, lanes of one channel the same one.
+//   * the outputs of a chunk overlap whenever D < T: the chunk's span of samples for a tile of
+//     taps, (outputs - 1) * D + tt, is staged once, widened to double (PCM16 converted on the way,
+//     in float).  With D >= tt the tiles of the outputs do not overlap, and each output's tt
+//     samples are staged at a stride of tt + 1 (odd: the lanes' reads fall on different banks).
+//     Either way output ml of the chunk reads xs[ml * ss + e].
+//   * W is read once per output and channel from memory (L2); the phase index walks from output to
+//     output by additions mod P.
+// The sums are the definition's in its order (re, im from 0.0, t ascending, one fma each).  No f64
+// MFMA: its internal summation is not that chain.  The kernel reads nothing it wrote, so it needs
+// no fences; the outputs are plain vector stores.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include <cerrno>
+#include <cmath>
+#include <cstdint>
+#include <memory>
+#include <new>
+#include <type_traits>
+
+#include "mifsk.h"
+#include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
+
+namespace mifsk {
+
+constexpr int kChO = 8;					// outputs per lane
+constexpr uint32_t kChWaves = 4u;			// waves of a workgroup
+constexpr uint32_t kChTile = 64u;			// taps staged at a time, at most
+constexpr uint32_t kChLdsTwo = 64u * 1024u;		// two workgroups per CU up to here
+constexpr uint32_t kChLdsMax = 144u * 1024u;
+constexpr uint32_t kChMaxRows = 65535u;			// streams per launch (grid.y)
+constexpr uint32_t kChMaxP = 1u << 20, kChMaxT = 4096u, kChMaxK = 4096u, kChMaxD = 65535u;
+constexpr uint64_t kChMaxKT = 1ull << 22;
+
+struct ChannelArgs {
+    const double2	*gt;		// G transposed, [T][K]
+    const double2	*w;		// [P]: cos, sin
+    const uint32_t	*dq;		// [K]: (r - q[k]) mod P
+    const void		*x;
+    size_t		stride;		// elements
+    const uint32_t	*nsamples_v;
+    uint32_t		nsamples_u;
+    uint32_t		T, D, K, P;
+    uint32_t		s0;		// first stream of this launch
+    uint32_t		cwshift;	// cw = 1 << cwshift channel lanes of a wave
+    uint32_t		tt;		// taps per tile, a power of two
+    uint32_t		ss;		// LDS samples between neighbouring outputs: D, or tt + 1
+    float		*rows;
+    size_t		out_stride;
+    uint32_t		nout_cap;
+    uint32_t		*nout;
+};
+
+// element `at` of a row as the definition widens it
+template <bool CX, bool S16>
+__device__ __forceinline__ auto channel_sample( const void *row, uint64_t at )
+{
+    if constexpr ( CX ) {
+	if constexpr ( S16 ) {
+	    const short2 v = reinterpret_cast<const short2 *>(row)[at];
+	    return double2{(double)( (float)v.x / 32768.0f ), (double)( (float)v.y / 32768.0f )};
+	} else {
+	    const float2 v = reinterpret_cast<const float2 *>(row)[at];
+	    return double2{(double)v.x, (double)v.y};
+	}
+    } else {
+	if constexpr ( S16 )
+	    return (double)( (float)reinterpret_cast<const int16_t *>(row)[at] / 32768.0f );
+	else
+	    return (double)reinterpret_cast<const float *>(row)[at];
+    }
+}
+
+// NC: channels per lane.  CX: complex rows.  S16: PCM16 scalars.
+template <int NC, bool CX, bool S16>
+__global__ __launch_bounds__(256)
+void channelize_kernel( const ChannelArgs A )
+{
+    using XT = std::conditional_t<CX, double2, double>;
+    extern __shared__ double2 ch_lds[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t T = A.T, D = A.D, K = A.K, P = A.P, tt = A.tt, ss = A.ss;
+    const uint32_t cw = 1u << A.cwshift, cshift = A.cwshift + ( NC == 2 ? 1u : 0u ), C = 1u << cshift;
+    const uint32_t ogw = 64u >> A.cwshift;			// groups of outputs in a wave
+    const uint32_t NOG = kChWaves * ogw, OB = NOG * (uint32_t)kChO;	// ... and outputs in a chunk
+    const uint32_t cl = lane & ( cw - 1u ), ol = wave * ogw + ( lane >> A.cwshift );
+    // LDS: tt * C table entries [t][NC][cw] | (OB - 1) * ss + tt samples
+    double2 *gl = ch_lds;
+    XT *xs = reinterpret_cast<XT *>(ch_lds + (size_t)tt * C);
+    const uint32_t R = ( OB - 1u ) * ss + tt;
+
+    const uint32_t s = A.s0 + blockIdx.y, k0 = blockIdx.z * C;
+    const uint32_t n_row = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
+    const uint32_t nv = n_row < A.stride ? n_row : (uint32_t)A.stride;	// elements the row holds
+    const char *row = reinterpret_cast<const char *>(A.x)
+	+ (size_t)s * A.stride * ( ( S16 ? 2u : 4u ) * ( CX ? 2u : 1u ) );
+    // outputs that exist, of those the rows have room for: output m < cnt reads x[m D + t], t < T,
+    // all below nv
+    const uint32_t fit = nv >= T ? ( nv - T ) / D + 1u : 0u;
+    const uint32_t cnt = fit < A.nout_cap ? fit : A.nout_cap;
+    const uint64_t m0 = (uint64_t)blockIdx.x * OB;
+    if ( blockIdx.x == 0u )
+	for ( uint32_t c = tid; c < C; c += blockDim.x )
+	    if ( k0 + c < K )
+		A.nout[(size_t)s * K + k0 + c] = cnt;
+
+    uint32_t k[NC];
+    double re[kChO][NC], im[kChO][NC];
+#pragma unroll
+    for ( int j = 0; j < NC; j++ ) {
+	k[j] = k0 + (uint32_t)j * cw + cl;
+#pragma unroll
+	for ( int o = 0; o < kChO; o++ ) {
+	    re[o][j] = 0.0;
+	    im[o][j] = 0.0;
+	}
+    }
+    if ( m0 < cnt ) {						// (the whole workgroup)
+	const XT *xp = xs + ol * ss;
+	const uint32_t os = NOG * ss;				// from one of the lane's outputs to the next
+	for ( uint32_t t0 = 0; t0 < T; t0 += tt ) {
+	    const uint32_t tl = T - t0 < tt ? T - t0 : tt;
+	    __syncthreads();					// the tile before has been read
+	    for ( uint32_t i = tid; i < tt * C; i += blockDim.x ) {
+		const uint32_t e = i >> cshift, kk = k0 + ( i & ( C - 1u ) );
+		double2 g = {0.0, 0.0};
+		if ( e < tl && kk < K )
+		    g = A.gt[(size_t)( t0 + e ) * K + kk];
+		gl[i] = g;
+	    }
+	    for ( uint32_t i = tid; i < R; i += blockDim.x ) {
+		uint64_t at;
+		bool in = true;
+		if ( D < tt )					// one span: output ml's tile starts at ml * D
+		    at = m0 * D + t0 + i;
+		else {						// a tile per output, ss = tt + 1 apart
+		    const uint32_t ml = i / ss, e = i - ml * ss;
+		    at = ( m0 + ml ) * D + t0 + e;
+		    in = e < tt;
+		}
+		XT v = {};
+		if ( in && at < nv )
+		    v = channel_sample<CX, S16>(row, at);
+		xs[i] = v;
+	    }
+	    __syncthreads();
+#pragma unroll 2
+	    for ( uint32_t e = 0; e < tl; e++ ) {
+		double2 g[NC];
+#pragma unroll
+		for ( int j = 0; j < NC; j++ )
+		    g[j] = gl[( e * (uint32_t)NC + (uint32_t)j ) * cw + cl];
+#pragma unroll
+		for ( int o = 0; o < kChO; o++ ) {
+		    const XT x = xp[(uint32_t)o * os + e];
+#pragma unroll
+		    for ( int j = 0; j < NC; j++ ) {
+			if constexpr ( CX ) {
+			    re[o][j] = fma(x.x, g[j].x, re[o][j]);
+			    re[o][j] = fma(-x.y, g[j].y, re[o][j]);
+			    im[o][j] = fma(x.x, g[j].y, im[o][j]);
+			    im[o][j] = fma(x.y, g[j].x, im[o][j]);
+			} else {
+			    re[o][j] = fma(x, g[j].x, re[o][j]);
+			    im[o][j] = fma(x, g[j].y, im[o][j]);
+			}
+		    }
+		}
+	    }
+	}
+    }
+    // p = (dq * ((m D) mod P)) mod P for m = m0 + ol + o NOG: from o to o + 1 it grows by
+    // (dq * ((NOG D) mod P)) mod P
+    const uint32_t md0 = (uint32_t)( ( ( m0 + ol ) * D ) % P ), mdstep = (uint32_t)( ( (uint64_t)NOG * D ) % P );
+#pragma unroll
+    for ( int j = 0; j < NC; j++ ) {
+	if ( k[j] >= K )
+	    continue;
+	const uint32_t dq = A.dq[k[j]];
+	uint32_t p = (uint32_t)( ( (uint64_t)dq * md0 ) % P );
+	const uint32_t pstep = (uint32_t)( ( (uint64_t)dq * mdstep ) % P );
+	float *out = A.rows + ( (size_t)s * K + k[j] ) * A.out_stride;
+#pragma unroll
+	for ( int o = 0; o < kChO; o++ ) {
+	    const uint64_t m = m0 + ol + (uint32_t)o * NOG;
+	    if ( m < A.out_stride ) {
+		float v = 0.0f;
+		if ( m < cnt ) {
+		    const double2 w = A.w[p];
+		    v = (float)fma(re[o][j], w.x, -( im[o][j] * w.y ));
+		}
+		out[m] = v;
+	    }
+	    p += pstep;
+	    if ( p >= P )
+		p -= P;
+	}
+    }
+}
+
+namespace {
+
+// what both table makers refuse of params
+int channel_check_params( const mifsk_channel_params *p )
+{
+    if ( !p )
+	return -EINVAL;
+    if ( ( p->kind != MIFSK_FEED_F32 && p->kind != MIFSK_FEED_S16 ) || ( p->flags & ~MIFSK_CHANNEL_COMPLEX ) )
+	return -EINVAL;
+    if ( p->phase_steps == 0 || p->phase_steps > kChMaxP )
+	return -EINVAL;
+    if ( p->ntaps == 0 || p->ntaps > kChMaxT || !p->taps )
+	return -EINVAL;
+    if ( p->decim == 0 || p->decim > kChMaxD )
+	return -EINVAL;
+    if ( p->nchannels == 0 || p->nchannels > kChMaxK || !p->centres )
+	return -EINVAL;
+    if ( (uint64_t)p->nchannels * p->ntaps > kChMaxKT )
+	return -EINVAL;
+    for ( uint32_t k = 0; k < p->nchannels; k++ ) {
+	const int64_t q = p->centres[k];
+	if ( q >= (int64_t)p->phase_steps || -q >= (int64_t)p->phase_steps )
+	    return -EINVAL;
+    }
+    return 0;
+}
+
+// a centre reduced to [0, P)
+inline int64_t channel_reduce( int64_t q, int64_t P )
+{
+    q %= P;
+    return q < 0 ? q + P : q;
+}
+
+constexpr double kTwoPi = 6.283185307179586476925286766559;
+
+// channel k's G, tap t at g[t * gstride]: THE table code, for the plan and mifsk_channel_table
+void channel_table( const mifsk_channel_params *p, uint32_t k, double2 *g, size_t gstride )
+{
+    const int64_t P = p->phase_steps, q = channel_reduce(p->centres[k], P);
+    for ( uint32_t t = 0; t < p->ntaps; t++ ) {
+	const int64_t idx = ( q * (int64_t)t ) % P;
+	double s, c;
+	sincos(kTwoPi * (double)idx / (double)P, &s, &c);
+	const double h = (double)p->taps[t];
+	g[(size_t)t * gstride] = double2{h * c, -( h * s )};
+    }
+}
+
+template <int NC, bool CX, bool S16>
+int launch_channel( const ChannelArgs &A, dim3 grid, size_t lds, hipStream_t st )
+{
+    if ( lds > 48u * 1024u
+	    && hipFuncSetAttribute(reinterpret_cast<const void *>(&channelize_kernel<NC, CX, S16>),
+				   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess )
+	return -EIO;
+    hipLaunchKernelGGL(( channelize_kernel<NC, CX, S16> ), grid, dim3(64u * kChWaves), lds, st, A);
+    return 0;
+}
+
+template <int NC>
+int launch_channel_kind( bool cx, bool s16, const ChannelArgs &A, dim3 grid, size_t lds, hipStream_t st )
+{
+    if ( cx )
+	return s16 ? launch_channel<NC, true, true>(A, grid, lds, st) : launch_channel<NC, true, false>(A, grid, lds, st);
+    return s16 ? launch_channel<NC, false, true>(A, grid, lds, st) : launch_channel<NC, false, false>(A, grid, lds, st);
+}
+
+} // namespace
+} // namespace mifsk
+
+struct mifsk_channel_plan {
+    int				device;
+    bool			cx, s16;
+    uint32_t			P, T, D, K;
+    mifsk::DevMem<double2>	gt, w;
+    mifsk::DevMem<uint32_t>	dq;
+};
+
+extern "C" int mifsk_channel_table( const mifsk_channel_params *params, uint32_t k, double *g_out )
+{
+    if ( int rc = mifsk::channel_check_params(params) )
+	return rc;
+    if ( k >= params->nchannels || !g_out )
+	return -EINVAL;
+    static_assert(sizeof(double2) == 2 * sizeof(double), "G is [ntaps][2] doubles");
+    mifsk::channel_table(params, k, reinterpret_cast<double2 *>(g_out), 1);
+    return 0;
+}
+
+extern "C" int mifsk_channel_taps( uint32_t ntaps, double cutoff_hz, double sample_rate, double gain, float *out )
+{
+    if ( ntaps == 0 || ntaps > mifsk::kChMaxT || !out )
+	return -EINVAL;
+    if ( !( cutoff_hz > 0.0 ) || !( sample_rate > 0.0 ) || !std::isfinite(cutoff_hz) || !std::isfinite(sample_rate) )
+	return -EINVAL;
+    if ( ntaps == 1 ) {
+	out[0] = (float)gain;
+	return 0;
+    }
+    double h[mifsk::kChMaxT];
+    const double f = 2.0 * cutoff_hz / sample_rate, mid = (double)( ntaps - 1u ) / 2.0;
+    double sum = 0.0;
+    for ( uint32_t t = 0; t < ntaps; t++ ) {
+	const double a = M_PI * ( f * ( (double)t - mid ) );
+	const double sinc = a == 0.0 ? 1.0 : sin(a) / a;
+	h[t] = f * sinc * ( 0.54 - 0.46 * cos(mifsk::kTwoPi * (double)t / (double)( ntaps - 1u )) );
+	sum += h[t];
+    }
+    for ( uint32_t t = 0; t < ntaps; t++ )
+	out[t] = (float)( h[t] * ( gain / sum ) );
+    return 0;
+}
+
+extern "C" int mifsk_channel_plan_create( mifsk_ctx *ctx, const mifsk_channel_params *params, mifsk_channel_plan **out )
+{
+    using namespace mifsk;
+    if ( !ctx || !params || !out )
+	return -EINVAL;
+    if ( int rc = channel_check_params(params) )
+	return rc;
+    const uint32_t P = params->phase_steps, T = params->ntaps, K = params->nchannels;
+    const size_t ngt = (size_t)T * K;
+    const std::unique_ptr<double2[]> gt(new (std::nothrow) double2[ngt]), w(new (std::nothrow) double2[P]);
+    const std::unique_ptr<uint32_t[]> dq(new (std::nothrow) uint32_t[K]);
+    if ( !gt || !w || !dq )
+	return -ENOMEM;
+    for ( uint32_t k = 0; k < K; k++ ) {
+	channel_table(params, k, gt.get() + k, K);
+	dq[k] = (uint32_t)channel_reduce((int64_t)params->out_centre - channel_reduce(params->centres[k], P), P);
+    }
+    for ( uint32_t p = 0; p < P; p++ ) {
+	double s, c;
+	sincos(kTwoPi * (double)p / (double)P, &s, &c);
+	w[p] = double2{c, s};
+    }
+    mifsk_channel_plan *plan = new (std::nothrow) mifsk_channel_plan;
+    if ( !plan )
+	return -ENOMEM;
+    plan->device = ctx->device;
+    plan->cx = ( params->flags & MIFSK_CHANNEL_COMPLEX ) != 0;
+    plan->s16 = params->kind == MIFSK_FEED_S16;
+    plan->P = P;
+    plan->T = T;
+    plan->D = params->decim;
+    plan->K = K;
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : -EIO;
+    if ( rc == 0 ) rc = plan->gt.alloc(ngt);
+    if ( rc == 0 ) rc = plan->w.alloc(P);
+    if ( rc == 0 ) rc = plan->dq.alloc(K);
+    if ( rc == 0
+	    && ( hipMemcpy(plan->gt.p, gt.get(), ngt * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
+		|| hipMemcpy(plan->w.p, w.get(), P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
+		|| hipMemcpy(plan->dq.p, dq.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ) )
+	rc = -EIO;
+    if ( rc ) {
+	delete plan;
+	return rc;
+    }
+    *out = plan;
+    return 0;
+}
+
+extern "C" void mifsk_channel_plan_destroy( mifsk_channel_plan *plan )
+{
+    if ( !plan )
+	return;
+    (void)hipSetDevice(plan->device);
+    (void)hipDeviceSynchronize();		// no kernel reads the tables any more
+    delete plan;
+}
+
+extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream )
+{
+    using namespace mifsk;
+    if ( !plan || !io || !io->d_samples || !io->d_rows || !io->d_nout )
+	return -EINVAL;
+    if ( io->nstreams <= 0 )
+	return -EINVAL;
+    const uint32_t vec = 16u / ( ( plan->s16 ? 2u : 4u ) * ( plan->cx ? 2u : 1u ) );	// elements of 16 bytes
+    if ( ( (uintptr_t)io->d_samples & 15u ) || io->stream_stride % vec != 0 )
+	return -EINVAL;
+    if ( ( (uintptr_t)io->d_rows & 15u ) || io->out_stride == 0 || io->out_stride % 4u != 0
+	    || io->out_stride > 0xFFFFFFFCull )
+	return -EINVAL;
+    if ( io->nout_cap > io->out_stride )
+	return -EINVAL;
+    if ( (uint64_t)io->nstreams * plan->K > 0x7FFFFFFFull )
+	return -EINVAL;
+
+    ChannelArgs A = {};
+    A.gt = plan->gt.p;
+    A.w = plan->w.p;
+    A.dq = plan->dq.p;
+    A.x = io->d_samples;
+    A.stride = io->stream_stride;
+    A.nsamples_v = io->d_nsamples;
+    A.nsamples_u = io->nsamples;
+    A.T = plan->T;
+    A.D = plan->D;
+    A.K = plan->K;
+    A.P = plan->P;
+    A.rows = io->d_rows;
+    A.out_stride = io->out_stride;
+    A.nout_cap = io->nout_cap;
+    A.nout = io->d_nout;
+
+    // two channels per lane as soon as there are two; cw channel lanes, the rest of a wave's lanes
+    // are groups of outputs
+    const uint32_t nc = plan->K > 1u ? 2u : 1u;
+    const uint32_t ncl = ( plan->K + nc - 1u ) / nc;
+    while ( ( 1u << A.cwshift ) < ncl && A.cwshift < 6u )
+	A.cwshift++;
+    const uint32_t C = ( 1u << A.cwshift ) * nc;
+    const uint32_t OB = kChWaves * ( 64u >> A.cwshift ) * (uint32_t)kChO;
+    // the tile of taps: the largest power of two with which table and samples fit, two workgroups
+    // per CU down to 16 taps
+    const size_t esz = plan->cx ? 16u : 8u;
+    auto lds_of = [&]( uint32_t tt ) {
+	const uint32_t ss = A.D < tt ? A.D : tt + 1u;
+	return (size_t)tt * C * sizeof(double2) + ( (size_t)( OB - 1u ) * ss + tt ) * esz;
+    };
+    uint32_t tt = kChTile;
+    while ( tt / 2u >= A.T )
+	tt /= 2u;
+    uint32_t two = tt;
+    while ( two > 16u && lds_of(two) > kChLdsTwo )
+	two /= 2u;
+    if ( lds_of(two) <= kChLdsTwo )
+	tt = two;
+    while ( tt > 1u && lds_of(tt) > kChLdsMax )
+	tt /= 2u;
+    A.tt = tt;
+    A.ss = A.D < tt ? A.D : tt + 1u;
+    const size_t lds = lds_of(tt);
+
+    if ( hipSetDevice(plan->device) != hipSuccess )
+	return -EIO;
+    const uint32_t nchunks = (uint32_t)( ( io->out_stride + OB - 1u ) / OB );
+    const uint32_t gz = ( plan->K + C - 1u ) / C;
+    const hipStream_t st = (hipStream_t)stream;
+    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kChMaxRows ) {
+	const uint32_t rows = (uint32_t)io->nstreams - s0 < kChMaxRows ? (uint32_t)io->nstreams - s0 : kChMaxRows;
+	A.s0 = s0;
+	const dim3 grid(nchunks, rows, gz);
+	const int rc = nc == 2u ? launch_channel_kind<2>(plan->cx, plan->s16, A, grid, lds, st)
+				: launch_channel_kind<1>(plan->cx, plan->s16, A, grid, lds, st);
+	if ( rc )
+	    return rc;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
