@@ -1113,6 +1113,101 @@ int  mifsk_channel_table( const mifsk_channel_params *params, uint32_t k, double
  * that is not positive and finite. */
 int  mifsk_channel_taps( uint32_t ntaps, double cutoff_hz, double sample_rate, double gain, float *out );
 
+/* ---- multiplexer: a batch of transmitted rows on the carriers of one capture ---- */
+
+/* The channelizer's mirror on the transmit side: interpolate -> analytic signal -> move to the
+ * channel's carrier -> sum, for nchannels baseband rows per stream.  Input row s * nchannels + k
+ * is channel k of stream s: float32, exactly the d_out / out_stride / d_nsamples_out that
+ * mifsk_tx_synthesize_batch writes; its valid length is N_k = min(nsamples[s * nchannels + k],
+ * stream_stride) (a length above the stride is legal, as it is there).  The output is one row per
+ * stream at fs_out = L fs_in: real, or -- MIFSK_MUX_COMPLEX -- interleaved I, Q (an element is then
+ * one complex sample), float32 or PCM16 (kind).
+ *   With P = phase_steps, T = ntaps, h = taps, L = interp, q[k] = centres[k] and r = in_centre,
+ * both reduced to [0, P) (a centre is in steps of fs_out / P Hz, negative allowed), the tables are
+ * made on the host in double with the C library (every product rounded once, integers in 64 bits):
+ *   G[t] = ( (double)h[t] * c, (double)h[t] * s ),  (s, c) = sincos(2 pi ((r t) mod P) / P),  t < T
+ *   W[p] = ( cos, sin ) of 2 pi p / P,  p < P
+ * G is ONE table for all channels: the band-pass at the input rows' tone centre r, which keeps the
+ * positive-frequency image of the zero-stuffed row (so h wants a cutoff below r fs_out / P Hz and
+ * r well inside 0 .. fs_in / 2).
+ *   Stream s has M_s = (Nmax_s - 1) L + T outputs (the last sample's whole filter tail), Nmax_s the
+ * largest N_k of its rows; M_s = 0 when Nmax_s = 0; M_s is computed in 64 bits and cut at nout_cap.
+ * Output n: o = oi = 0.0, then for k ascending:
+ *   m = n div L, phi = n mod L, re = im = 0.0
+ *   for j = 0, 1, ... while t = phi + j L < T, with i = m - j:
+ *     if 0 <= i < N_k:  re = fma((double)x_k[i], G[t].re, re);  im = fma((double)x_k[i], G[t].im, im)
+ *     (a term whose i lies outside the row is skipped, not multiplied by zero)
+ *   if gains:  re = re * (double)gains[k];  im = im * (double)gains[k]
+ *   p = (((q[k] - r) mod P) * (n mod P)) mod P,  (C, S) = W[p]
+ *   o = fma(re, C, o);  o = fma(-im, S, o)
+ *   with MIFSK_MUX_COMPLEX also:  oi = fma(re, S, oi);  oi = fma(im, C, oi)
+ * out[n] = (float)o, and (float)oi beside it for complex rows: the sum over the channels, in channel
+ * order, of each row's analytic signal moved from r to q[k].  With L > T the phases phi >= T have no
+ * tap and give re = im = 0.0.  For PCM16 output (kind == MIFSK_FEED_S16) each float v becomes a
+ * 16-bit value by the write conversion of oracle/shim/sndfile_shim.c: t = v * 32767.0f, t > 32767.0f
+ * -> 32767.0f, t < -32768.0f -> -32768.0f, (int16_t)lrintf(t) (round to nearest even); a NaN gives
+ * 0.  Elements from min(M_s, nout_cap) to out_stride are written as zero and d_nout[s] = min(M_s,
+ * nout_cap).  Gain is the taps' business: G keeps one of the L images of one side of the spectrum,
+ * so unit gain for a real output wants taps that sum to 2 L (mifsk_channel_taps(T, fc, fs_out,
+ * 2 L)); a complex output is then the rows' analytic signal, of that same amplitude in I and in
+ * Q.  gains are data (finite or not); NaN and Inf propagate as the arithmetic says.
+ *   The sum over the channels of one output is ONE chain in channel order, and the sum over the
+ * taps one chain in tap order: no f64 MFMA and no split of either over lanes (the reason is the
+ * carrier survey's: a tree is another sum).
+ *   mifsk_mux_plan_create checks, in this order and before any HIP call: -EINVAL for a NULL ctx,
+ * params or out; for a kind that is neither MIFSK_FEED_F32 nor MIFSK_FEED_S16, or flags beyond
+ * MIFSK_MUX_COMPLEX; for phase_steps outside 1 .. 2^20; for ntaps outside 1 .. 4096 or NULL taps;
+ * for interp outside 1 .. 65535; for nchannels outside 1 .. 4096 or NULL centres; for a centre with
+ * |centre| >= phase_steps; for |in_centre| >= phase_steps.  Then it builds G and W and uploads them
+ * once (-ENOMEM, -EIO).  The plan belongs to ctx's device and must be destroyed before the context;
+ * it is read only and may be used from several threads and streams at once.
+ * mifsk_mux_plan_destroy has mifsk_channel_plan_destroy's rule: it SYNCHRONISES THE DEVICE before
+ * it frees the tables.
+ *   mifsk_multiplex_batch checks, in this order and before any HIP call: -EINVAL for a NULL plan,
+ * io, d_samples, d_out or d_nout; for nstreams <= 0; for an input base that is not 16-byte aligned
+ * or a stream_stride that is no multiple of 4; for an output base that is not 16-byte aligned,
+ * out_stride == 0, out_stride not a whole number of 16-byte vectors of the output kind (4 real
+ * floats, 8 real PCM16, 2 complex floats, 4 complex PCM16) or above 2^32 - 8; for nout_cap >
+ * out_stride; for nstreams * nchannels above 2^31 - 1.  Asynchronous on `stream`; it allocates
+ * nothing and synchronises nothing.  Whatever the arguments hold, nothing outside nstreams *
+ * nchannels * stream_stride input floats is read and nothing outside the two output arrays is
+ * written; nothing written is read back, and the outputs are plain vector stores. */
+#define MIFSK_MUX_COMPLEX	1u	/* output rows are interleaved I, Q */
+
+typedef struct mifsk_mux_params {
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16 (the OUTPUT scalars)  */
+    uint32_t		flags;		/* MIFSK_MUX_COMPLEX                                     */
+    uint32_t		phase_steps;	/* P: 1 .. 2^20                                          */
+    uint32_t		ntaps;		/* T: 1 .. 4096                                          */
+    const float		*taps;		/* [ntaps], host                                         */
+    uint32_t		interp;		/* L: 1 .. 65535                                         */
+    uint32_t		nchannels;	/* K: 1 .. 4096                                          */
+    const int32_t	*centres;	/* [nchannels], host; |centre| < P, in steps of fs_out/P */
+    int32_t		in_centre;	/* r, same unit; |r| < P                                 */
+    const float		*gains;		/* [nchannels], host, or NULL: no gain step              */
+} mifsk_mux_params;			/* 56 bytes */
+
+typedef struct mifsk_mux_plan mifsk_mux_plan;
+
+typedef struct mifsk_mux_io {
+    const float		*d_samples;	/* [nstreams * nchannels][stream_stride]                 */
+    size_t		stream_stride;	/* floats between input rows, % 4 == 0                   */
+    const uint32_t	*d_nsamples;	/* [nstreams * nchannels]; NULL -> all = nsamples        */
+    uint32_t		nsamples;
+    int			nstreams;
+    void		*d_out;		/* [nstreams][out_stride] elements of the plan's kind    */
+    size_t		out_stride;	/* elements between output rows, whole 16-byte vectors   */
+    uint32_t		nout_cap;	/* outputs per stream at most, <= out_stride             */
+    uint32_t		*d_nout;	/* [nstreams]                                            */
+} mifsk_mux_io;				/* 64 bytes */
+
+int  mifsk_mux_plan_create( mifsk_ctx *ctx, const mifsk_mux_params *params, mifsk_mux_plan **out );
+void mifsk_mux_plan_destroy( mifsk_mux_plan *plan );
+int  mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream );
+/* host only, no context: G as the plan makes it, [ntaps][2] doubles.  -EINVAL for what
+ * mifsk_mux_plan_create refuses of params, or a NULL g_out. */
+int  mifsk_mux_table( const mifsk_mux_params *params, double *g_out );
+
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 
 /* Streams are independent: device k of `world` owns the contiguous, balanced

@@ -16,11 +16,13 @@ import numpy as np
 
 from . import _lib
 from ._lib import ModemArgs, RxConfig  # noqa: F401
+from ._lib import MUX_COMPLEX, MuxIO, MuxParams  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
            "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones",
-           "channel_taps", "ChannelPlan", "channelize"]
+           "channel_taps", "ChannelPlan", "channelize",
+           "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -669,6 +671,126 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     rc = lib.mifsk_channelize_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_channelize_batch failed: %d" % rc)
+    return out
+
+
+def _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains):
+    """(mifsk_mux_params, the arrays it points to)"""
+    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    centres = np.ascontiguousarray(centres, np.int32).reshape(-1)
+    p = _lib.MuxParams()
+    p.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    p.flags = _lib.MUX_COMPLEX if complex_output else 0
+    p.phase_steps, p.ntaps, p.taps = int(phase_steps), taps.size, taps.ctypes.data
+    p.interp, p.nchannels, p.centres = int(interp), centres.size, centres.ctypes.data
+    p.in_centre = int(in_centre)
+    if gains is not None:
+        gains = np.ascontiguousarray(gains, np.float32).reshape(-1)
+        assert gains.size == centres.size, "one gain per channel"
+        p.gains = gains.ctypes.data
+    return p, (taps, centres, gains)
+
+
+def mux_table(taps, in_centre, phase_steps):
+    """mifsk_mux_table: G as a multiplexer plan makes it, float64 [ntaps, 2] (host only)."""
+    p, _keep = _mux_params(taps, 1, [0], in_centre, phase_steps, False, False, None)
+    g = np.empty((p.ntaps, 2), np.float64)
+    rc = _lib.load().mifsk_mux_table(C.byref(p), g.ctypes.data)
+    if rc != 0:
+        raise ValueError("mifsk_mux_table failed: %d" % rc)
+    return g
+
+
+class MuxPlan:
+    """mifsk_mux_plan: the tables of a multiplexer on ctx's device.
+
+    taps       : float32 filter taps at the OUTPUT rate (channel_taps(T, fc, fs_out, 2 * interp) for
+                 unit gain), 1 .. 4096
+    interp     : output samples per input sample
+    centres    : where each channel goes, in steps of fs_out / phase_steps Hz, negative allowed
+    in_centre  : the input rows' tone centre, same unit: the band the filter keeps
+    complex_output: rows are interleaved I, Q; s16: the scalars are PCM16
+    gains      : None, or one float per channel"""
+
+    def __init__(self, ctx, taps, interp, centres, in_centre, phase_steps, complex_output=False, s16=False,
+                 gains=None):
+        self._lib = _lib.load()
+        p, _keep = _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains)
+        h = C.c_void_p()
+        rc = self._lib.mifsk_mux_plan_create(ctx.handle, C.byref(p), C.byref(h))
+        if rc != 0:
+            raise (ValueError if rc == -22 else RuntimeError)("mifsk_mux_plan_create failed: %d" % rc)
+        self.handle = h
+        self.ctx = ctx                      # the plan must not outlive its context
+        self.ntaps, self.interp, self.nchannels = p.ntaps, p.interp, p.nchannels
+        self.complex_output, self.s16 = bool(complex_output), bool(s16)
+
+    def close(self):
+        if self.handle:
+            self._lib.mifsk_mux_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
+    """mifsk_multiplex_batch: the channels of every stream summed into one wideband row.
+
+    samples : float32 CUDA tensor [nstreams * nchannels, stride], what synthesize_batch returns: row
+              s * nchannels + k is channel k of stream s.  Rows are 16-byte aligned, stride % 4 == 0.
+    nsamples: optional torch.int32/uint32 CUDA tensor [nstreams * nchannels]; default: the rows' width
+    nout_cap: outputs per stream at most (None: what full rows give, (width - 1) * interp + ntaps)
+    out     : a dict a former call with the same shapes returned, to reuse its tensors
+    Returns {"rows": [nstreams, out_stride] (complex plans: [nstreams, out_stride, 2]) float32 or int16,
+    "nsamples": int32 [nstreams]}; a row is zero behind its count.  Allocated on the launch stream.
+    No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert samples.is_cuda and samples.dtype == torch.float32
+    assert samples.dim() == 2 and samples.stride(1) == 1
+    nrows, width = samples.shape
+    K = plan.nchannels
+    assert nrows > 0 and nrows % K == 0, "samples holds nchannels rows per stream"
+    nstreams = nrows // K
+    row_stride = samples.stride(0) if nrows > 1 else int(width)
+    assert nrows > 1 or width % 4 == 0, "a lone row must be padded to a multiple of 4 floats"
+    _check_nsamples(torch, nsamples, nrows)
+    dtype = torch.int16 if plan.s16 else torch.float32
+    vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
+    if out is None:
+        full = (int(width) - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap)
+        out_stride = max(vec, (full + vec - 1) // vec * vec)
+        shape = (nstreams, out_stride, 2) if plan.complex_output else (nstreams, out_stride)
+        with _on(torch, stream):
+            out = {"rows": torch.empty(shape, dtype=dtype, device=samples.device),
+                   "nsamples": torch.empty((nstreams,), dtype=torch.int32, device=samples.device)}
+        if stream is not None:
+            cur = torch.cuda.current_stream()       # (see _torch_outputs)
+            for t in out.values():
+                t.record_stream(cur)
+    else:
+        assert out["rows"].dim() == (3 if plan.complex_output else 2) and out["rows"].shape[0] == nstreams
+        assert out["rows"].is_contiguous() and (not plan.complex_output or out["rows"].shape[2] == 2)
+        assert out["rows"].dtype == dtype and out["nsamples"].shape == (nstreams,)
+        assert out["nsamples"].dtype == torch.int32 and out["nsamples"].is_contiguous()
+    out_stride = out["rows"].shape[1]
+    io = _lib.MuxIO()
+    io.d_samples = samples.data_ptr()
+    io.stream_stride = row_stride
+    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
+    io.nsamples = int(width)
+    io.nstreams = nstreams
+    io.d_out = out["rows"].data_ptr()
+    io.out_stride = out_stride
+    io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
+    io.d_nout = out["nsamples"].data_ptr()
+    rc = lib.mifsk_multiplex_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_multiplex_batch failed: %d" % rc)
     return out
 
 

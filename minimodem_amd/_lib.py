@@ -275,7 +275,24 @@ class ChannelIO(C.Structure):
                 ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
 
 
+MUX_COMPLEX = 1
+
+
+class MuxParams(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("phase_steps", C.c_uint32), ("ntaps", C.c_uint32),
+                ("taps", C.c_void_p), ("interp", C.c_uint32), ("nchannels", C.c_uint32), ("centres", C.c_void_p),
+                ("in_centre", C.c_int32), ("gains", C.c_void_p)]
+
+
+class MuxIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("d_out", C.c_void_p),
+                ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
+assert C.sizeof(MuxParams) == 56 and MuxParams.centres.offset == 32 and MuxParams.gains.offset == 48
+assert C.sizeof(MuxIO) == 64 and MuxIO.d_out.offset == 32 and MuxIO.d_nout.offset == 56
 assert C.sizeof(ChannelParams) == 48 and ChannelParams.centres.offset == 32
 assert C.sizeof(ChannelIO) == 64 and ChannelIO.d_rows.offset == 32 and ChannelIO.d_nout.offset == 56
 assert C.sizeof(CarrierIO) == 88 and CarrierIO.first.offset == 40 and CarrierIO.d_band.offset == 64
@@ -318,6 +335,7 @@ EXPORTS = [
     "mifsk_detect_carrier_batch", "mifsk_carrier_windows", "mifsk_carrier_tones",
     "mifsk_channel_plan_create", "mifsk_channel_plan_destroy", "mifsk_channelize_batch",
     "mifsk_channel_table", "mifsk_channel_taps",
+    "mifsk_mux_plan_create", "mifsk_mux_plan_destroy", "mifsk_multiplex_batch", "mifsk_mux_table",
 ]
 
 _lib = None
@@ -560,5 +578,13 @@ def load():
     lib.mifsk_channel_table.argtypes = [C.POINTER(ChannelParams), C.c_uint32, C.c_void_p]
     lib.mifsk_channel_taps.restype = C.c_int
     lib.mifsk_channel_taps.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    lib.mifsk_mux_plan_create.restype = C.c_int
+    lib.mifsk_mux_plan_create.argtypes = [C.c_void_p, C.POINTER(MuxParams), C.POINTER(C.c_void_p)]
+    lib.mifsk_mux_plan_destroy.restype = None
+    lib.mifsk_mux_plan_destroy.argtypes = [C.c_void_p]
+    lib.mifsk_multiplex_batch.restype = C.c_int
+    lib.mifsk_multiplex_batch.argtypes = [C.c_void_p, C.POINTER(MuxIO), C.c_void_p]
+    lib.mifsk_mux_table.restype = C.c_int
+    lib.mifsk_mux_table.argtypes = [C.POINTER(MuxParams), C.c_void_p]
     _lib = lib
     return lib

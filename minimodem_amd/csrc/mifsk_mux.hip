@@ -1,0 +1,499 @@
+// mifsk_mux.hip -- the multiplexer (include/mifsk.h): mifsk_mux_plan_create / _destroy,
+// mifsk_multiplex_batch, and the host helper mifsk_mux_table.
+//
+// One output n = m L + phi of one channel is a polyphase sum: the taps phi, phi + L, ... against the
+// samples x[m], x[m - 1], ...  The kernel is laid out around what feeds the FP64 pipe:
+//   * a lane owns kMxO outputs of ONE phase, n, n + L, ..., n + 7 L.  They share every G entry,
+//     and their samples are a sliding window x[m - j + u]: one 16-byte table read and ONE new
+//     sample per tap step feed 2 * kMxO FMAs.  The window lives in registers; the tap loop is
+//     unrolled by kMxO so that the shift is a renaming.
+//   * slot E = 256 * block + thread is group g = E div L, phase phi = E mod L; the slot's outputs
+//     are (8 g + u) L + phi.  Lanes of a wave are consecutive slots: consecutive phases read
+//     consecutive table entries and store consecutive outputs, lanes of one group read the same
+//     sample (a broadcast), and with L < 64 a wave spans several groups, whose windows lie 8
+//     samples apart -- the staged samples are padded by one double per 8 so that those reads fall
+//     on different banks.
+//   * channels run in the lane's loop in order, (o, oi) of each owned output in registers: the sum
+//     over the channels is the definition's chain.  The block's span of each channel's row is
+//     staged in LDS, widened to double once, for as many channels at a time as fit beside G
+//     (which is staged whole: 16 B * T <= 64 KiB); a wave stages a channel, so the row and its
+//     length are the wave's.  A tap step's table entry and sample are read a step ahead.
+//   * a block whose span lies wholly inside a channel's row takes the window path; one that
+//     overlaps an end of the row takes a path that tests every term (a term outside the row is
+//     skipped, not multiplied by zero: the taps may be anything); one beyond the row has re = im =
+//     0.0 without a look at the taps.
+//   * W is read from memory (L2) once per output and channel; the phase index walks from n to
+//     n + L by an addition mod P, and starts from a product reduced mod P in exact double
+//     arithmetic (both factors are below 2^20).
+// The kernel reads nothing it wrote, so it needs no fences; the outputs are plain vector stores.
+// Blocks beyond the stream's outputs store zeros only; block 0 stores the count.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include <cerrno>
+#include <cmath>
+#include <cstdint>
+#include <memory>
+#include <new>
+
+#include "mifsk.h"
+#include "mifsk_ctx.h"
+#include "mifsk_hostmem.h"
+
+namespace mifsk {
+
+constexpr int kMxO = 8;					// outputs per lane
+constexpr uint32_t kMxThreads = 256u;
+constexpr uint32_t kMxLdsSamples = 48u * 1024u;		// table + samples: stage channels up to here (3 workgroups per CU)
+constexpr uint32_t kMxMaxRows = 65535u;			// streams per launch (grid.y)
+constexpr uint32_t kMxMaxP = 1u << 20, kMxMaxT = 4096u, kMxMaxK = 4096u, kMxMaxL = 65535u;
+
+struct MuxArgs {
+    const double2	*g;		// [T]
+    const double2	*w;		// [P]: cos, sin
+    const uint32_t	*dq;		// [K]: (q[k] - r) mod P
+    const uint32_t	*ps;		// [K]: (dq[k] * (L mod P)) mod P
+    const float		*gains;		// [K] or NULL
+    const float		*x;
+    size_t		stride;		// floats between input rows
+    const uint32_t	*nsamples_v;
+    uint32_t		nsamples_u;
+    uint32_t		T, L, K, P;
+    uint32_t		jmax;		// ceil(T / L): tap steps of phase 0
+    uint32_t		span;		// samples staged per channel, at most
+    uint32_t		spanp;		// ... and doubles between the channels' spans (padded)
+    uint32_t		cb;		// channels staged at a time
+    uint32_t		s0;		// first stream of this launch
+    void		*out;
+    size_t		out_stride;	// elements
+    uint32_t		nout_cap;
+    uint32_t		*nout;
+};
+
+// where sample e of a staged span lies: one double of padding per 8
+__device__ __forceinline__ uint32_t mux_pad( uint32_t e ) { return e + ( e >> 3 ); }
+
+// (a * b) mod P for a, b < P <= 2^20: the product is exact in double, the quotient off by one at most
+__device__ __forceinline__ uint32_t mux_mulmod( uint32_t a, uint32_t b, uint32_t P, double inv_p )
+{
+    const double prod = (double)a * (double)b, dp = (double)P;
+    double r = fma(-floor(prod * inv_p), dp, prod);
+    if ( r < 0.0 )
+	r += dp;
+    if ( r >= dp )
+	r -= dp;
+    return (uint32_t)r;
+}
+
+// the float as the PCM16 write conversion stores it
+__device__ __forceinline__ int16_t mux_s16( float v )
+{
+    float t = v * 32767.0f;
+    if ( t > 32767.0f )
+	t = 32767.0f;
+    if ( t < -32768.0f )
+	t = -32768.0f;
+    return t != t ? (int16_t)0 : (int16_t)(int)rintf(t);
+}
+
+// CX: complex rows.  S16: PCM16 scalars.
+template <bool CX, bool S16>
+__global__ __launch_bounds__(256)
+void multiplex_kernel( const MuxArgs A )
+{
+    extern __shared__ double2 mx_lds[];
+    __shared__ uint32_t nmax_sh;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t T = A.T, L = A.L, K = A.K, P = A.P, jmax = A.jmax;
+    double2 *gl = mx_lds;					// T table entries | cb spans of samples
+    double *xs = reinterpret_cast<double *>(mx_lds + T);
+
+    const uint32_t s = A.s0 + blockIdx.y;
+    const size_t row0 = (size_t)s * K;
+    auto row_len = [&]( uint32_t k ) {
+	const uint32_t n = A.nsamples_v ? A.nsamples_v[row0 + k] : A.nsamples_u;
+	return n < A.stride ? n : (uint32_t)A.stride;
+    };
+    if ( tid == 0 )
+	nmax_sh = 0u;
+    __syncthreads();
+    {
+	uint32_t mine = 0u;
+	for ( uint32_t k = tid; k < K; k += kMxThreads ) {
+	    const uint32_t n = row_len(k);
+	    mine = n > mine ? n : mine;
+	}
+	if ( mine )
+	    atomicMax(&nmax_sh, mine);
+    }
+    for ( uint32_t t = tid; t < T; t += kMxThreads )
+	gl[t] = A.g[t];
+    __syncthreads();
+    const uint32_t nmax = nmax_sh;
+    const uint64_t total = nmax ? (uint64_t)( nmax - 1u ) * L + T : 0ull;
+    const uint32_t cnt = total < A.nout_cap ? (uint32_t)total : A.nout_cap;
+    if ( blockIdx.x == 0u && tid == 0u )
+	A.nout[s] = cnt;
+
+    // this lane's slot, and the groups of the block
+    const uint64_t e0 = (uint64_t)blockIdx.x * kMxThreads;
+    const uint64_t g_first = e0 / L, g_last = ( e0 + kMxThreads - 1u ) / L;
+    const uint64_t g = ( e0 + tid ) / L;
+    const uint32_t phi = (uint32_t)( ( e0 + tid ) - g * L );
+    const int64_t m0 = (int64_t)( g * kMxO );			// the lane's first m
+    const uint64_t n0 = (uint64_t)m0 * L + phi;			// ... and first output
+    const int64_t lo = (int64_t)( g_first * kMxO ) - (int64_t)( jmax - 1u );	// the block's span of samples
+    const int64_t hi = (int64_t)( g_last * kMxO ) + ( kMxO - 1 );
+    const uint32_t span = (uint32_t)( hi - lo + 1 );		// <= A.span
+    const uint32_t xb = (uint32_t)( m0 - lo );			// >= jmax - 1
+
+    double o[kMxO], oi[kMxO];
+#pragma unroll
+    for ( int u = 0; u < kMxO; u++ ) {
+	o[u] = 0.0;
+	oi[u] = 0.0;
+    }
+    if ( g_first * kMxO * L < cnt ) {				// (the whole workgroup)
+	const double inv_p = 1.0 / (double)P;
+	const uint32_t nm0 = (uint32_t)( n0 % P );
+	for ( uint32_t k0 = 0; k0 < K; k0 += A.cb ) {
+	    const uint32_t cbn = K - k0 < A.cb ? K - k0 : A.cb;
+	    __syncthreads();					// the spans before have been read
+	    // a wave per channel: the row and its length are the wave's, the lanes read along the row
+	    for ( uint32_t c = tid >> 6; c < cbn; c += kMxThreads / 64u ) {
+		const int64_t nk = row_len(k0 + c);
+		const float *xr = A.x + ( row0 + k0 + c ) * A.stride;
+		double *xc = xs + (size_t)c * A.spanp;
+		for ( uint32_t e = tid & 63u; e < span; e += 64u ) {
+		    const int64_t i = lo + e;
+		    xc[mux_pad(e)] = i >= 0 && i < nk ? (double)xr[i] : 0.0;
+		}
+	    }
+	    __syncthreads();
+	    for ( uint32_t c = 0; c < cbn; c++ ) {
+		const uint32_t k = k0 + c;
+		const int64_t nk = row_len(k);
+		const double *xc = xs + (size_t)c * A.spanp;
+		double re[kMxO], im[kMxO];
+		double2 w[kMxO];
+		// p = (dq * (n mod P)) mod P; from n to n + L it grows by ps = (dq * (L mod P)) mod P.
+		// W is asked for here, ahead of the taps, and used behind them.
+		{
+		    uint32_t p = mux_mulmod(A.dq[k], nm0, P, inv_p);
+		    const uint32_t ps = A.ps[k];
+#pragma unroll
+		    for ( int u = 0; u < kMxO; u++ ) {
+			w[u] = A.w[p];
+			p += ps;
+			if ( p >= P )
+			    p -= P;
+		    }
+		}
+#pragma unroll
+		for ( int u = 0; u < kMxO; u++ ) {
+		    re[u] = 0.0;
+		    im[u] = 0.0;
+		}
+		if ( lo >= 0 && hi < nk ) {
+		    // every term of every lane exists: the window in registers, slot (v & 7) holds
+		    // x[m0 + v] for the 8 values of v in use
+		    double win[kMxO];
+#pragma unroll
+		    for ( int u = 0; u < kMxO; u++ )
+			win[u] = xc[mux_pad(xb + (uint32_t)u)];
+		    // The table entry and the sample of a step are fetched a step ahead, outside any
+		    // test (their indices are clamped into the table and the span), so that the reads
+		    // are in flight during the FMAs before them; what a lane past its last tap fetches
+		    // or puts into the window is never used.
+		    uint32_t t = phi;
+		    double2 gn = gl[t < T ? t : T - 1u];
+		    double xn = 0.0;
+		    for ( uint32_t j0 = 0; j0 < jmax; j0 += (uint32_t)kMxO ) {
+#pragma unroll
+			for ( int r = 0; r < kMxO; r++ ) {
+			    const uint32_t j = j0 + (uint32_t)r, tn = t + L;
+			    const double2 gt = gn;
+			    if ( r > 0 || j0 > 0u )
+				win[( kMxO - r ) & 7] = xn;		// x[m0 - j]
+			    gn = gl[tn < T ? tn : T - 1u];
+			    xn = xc[mux_pad(xb - ( j + 1u < jmax ? j + 1u : jmax - 1u ))];
+			    if ( t < T ) {
+#pragma unroll
+				for ( int u = 0; u < kMxO; u++ ) {
+				    re[u] = fma(win[( u - r ) & 7], gt.x, re[u]);
+				    im[u] = fma(win[( u - r ) & 7], gt.y, im[u]);
+				}
+			    }
+			    t = tn;
+			}
+		    }
+		} else if ( lo < nk ) {
+		    // an end of the row inside the span: term by term
+		    uint32_t t = phi;
+		    for ( uint32_t j = 0; j < jmax && t < T; j++, t += L ) {
+			const double2 gt = gl[t];
+#pragma unroll
+			for ( int u = 0; u < kMxO; u++ ) {
+			    const int64_t i = m0 + u - (int64_t)j;
+			    if ( i >= 0 && i < nk ) {
+				const double x = xc[mux_pad(xb + (uint32_t)u - j)];
+				re[u] = fma(x, gt.x, re[u]);
+				im[u] = fma(x, gt.y, im[u]);
+			    }
+			}
+		    }
+		}
+		if ( A.gains ) {
+		    const double gain = (double)A.gains[k];
+#pragma unroll
+		    for ( int u = 0; u < kMxO; u++ ) {
+			re[u] = re[u] * gain;
+			im[u] = im[u] * gain;
+		    }
+		}
+#pragma unroll
+		for ( int u = 0; u < kMxO; u++ ) {
+		    o[u] = fma(re[u], w[u].x, o[u]);
+		    o[u] = fma(-im[u], w[u].y, o[u]);
+		    if constexpr ( CX ) {
+			oi[u] = fma(re[u], w[u].y, oi[u]);
+			oi[u] = fma(im[u], w[u].x, oi[u]);
+		    }
+		}
+	    }
+	}
+    }
+    char *out = reinterpret_cast<char *>(A.out) + (size_t)s * A.out_stride * ( ( S16 ? 2u : 4u ) * ( CX ? 2u : 1u ) );
+#pragma unroll
+    for ( int u = 0; u < kMxO; u++ ) {
+	const uint64_t n = n0 + (uint64_t)u * L;
+	if ( n >= A.out_stride )
+	    continue;
+	const float vr = n < cnt ? (float)o[u] : 0.0f, vi = n < cnt ? (float)oi[u] : 0.0f;
+	if constexpr ( CX ) {
+	    if constexpr ( S16 )
+		reinterpret_cast<short2 *>(out)[n] = short2{n < cnt ? mux_s16(vr) : (int16_t)0, n < cnt ? mux_s16(vi) : (int16_t)0};
+	    else
+		reinterpret_cast<float2 *>(out)[n] = float2{vr, vi};
+	} else {
+	    if constexpr ( S16 )
+		reinterpret_cast<int16_t *>(out)[n] = n < cnt ? mux_s16(vr) : (int16_t)0;
+	    else
+		reinterpret_cast<float *>(out)[n] = vr;
+	}
+    }
+}
+
+namespace {
+
+// what both table makers refuse of params
+int mux_check_params( const mifsk_mux_params *p )
+{
+    if ( !p )
+	return -EINVAL;
+    if ( ( p->kind != MIFSK_FEED_F32 && p->kind != MIFSK_FEED_S16 ) || ( p->flags & ~MIFSK_MUX_COMPLEX ) )
+	return -EINVAL;
+    if ( p->phase_steps == 0 || p->phase_steps > kMxMaxP )
+	return -EINVAL;
+    if ( p->ntaps == 0 || p->ntaps > kMxMaxT || !p->taps )
+	return -EINVAL;
+    if ( p->interp == 0 || p->interp > kMxMaxL )
+	return -EINVAL;
+    if ( p->nchannels == 0 || p->nchannels > kMxMaxK || !p->centres )
+	return -EINVAL;
+    const int64_t P = p->phase_steps;
+    for ( uint32_t k = 0; k < p->nchannels; k++ ) {
+	const int64_t q = p->centres[k];
+	if ( q >= P || -q >= P )
+	    return -EINVAL;
+    }
+    const int64_t r = p->in_centre;
+    if ( r >= P || -r >= P )
+	return -EINVAL;
+    return 0;
+}
+
+// a centre reduced to [0, P)
+inline int64_t mux_reduce( int64_t q, int64_t P )
+{
+    q %= P;
+    return q < 0 ? q + P : q;
+}
+
+constexpr double kMxTwoPi = 6.283185307179586476925286766559;
+
+// G: THE table code, for the plan and mifsk_mux_table
+void mux_table( const mifsk_mux_params *p, double2 *g )
+{
+    const int64_t P = p->phase_steps, r = mux_reduce(p->in_centre, P);
+    for ( uint32_t t = 0; t < p->ntaps; t++ ) {
+	const int64_t idx = ( r * (int64_t)t ) % P;
+	double s, c;
+	sincos(kMxTwoPi * (double)idx / (double)P, &s, &c);
+	const double h = (double)p->taps[t];
+	g[t] = double2{h * c, h * s};
+    }
+}
+
+template <bool CX, bool S16>
+int launch_mux( const MuxArgs &A, dim3 grid, size_t lds, hipStream_t st )
+{
+    if ( lds > 48u * 1024u
+	    && hipFuncSetAttribute(reinterpret_cast<const void *>(&multiplex_kernel<CX, S16>),
+				   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess )
+	return -EIO;
+    hipLaunchKernelGGL(( multiplex_kernel<CX, S16> ), grid, dim3(kMxThreads), lds, st, A);
+    return 0;
+}
+
+} // namespace
+} // namespace mifsk
+
+struct mifsk_mux_plan {
+    int				device;
+    bool			cx, s16;
+    uint32_t			P, T, L, K;
+    mifsk::DevMem<double2>	g, w;
+    mifsk::DevMem<uint32_t>	dq, ps;
+    mifsk::DevMem<float>	gains;		// empty: no gain step
+};
+
+extern "C" int mifsk_mux_table( const mifsk_mux_params *params, double *g_out )
+{
+    if ( int rc = mifsk::mux_check_params(params) )
+	return rc;
+    if ( !g_out )
+	return -EINVAL;
+    static_assert(sizeof(double2) == 2 * sizeof(double), "G is [ntaps][2] doubles");
+    mifsk::mux_table(params, reinterpret_cast<double2 *>(g_out));
+    return 0;
+}
+
+extern "C" int mifsk_mux_plan_create( mifsk_ctx *ctx, const mifsk_mux_params *params, mifsk_mux_plan **out )
+{
+    using namespace mifsk;
+    if ( !ctx || !params || !out )
+	return -EINVAL;
+    if ( int rc = mux_check_params(params) )
+	return rc;
+    const uint32_t P = params->phase_steps, T = params->ntaps, K = params->nchannels, L = params->interp;
+    const std::unique_ptr<double2[]> g(new (std::nothrow) double2[T]), w(new (std::nothrow) double2[P]);
+    const std::unique_ptr<uint32_t[]> dq(new (std::nothrow) uint32_t[K]), ps(new (std::nothrow) uint32_t[K]);
+    if ( !g || !w || !dq || !ps )
+	return -ENOMEM;
+    mux_table(params, g.get());
+    const int64_t r = mux_reduce(params->in_centre, P);
+    for ( uint32_t k = 0; k < K; k++ ) {
+	dq[k] = (uint32_t)mux_reduce(mux_reduce(params->centres[k], P) - r, P);
+	ps[k] = (uint32_t)( ( (uint64_t)dq[k] * ( L % P ) ) % P );
+    }
+    for ( uint32_t p = 0; p < P; p++ ) {
+	double s, c;
+	sincos(kMxTwoPi * (double)p / (double)P, &s, &c);
+	w[p] = double2{c, s};
+    }
+    mifsk_mux_plan *plan = new (std::nothrow) mifsk_mux_plan;
+    if ( !plan )
+	return -ENOMEM;
+    plan->device = ctx->device;
+    plan->cx = ( params->flags & MIFSK_MUX_COMPLEX ) != 0;
+    plan->s16 = params->kind == MIFSK_FEED_S16;
+    plan->P = P;
+    plan->T = T;
+    plan->L = L;
+    plan->K = K;
+    int rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : -EIO;
+    if ( rc == 0 ) rc = plan->g.alloc(T);
+    if ( rc == 0 ) rc = plan->w.alloc(P);
+    if ( rc == 0 ) rc = plan->dq.alloc(K);
+    if ( rc == 0 ) rc = plan->ps.alloc(K);
+    if ( rc == 0 && params->gains ) rc = plan->gains.alloc(K);
+    if ( rc == 0
+	    && ( hipMemcpy(plan->g.p, g.get(), T * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
+		|| hipMemcpy(plan->w.p, w.get(), P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
+		|| hipMemcpy(plan->dq.p, dq.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess
+		|| hipMemcpy(plan->ps.p, ps.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess
+		|| ( params->gains
+		    && hipMemcpy(plan->gains.p, params->gains, K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ) ) )
+	rc = -EIO;
+    if ( rc ) {
+	delete plan;
+	return rc;
+    }
+    *out = plan;
+    return 0;
+}
+
+extern "C" void mifsk_mux_plan_destroy( mifsk_mux_plan *plan )
+{
+    if ( !plan )
+	return;
+    (void)hipSetDevice(plan->device);
+    (void)hipDeviceSynchronize();		// no kernel reads the tables any more
+    delete plan;
+}
+
+extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream )
+{
+    using namespace mifsk;
+    if ( !plan || !io || !io->d_samples || !io->d_out || !io->d_nout )
+	return -EINVAL;
+    if ( io->nstreams <= 0 )
+	return -EINVAL;
+    if ( ( (uintptr_t)io->d_samples & 15u ) || io->stream_stride % 4u != 0 )
+	return -EINVAL;
+    const uint32_t vec = 16u / ( ( plan->s16 ? 2u : 4u ) * ( plan->cx ? 2u : 1u ) );	// elements of 16 bytes
+    if ( ( (uintptr_t)io->d_out & 15u ) || io->out_stride == 0 || io->out_stride % vec != 0
+	    || io->out_stride > 0xFFFFFFF8ull )
+	return -EINVAL;
+    if ( io->nout_cap > io->out_stride )
+	return -EINVAL;
+    if ( (uint64_t)io->nstreams * plan->K > 0x7FFFFFFFull )
+	return -EINVAL;
+
+    MuxArgs A = {};
+    A.g = plan->g.p;
+    A.w = plan->w.p;
+    A.dq = plan->dq.p;
+    A.ps = plan->ps.p;
+    A.gains = plan->gains.p;
+    A.x = io->d_samples;
+    A.stride = io->stream_stride;
+    A.nsamples_v = io->d_nsamples;
+    A.nsamples_u = io->nsamples;
+    A.T = plan->T;
+    A.L = plan->L;
+    A.K = plan->K;
+    A.P = plan->P;
+    A.out = io->d_out;
+    A.out_stride = io->out_stride;
+    A.nout_cap = io->nout_cap;
+    A.nout = io->d_nout;
+
+    // a block's 256 slots touch at most 255 / L + 2 groups of 8 values of m, and jmax - 1 samples
+    // before the first; as many channels' spans at a time as fit beside the table, one at least
+    A.jmax = ( plan->T + plan->L - 1u ) / plan->L;
+    A.span = (uint32_t)kMxO * ( ( kMxThreads - 1u ) / plan->L + 2u ) + A.jmax - 1u;
+    A.spanp = A.span + ( A.span >> 3 ) + 1u;
+    const size_t table = (size_t)plan->T * sizeof(double2), one = (size_t)A.spanp * sizeof(double);
+    A.cb = table + one < kMxLdsSamples ? (uint32_t)( ( kMxLdsSamples - table ) / one ) : 1u;
+    if ( A.cb > plan->K )
+	A.cb = plan->K;
+    const size_t lds = table + (size_t)A.cb * one;
+
+    if ( hipSetDevice(plan->device) != hipSuccess )
+	return -EIO;
+    // slots: L per group of 8 L outputs
+    const uint64_t ngroups = ( io->out_stride + (uint64_t)kMxO * plan->L - 1u ) / ( (uint64_t)kMxO * plan->L );
+    const uint32_t nblocks = (uint32_t)( ( ngroups * plan->L + kMxThreads - 1u ) / kMxThreads );
+    const hipStream_t st = (hipStream_t)stream;
+    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kMxMaxRows ) {
+	const uint32_t rows = (uint32_t)io->nstreams - s0 < kMxMaxRows ? (uint32_t)io->nstreams - s0 : kMxMaxRows;
+	A.s0 = s0;
+	const dim3 grid(nblocks, rows, 1);
+	const int rc = plan->cx ? ( plan->s16 ? launch_mux<true, true>(A, grid, lds, st) : launch_mux<true, false>(A, grid, lds, st) )
+				: ( plan->s16 ? launch_mux<false, true>(A, grid, lds, st) : launch_mux<false, false>(A, grid, lds, st) );
+	if ( rc )
+	    return rc;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+}
