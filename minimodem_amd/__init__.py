@@ -75,8 +75,27 @@ def rx_config(baudmode="1200", **opts):
     return cfg
 
 
-class Context:
+class _Handle:
+    """A library handle that is destroyed once: `handle`, close() and __del__.  A subclass names the
+    library's destroy function and sets `_lib` and `handle` when it has made one."""
+    handle = None
+    _destroy = None
+
+    def close(self):
+        if self.handle:
+            getattr(self._lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """A device context (twiddle tables etc.); one per process/GPU."""
+    _destroy = "mifsk_ctx_destroy"
 
     def __init__(self, device=-1):
         self._lib = _lib.load()
@@ -198,17 +217,6 @@ class Context:
         if rc != 0:
             raise RuntimeError("mifsk_selftest_wave_max failed: %d" % rc)
         return out
-
-    def close(self):
-        if self.handle:
-            self._lib.mifsk_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _torch():
@@ -551,17 +559,22 @@ def channel_taps(ntaps, cutoff, sample_rate, gain=1.0):
     return out
 
 
-def _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16):
-    """(mifsk_channel_params, the arrays it points to)"""
+def _phase_params(p, taps, centres, phase_steps, flags, s16):
+    """the fields mifsk_channel_params and mifsk_mux_params share -> (p, [the arrays it points to])"""
     taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
     centres = np.ascontiguousarray(centres, np.int32).reshape(-1)
-    p = _lib.ChannelParams()
-    p.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
-    p.flags = _lib.CHANNEL_COMPLEX if complex_input else 0
+    p.kind, p.flags = _lib.FEED_S16 if s16 else _lib.FEED_F32, flags
     p.phase_steps, p.ntaps, p.taps = int(phase_steps), taps.size, taps.ctypes.data
-    p.decim, p.nchannels, p.centres = int(decim), centres.size, centres.ctypes.data
-    p.out_centre = int(out_centre)
-    return p, (taps, centres)
+    p.nchannels, p.centres = centres.size, centres.ctypes.data
+    return p, [taps, centres]
+
+
+def _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16):
+    """(mifsk_channel_params, the arrays it points to)"""
+    p, keep = _phase_params(_lib.ChannelParams(), taps, centres, phase_steps,
+                            _lib.CHANNEL_COMPLEX if complex_input else 0, s16)
+    p.decim, p.out_centre = int(decim), int(out_centre)
+    return p, keep
 
 
 def channel_table(taps, centres, k, phase_steps):
@@ -574,7 +587,60 @@ def channel_table(taps, centres, k, phase_steps):
     return g
 
 
-class ChannelPlan:
+class _PhasePlan(_Handle):
+    """what ChannelPlan and MuxPlan share: the handle the library makes of the parameters"""
+
+    def _create(self, ctx, params, create, destroy):
+        self._lib, self._destroy = _lib.load(), destroy
+        p, _keep = params
+        h = C.c_void_p()
+        rc = getattr(self._lib, create)(ctx.handle, C.byref(p), C.byref(h))
+        if rc != 0:
+            raise (ValueError if rc == -22 else RuntimeError)("%s failed: %d" % (create, rc))
+        self.handle = h
+        self.ctx = ctx                      # the plan must not outlive its context
+        self.ntaps, self.nchannels, self.s16 = p.ntaps, p.nchannels, p.kind == _lib.FEED_S16
+        return p
+
+
+def _row_outputs(torch, nrows, full, vec, dtype, tail, device, stream, out):
+    """The outputs of channelize and multiplex, {"rows": `dtype` [nrows, out_stride, *tail], "nsamples":
+    int32 [nrows]}: made on the launch stream, out_stride the whole vectors of `vec` elements that hold
+    `full` (one at least), or `out`, a dict of a former call, when its tensors are of that kind (`full`
+    is not looked at then)."""
+    if out is None:
+        out_stride = max(vec, (full + vec - 1) // vec * vec)
+        with _on(torch, stream):
+            out = {"rows": torch.empty((nrows, out_stride) + tail, dtype=dtype, device=device),
+                   "nsamples": torch.empty((nrows,), dtype=torch.int32, device=device)}
+        if stream is not None:
+            cur = torch.cuda.current_stream()       # (see _torch_outputs)
+            for t in out.values():
+                t.record_stream(cur)
+    else:
+        rows, counts = out["rows"], out["nsamples"]
+        assert rows.dim() == 2 + len(tail) and rows.shape[0] == nrows and tuple(rows.shape[2:]) == tail
+        assert rows.dtype == dtype and rows.is_contiguous()
+        assert counts.shape == (nrows,) and counts.dtype == torch.int32 and counts.is_contiguous()
+    return out
+
+
+def _phase_io(io, rows_field, samples, row_stride, width, nsamples, nstreams, out, nout_cap):
+    """the fields mifsk_channel_io and mifsk_mux_io share (the output rows are `rows_field`) -> io"""
+    out_stride = out["rows"].shape[1]
+    io.d_samples = samples.data_ptr()
+    io.stream_stride = row_stride
+    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
+    io.nsamples = int(width)
+    io.nstreams = nstreams
+    setattr(io, rows_field, out["rows"].data_ptr())
+    io.out_stride = out_stride
+    io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
+    io.d_nout = out["nsamples"].data_ptr()
+    return io
+
+
+class ChannelPlan(_PhasePlan):
     """mifsk_channel_plan: the tables of a channelizer on ctx's device.
 
     taps       : float32 filter taps (channel_taps), 1 .. 4096
@@ -584,27 +650,9 @@ class ChannelPlan:
     complex_input: rows are interleaved I, Q; s16: the scalars are PCM16"""
 
     def __init__(self, ctx, taps, decim, centres, out_centre, phase_steps, complex_input=False, s16=False):
-        self._lib = _lib.load()
-        p, _keep = _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16)
-        h = C.c_void_p()
-        rc = self._lib.mifsk_channel_plan_create(ctx.handle, C.byref(p), C.byref(h))
-        if rc != 0:
-            raise (ValueError if rc == -22 else RuntimeError)("mifsk_channel_plan_create failed: %d" % rc)
-        self.handle = h
-        self.ctx = ctx                      # the plan must not outlive its context
-        self.ntaps, self.decim, self.nchannels = p.ntaps, p.decim, p.nchannels
-        self.complex_input, self.s16 = bool(complex_input), bool(s16)
-
-    def close(self):
-        if self.handle:
-            self._lib.mifsk_channel_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        p = self._create(ctx, _channel_params(taps, decim, centres, out_centre, phase_steps, complex_input, s16),
+                         "mifsk_channel_plan_create", "mifsk_channel_plan_destroy")
+        self.decim, self.complex_input = p.decim, bool(complex_input)
 
 
 def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
@@ -642,32 +690,9 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_input else 1))
     assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d elements" % vec
     _check_nsamples(torch, nsamples, nstreams)
-    nrows = nstreams * plan.nchannels
-    if out is None:
-        full = carrier_windows(width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap)
-        out_stride = max(4, (full + 3) // 4 * 4)
-        with _on(torch, stream):
-            out = {"rows": torch.empty((nrows, out_stride), dtype=torch.float32, device=samples.device),
-                   "nsamples": torch.empty((nrows,), dtype=torch.int32, device=samples.device)}
-        if stream is not None:
-            cur = torch.cuda.current_stream()       # (see _torch_outputs)
-            for t in out.values():
-                t.record_stream(cur)
-    else:
-        assert out["rows"].dim() == 2 and out["rows"].shape[0] == nrows and out["rows"].is_contiguous()
-        assert out["rows"].dtype == torch.float32 and out["nsamples"].shape == (nrows,)
-        assert out["nsamples"].dtype == torch.int32 and out["nsamples"].is_contiguous()
-    out_stride = out["rows"].shape[1]
-    io = _lib.ChannelIO()
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = row_stride
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = int(width)
-    io.nstreams = nstreams
-    io.d_rows = out["rows"].data_ptr()
-    io.out_stride = out_stride
-    io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
-    io.d_nout = out["nsamples"].data_ptr()
+    full = out is None and (carrier_windows(width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap))
+    out = _row_outputs(torch, nstreams * plan.nchannels, full, 4, torch.float32, (), samples.device, stream, out)
+    io = _phase_io(_lib.ChannelIO(), "d_rows", samples, row_stride, width, nsamples, nstreams, out, nout_cap)
     rc = lib.mifsk_channelize_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_channelize_batch failed: %d" % rc)
@@ -676,19 +701,14 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
 
 def _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains):
     """(mifsk_mux_params, the arrays it points to)"""
-    taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
-    centres = np.ascontiguousarray(centres, np.int32).reshape(-1)
-    p = _lib.MuxParams()
-    p.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
-    p.flags = _lib.MUX_COMPLEX if complex_output else 0
-    p.phase_steps, p.ntaps, p.taps = int(phase_steps), taps.size, taps.ctypes.data
-    p.interp, p.nchannels, p.centres = int(interp), centres.size, centres.ctypes.data
-    p.in_centre = int(in_centre)
+    p, keep = _phase_params(_lib.MuxParams(), taps, centres, phase_steps, _lib.MUX_COMPLEX if complex_output else 0, s16)
+    p.interp, p.in_centre = int(interp), int(in_centre)
     if gains is not None:
         gains = np.ascontiguousarray(gains, np.float32).reshape(-1)
-        assert gains.size == centres.size, "one gain per channel"
+        assert gains.size == p.nchannels, "one gain per channel"
         p.gains = gains.ctypes.data
-    return p, (taps, centres, gains)
+        keep.append(gains)
+    return p, keep
 
 
 def mux_table(taps, in_centre, phase_steps):
@@ -701,7 +721,7 @@ def mux_table(taps, in_centre, phase_steps):
     return g
 
 
-class MuxPlan:
+class MuxPlan(_PhasePlan):
     """mifsk_mux_plan: the tables of a multiplexer on ctx's device.
 
     taps       : float32 filter taps at the OUTPUT rate (channel_taps(T, fc, fs_out, 2 * interp) for
@@ -714,27 +734,9 @@ class MuxPlan:
 
     def __init__(self, ctx, taps, interp, centres, in_centre, phase_steps, complex_output=False, s16=False,
                  gains=None):
-        self._lib = _lib.load()
-        p, _keep = _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains)
-        h = C.c_void_p()
-        rc = self._lib.mifsk_mux_plan_create(ctx.handle, C.byref(p), C.byref(h))
-        if rc != 0:
-            raise (ValueError if rc == -22 else RuntimeError)("mifsk_mux_plan_create failed: %d" % rc)
-        self.handle = h
-        self.ctx = ctx                      # the plan must not outlive its context
-        self.ntaps, self.interp, self.nchannels = p.ntaps, p.interp, p.nchannels
-        self.complex_output, self.s16 = bool(complex_output), bool(s16)
-
-    def close(self):
-        if self.handle:
-            self._lib.mifsk_mux_plan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        p = self._create(ctx, _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains),
+                         "mifsk_mux_plan_create", "mifsk_mux_plan_destroy")
+        self.interp, self.complex_output = p.interp, bool(complex_output)
 
 
 def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
@@ -761,33 +763,9 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     _check_nsamples(torch, nsamples, nrows)
     dtype = torch.int16 if plan.s16 else torch.float32
     vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
-    if out is None:
-        full = (int(width) - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap)
-        out_stride = max(vec, (full + vec - 1) // vec * vec)
-        shape = (nstreams, out_stride, 2) if plan.complex_output else (nstreams, out_stride)
-        with _on(torch, stream):
-            out = {"rows": torch.empty(shape, dtype=dtype, device=samples.device),
-                   "nsamples": torch.empty((nstreams,), dtype=torch.int32, device=samples.device)}
-        if stream is not None:
-            cur = torch.cuda.current_stream()       # (see _torch_outputs)
-            for t in out.values():
-                t.record_stream(cur)
-    else:
-        assert out["rows"].dim() == (3 if plan.complex_output else 2) and out["rows"].shape[0] == nstreams
-        assert out["rows"].is_contiguous() and (not plan.complex_output or out["rows"].shape[2] == 2)
-        assert out["rows"].dtype == dtype and out["nsamples"].shape == (nstreams,)
-        assert out["nsamples"].dtype == torch.int32 and out["nsamples"].is_contiguous()
-    out_stride = out["rows"].shape[1]
-    io = _lib.MuxIO()
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = row_stride
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = int(width)
-    io.nstreams = nstreams
-    io.d_out = out["rows"].data_ptr()
-    io.out_stride = out_stride
-    io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
-    io.d_nout = out["nsamples"].data_ptr()
+    full = out is None and ((int(width) - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap))
+    out = _row_outputs(torch, nstreams, full, vec, dtype, (2,) if plan.complex_output else (), samples.device, stream, out)
+    io = _phase_io(_lib.MuxIO(), "d_out", samples, row_stride, width, nsamples, nstreams, out, nout_cap)
     rc = lib.mifsk_multiplex_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_multiplex_batch failed: %d" % rc)
@@ -1085,7 +1063,7 @@ class _DevArray:
                                          "data": (int(ptr), False), "version": 2, "strides": None}
 
 
-class Pipeline:
+class Pipeline(_Handle):
     """mifsk_pipeline_*: `depth` batches in flight behind the C ABI -- lanes of a context, a HIP
     stream and a completion event each, and (outputs(...)) one set of output arrays per lane,
     all owned by the library.  submit() is mifsk_demod_batch as the pipeline's next pass and
@@ -1096,6 +1074,7 @@ class Pipeline:
         t = pipe.submit(cfg, samples)            # ... more submits: they overlap on the device
         pipe.wait(t); out = pipe.result(t)       # dict of torch views of that pass's set
     """
+    _destroy = "mifsk_pipeline_destroy"
 
     def __init__(self, device=-1, depth=3):
         self._lib = _lib.load()
@@ -1207,14 +1186,7 @@ class Pipeline:
     def close(self):
         if self.handle:
             self._views = {}
-            self._lib.mifsk_pipeline_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 class ByteGatherer:
@@ -1307,7 +1279,7 @@ class ByteGatherer:
         return self._rx[self._last if slot is None else slot % self.slots][0 if self.loopback else r - 1]
 
 
-class NativeGatherer:
+class NativeGatherer(_Handle):
     """mifsk_gather_*: the same gather behind the C ABI (csrc/mifsk_gather.cpp: RCCL opened with
     dlopen, a communicator of the library's own).  Interface of ByteGatherer -- start(bytes,
     nbytes) enqueues ONE gather on torch's current stream and returns no handles (it is complete
@@ -1317,6 +1289,7 @@ class NativeGatherer:
 
     `dist`: a torch.distributed module whose default group carries rank 0's id to the others
     (None at world size 1); the communicator itself is made by the library."""
+    _destroy = "mifsk_gather_destroy"
 
     def __init__(self, dist, rank, world, cols=None, rows=None, slots=2, loopback=False, device=-1):
         torch = _torch()
@@ -1387,17 +1360,6 @@ class NativeGatherer:
         b = torch.as_tensor(_DevArray(pb.value, (rows.value, cols.value), "|u1"), device=dev)
         n = torch.as_tensor(_DevArray(pn.value, (rows.value,), "<i4"), device=dev)
         return b, n
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.mifsk_gather_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:		# noqa: BLE001
-            pass
 
 
 DECODERS = {"ascii8": 0, "baudot": 1, "binary": 2, "callerid": 3, "uic-ground": 4, "uic-train": 5}
@@ -1832,7 +1794,7 @@ class SlabSession:
         return res
 
 
-class Session:
+class Session(_Handle):
     """mifsk_session_*: SlabSession's job behind the C ABI (csrc/mifsk_session.cpp) -- the
     unconsumed tails, origins, loop state, RING cells and output arrays are the library's.
     feed(new, final) returns one dict per stream of what THIS feed made of it (numpy copies).
@@ -1843,6 +1805,7 @@ class Session:
     tensor [n, k] whose row i holds stream i's nsamples[i] new samples (default: k for every
     stream), produced on the current torch stream.  rxnoise is the --Xrxnoise term, added to the
     new samples on the device."""
+    _destroy = "mifsk_session_destroy"
 
     def __init__(self, ctx, cfg, nstreams, engine=None, ring_exact=False, want_frames=True, resident=False):
         self._lib = _lib.load()
@@ -1927,17 +1890,6 @@ class Session:
         if rc != 0:
             raise RuntimeError("mifsk_session_info_get failed: %d" % rc)
         return _struct_dict(info, drop_reserved=True)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.mifsk_session_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:		# noqa: BLE001
-            pass
 
 
 def scan_plan(cfg, kind):

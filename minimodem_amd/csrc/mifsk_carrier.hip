@@ -29,6 +29,7 @@
 #include <cstdint>
 
 #include "mifsk.h"
+#include "mifsk_batch.h"
 #include "mifsk_ctx.h"
 #include "mifsk_devlib.h"
 
@@ -38,7 +39,6 @@ constexpr int kCarW = 8;				// windows per lane
 constexpr uint32_t kCarTile = 64u;			// samples of each window staged at a time
 constexpr uint32_t kCarMaxLds = 160u * 1024u;		// a workgroup may have all of a CU's LDS
 constexpr uint32_t kCarBigTable = 40u * 1024u;		// a table beyond this: one workgroup of 8 waves per CU
-constexpr uint32_t kCarMaxRows = 65535u;		// streams per launch (grid.y)
 
 struct CarrierArgs {
     const double	*cs;		// the context's spectrum table, [N][2]
@@ -256,17 +256,6 @@ void carrier_survey_kernel( const CarrierArgs A )
 
 namespace {
 
-template <int NB, bool TWLDS>
-int launch_carrier( const CarrierArgs &A, dim3 grid, unsigned threads, size_t lds, hipStream_t st )
-{
-    if ( lds > 48u * 1024u
-	    && hipFuncSetAttribute(reinterpret_cast<const void *>(&carrier_survey_kernel<NB, TWLDS>),
-				   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess )
-	return -EIO;
-    hipLaunchKernelGGL(( carrier_survey_kernel<NB, TWLDS> ), grid, dim3(threads), lds, st, A);
-    return 0;
-}
-
 // the negative shift --auto-carrier applies, in the reference's float arithmetic
 // (minimodem.c:1203-1206; demod_batch_wave in mifsk_capi.cpp)
 int carrier_b_shift( const mifsk_rx_config *cfg )
@@ -317,13 +306,9 @@ extern "C" int mifsk_detect_carrier_batch( mifsk_ctx *ctx, const mifsk_rx_config
 	return -EINVAL;
     if ( io->nstreams <= 0 || io->nwindows == 0 )
 	return -EINVAL;
-    if ( io->kind != MIFSK_FEED_F32 && io->kind != MIFSK_FEED_S16 )
-	return -EINVAL;
+    if ( int rc = feed_rows_check(io->kind, io->rxnoise, io->d_samples, io->stream_stride) )
+	return rc;
     const bool s16 = io->kind == MIFSK_FEED_S16;
-    if ( !s16 && !( io->rxnoise == 0.0f ) )
-	return -EINVAL;
-    if ( io->stream_stride % ( s16 ? 8u : 4u ) != 0 || ( (uintptr_t)io->d_samples & 15u ) )
-	return -EINVAL;			// rows are 16-byte aligned, as every entry takes them
     if ( int rc = mifsk_check_cfg(cfg) )
 	return rc;
     if ( cfg->nbands < 2 )
@@ -395,22 +380,16 @@ extern "C" int mifsk_detect_carrier_batch( mifsk_ctx *ctx, const mifsk_rx_config
     const uint32_t WB = A.WG * (uint32_t)kCarW;
     const uint32_t nchunks = (uint32_t)( ( (uint64_t)A.nwindows + WB - 1u ) / WB );
     const hipStream_t st = (hipStream_t)stream;
-    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kCarMaxRows ) {
-	const uint32_t rows = (uint32_t)io->nstreams - s0 < kCarMaxRows ? (uint32_t)io->nstreams - s0 : kCarMaxRows;
+    return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	// a workgroup walks several chunks of a row once the chip is full: the table is loaded once
 	uint32_t gx = ( 8u * (uint32_t)ctx->ncu + rows - 1u ) / rows;
 	gx = gx < nchunks ? gx : nchunks;
 	A.s0 = s0;
-	const dim3 grid(gx, rows);
-	int rc;
+	const dim3 grid(gx, rows), block(64u * waves);
 	if ( nb == 2 )
-	    rc = tw_lds ? launch_carrier<2, true>(A, grid, 64u * waves, lds, st)
-			: launch_carrier<2, false>(A, grid, 64u * waves, lds, st);
-	else
-	    rc = tw_lds ? launch_carrier<1, true>(A, grid, 64u * waves, lds, st)
-			: launch_carrier<1, false>(A, grid, 64u * waves, lds, st);
-	if ( rc )
-	    return rc;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	    return tw_lds ? launch_lds(carrier_survey_kernel<2, true>, grid, block, lds, st, A)
+			  : launch_lds(carrier_survey_kernel<2, false>, grid, block, lds, st, A);
+	return tw_lds ? launch_lds(carrier_survey_kernel<1, true>, grid, block, lds, st, A)
+		      : launch_lds(carrier_survey_kernel<1, false>, grid, block, lds, st, A);
+    });
 }

@@ -38,7 +38,7 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
-#include "mifsk_hostmem.h"
+#include "mifsk_phase.h"
 
 namespace mifsk {
 
@@ -47,8 +47,7 @@ constexpr uint32_t kChWaves = 4u;			// waves of a workgroup
 constexpr uint32_t kChTile = 64u;			// taps staged at a time, at most
 constexpr uint32_t kChLdsTwo = 64u * 1024u;		// two workgroups per CU up to here
 constexpr uint32_t kChLdsMax = 144u * 1024u;
-constexpr uint32_t kChMaxRows = 65535u;			// streams per launch (grid.y)
-constexpr uint32_t kChMaxP = 1u << 20, kChMaxT = 4096u, kChMaxK = 4096u, kChMaxD = 65535u;
+constexpr uint32_t kChMaxD = 65535u;
 constexpr uint64_t kChMaxKT = 1ull << 22;
 
 struct ChannelArgs {
@@ -222,78 +221,27 @@ namespace {
 // what both table makers refuse of params
 int channel_check_params( const mifsk_channel_params *p )
 {
-    if ( !p )
-	return -EINVAL;
-    if ( ( p->kind != MIFSK_FEED_F32 && p->kind != MIFSK_FEED_S16 ) || ( p->flags & ~MIFSK_CHANNEL_COMPLEX ) )
-	return -EINVAL;
-    if ( p->phase_steps == 0 || p->phase_steps > kChMaxP )
-	return -EINVAL;
-    if ( p->ntaps == 0 || p->ntaps > kChMaxT || !p->taps )
-	return -EINVAL;
+    if ( int rc = phase_check_params(p, MIFSK_CHANNEL_COMPLEX) )
+	return rc;
     if ( p->decim == 0 || p->decim > kChMaxD )
-	return -EINVAL;
-    if ( p->nchannels == 0 || p->nchannels > kChMaxK || !p->centres )
 	return -EINVAL;
     if ( (uint64_t)p->nchannels * p->ntaps > kChMaxKT )
 	return -EINVAL;
-    for ( uint32_t k = 0; k < p->nchannels; k++ ) {
-	const int64_t q = p->centres[k];
-	if ( q >= (int64_t)p->phase_steps || -q >= (int64_t)p->phase_steps )
-	    return -EINVAL;
-    }
     return 0;
 }
 
-// a centre reduced to [0, P)
-inline int64_t channel_reduce( int64_t q, int64_t P )
-{
-    q %= P;
-    return q < 0 ? q + P : q;
-}
-
-constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-// channel k's G, tap t at g[t * gstride]: THE table code, for the plan and mifsk_channel_table
+// channel k's G, tap t at g[t * gstride]: the taps turned back by the channel's centre
 void channel_table( const mifsk_channel_params *p, uint32_t k, double2 *g, size_t gstride )
 {
-    const int64_t P = p->phase_steps, q = channel_reduce(p->centres[k], P);
-    for ( uint32_t t = 0; t < p->ntaps; t++ ) {
-	const int64_t idx = ( q * (int64_t)t ) % P;
-	double s, c;
-	sincos(kTwoPi * (double)idx / (double)P, &s, &c);
-	const double h = (double)p->taps[t];
-	g[(size_t)t * gstride] = double2{h * c, -( h * s )};
-    }
-}
-
-template <int NC, bool CX, bool S16>
-int launch_channel( const ChannelArgs &A, dim3 grid, size_t lds, hipStream_t st )
-{
-    if ( lds > 48u * 1024u
-	    && hipFuncSetAttribute(reinterpret_cast<const void *>(&channelize_kernel<NC, CX, S16>),
-				   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess )
-	return -EIO;
-    hipLaunchKernelGGL(( channelize_kernel<NC, CX, S16> ), grid, dim3(64u * kChWaves), lds, st, A);
-    return 0;
-}
-
-template <int NC>
-int launch_channel_kind( bool cx, bool s16, const ChannelArgs &A, dim3 grid, size_t lds, hipStream_t st )
-{
-    if ( cx )
-	return s16 ? launch_channel<NC, true, true>(A, grid, lds, st) : launch_channel<NC, true, false>(A, grid, lds, st);
-    return s16 ? launch_channel<NC, false, true>(A, grid, lds, st) : launch_channel<NC, false, false>(A, grid, lds, st);
+    phase_rotated_taps(p->taps, p->ntaps, p->centres[k], p->phase_steps, true, g, gstride);
 }
 
 } // namespace
 } // namespace mifsk
 
-struct mifsk_channel_plan {
-    int				device;
-    bool			cx, s16;
-    uint32_t			P, T, D, K;
-    mifsk::DevMem<double2>	gt, w;
-    mifsk::DevMem<uint32_t>	dq;
+struct mifsk_channel_plan : mifsk::PhasePlanCommon {
+    uint32_t			D;
+    mifsk::DevMem<double2>	gt;
 };
 
 extern "C" int mifsk_channel_table( const mifsk_channel_params *params, uint32_t k, double *g_out )
@@ -309,7 +257,7 @@ extern "C" int mifsk_channel_table( const mifsk_channel_params *params, uint32_t
 
 extern "C" int mifsk_channel_taps( uint32_t ntaps, double cutoff_hz, double sample_rate, double gain, float *out )
 {
-    if ( ntaps == 0 || ntaps > mifsk::kChMaxT || !out )
+    if ( ntaps == 0 || ntaps > mifsk::kPhaseMaxTaps || !out )
 	return -EINVAL;
     if ( !( cutoff_hz > 0.0 ) || !( sample_rate > 0.0 ) || !std::isfinite(cutoff_hz) || !std::isfinite(sample_rate) )
 	return -EINVAL;
@@ -317,7 +265,7 @@ extern "C" int mifsk_channel_taps( uint32_t ntaps, double cutoff_hz, double samp
 	out[0] = (float)gain;
 	return 0;
     }
-    double h[mifsk::kChMaxT];
+    double h[mifsk::kPhaseMaxTaps];
     const double f = 2.0 * cutoff_hz / sample_rate, mid = (double)( ntaps - 1u ) / 2.0;
     double sum = 0.0;
     for ( uint32_t t = 0; t < ntaps; t++ ) {
@@ -338,74 +286,36 @@ extern "C" int mifsk_channel_plan_create( mifsk_ctx *ctx, const mifsk_channel_pa
 	return -EINVAL;
     if ( int rc = channel_check_params(params) )
 	return rc;
-    const uint32_t P = params->phase_steps, T = params->ntaps, K = params->nchannels;
+    const uint32_t T = params->ntaps, K = params->nchannels;
     const size_t ngt = (size_t)T * K;
-    const std::unique_ptr<double2[]> gt(new (std::nothrow) double2[ngt]), w(new (std::nothrow) double2[P]);
-    const std::unique_ptr<uint32_t[]> dq(new (std::nothrow) uint32_t[K]);
-    if ( !gt || !w || !dq )
+    const auto gt = host_array<double2>(ngt);
+    const auto dq = host_array<uint32_t>(K);
+    std::unique_ptr<mifsk_channel_plan> plan(new (std::nothrow) mifsk_channel_plan);
+    if ( !gt || !dq || !plan )
 	return -ENOMEM;
     for ( uint32_t k = 0; k < K; k++ ) {
 	channel_table(params, k, gt.get() + k, K);
-	dq[k] = (uint32_t)channel_reduce((int64_t)params->out_centre - channel_reduce(params->centres[k], P), P);
+	dq[k] = phase_diff(params->out_centre, params->centres[k], params->phase_steps);
     }
-    for ( uint32_t p = 0; p < P; p++ ) {
-	double s, c;
-	sincos(kTwoPi * (double)p / (double)P, &s, &c);
-	w[p] = double2{c, s};
-    }
-    mifsk_channel_plan *plan = new (std::nothrow) mifsk_channel_plan;
-    if ( !plan )
-	return -ENOMEM;
-    plan->device = ctx->device;
-    plan->cx = ( params->flags & MIFSK_CHANNEL_COMPLEX ) != 0;
-    plan->s16 = params->kind == MIFSK_FEED_S16;
-    plan->P = P;
-    plan->T = T;
     plan->D = params->decim;
-    plan->K = K;
-    int rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : -EIO;
-    if ( rc == 0 ) rc = plan->gt.alloc(ngt);
-    if ( rc == 0 ) rc = plan->w.alloc(P);
-    if ( rc == 0 ) rc = plan->dq.alloc(K);
-    if ( rc == 0
-	    && ( hipMemcpy(plan->gt.p, gt.get(), ngt * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
-		|| hipMemcpy(plan->w.p, w.get(), P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
-		|| hipMemcpy(plan->dq.p, dq.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess ) )
-	rc = -EIO;
-    if ( rc ) {
-	delete plan;
+    int rc = phase_plan_init(*plan, ctx->device, params, ( params->flags & MIFSK_CHANNEL_COMPLEX ) != 0, dq.get());
+    if ( rc == 0 )
+	rc = upload(plan->gt, gt.get(), ngt);
+    if ( rc )
 	return rc;
-    }
-    *out = plan;
+    *out = plan.release();
     return 0;
 }
 
-extern "C" void mifsk_channel_plan_destroy( mifsk_channel_plan *plan )
-{
-    if ( !plan )
-	return;
-    (void)hipSetDevice(plan->device);
-    (void)hipDeviceSynchronize();		// no kernel reads the tables any more
-    delete plan;
-}
+extern "C" void mifsk_channel_plan_destroy( mifsk_channel_plan *plan ) { mifsk::phase_plan_destroy(plan); }
 
 extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream )
 {
     using namespace mifsk;
-    if ( !plan || !io || !io->d_samples || !io->d_rows || !io->d_nout )
+    if ( !plan || !io )
 	return -EINVAL;
-    if ( io->nstreams <= 0 )
-	return -EINVAL;
-    const uint32_t vec = 16u / ( ( plan->s16 ? 2u : 4u ) * ( plan->cx ? 2u : 1u ) );	// elements of 16 bytes
-    if ( ( (uintptr_t)io->d_samples & 15u ) || io->stream_stride % vec != 0 )
-	return -EINVAL;
-    if ( ( (uintptr_t)io->d_rows & 15u ) || io->out_stride == 0 || io->out_stride % 4u != 0
-	    || io->out_stride > 0xFFFFFFFCull )
-	return -EINVAL;
-    if ( io->nout_cap > io->out_stride )
-	return -EINVAL;
-    if ( (uint64_t)io->nstreams * plan->K > 0x7FFFFFFFull )
-	return -EINVAL;
+    if ( int rc = phase_check_io(*plan, io, io->d_rows, rows_vec(plan->cx, plan->s16), 4u, 0xFFFFFFFCull) )
+	return rc;
 
     ChannelArgs A = {};
     A.gt = plan->gt.p;
@@ -458,14 +368,15 @@ extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mif
     const uint32_t nchunks = (uint32_t)( ( io->out_stride + OB - 1u ) / OB );
     const uint32_t gz = ( plan->K + C - 1u ) / C;
     const hipStream_t st = (hipStream_t)stream;
-    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kChMaxRows ) {
-	const uint32_t rows = (uint32_t)io->nstreams - s0 < kChMaxRows ? (uint32_t)io->nstreams - s0 : kChMaxRows;
+    return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	A.s0 = s0;
-	const dim3 grid(nchunks, rows, gz);
-	const int rc = nc == 2u ? launch_channel_kind<2>(plan->cx, plan->s16, A, grid, lds, st)
-				: launch_channel_kind<1>(plan->cx, plan->s16, A, grid, lds, st);
-	if ( rc )
-	    return rc;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	const dim3 grid(nchunks, rows, gz), block(64u * kChWaves);
+	auto launch = [&]( auto per_lane ) {
+	    return dispatch_kind(plan->cx, plan->s16, [&]( auto cx, auto s16 ) {
+		return launch_lds(channelize_kernel<decltype(per_lane)::value, decltype(cx)::value, decltype(s16)::value>,
+				  grid, block, lds, st, A);
+	    });
+	};
+	return nc == 2u ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
+    });
 }

@@ -37,15 +37,14 @@
 
 #include "mifsk.h"
 #include "mifsk_ctx.h"
-#include "mifsk_hostmem.h"
+#include "mifsk_phase.h"
 
 namespace mifsk {
 
 constexpr int kMxO = 8;					// outputs per lane
 constexpr uint32_t kMxThreads = 256u;
 constexpr uint32_t kMxLdsSamples = 48u * 1024u;		// table + samples: stage channels up to here (3 workgroups per CU)
-constexpr uint32_t kMxMaxRows = 65535u;			// streams per launch (grid.y)
-constexpr uint32_t kMxMaxP = 1u << 20, kMxMaxT = 4096u, kMxMaxK = 4096u, kMxMaxL = 65535u;
+constexpr uint32_t kMxMaxL = 65535u;
 
 struct MuxArgs {
     const double2	*g;		// [T]
@@ -288,72 +287,26 @@ namespace {
 // what both table makers refuse of params
 int mux_check_params( const mifsk_mux_params *p )
 {
-    if ( !p )
-	return -EINVAL;
-    if ( ( p->kind != MIFSK_FEED_F32 && p->kind != MIFSK_FEED_S16 ) || ( p->flags & ~MIFSK_MUX_COMPLEX ) )
-	return -EINVAL;
-    if ( p->phase_steps == 0 || p->phase_steps > kMxMaxP )
-	return -EINVAL;
-    if ( p->ntaps == 0 || p->ntaps > kMxMaxT || !p->taps )
-	return -EINVAL;
+    if ( int rc = phase_check_params(p, MIFSK_MUX_COMPLEX) )
+	return rc;
     if ( p->interp == 0 || p->interp > kMxMaxL )
 	return -EINVAL;
-    if ( p->nchannels == 0 || p->nchannels > kMxMaxK || !p->centres )
-	return -EINVAL;
-    const int64_t P = p->phase_steps;
-    for ( uint32_t k = 0; k < p->nchannels; k++ ) {
-	const int64_t q = p->centres[k];
-	if ( q >= P || -q >= P )
-	    return -EINVAL;
-    }
-    const int64_t r = p->in_centre;
-    if ( r >= P || -r >= P )
-	return -EINVAL;
-    return 0;
+    return phase_centre_ok(p->in_centre, p->phase_steps) ? 0 : -EINVAL;
 }
 
-// a centre reduced to [0, P)
-inline int64_t mux_reduce( int64_t q, int64_t P )
-{
-    q %= P;
-    return q < 0 ? q + P : q;
-}
-
-constexpr double kMxTwoPi = 6.283185307179586476925286766559;
-
-// G: THE table code, for the plan and mifsk_mux_table
+// G: the taps turned forward by the rows' centre
 void mux_table( const mifsk_mux_params *p, double2 *g )
 {
-    const int64_t P = p->phase_steps, r = mux_reduce(p->in_centre, P);
-    for ( uint32_t t = 0; t < p->ntaps; t++ ) {
-	const int64_t idx = ( r * (int64_t)t ) % P;
-	double s, c;
-	sincos(kMxTwoPi * (double)idx / (double)P, &s, &c);
-	const double h = (double)p->taps[t];
-	g[t] = double2{h * c, h * s};
-    }
-}
-
-template <bool CX, bool S16>
-int launch_mux( const MuxArgs &A, dim3 grid, size_t lds, hipStream_t st )
-{
-    if ( lds > 48u * 1024u
-	    && hipFuncSetAttribute(reinterpret_cast<const void *>(&multiplex_kernel<CX, S16>),
-				   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess )
-	return -EIO;
-    hipLaunchKernelGGL(( multiplex_kernel<CX, S16> ), grid, dim3(kMxThreads), lds, st, A);
-    return 0;
+    phase_rotated_taps(p->taps, p->ntaps, p->in_centre, p->phase_steps, false, g, 1);
 }
 
 } // namespace
 } // namespace mifsk
 
-struct mifsk_mux_plan {
-    int				device;
-    bool			cx, s16;
-    uint32_t			P, T, L, K;
-    mifsk::DevMem<double2>	g, w;
-    mifsk::DevMem<uint32_t>	dq, ps;
+struct mifsk_mux_plan : mifsk::PhasePlanCommon {
+    uint32_t			L;
+    mifsk::DevMem<double2>	g;
+    mifsk::DevMem<uint32_t>	ps;
     mifsk::DevMem<float>	gains;		// empty: no gain step
 };
 
@@ -376,79 +329,36 @@ extern "C" int mifsk_mux_plan_create( mifsk_ctx *ctx, const mifsk_mux_params *pa
     if ( int rc = mux_check_params(params) )
 	return rc;
     const uint32_t P = params->phase_steps, T = params->ntaps, K = params->nchannels, L = params->interp;
-    const std::unique_ptr<double2[]> g(new (std::nothrow) double2[T]), w(new (std::nothrow) double2[P]);
-    const std::unique_ptr<uint32_t[]> dq(new (std::nothrow) uint32_t[K]), ps(new (std::nothrow) uint32_t[K]);
-    if ( !g || !w || !dq || !ps )
+    const auto g = host_array<double2>(T);
+    const auto dq = host_array<uint32_t>(K), ps = host_array<uint32_t>(K);
+    std::unique_ptr<mifsk_mux_plan> plan(new (std::nothrow) mifsk_mux_plan);
+    if ( !g || !dq || !ps || !plan )
 	return -ENOMEM;
     mux_table(params, g.get());
-    const int64_t r = mux_reduce(params->in_centre, P);
     for ( uint32_t k = 0; k < K; k++ ) {
-	dq[k] = (uint32_t)mux_reduce(mux_reduce(params->centres[k], P) - r, P);
+	dq[k] = phase_diff(params->centres[k], params->in_centre, P);
 	ps[k] = (uint32_t)( ( (uint64_t)dq[k] * ( L % P ) ) % P );
     }
-    for ( uint32_t p = 0; p < P; p++ ) {
-	double s, c;
-	sincos(kMxTwoPi * (double)p / (double)P, &s, &c);
-	w[p] = double2{c, s};
-    }
-    mifsk_mux_plan *plan = new (std::nothrow) mifsk_mux_plan;
-    if ( !plan )
-	return -ENOMEM;
-    plan->device = ctx->device;
-    plan->cx = ( params->flags & MIFSK_MUX_COMPLEX ) != 0;
-    plan->s16 = params->kind == MIFSK_FEED_S16;
-    plan->P = P;
-    plan->T = T;
     plan->L = L;
-    plan->K = K;
-    int rc = hipSetDevice(ctx->device) == hipSuccess ? 0 : -EIO;
-    if ( rc == 0 ) rc = plan->g.alloc(T);
-    if ( rc == 0 ) rc = plan->w.alloc(P);
-    if ( rc == 0 ) rc = plan->dq.alloc(K);
-    if ( rc == 0 ) rc = plan->ps.alloc(K);
-    if ( rc == 0 && params->gains ) rc = plan->gains.alloc(K);
-    if ( rc == 0
-	    && ( hipMemcpy(plan->g.p, g.get(), T * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
-		|| hipMemcpy(plan->w.p, w.get(), P * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess
-		|| hipMemcpy(plan->dq.p, dq.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess
-		|| hipMemcpy(plan->ps.p, ps.get(), K * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess
-		|| ( params->gains
-		    && hipMemcpy(plan->gains.p, params->gains, K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ) ) )
-	rc = -EIO;
-    if ( rc ) {
-	delete plan;
+    int rc = phase_plan_init(*plan, ctx->device, params, ( params->flags & MIFSK_MUX_COMPLEX ) != 0, dq.get());
+    if ( rc == 0 ) rc = upload(plan->g, g.get(), T);
+    if ( rc == 0 ) rc = upload(plan->ps, ps.get(), K);
+    if ( rc == 0 && params->gains ) rc = upload(plan->gains, params->gains, K);
+    if ( rc )
 	return rc;
-    }
-    *out = plan;
+    *out = plan.release();
     return 0;
 }
 
-extern "C" void mifsk_mux_plan_destroy( mifsk_mux_plan *plan )
-{
-    if ( !plan )
-	return;
-    (void)hipSetDevice(plan->device);
-    (void)hipDeviceSynchronize();		// no kernel reads the tables any more
-    delete plan;
-}
+extern "C" void mifsk_mux_plan_destroy( mifsk_mux_plan *plan ) { mifsk::phase_plan_destroy(plan); }
 
 extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream )
 {
     using namespace mifsk;
-    if ( !plan || !io || !io->d_samples || !io->d_out || !io->d_nout )
+    if ( !plan || !io )
 	return -EINVAL;
-    if ( io->nstreams <= 0 )
-	return -EINVAL;
-    if ( ( (uintptr_t)io->d_samples & 15u ) || io->stream_stride % 4u != 0 )
-	return -EINVAL;
-    const uint32_t vec = 16u / ( ( plan->s16 ? 2u : 4u ) * ( plan->cx ? 2u : 1u ) );	// elements of 16 bytes
-    if ( ( (uintptr_t)io->d_out & 15u ) || io->out_stride == 0 || io->out_stride % vec != 0
-	    || io->out_stride > 0xFFFFFFF8ull )
-	return -EINVAL;
-    if ( io->nout_cap > io->out_stride )
-	return -EINVAL;
-    if ( (uint64_t)io->nstreams * plan->K > 0x7FFFFFFFull )
-	return -EINVAL;
+    if ( int rc = phase_check_io(*plan, io, io->d_out, 4u, rows_vec(plan->cx, plan->s16), 0xFFFFFFF8ull) )
+	return rc;
 
     MuxArgs A = {};
     A.g = plan->g.p;
@@ -486,14 +396,11 @@ extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mu
     const uint64_t ngroups = ( io->out_stride + (uint64_t)kMxO * plan->L - 1u ) / ( (uint64_t)kMxO * plan->L );
     const uint32_t nblocks = (uint32_t)( ( ngroups * plan->L + kMxThreads - 1u ) / kMxThreads );
     const hipStream_t st = (hipStream_t)stream;
-    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kMxMaxRows ) {
-	const uint32_t rows = (uint32_t)io->nstreams - s0 < kMxMaxRows ? (uint32_t)io->nstreams - s0 : kMxMaxRows;
+    return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	A.s0 = s0;
-	const dim3 grid(nblocks, rows, 1);
-	const int rc = plan->cx ? ( plan->s16 ? launch_mux<true, true>(A, grid, lds, st) : launch_mux<true, false>(A, grid, lds, st) )
-				: ( plan->s16 ? launch_mux<false, true>(A, grid, lds, st) : launch_mux<false, false>(A, grid, lds, st) );
-	if ( rc )
-	    return rc;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	return dispatch_kind(plan->cx, plan->s16, [&]( auto cx, auto s16 ) {
+	    return launch_lds(multiplex_kernel<decltype(cx)::value, decltype(s16)::value>, dim3(nblocks, rows, 1),
+			      dim3(kMxThreads), lds, st, A);
+	});
+    });
 }

@@ -31,13 +31,13 @@
 #include <cstdint>
 
 #include "mifsk.h"
+#include "mifsk_batch.h"
 #include "mifsk_ctx.h"
 #include "mifsk_devlib.h"
 
 namespace mifsk {
 
 constexpr uint32_t kSoftMaxLdsFloats = 12288u;		// 48 KiB of the 64 a workgroup may have
-constexpr uint32_t kSoftMaxRows = 65535u;		// streams per launch (grid.y)
 
 struct SoftArgs {
     const DevCfg	*cfg;
@@ -384,13 +384,9 @@ extern "C" int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
 	return -EINVAL;
     if ( io->nstreams <= 0 || io->frames_cap == 0 )
 	return -EINVAL;
-    if ( io->kind != MIFSK_FEED_F32 && io->kind != MIFSK_FEED_S16 )
-	return -EINVAL;
+    if ( int rc = feed_rows_check(io->kind, io->rxnoise, io->d_samples, io->stream_stride) )
+	return rc;			// (coalesced 16-byte staging)
     const bool s16 = io->kind == MIFSK_FEED_S16;
-    if ( !s16 && !( io->rxnoise == 0.0f ) )
-	return -EINVAL;
-    if ( io->stream_stride % ( s16 ? 8u : 4u ) != 0 || ( (uintptr_t)io->d_samples & 15u ) )
-	return -EINVAL;			// rows must be 16-byte aligned (coalesced 16-byte staging)
     if ( int rc = mifsk_check_cfg(cfg) )
 	return rc;
     if ( cfg->auto_carrier_threshold > 0.0f )
@@ -438,8 +434,7 @@ extern "C" int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
     const unsigned waves = (unsigned)( ( cases + 63u ) / 64u );
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t per = 256u / d.n_bits;			// frames per block of softbits_rawbits_kernel
-    for ( uint32_t s0 = 0; s0 < (uint32_t)io->nstreams; s0 += kSoftMaxRows ) {
-	const uint32_t rows = (uint32_t)io->nstreams - s0 < kSoftMaxRows ? (uint32_t)io->nstreams - s0 : kSoftMaxRows;
+    return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	A.s0 = s0;
 	if ( s16 )
 	    launch_softbits<int16_t>(A, long_windows, dim3(waves, rows), st);
@@ -449,6 +444,6 @@ extern "C" int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
 	    hipLaunchKernelGGL(softbits_rawbits_kernel, dim3(( A.frames_cap + per - 1u ) / per, rows), dim3(256), 0, st,
 		    (const float2 *)A.mag, A.nframes, A.frames_cap, d.n_bits, s0,
 		    reinterpret_cast<unsigned long long *>(io->d_rawbits));
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -EIO;
+	return 0;
+    });
 }

@@ -3,34 +3,19 @@ restatement (tools/channel_ref.c, compiled into a temporary shared object), a ve
 evaluation of the definition, and the two end-to-end inputs with their condition."""
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = np.float32
-COMPLEX, S16 = 1, 2                 # channel_ref.c's kind bits
-KINDS = {"real-f32": 0, "real-s16": S16, "complex-f32": COMPLEX, "complex-s16": COMPLEX | S16}
+import _phase
+from _phase import COMPLEX, F32, KINDS, ROOT, S16, same_bits  # noqa: F401 (for the tests)
 
 
-@functools.lru_cache(maxsize=None)
 def ref_lib():
-    """tools/channel_ref.c as a shared object in a temporary directory: the machine's C compiler,
-    ROCm's clang where there is none; -O2 -ffp-contract=off"""
-    cc = shutil.which("cc") or shutil.which("gcc") or "/opt/rocm/lib/llvm/bin/clang"
-    so = os.path.join(tempfile.mkdtemp(prefix="channel_ref"), "channel_ref.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tools", "channel_ref.c"), "-lm"], check=True)
-    lib = C.CDLL(so)
-    lib.channel_ref_table.restype = None
-    lib.channel_ref_table.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.channel_ref.restype = C.c_uint64
-    lib.channel_ref.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
-                                C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p]
-    return lib
+    """tools/channel_ref.c as a shared object (_phase.ref_lib)"""
+    return _phase.ref_lib("channel_ref", (
+        ("channel_ref_table", None, (C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p)),
+        ("channel_ref", C.c_uint64, (C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p))))
 
 
 # the sampled product of the GPU test's sizes
@@ -107,11 +92,7 @@ def numpy_channelize(x, kind, P, taps, D, centres, r):
 
 def same_f32(a, b):
     """equal float bit patterns, any NaN equal to any NaN"""
-    a, b = np.asarray(a, F32), np.asarray(b, F32)
-    if a.shape != b.shape:
-        return False
-    nan = np.isnan(a) & np.isnan(b)
-    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | nan))
+    return same_bits(np.asarray(a, F32), np.asarray(b, F32))
 
 
 # ---------------------------------------------------------------------------

@@ -3,40 +3,20 @@
 definition with its rounding bound, the sampled sizes of the GPU test, and the closed-loop input."""
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = np.float32
-COMPLEX, S16 = 1, 2                 # mux_ref.c's kind bits
-KINDS = {"real-f32": 0, "real-s16": S16, "complex-f32": COMPLEX, "complex-s16": COMPLEX | S16}
+import _phase
+from _phase import COMPLEX, F32, KINDS, ROOT, S16, same_bits, vec_of  # noqa: F401 (for the tests)
 
 
-@functools.lru_cache(maxsize=None)
 def ref_lib():
-    """tools/mux_ref.c as a shared object in a temporary directory: the machine's C compiler, ROCm's
-    clang where there is none; -O2 -ffp-contract=off"""
-    cc = shutil.which("cc") or shutil.which("gcc") or "/opt/rocm/lib/llvm/bin/clang"
-    so = os.path.join(tempfile.mkdtemp(prefix="mux_ref"), "mux_ref.so")
-    subprocess.run([cc, "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so,
-                    os.path.join(ROOT, "tools", "mux_ref.c"), "-lm"], check=True)
-    lib = C.CDLL(so)
-    lib.mux_ref_table.restype = None
-    lib.mux_ref_table.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.mux_ref.restype = C.c_uint64
-    lib.mux_ref.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
-                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64,
-                            C.c_uint64, C.c_void_p]
-    return lib
-
-
-def vec_of(kind):
-    """output elements in 16 bytes"""
-    return 16 // ((2 if kind & S16 else 4) * (2 if kind & COMPLEX else 1))
+    """tools/mux_ref.c as a shared object (_phase.ref_lib)"""
+    return _phase.ref_lib("mux_ref", (
+        ("mux_ref_table", None, (C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p)),
+        ("mux_ref", C.c_uint64, (C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_uint64, C.c_void_p))))
 
 
 def full_outputs(n, L, T):
@@ -107,17 +87,6 @@ def numpy_multiplex(x, lens, P, taps, L, centres, r, gains=None):
         out[:y.size] += y * np.exp(2j * np.pi * p / P)
         mag[:y.size] += np.convolve(np.abs(up), np.abs(h)) * abs(gain)
     return out, mag
-
-
-def same_bits(a, b):
-    """equal bit patterns of two float32 or two int16 arrays, any NaN equal to any NaN"""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    if a.dtype == np.int16:
-        return bool(np.array_equal(a, b))
-    nan = np.isnan(a) & np.isnan(b)
-    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | nan))
 
 
 # ---------------------------------------------------------------------------

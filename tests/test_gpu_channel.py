@@ -1,6 +1,6 @@
 """mifsk_channelize_batch (include/mifsk.h, minimodem_amd/csrc/mifsk_channel.hip) against the host
 restatement tools/channel_ref.c: every output of every case bit for bit on the float patterns, no
-tolerance (a NaN equals a NaN).  Rows are at most 40 000 elements, batches at most 9 rows; both
+tolerance (a NaN equals a NaN).  Rows are at most 40 000 elements, batches at most 9 rows (but for one of 65 537 rows of 16); both
 output arrays are made with guard cells around them, which every call must leave alone."""
 import ctypes as C
 
@@ -347,3 +347,27 @@ def test_every_signal_of_a_recording_decodes_on_the_device(gpu, make):
     for k, payload in enumerate(c["payloads"]):
         decoded = res["bytes"][k, :int(res["nbytes"][k])].tobytes()
         assert Ch.payload_condition(decoded, payload), (k, decoded, payload)
+
+
+# ---------------------------------------------------------------------------
+# more rows than one launch takes (65 535, the grid's y limit): the row-block loop
+# ---------------------------------------------------------------------------
+def test_a_batch_of_more_rows_than_one_launch_takes(gpu):
+    M, torch, _ctx = gpu
+    rng = np.random.default_rng(65537)
+    nrows, n, cut = 65537, 16, 40000
+    x = rng.standard_normal((nrows, n)).astype(F32)
+    P, taps, D, centres, r = 7, np.array([0.75, -0.5], F32), 1, np.array([3], np.int32), 1
+    plan = make_plan(gpu, 0, P, taps, D, centres, r)
+    d = torch.from_numpy(x).cuda()
+    whole = M.channelize(plan, d)
+    parts = [M.channelize(plan, d[:cut]), M.channelize(plan, d[cut:])]
+    torch.cuda.synchronize()
+    plan.close()
+    rows, nout = whole["rows"].cpu().numpy(), whole["nsamples"].cpu().numpy()
+    assert rows.shape == (nrows, 16) and np.all(nout == n - 1)
+    assert Ch.same_f32(rows, np.concatenate([p["rows"].cpu().numpy() for p in parts]))
+    assert np.array_equal(nout, np.concatenate([p["nsamples"].cpu().numpy() for p in parts]))
+    for s in (0, 65534, 65535, 65536):
+        want = Ch.ref_channelize(x[s], 0, P, taps, D, centres, r)
+        assert want.shape == (1, n - 1) and Ch.same_f32(rows[s, :n - 1], want[0]) and rows[s, n - 1] == 0, s

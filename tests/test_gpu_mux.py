@@ -1,6 +1,6 @@
 """mifsk_multiplex_batch (include/mifsk.h, minimodem_amd/csrc/mifsk_mux.hip) against the host
 restatement tools/mux_ref.c: every output element and every count of every case bit for bit, no
-tolerance (a NaN equals a NaN).  Rows are a few thousand outputs (one case just over 2^20); both
+tolerance (a NaN equals a NaN).  Rows are a few thousand outputs (one case just over 2^20, one of 65 537 streams of 8 samples); both
 output arrays are made with guard cells around them, which every call must leave alone."""
 import ctypes as C
 
@@ -436,3 +436,28 @@ def test_the_four_step_chain_on_the_device(gpu, cx):
     for k, payload in enumerate(c["payloads"]):
         decoded = res["bytes"][k, :int(res["nbytes"][k])].tobytes()
         assert Ch.payload_condition(decoded, payload), (k, decoded, payload)
+
+
+# ---------------------------------------------------------------------------
+# more streams than one launch takes (65 535, the grid's y limit): the row-block loop
+# ---------------------------------------------------------------------------
+def test_a_batch_of_more_streams_than_one_launch_takes(gpu):
+    M, torch, _ctx = gpu
+    rng = np.random.default_rng(65537)
+    ns, n, cut = 65537, 8, 40000
+    x = rng.standard_normal((ns, n)).astype(F32)
+    P, taps, L, centres, r = 7, np.array([0.75, -0.5, 0.25], F32), 2, np.array([3], np.int32), 1
+    full = Mx.full_outputs(n, L, taps.size)
+    plan = make_plan(gpu, 0, P, taps, L, centres, r)
+    d = torch.from_numpy(x).cuda()
+    whole = M.multiplex(plan, d)
+    parts = [M.multiplex(plan, d[:cut]), M.multiplex(plan, d[cut:])]
+    torch.cuda.synchronize()
+    plan.close()
+    rows, nout = whole["rows"].cpu().numpy(), whole["nsamples"].cpu().numpy()
+    assert rows.shape == (ns, default_stride(0, n, L, taps.size)) and np.all(nout == full)
+    assert Mx.same_bits(rows, np.concatenate([p["rows"].cpu().numpy() for p in parts]))
+    assert np.array_equal(nout, np.concatenate([p["nsamples"].cpu().numpy() for p in parts]))
+    for s in (0, 65534, 65535, 65536):
+        want, cnt = Mx.ref_multiplex(x[s:s + 1], None, 0, P, taps, L, centres, r)
+        assert cnt == full and Mx.same_bits(rows[s], want), s

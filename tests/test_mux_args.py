@@ -169,6 +169,27 @@ def test_mux_table_equals_the_restatement_bit_for_bit(P):
         assert np.array_equal(g1[:, 0], ch[:, 0]) and np.array_equal(g1[:, 1], -ch[:, 1])
 
 
+@pytest.mark.parametrize("P", [1, 7, 4800, 1 << 20])
+def test_mux_table_is_the_channelizers_table_with_the_second_column_negated(P):
+    """The two tables are one routine (mifsk_phase.h, phase_rotated_taps): entry for entry the same bits
+    but for the sign bit of the second column (IEEE negation: of zeros and NaNs too)."""
+    rng = np.random.default_rng(P + 1)
+    special = np.array([0.0, -0.0, 1e-40, -1e-40, np.inf, -np.inf], F32)
+    assert np.all(np.abs(special[2:4]) < np.finfo(F32).tiny) and np.all(special[2:4] != 0)     # subnormal
+    taps = np.concatenate([special, rng.standard_normal(19).astype(F32), special[::-1]])
+    sign = np.uint64(1) << np.uint64(63)
+    tried = 0
+    for q in (0, 1, -1, P - 1, -(P - 1)):
+        if abs(q) >= P:
+            continue
+        mx = M.mux_table(taps, q, P).view(np.uint64)
+        ch = M.channel_table(taps, [q], 0, P).view(np.uint64)
+        assert mx.shape == ch.shape == (taps.size, 2)
+        assert np.array_equal(mx[:, 0], ch[:, 0]) and np.array_equal(mx[:, 1], ch[:, 1] ^ sign), (P, q)
+        tried += 1
+    assert tried == (3 if P == 1 else 5)                # P = 1: 0, P - 1 and -(P - 1) are all 0
+
+
 @pytest.mark.parametrize("gains", [False, True], ids=["plain", "gains"])
 @pytest.mark.parametrize("name", list(Mx.KINDS))
 def test_the_restatement_against_float64(name, gains):

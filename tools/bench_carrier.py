@@ -22,16 +22,14 @@ outputs written once.
 
 Needs the GPU: there is no other path.
 """
-import argparse
 import json
-import os
 import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _benchsteps as B
+
+sys.path.insert(0, B.ROOT)
 
 HBM_PEAK = 8.0e12
 WORKLOADS = {
@@ -42,7 +40,7 @@ WORKLOADS = {
     "rtty": ("rtty", 64, 2880000, 0, False, False),
     "1200-hop8": ("1200", 1024, 480000, 8, False, False),
 }
-LIMITS = {"fma64": 120, "legacy": 120}          # seconds; a workload step: 240
+LIMITS = {"workload": 240, "legacy": 120}       # seconds
 
 
 def make_rows(torch, cfg, rows, n, pcm16):
@@ -79,25 +77,11 @@ def step_workload(name, rounds, window_ms, preheat_ms):
     def call():
         M.carrier_survey(ctx, cfg, d, window=window, hop=hop, spectrum=spectrum, out=out)
 
-    def timed(k):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(k):
-            call()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / k
-
-    t0 = time.perf_counter()
-    while (time.perf_counter() - t0) * 1e3 < preheat_ms:
-        call()
-        torch.cuda.synchronize()
-    k = max(2, int(window_ms / max(timed(2), 1e-3)))
-    ms = [timed(k) for _ in range(rounds)]
+    k, ms = B.timed_windows(call, rounds, window_ms, preheat_ms)
     band = out["band"]
     found = int((band >= 0).sum())
     assert int((band == -2).sum()) == 0 and found > rows * nwin // 4, (found, rows * nwin)
-    med = statistics.median(ms)
+    med = ms["median"]
     windows = rows * nwin
     fma = windows * int(cfg.nbands) * window * 2
     read = rows * n * (2 if pcm16 else 4)
@@ -106,7 +90,7 @@ def step_workload(name, rounds, window_ms, preheat_ms):
                         "pcm16": pcm16, "spectrum": spectrum, "nbands": int(cfg.nbands), "fftsize": int(cfg.fftsize),
                         "windows": windows, "windows_with_a_band": found},
            "device": ctx.device_name, "launches_per_window": k, "rounds": rounds,
-           "ms": {"median": med, "min": min(ms), "max": max(ms)},
+           "ms": ms,
            "windows_per_s": windows / med * 1e3, "fma_per_s": fma / med * 1e3,
            "bytes_read": read, "bytes_written": written,
            "read_bytes_per_s": read / med * 1e3, "written_bytes_per_s": written / med * 1e3,
@@ -136,63 +120,20 @@ def step_legacy():
                       "windows_per_s": 256 / med, "windows_with_a_band": sum(b >= 0 for b in bands)}))
 
 
-def run_step(argv, limit):
-    """one step in a process of its own: its last line of output as JSON, or the run ends here"""
-    try:
-        p = subprocess.run(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=limit, text=True)
-    except subprocess.TimeoutExpired:
-        sys.exit("%s: no result within %d s; nothing further is started" % (" ".join(argv), limit))
-    if p.returncode != 0:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-        sys.exit("%s: exit status %d; nothing further is started" % (" ".join(argv), p.returncode))
-    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    return json.loads(lines[-1]), p.stdout
+def show(name, r, peak):
+    print("%-14s %8.3f ms  %.3e windows/s  %.2f TFMA/s (%.0f %% of %.2f)  read %.2f TB/s" % (
+        name, r["ms"]["median"], r["windows_per_s"], r["fma_per_s"] * 1e-12,
+        100 * r["share_of_measured_fma64"], peak * 1e-12, r["read_bytes_per_s"] * 1e-12), flush=True)
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--step", help="(internal) run one step in this process")
-    ap.add_argument("--only", nargs="*", help="workloads to run (default: all)")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--window-ms", type=float, default=300.0)
-    ap.add_argument("--preheat-ms", type=float, default=300.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "carrier_survey.json"))
-    a = ap.parse_args()
-    if a.step == "legacy":
-        return step_legacy()
-    if a.step:
-        return step_workload(a.step, a.rounds, a.window_ms, a.preheat_ms)
-
-    result = {"method": {"events": "one pair around K launches on one stream", "rounds": a.rounds,
-                         "window_ms": a.window_ms, "preheat_ms": a.preheat_ms,
-                         "fma_count": "windows x bands x samples x 2"}}
-    ub = os.path.join(ROOT, "tools", "ubench", "fma64_rate")
-    if not os.path.exists(ub):
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-o", ub, ub + ".hip"], check=True)
-    fma, text = run_step([ub], LIMITS["fma64"])
-    result["fma64"] = dict(fma, output=text.splitlines()[:-1])
-    peak = fma["fma64_per_s"]
-    me = [sys.executable, os.path.abspath(__file__), "--rounds", str(a.rounds), "--window-ms", str(a.window_ms),
-          "--preheat-ms", str(a.preheat_ms)]
-    result["workloads"] = {}
-    for name in (a.only or list(WORKLOADS)):
-        r, _ = run_step(me + ["--step", name], 240)
-        r["share_of_measured_fma64"] = r["fma_per_s"] / peak
-        result["workloads"][name] = r
-        print("%-14s %8.3f ms  %.3e windows/s  %.2f TFMA/s (%.0f %% of %.2f)  read %.2f TB/s" % (
-            name, r["ms"]["median"], r["windows_per_s"], r["fma_per_s"] * 1e-12,
-            100 * r["share_of_measured_fma64"], peak * 1e-12, r["read_bytes_per_s"] * 1e-12), flush=True)
-    legacy, _ = run_step(me + ["--step", "legacy"], LIMITS["legacy"])
+def finish(result, step):
+    legacy = step("legacy", LIMITS["legacy"])
     result["legacy_host_loop"] = legacy
     if "1200" in result["workloads"]:
         result["batched_over_legacy_windows_per_s"] = result["workloads"]["1200"]["windows_per_s"] / legacy["windows_per_s"]
         assert result["batched_over_legacy_windows_per_s"] > 1.0, "the batched call must be faster per window"
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
-    print(json.dumps(result))
 
 
 if __name__ == "__main__":
-    main()
+    B.main(__file__, __doc__, "carrier_survey.json", 300.0, "windows x bands x samples x 2",
+           WORKLOADS, LIMITS["workload"], step_workload, show, steps={"legacy": step_legacy}, finish=finish)

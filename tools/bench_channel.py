@@ -17,23 +17,19 @@ plus the outputs written once.
 
 Needs the GPU: there is no other path.
 """
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _benchsteps as B
+
+sys.path.insert(0, B.ROOT)
 
 WORKLOADS = {
     # name: (rows, elements per row, input rate, complex, pcm16, channels, taps, cutoff, decimation, phase steps)
     "real-48k": (64, 2880000, 48000.0, False, False, 16, 385, 400.0, 1, 4800),
     "iq-1.92M": (8, 19200000, 1920000.0, True, True, 64, 513, 9000.0, 40, 19200),
 }
-LIMITS = {"fma64": 120, "workload": 300}          # seconds
+LIMIT = 300                 # seconds a workload step may take
 
 
 def step_workload(name, rounds, window_ms, preheat_ms):
@@ -60,26 +56,12 @@ def step_workload(name, rounds, window_ms, preheat_ms):
     def call():
         M.channelize(plan, d, out=out)
 
-    def timed(k):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(k):
-            call()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / k
-
-    t0 = time.perf_counter()
-    while (time.perf_counter() - t0) * 1e3 < preheat_ms:
-        call()
-        torch.cuda.synchronize()
-    k = max(2, int(window_ms / max(timed(2), 1e-3)))
-    ms = [timed(k) for _ in range(rounds)]
+    k, ms = B.timed_windows(call, rounds, window_ms, preheat_ms)
     nout = M.carrier_windows(n, T, D)
     counts = out["nsamples"].cpu().numpy()
     assert counts.shape == (rows * K,) and (counts == nout).all(), (counts[:4], nout)
     assert bool(torch.isfinite(out["rows"][::max(1, rows * K // 8), :4096]).all())
-    med = statistics.median(ms)
+    med = ms["median"]
     outputs = rows * K * nout
     fma = outputs * T * (4 if cx else 2)
     read = rows * n * (2 if s16 else 4) * (2 if cx else 1)
@@ -87,7 +69,7 @@ def step_workload(name, rounds, window_ms, preheat_ms):
     res = {"workload": {"rows": rows, "elements_per_row": n, "input_rate": fs, "complex": cx, "pcm16": s16,
                         "channels": K, "taps": T, "decimation": D, "phase_steps": P, "outputs": outputs},
            "device": ctx.device_name, "launches_per_window": k, "rounds": rounds,
-           "ms": {"median": med, "min": min(ms), "max": max(ms)},
+           "ms": ms,
            "outputs_per_s": outputs / med * 1e3, "fma_per_s": fma / med * 1e3,
            "input_seconds_per_s": rows * n / fs / med * 1e3,
            "bytes_read": read, "bytes_written": written,
@@ -97,56 +79,12 @@ def step_workload(name, rounds, window_ms, preheat_ms):
     print(json.dumps(res))
 
 
-def run_step(argv, limit):
-    """one step in a process of its own: its last line of output as JSON, or the run ends here"""
-    try:
-        p = subprocess.run(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=limit, text=True)
-    except subprocess.TimeoutExpired:
-        sys.exit("%s: no result within %d s; nothing further is started" % (" ".join(argv), limit))
-    if p.returncode != 0:
-        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-        sys.exit("%s: exit status %d; nothing further is started" % (" ".join(argv), p.returncode))
-    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
-    return json.loads(lines[-1]), p.stdout
-
-
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--step", help="(internal) run one step in this process")
-    ap.add_argument("--only", nargs="*", help="workloads to run (default: all)")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--window-ms", type=float, default=600.0)
-    ap.add_argument("--preheat-ms", type=float, default=300.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channelize.json"))
-    a = ap.parse_args()
-    if a.step:
-        return step_workload(a.step, a.rounds, a.window_ms, a.preheat_ms)
-
-    result = {"method": {"events": "one pair around K launches on one stream", "rounds": a.rounds,
-                         "window_ms": a.window_ms, "preheat_ms": a.preheat_ms,
-                         "fma_count": "outputs x taps x 2 (real rows) or 4 (complex rows)"}}
-    ub = os.path.join(ROOT, "tools", "ubench", "fma64_rate")
-    if not os.path.exists(ub):
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-o", ub, ub + ".hip"], check=True)
-    fma, text = run_step([ub], LIMITS["fma64"])
-    result["fma64"] = dict(fma, output=text.splitlines()[:-1])
-    peak = fma["fma64_per_s"]
-    me = [sys.executable, os.path.abspath(__file__), "--rounds", str(a.rounds), "--window-ms", str(a.window_ms),
-          "--preheat-ms", str(a.preheat_ms)]
-    result["workloads"] = {}
-    for name in (a.only or list(WORKLOADS)):
-        r, _ = run_step(me + ["--step", name], LIMITS["workload"])
-        r["share_of_measured_fma64"] = r["fma_per_s"] / peak
-        result["workloads"][name] = r
-        print("%-10s %9.3f ms  %.3e outputs/s  %.2f TFMA/s (%.0f %% of %.2f)  %.0f s of input per s" % (
-            name, r["ms"]["median"], r["outputs_per_s"], r["fma_per_s"] * 1e-12,
-            100 * r["share_of_measured_fma64"], peak * 1e-12, r["input_seconds_per_s"]), flush=True)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(result, f, indent=1)
-        f.write("\n")
-    print(json.dumps(result))
+def show(name, r, peak):
+    print("%-10s %9.3f ms  %.3e outputs/s  %.2f TFMA/s (%.0f %% of %.2f)  %.0f s of input per s" % (
+        name, r["ms"]["median"], r["outputs_per_s"], r["fma_per_s"] * 1e-12,
+        100 * r["share_of_measured_fma64"], peak * 1e-12, r["input_seconds_per_s"]), flush=True)
 
 
 if __name__ == "__main__":
-    main()
+    B.main(__file__, __doc__, "channelize.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
+           WORKLOADS, LIMIT, step_workload, show)
