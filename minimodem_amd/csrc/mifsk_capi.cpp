@@ -367,14 +367,6 @@ static void derive_cfg( mifsk_ctx *ctx, const mifsk_rx_config &cfg, DevCfg &d )
     }
 }
 
-int mifsk_check_cfg( const mifsk_rx_config *cfg )
-{
-    if ( !cfg || cfg->expect_n_bits == 0 || cfg->expect_n_bits > MIFSK_MAX_FRAME_BITS
-	    || cfg->bit_nsamples == 0 || cfg->fftsize < 2 )
-	return -EINVAL;
-    return 0;
-}
-
 // ---------------------------------------------------------------------------
 // batch entry points
 // ---------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 //   expect strings                               src/minimodem.c:442-487,1115-1131
 //   search grid                                  src/minimodem.c:1236-1263,1366
 //   bit windows inside fsk_find_frame            src/fsk.c:183,204,465
+#include <algorithm>
 #include <cerrno>
 #include <cmath>
 #include <cstdlib>
@@ -278,6 +279,15 @@ extern "C" int mifsk_rx_config_init( mifsk_rx_config *cfg, const mifsk_modem_arg
     return 0;
 }
 
+// -EINVAL for a configuration the kernels cannot take (mifsk_ctx.h; mifsk_timesplit.h for the sources that build without it)
+int mifsk_check_cfg( const mifsk_rx_config *cfg )
+{
+    if ( !cfg || cfg->expect_n_bits == 0 || cfg->expect_n_bits > MIFSK_MAX_FRAME_BITS
+	    || cfg->bit_nsamples == 0 || cfg->fftsize < 2 )
+	return -EINVAL;
+    return 0;
+}
+
 extern "C" size_t mifsk_max_frames( const mifsk_rx_config *cfg, size_t nsamples )
 {
     // every decoded frame advances the cursor by at least
@@ -285,6 +295,17 @@ extern "C" size_t mifsk_max_frames( const mifsk_rx_config *cfg, size_t nsamples 
     size_t adv = cfg->frame_nsamples > cfg->nsamples_overscan
 		? cfg->frame_nsamples - cfg->nsamples_overscan : 1;
     return nsamples / adv + 2;
+}
+
+extern "C" size_t mifsk_max_episodes( const mifsk_rx_config *cfg, size_t nsamples )
+{
+    if ( !cfg )
+	return 0;
+    // an episode is at least one frame followed by 21 searches without confidence,
+    // each of which moves the cursor by the search range (minimodem.c:1292-1321,1407)
+    const size_t adv = cfg->frame_nsamples > cfg->nsamples_overscan ? cfg->frame_nsamples - cfg->nsamples_overscan : 1;
+    const size_t tm = std::min(cfg->try_max[0], cfg->try_max[1]);
+    return nsamples / ( adv + 21 * ( tm ? tm : 1 ) ) + 2;
 }
 
 extern "C" size_t mifsk_stream_padding( const mifsk_rx_config *cfg )

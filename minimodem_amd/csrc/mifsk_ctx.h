@@ -15,8 +15,6 @@
 namespace mifsk {
 struct HostWork;
 void host_work_destroy( HostWork *w );		// (mifsk_hostpipe.cpp)
-// what the time split's planner refuses whatever the lengths are, host only (mifsk_timesplit.hip)
-int time_split_check_params( const mifsk_rx_config *cfg, const mifsk_time_split *params );
 }
 
 using mifsk::DevCfg;
@@ -80,7 +78,7 @@ struct mifsk_ctx {
 	return -EIO; } } while (0)
 
 
-// -EINVAL for a configuration the kernels cannot take (mifsk_capi.cpp)
+// -EINVAL for a configuration the kernels cannot take (mifsk_config.cpp)
 int mifsk_check_cfg( const mifsk_rx_config *cfg );
 
 namespace mifsk {

@@ -40,6 +40,7 @@
 #include "mifsk_ctx.h"
 #include "mifsk_hostmem.h"
 #include "mifsk_outputs.h"
+#include "mifsk_timesplit.h"
 
 namespace mifsk {
 
@@ -738,17 +739,6 @@ struct mifsk_files {
     bool				time_split = false;
     std::vector<mifsk_time_split_stats>	tsplit;
 };
-
-extern "C" size_t mifsk_max_episodes( const mifsk_rx_config *cfg, size_t nsamples )
-{
-    if ( !cfg )
-	return 0;
-    // an episode is at least one frame followed by 21 searches without confidence,
-    // each of which moves the cursor by the search range (minimodem.c:1292-1321,1407)
-    const size_t adv = cfg->frame_nsamples > cfg->nsamples_overscan ? cfg->frame_nsamples - cfg->nsamples_overscan : 1;
-    const size_t tm = std::min(cfg->try_max[0], cfg->try_max[1]);
-    return nsamples / ( adv + 21 * ( tm ? tm : 1 ) ) + 2;
-}
 
 // ---- headers (threads): format, rate, where the samples start, how many
 static void read_headers( mifsk_files *F, const char *const *paths, int nfiles )

@@ -10,9 +10,16 @@
 // when the CONTROL fields of X_k equal those of S_{k-1} (translated by L; DESIGN.md "cutting a
 // stream in time") everything row k decodes is what one call decodes there.  A rejected chunk
 // is run again from S_{k-1}: a round re-runs every row whose starting state disagrees with its
-// predecessor's current pause (settled or not) in one batch, and the consistent prefix is settled.  The stitch kernels below turn the per-row outputs into one stream's outputs,
-// fixing up the BOOKKEEPING fields (counts, frame indices, episode totals) that the rows cannot
-// know.  The loop kernels themselves are the existing ones, called through mifsk_demod_slab.
+// predecessor's current pause (settled or not) in one batch, and the consistent prefix is settled.
+// The stitch kernels below turn the per-row outputs into one stream's outputs, fixing up the
+// BOOKKEEPING fields (counts, frame indices, episode totals) that the rows cannot know.  The loop
+// kernels themselves are the existing ones, called through mifsk_demod_slab.
+//
+// Here: the kernels and the driver, a Job whose phases run() calls in order -- uncut(), or gather(),
+// pass_a(), pass_b(), rounds(), tails(), stitch().  What the host decides between the launches (the
+// planner, the row table, which rows a round settles, drops or runs again, where the tails go) is
+// plain C++ in mifsk_timesplit_plan.cpp (mifsk_timesplit.h), checked on a CPU by
+// tools/timesplit_rounds.cpp.
 //
 // Field classification of mifsk_stream_state (both engines):
 //   control      base, rp (relative), advance, flags, noconfidence (saturating: every value
@@ -32,38 +39,13 @@
 #include "mifsk_ctx.h"
 #include "mifsk_hostmem.h"
 #include "mifsk_outputs.h"
+#include "mifsk_timesplit.h"
 
 using mifsk::StreamMem;
 
+using namespace mifsk::timesplit;
+
 namespace {
-
-constexpr uint32_t kSentinel = 0xFFFFFFFFu;	// ep_first of an episode that began before the row
-constexpr uint32_t kNoconfSat = 21u;		// FSK_MAX_NOCONFIDENCE_BITS + 1 (minimodem.c:1294)
-constexpr double kDefaultWarmupSeconds = 10.0;	// DESIGN.md "cutting a stream in time"
-constexpr uint32_t kChunksPerCu = 4;
-// The rows are laid out apart, so the copy holds the recording plus (K - 1) * W samples of
-// warm-up overlap; the library's choice of K keeps that overlap within this many bytes.
-constexpr uint64_t kOverlapBudget = 4ull << 30;
-
-// A row's starting state with the bookkeeping zeroed: the row's outputs then count from 0 and
-// its running episode values are deltas against the state it starts from.  `shift` moves the
-// state into the coordinates of a row that starts `shift` samples later.
-__host__ __device__ inline mifsk_stream_state reset_book( mifsk_stream_state s, uint64_t shift )
-{
-    s.base -= shift;
-    s.rp -= shift;
-    s.carrier_nsamples = 0;
-    s.nframes_total = 0;
-    s.confidence_total = 0.0f;
-    s.amplitude_total = 0.0f;
-    s.nframes_decoded = 0;
-    s.first_band = -1;
-    s.ep_first = ( s.flags & MIFSK_STATE_CARRIER ) ? kSentinel : 0u;
-    s.nbytes_total = 0;
-    s.nepisodes_total = 0;
-    s.status = 0;
-    return s;
-}
 
 __device__ inline bool same_control( const mifsk_stream_state &p, const mifsk_stream_state &x,
 	uint64_t L )
@@ -75,19 +57,6 @@ __device__ inline bool same_control( const mifsk_stream_state &p, const mifsk_st
 	&& __float_as_uint(p.peak_confidence) == __float_as_uint(x.peak_confidence)
 	&& p.carrier_band == x.carrier_band && p.b_mark == x.b_mark;
 }
-
-// Several recordings are cut by one plan (mifsk_demod_long_batch): all streams' chunks are rows of
-// one flat batch, row rowbase[m] + k being chunk k of stream m, and stream m's tail is row R + m
-// behind the R chunk rows.  A row is verified against its predecessor only inside its own stream.
-struct RowRef {
-    uint32_t	m, k;		// chunk k of stream m (k == K of the stream: its tail)
-};
-
-struct StreamRef {
-    uint64_t	n;		// the stream's length
-    uint64_t	tail_off;	// where its tail starts
-    uint32_t	rowbase, K;	// its chunks are rows rowbase .. rowbase + K - 1
-};
 
 // One PCM16 sample as a float: the expression of ingest_s16_kernel (mifsk_ingest.hip), so that a
 // row gathered from PCM16 is bit for bit the row gathered from mifsk_ingest_s16's floats.
@@ -496,123 +465,6 @@ __global__ void ts_episodes( StitchArgs a )
     }
 }
 
-uint64_t gcd64( uint64_t a, uint64_t b )
-{
-    while ( b ) {
-	const uint64_t t = a % b;
-	a = b;
-	b = t;
-    }
-    return a;
-}
-
-const unsigned kKnownFlags = MIFSK_IO_RING_EXACT | MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE
-			   | MIFSK_TIME_SPLIT_REJECT_ALL;
-
-} // namespace
-
-// What the planner refuses whatever the lengths are (host only; the entry points that take host
-// memory or files ask this before they touch the device or a file): the configuration, the flags,
-// a warmup below 2 * samplebuf_size, a chunk off the lattice.
-int mifsk::time_split_check_params( const mifsk_rx_config *cfg, const mifsk_time_split *params )
-{
-    if ( mifsk_check_cfg(cfg) )
-	return -EINVAL;
-    mifsk_time_split p;
-    std::memset(&p, 0, sizeof(p));
-    if ( params )
-	p = *params;
-    if ( p.flags & ~kKnownFlags )
-	return -EINVAL;
-    if ( ( p.flags & MIFSK_IO_ENGINE_WORKGROUP ) && ( p.flags & MIFSK_IO_ENGINE_WAVE ) )
-	return -EINVAL;
-    if ( p.flags & MIFSK_IO_RING_EXACT )
-	return -ENOTSUP;
-    if ( cfg->samplebuf_size < 2u )
-	return -EINVAL;
-    const uint64_t half = cfg->samplebuf_size / 2u;
-    const uint64_t lattice = half / gcd64(half, 4) * 4;		// lcm(samplebuf_size / 2, 4)
-    if ( p.warmup && p.warmup < 2ull * cfg->samplebuf_size )
-	return -EINVAL;
-    if ( p.chunk && ( p.chunk % lattice || p.chunk >= 0x7FFFFFF0ull ) )
-	return -EINVAL;
-    if ( p.warmup >= 0x7FFFFFF0ull )
-	return -EINVAL;		// (rows are uint32 lengths; keeps the planner's arithmetic exact)
-    return 0;
-}
-
-namespace {
-
-// the planner, for a batch of recordings cut by one W and one L (every row has the same stride,
-// a pass is one launch); chunks_hint: the chunk count that fills the chip (0: params->chunks or
-// the default of a host-only call)
-int plan( const mifsk_rx_config *cfg, const uint64_t *n, int nstreams, const mifsk_time_split *params,
-	uint32_t chunks_hint, mifsk_time_split_stats *out )
-{
-    if ( !cfg || !out || !n || nstreams <= 0 )
-	return -EINVAL;
-    if ( const int rc = mifsk::time_split_check_params(cfg, params) )
-	return rc;
-    mifsk_time_split p;
-    std::memset(&p, 0, sizeof(p));
-    if ( params )
-	p = *params;
-    const uint64_t half = cfg->samplebuf_size / 2u;
-    const uint64_t lattice = half / gcd64(half, 4) * 4;		// lcm(samplebuf_size / 2, 4)
-    const uint64_t wmin = 2ull * cfg->samplebuf_size;
-    uint64_t W = p.warmup;
-    if ( !W ) {
-	W = (uint64_t)( kDefaultWarmupSeconds * cfg->sample_rate );
-	W = std::max(W, wmin);
-    }
-    // what the chunks have to cover, and the longest stream
-    uint64_t cover = 0, longest = 0;
-    for ( int m = 0; m < nstreams; m++ ) {
-	if ( n[m] >= ( 1ull << 62 ) )
-	    return -EINVAL;
-	longest = std::max(longest, n[m]);
-	if ( n[m] > W )
-	    cover += n[m] - W;
-	if ( cover >= ( 1ull << 62 ) )
-	    return -EINVAL;
-    }
-    uint64_t L = p.chunk;
-    uint64_t rows = (uint64_t)nstreams;
-    bool split = false;
-    if ( cover ) {
-	if ( !L ) {
-	    // (sum of K_m - 1 <= cover / L <= target: the cap bounds the rows' warm-up overlap)
-	    uint64_t target = p.chunks ? p.chunks : ( chunks_hint ? chunks_hint : 1024u );
-	    target = std::min(target, std::max<uint64_t>(2, kOverlapBudget / ( W * sizeof(float) )));
-	    L = ( cover + target - 1 ) / target;
-	    L = std::max(lattice, ( L + lattice - 1 ) / lattice * lattice);
-	}
-	rows = 0;
-	for ( int m = 0; m < nstreams; m++ )
-	    rows += n[m] > W ? ( n[m] - W ) / L + 1 : 1;
-	split = rows > (uint64_t)nstreams;
-	// the library's choice: a split pays when a row (about L + 2 W) is well short of the whole
-	if ( !p.chunk && !p.warmup && 4 * W > longest )
-	    split = false;
-    }
-    if ( split && ( L + W >= 0x7FFFFFF0ull || rows > 0x7FFFFFFull ) )
-	return -EINVAL;
-    if ( !split && longest > 0xFFFFFFF0ull )
-	return -EINVAL;
-    for ( int m = 0; m < nstreams; m++ ) {
-	const uint64_t K = split && n[m] > W ? ( n[m] - W ) / L + 1 : 1;
-	mifsk_time_split_stats &o = out[m];
-	std::memset(&o, 0, sizeof(o));
-	o.nsamples = n[m];
-	o.warmup = W;
-	o.lattice = lattice;
-	o.nchunks = (uint32_t)K;
-	o.chunk = split ? L : n[m];		// (one chunk everywhere: the single call, no cut)
-	o.samples_speculative = 2 * ( K - 1 ) * W;
-    }
-    return 0;
-}
-
 unsigned blocks_for( uint64_t stride )
 {
     return (unsigned)std::min<uint64_t>(64, std::max<uint64_t>(1, ( stride / 4 + 255 ) / 256));
@@ -649,28 +501,6 @@ void gather_tails( const Src &src, dim3 grid, hipStream_t st, const StreamRef *s
 			   (uint64_t)src.stride, streams, tails, stride, nstreams, 0.0f);
 }
 
-// The rows: stream m's chunks are rows rowbase[m] .. rowbase[m] + K_m - 1, its tail (the final
-// slab) is row R + m
-void row_table( const uint64_t *nsamples, const std::vector<mifsk_time_split_stats> &ps, int R,
-	std::vector<StreamRef> &hs, std::vector<RowRef> &hrow, std::vector<uint32_t> &hns )
-{
-    const int M = (int)ps.size();
-    const uint64_t L = ps[0].chunk, W = ps[0].warmup;
-    for ( int m = 0, r = 0; m < M; m++ ) {
-	hs[m].n = nsamples[m];
-	hs[m].tail_off = 0;
-	hs[m].rowbase = (uint32_t)r;
-	hs[m].K = ps[m].nchunks;
-	for ( uint32_t k = 0; k < hs[m].K; k++, r++ ) {
-	    hrow[r].m = (uint32_t)m;
-	    hrow[r].k = k;
-	    hns[r] = (uint32_t)( k + 1 < hs[m].K ? L + W : nsamples[m] - k * L );
-	}
-	hrow[R + m].m = (uint32_t)m;
-	hrow[R + m].k = hs[m].K;
-    }
-}
-
 // Rows [lo, lo + count) of `b`, the batch of all rows from row 0 on: their samples and lengths,
 // their part of the per-row result buffers, and their four counts, which lie nrows apart in `cnt`.
 mifsk_demod_io rows_of( mifsk_demod_io b, uint32_t *cnt, int nrows, int lo, int count )
@@ -686,47 +516,284 @@ mifsk_demod_io rows_of( mifsk_demod_io b, uint32_t *cnt, int nrows, int lo, int 
     return b;
 }
 
-// The host half of a round, which launches nothing.  From the codes of ts_verify: every stream's
-// settled prefix grows over the rows that are consistent (accepted, unless they ran again) or
-// dropped, and every unsettled row whose code is 0 is marked to run again in `hmark` -- rows
-// [lo, hi] hold them all; lo < 0: there is none, the rounds are over.
-void settle_round( const std::vector<uint32_t> &hcode, const std::vector<StreamRef> &hs,
-	const std::vector<uint32_t> &hns, std::vector<uint8_t> &settled, std::vector<uint8_t> &drop,
-	std::vector<uint8_t> &ran, std::vector<mifsk_time_split_stats> &ps, std::vector<uint8_t> &hmark,
-	int &lo, int &hi )
-{
-    lo = hi = -1;
-    std::fill(hmark.begin(), hmark.end(), 0);
-    for ( size_t m = 0; m < hs.size(); m++ ) {
-	const int r0 = (int)hs[m].rowbase, r1 = r0 + (int)hs[m].K;
-	for ( int r = r0 + 1; r < r1; r++ ) {
-	    if ( settled[r] )
-		continue;
-	    if ( !settled[r - 1] )
-		break;
-	    if ( drop[r - 1] || ( hcode[r] & 2u ) ) {
-		drop[r] = settled[r] = 1;
-	    } else if ( hcode[r] & 1u ) {
-		settled[r] = 1;
-		ps[m].accepted += !ran[r];
-	    } else {
-		break;
-	    }
-	}
-	bool any = false;
-	for ( int r = r0 + 1; r < r1; r++ )
-	    if ( !settled[r] && hcode[r] == 0u ) {	// (behind a finished row: wait for it to settle)
-		hmark[r] = 1;
-		any = true;
-		if ( lo < 0 )
-		    lo = r;
-		hi = r;
-		ran[r] = 1;
-		ps[m].rerun++;
-		ps[m].samples_rerun += hns[r];
-	    }
-	ps[m].rounds += any;
+// a per-call device array of T, allocated and freed in the order of the call's stream
+template <class T>
+struct Buf : StreamMem {
+    using StreamMem::StreamMem;
+    T *d() const { return (T *)p; }
+    int make( size_t n ) { return alloc(n * sizeof(T)); }
+};
+
+// One call from its plan to its outputs: the arguments, the row layout, every host array that a
+// copy on the stream reads or writes (all of them live to the end of the call) and the device
+// buffers.  run() calls the phases in order: uncut(), or gather(), pass_a(), pass_b(), rounds(),
+// tails(), stitch().
+struct Job {
+    mifsk_ctx			*ctx;
+    const mifsk_rx_config	*cfg;
+    const Src			src;
+    const float			rxnoise;
+    const uint64_t		*nsamples;
+    const mifsk_demod_io	*io_out;
+    void			*stream;
+    const hipStream_t		st;
+    const unsigned		flags, engine;
+    std::vector<mifsk_time_split_stats> ps;	// the plan, then the call's statistics
+    RowLayout			lay;
+
+    // host
+    std::vector<uint32_t>	hn;		// uncut: the rows' lengths
+    struct { StreamRef s; RowRef r; } one;	// uncut: the table of a lone row that is gathered
+    RowFlags			f{lay};
+    std::vector<uint32_t>	hcode;		// [nrows] ts_verify's codes of a round
+    std::vector<mifsk_stream_state> last;	// [M] the last chunks' pauses, then the tails' starts
+    mifsk_demod_io		b;		// pass B's batch of all R rows: re-runs and tails are rows_of it
+
+    // device (the uncut batch uses the first two only)
+    Buf<float>			pad{st};	// uncut: the rows as floats, every row defined up to its stride
+    StreamMem			table{st};	// uncut: the rows' lengths, or `one`
+    Buf<float>			rows{st};	// [R][rstride]: the chunks, laid out apart
+    // [nrows] each: pass A's runs from zero to their pauses, the guesses at the chunks' entry states;
+    // the state a row's kept outputs started from; the state that run paused in (a tail's: finished);
+    // a round's re-runs, from start to pause ([R + m]: stream m's last pause, on its way to the host)
+    Buf<mifsk_stream_state>	guess{st}, start{st}, pause{st}, rerun{st};
+    // [4][nrows]: nframes, nbytes, nepisodes, status of the kept runs, and of a round's re-runs
+    Buf<uint32_t>		counts{st}, rerun_counts{st};
+    Buf<uint32_t>		code{st};	// [nrows] ts_verify
+    // [nrows] bytes with two tenants and one hand-over: a round's marks (d_mark) from gather() to
+    // the end of rounds(), the drop flags (d_drop) from the end of tails() on, which copies them over
+    Buf<uint8_t>		row_flags{st};
+    uint8_t			*d_mark = nullptr;
+    const uint8_t		*d_drop = nullptr;
+    Buf<mifsk_frame>		rframes{st};	// [nrows][fcap]
+    Buf<uint8_t>		rbytes{st};	// [nrows][fcap], where the caller wants bytes
+    Buf<mifsk_episode>		reps{st};	// [nrows][ecap]
+    Buf<Agg>			pref{st};	// [nrows + M] ts_scan
+    Buf<uint32_t>		ns{st};		// [nrows] lay.hns
+    Buf<StreamRef>		streams{st};	// [M] lay.hs
+    Buf<RowRef>			rowref{st};	// [nrows] lay.hrow
+    Buf<float>			tail_rows{st};	// [M][tstride]
+
+    static constexpr unsigned	tb = 256;	// the small per-row kernels' block
+    unsigned blocks( int n ) const { return (unsigned)( ( n + tb - 1 ) / tb ); }
+
+    Job( mifsk_ctx *ctx_, const mifsk_rx_config *cfg_, const Src &src_, float rxnoise_, const uint64_t *nsamples_,
+	    unsigned flags_, const mifsk_demod_io *io_out_, void *stream_, std::vector<mifsk_time_split_stats> plan_ )
+	: ctx(ctx_), cfg(cfg_), src(src_), rxnoise(rxnoise_), nsamples(nsamples_), io_out(io_out_), stream(stream_),
+	  st((hipStream_t)stream_), flags(flags_), engine(flags_ & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE )),
+	  ps(std::move(plan_)), lay(cfg_, nsamples_, ps), hcode(lay.nrows, 0), last(lay.M)
+    {
     }
+
+    int uncut(), gather(), pass_a(), pass_b(), rounds(), tails(), stitch();
+};
+
+// No stream is cut: the existing call over the batch.  A batch of floats is taken where it is, and
+// so is a lone row of whole float4s (no allocation, no copy); any other lone row goes over a padded
+// copy, its stride being its length in whole float4s; PCM16 becomes floats through
+// mifsk_ingest_s16, as the host pipeline makes them (every row defined up to its stride)
+int Job::uncut()
+{
+    const int M = lay.M;
+    int rc;
+    const bool lone = M == 1;
+    const uint64_t stride = lone ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : src.stride;
+    mifsk_demod_io io = *io_out;
+    io.d_samples = (const float *)src.p;
+    if ( src.s16 || !lone ) {		// the lengths: for mifsk_ingest_s16, and of a batch's rows
+	hn.resize(M);
+	for ( int m = 0; m < M; m++ )
+	    hn[m] = (uint32_t)nsamples[m];
+	if ( ( rc = table.alloc(M * sizeof(uint32_t)) ) )
+	    return rc;
+	HIP_OK(hipMemcpyAsync(table.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_OK(hipStreamSynchronize(st));
+    }
+    if ( src.s16 ) {
+	if ( ( rc = pad.make((size_t)M * stride) ) )
+	    return rc;
+	if ( !src.p )
+	    HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
+	else if ( ( rc = mifsk_ingest_s16(ctx, (const int16_t *)src.p, src.stride, pad.d(), stride,
+					  (const uint32_t *)table.p, 0, M, rxnoise, stream) ) )
+	    return rc;
+	io.d_samples = pad.d();
+    } else if ( lone && nsamples[0] % 4u ) {
+	if ( ( rc = pad.make(stride) ) )
+	    return rc;
+	one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
+	if ( ( rc = table.alloc(sizeof(one)) ) )
+	    return rc;
+	HIP_OK(hipMemcpyAsync(table.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
+	HIP_OK(hipStreamSynchronize(st));
+	gather_rows(src, dim3(64, 1), st, (const StreamRef *)table.p,
+		    (const RowRef *)( (char *)table.p + sizeof(StreamRef) ), pad.d(), stride, 0, 1);
+	io.d_samples = pad.d();
+    }
+    io.stream_stride = stride;
+    io.d_nsamples = lone ? nullptr : (const uint32_t *)table.p;
+    io.nsamples = (uint32_t)( lone ? nsamples[0] : std::min<uint64_t>(stride, 0xFFFFFFFFull) );
+    io.nstreams = M;
+    io.d_counters = nullptr;
+    io.flags = engine;
+    io.reserved = 0;
+    if ( ( rc = mifsk_demod_batch(ctx, cfg, &io, stream) ) )
+	return rc;
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+// everything the call holds on the device but the tails' samples; the tables go up and the chunks
+// are copied apart
+int Job::gather()
+{
+    const size_t M = lay.M, R = lay.R, nrows = lay.nrows;
+    int rc;
+    if ( ( rc = rows.make(R * lay.rstride) )
+	    || ( rc = guess.make(nrows) ) || ( rc = start.make(nrows) )
+	    || ( rc = pause.make(nrows) ) || ( rc = rerun.make(nrows) )
+	    || ( rc = counts.make(4 * nrows) )
+	    || ( rc = rerun_counts.make(4 * nrows) )
+	    || ( rc = code.make(nrows) )
+	    || ( rc = row_flags.make(nrows) )
+	    || ( rc = rframes.make(nrows * lay.fcap) )
+	    || ( io_out->d_bytes && ( rc = rbytes.make(nrows * lay.fcap) ) )
+	    || ( rc = reps.make(nrows * lay.ecap) )
+	    || ( rc = pref.make(nrows + M) )
+	    || ( rc = ns.make(nrows) )
+	    || ( rc = streams.make(M) )
+	    || ( rc = rowref.make(nrows) ) )
+	return rc;
+    d_mark = row_flags.d();
+    HIP_OK(hipMemsetAsync(counts.p, 0, 4 * nrows * sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(d_mark, 0, nrows, st));
+    HIP_OK(hipMemcpyAsync(streams.p, lay.hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(rowref.p, lay.hrow.data(), nrows * sizeof(RowRef), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(ns.p, lay.hns.data(), nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    gather_rows(src, dim3(blocks_for(lay.rstride), (unsigned)std::min(lay.R, 65535)), st, streams.d(), rowref.d(),
+		rows.d(), lay.rstride, lay.L, lay.R);
+    return 0;
+}
+
+// pass A: rows 1 .. R-1, W samples each, from a zeroed state (a stream's row 0 is skipped); then
+// pass B's starting states
+int Job::pass_a()
+{
+    const unsigned gb = blocks(lay.nrows);
+    hipLaunchKernelGGL(ts_guess_init, dim3(gb), dim3(tb), 0, st, guess.d(), rowref.d(), lay.R);
+    mifsk_demod_io a;
+    std::memset(&a, 0, sizeof(a));
+    a.flags = engine;
+    a.d_samples = rows.d() + lay.rstride;
+    a.stream_stride = lay.rstride;
+    a.nsamples = (uint32_t)lay.W;
+    a.nstreams = lay.R - 1;
+    if ( const int rc = mifsk_demod_slab(ctx, cfg, &a, guess.d() + 1, nullptr, 0, stream) )
+	return rc;
+    hipLaunchKernelGGL(ts_prepare, dim3(gb), dim3(tb), 0, st, guess.d(), start.d(), pause.d(), rowref.d(), lay.R);
+    return 0;
+}
+
+// pass B: every row up to W samples into its stream's next chunk (a stream's last one to the
+// end; it stays a non-final slab: the tail finishes it)
+int Job::pass_b()
+{
+    std::memset(&b, 0, sizeof(b));
+    b.flags = engine;
+    b.d_samples = rows.d();
+    b.stream_stride = lay.rstride;
+    b.d_nsamples = ns.d();
+    b.nsamples = (uint32_t)( lay.L + lay.W );
+    b.d_frames = rframes.d();
+    b.d_bytes = rbytes.d();
+    b.frames_cap = lay.fcap;
+    b.d_episodes = reps.d();
+    b.episodes_cap = lay.ecap;
+    b = rows_of(b, counts.d(), lay.nrows, 0, lay.R);
+    return mifsk_demod_slab(ctx, cfg, &b, pause.d(), nullptr, 0, stream);
+}
+
+// Verify, and re-run what was rejected, in rounds.  Row k of a stream is CONSISTENT when the
+// state it started from agrees in control with the state row k-1 of that stream paused in;
+// a stream's settled rows are its consistent prefix.  A round re-runs every inconsistent row
+// of every stream at once from its predecessor's current state (settled or not: a row whose
+// predecessor changes again is simply inconsistent again), so the rounds follow the longest
+// run of rejections in any one stream, not their number and not the sum over the streams.
+int Job::rounds()
+{
+    const int R = lay.R, nrows = lay.nrows;
+    for ( uint32_t round = 0;; round++ ) {
+	// (MIFSK_TIME_SPLIT_REJECT_ALL: every guess of pass A is rejected)
+	const int reject = round == 0 && ( flags & MIFSK_TIME_SPLIT_REJECT_ALL );
+	hipLaunchKernelGGL(ts_verify, dim3(blocks(nrows)), dim3(tb), 0, st, (const mifsk_stream_state *)start.d(),
+			   (const mifsk_stream_state *)pause.d(), rowref.d(), code.d(), R, lay.L, reject);
+	HIP_OK(hipMemcpyAsync(hcode.data(), code.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	HIP_OK(hipStreamSynchronize(st));
+	const RowSpan span = settle_round(hcode, lay, f, ps);
+	if ( span.lo < 0 )
+	    return 0;
+	HIP_OK(hipMemcpyAsync(d_mark, f.mark.data(), nrows, hipMemcpyHostToDevice, st));
+	const int lo = span.lo, hi = span.hi, nr = hi - lo + 1;
+	hipLaunchKernelGGL(ts_seed, dim3(blocks(nr)), dim3(tb), 0, st, pause.d(), (const uint8_t *)d_mark, rowref.d(),
+			   rerun.d(), start.d(), lo, hi, lay.L);
+	const mifsk_demod_io r = rows_of(b, rerun_counts.d(), nrows, lo, nr);
+	if ( const int rc = mifsk_demod_slab(ctx, cfg, &r, rerun.d() + lo, nullptr, 0, stream) )
+	    return rc;
+	hipLaunchKernelGGL(ts_merge, dim3(blocks(nr)), dim3(tb), 0, st, (const mifsk_stream_state *)rerun.d(),
+			   (const uint8_t *)d_mark, (const uint32_t *)rerun_counts.d(), pause.d(), counts.d(), lo, hi,
+			   nrows);
+    }
+}
+
+// the tails: every stream's last chunk finished as a final slab from its paused state, all of
+// them one batch over a small buffer of their own (they do not sit at one stride in the rows);
+// then the drop flags take the marks' place
+int Job::tails()
+{
+    const int M = lay.M, R = lay.R;
+    const size_t stsz = sizeof(mifsk_stream_state);
+    hipLaunchKernelGGL(ts_last_states, dim3(blocks(M)), dim3(tb), 0, st, (const mifsk_stream_state *)pause.d(),
+		       streams.d(), rerun.d() + R, M);
+    HIP_OK(hipMemcpyAsync(last.data(), rerun.d() + R, M * stsz, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const Tails t = place_tails(lay, last, f.drop);
+    HIP_OK(hipMemcpyAsync(streams.p, lay.hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(start.d() + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(pause.d() + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
+    if ( t.live ) {
+	const uint64_t tstride = std::max<uint64_t>(4, ( t.longest + 3u ) & ~3ull);
+	if ( const int rc = tail_rows.make((size_t)M * tstride) )
+	    return rc;
+	HIP_OK(hipMemcpyAsync(ns.d() + R, lay.hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	gather_tails(src, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), st, streams.d(), tail_rows.d(),
+		     tstride, M);
+	mifsk_demod_io tio = rows_of(b, counts.d(), lay.nrows, R, M);
+	tio.d_samples = tail_rows.d();
+	tio.stream_stride = tstride;
+	tio.nsamples = (uint32_t)t.longest;
+	if ( const int rc = mifsk_demod_slab(ctx, cfg, &tio, pause.d() + R, nullptr, 1, stream) )
+	    return rc;
+    }
+    HIP_OK(hipMemcpyAsync(row_flags.p, f.drop.data(), lay.nrows, hipMemcpyHostToDevice, st));
+    d_mark = nullptr;
+    d_drop = row_flags.d();
+    return 0;
+}
+
+int Job::stitch()
+{
+    // (in the order of StitchArgs' fields)
+    const StitchArgs sa = { start.d(), pause.d(), counts.d(), d_drop, streams.d(), rowref.d(), lay.nrows, lay.R,
+			    b.d_frames, b.d_bytes, b.d_episodes, lay.fcap, lay.ecap, lay.L, pref.d(), *io_out,
+			    cfg->auto_carrier_threshold > 0.0f };
+    hipLaunchKernelGGL(ts_scan, dim3(lay.M), dim3(kScanThreads), 0, st, sa);
+    if ( io_out->d_frames || io_out->d_bits || io_out->d_bytes )
+	hipLaunchKernelGGL(ts_scatter, dim3(lay.nrows), dim3(256), 0, st, sa);
+    if ( io_out->d_episodes )
+	hipLaunchKernelGGL(ts_episodes, dim3(lay.nrows), dim3(64), 0, st, sa);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
 }
 
 // The entry points (which have checked the rows against the source's stride); mifsk_demod_long is
@@ -739,294 +806,43 @@ int run( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const Src &src, float rxnoi
     if ( !ctx || !io_out || !nsamples || nstreams <= 0 || mifsk_check_cfg(cfg)
 	    || ( (uintptr_t)src.p & 15u ) )
 	return -EINVAL;
-    const int M = nstreams;
     int rc;
-    for ( int m = 0; m < M; m++ )
+    for ( int m = 0; m < nstreams; m++ )
 	if ( nsamples[m] && !src.p )
 	    return -EINVAL;
-    if ( ( io_out->d_bytes || io_out->d_bits || io_out->d_frames ) && io_out->frames_cap == 0 )
-	return -EINVAL;
-    if ( io_out->d_episodes && io_out->episodes_cap == 0 )
+    if ( ( ( io_out->d_bytes || io_out->d_bits || io_out->d_frames ) && io_out->frames_cap == 0 )
+	    || ( io_out->d_episodes && io_out->episodes_cap == 0 ) )
 	return -EINVAL;
     const unsigned flags = params ? params->flags : 0u;
-    const unsigned engine = flags & ( MIFSK_IO_ENGINE_WORKGROUP | MIFSK_IO_ENGINE_WAVE );
     if ( ( flags & MIFSK_IO_ENGINE_WORKGROUP ) && cfg->auto_carrier_threshold > 0.0f )
 	return -EINVAL;
     if ( ( rc = mifsk::time_split_check_params(cfg, params) ) )
 	return rc;		// (before any HIP call)
     HIP_OK(hipSetDevice(ctx->device));
-    hipStream_t st = (hipStream_t)stream;
 
     // the chip's worth of chunks for this engine
     uint32_t hint = 0;
-    {
-	mifsk_launch_info li;
-	if ( mifsk_demod_plan_ex(ctx, cfg, 1, 0xFFFFFFFFu, flags & ~MIFSK_TIME_SPLIT_REJECT_ALL, &li) == 0 )
-	    hint = li.compute_units * kChunksPerCu;
-    }
-    std::vector<mifsk_time_split_stats> ps(M);
-    rc = plan(cfg, nsamples, M, params, hint, ps.data());
+    mifsk_launch_info li;
+    if ( mifsk_demod_plan_ex(ctx, cfg, 1, 0xFFFFFFFFu, flags & ~MIFSK_TIME_SPLIT_REJECT_ALL, &li) == 0 )
+	hint = li.compute_units * kChunksPerCu;
+    std::vector<mifsk_time_split_stats> ps(nstreams);
+    if ( ( rc = plan(cfg, nsamples, nstreams, params, hint, ps.data()) ) )
+	return rc;
+
+    Job j(ctx, cfg, src, rxnoise, nsamples, flags, io_out, stream, std::move(ps));
+    if ( j.lay.R == nstreams )
+	rc = j.uncut();
+    else
+	( rc = j.gather() ) || ( rc = j.pass_a() ) || ( rc = j.pass_b() ) || ( rc = j.rounds() )
+	    || ( rc = j.tails() ) || ( rc = j.stitch() );
     if ( rc )
 	return rc;
-    const uint64_t L = ps[0].chunk, W = ps[0].warmup;
-    uint64_t nchunkrows = 0;
-    for ( int m = 0; m < M; m++ )
-	nchunkrows += ps[m].nchunks;
-
-    mifsk_demod_io base;
-    std::memset(&base, 0, sizeof(base));
-    base.flags = engine;
-
-    if ( nchunkrows == (uint64_t)M ) {
-	// no stream is cut: the existing call over the batch.  A batch of floats is taken where it
-	// is, and so is a lone row of whole float4s (no allocation, no copy); any other lone row goes
-	// over a padded copy, its stride being its length in whole float4s; PCM16 becomes floats
-	// through mifsk_ingest_s16, as the host pipeline makes them (every row defined up to its stride)
-	StreamMem pad(st), dn(st);
-	const bool lone = M == 1;
-	const uint64_t stride = lone ? std::max<uint64_t>(4, ( nsamples[0] + 3u ) & ~3ull) : src.stride;
-	mifsk_demod_io io = *io_out;
-	io.d_samples = (const float *)src.p;
-	if ( src.s16 || !lone ) {		// the lengths: for mifsk_ingest_s16, and of a batch's rows
-	    std::vector<uint32_t> hn(M);
-	    for ( int m = 0; m < M; m++ )
-		hn[m] = (uint32_t)nsamples[m];
-	    if ( ( rc = dn.alloc(M * sizeof(uint32_t)) ) )
-		return rc;
-	    HIP_OK(hipMemcpyAsync(dn.p, hn.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	    HIP_OK(hipStreamSynchronize(st));		// (hn is gone after this block)
-	}
-	if ( src.s16 ) {
-	    if ( ( rc = pad.alloc((size_t)M * stride * sizeof(float)) ) )
-		return rc;
-	    if ( !src.p )
-		HIP_OK(hipMemsetAsync(pad.p, 0, (size_t)M * stride * sizeof(float), st));
-	    else if ( ( rc = mifsk_ingest_s16(ctx, (const int16_t *)src.p, src.stride,
-					      (float *)pad.p, stride, (const uint32_t *)dn.p, 0, M, rxnoise, stream) ) )
-		return rc;
-	    io.d_samples = (const float *)pad.p;
-	} else if ( lone && nsamples[0] % 4u ) {
-	    if ( ( rc = pad.alloc(stride * sizeof(float)) ) )
-		return rc;
-	    // (the one row's table, synchronised: it goes out of scope with this block)
-	    const struct { StreamRef s; RowRef r; } one = { { nsamples[0], 0, 0, 1 }, { 0, 0 } };
-	    if ( ( rc = dn.alloc(sizeof(one)) ) )
-		return rc;
-	    HIP_OK(hipMemcpyAsync(dn.p, &one, sizeof(one), hipMemcpyHostToDevice, st));
-	    HIP_OK(hipStreamSynchronize(st));
-	    gather_rows(src, dim3(64, 1), st, (const StreamRef *)dn.p,
-			(const RowRef *)( (char *)dn.p + sizeof(StreamRef) ), (float *)pad.p, stride, 0, 1);
-	    io.d_samples = (const float *)pad.p;
-	}
-	io.stream_stride = stride;
-	io.d_nsamples = lone ? nullptr : (const uint32_t *)dn.p;
-	io.nsamples = (uint32_t)( lone ? nsamples[0] : std::min<uint64_t>(stride, 0xFFFFFFFFull) );
-	io.nstreams = M;
-	io.d_counters = nullptr;
-	io.flags = engine;
-	io.reserved = 0;
-	rc = mifsk_demod_batch(ctx, cfg, &io, stream);
-	if ( rc )
-	    return rc;
-	HIP_OK(hipStreamSynchronize(st));
-	if ( stats )
-	    std::copy(ps.begin(), ps.end(), stats);
-	return 0;
-    }
-
-    const int R = (int)nchunkrows, nrows = R + M;
-    std::vector<StreamRef> hs(M);
-    std::vector<RowRef> hrow(nrows);
-    std::vector<uint32_t> hns(nrows, 0);
-    row_table(nsamples, ps, R, hs, hrow, hns);
-    const uint64_t rstride = ( L + W + 3u ) & ~3ull;
-    const size_t fcap = mifsk_max_frames(cfg, L + W);
-    const size_t ecap = mifsk_max_episodes(cfg, L + W) + 1;
-    StreamMem rows(st), X(st), I(st), S(st), Rr(st), cnt(st), rcnt(st), code(st), mark(st), rframes(st), rbytes(st),
-	      reps(st), pref(st), ns(st), streams(st), rowref(st), tails(st);
-    const size_t stsz = sizeof(mifsk_stream_state);
-    if ( ( rc = rows.alloc((size_t)R * rstride * sizeof(float)) )
-	    || ( rc = X.alloc(nrows * stsz) ) || ( rc = I.alloc(nrows * stsz) )
-	    || ( rc = S.alloc(nrows * stsz) ) || ( rc = Rr.alloc(nrows * stsz) )
-	    || ( rc = cnt.alloc(4 * (size_t)nrows * sizeof(uint32_t)) )
-	    || ( rc = rcnt.alloc(4 * (size_t)nrows * sizeof(uint32_t)) )
-	    || ( rc = code.alloc(nrows * sizeof(uint32_t)) )
-	    || ( rc = mark.alloc(nrows) )
-	    || ( rc = rframes.alloc(nrows * fcap * sizeof(mifsk_frame)) )
-	    || ( io_out->d_bytes && ( rc = rbytes.alloc(nrows * fcap) ) )
-	    || ( rc = reps.alloc(nrows * ecap * sizeof(mifsk_episode)) )
-	    || ( rc = pref.alloc(( (size_t)nrows + M ) * sizeof(Agg)) )
-	    || ( rc = ns.alloc(nrows * sizeof(uint32_t)) )
-	    || ( rc = streams.alloc(M * sizeof(StreamRef)) )
-	    || ( rc = rowref.alloc(nrows * sizeof(RowRef)) ) )
-	return rc;
-    auto *dX = (mifsk_stream_state *)X.p, *dI = (mifsk_stream_state *)I.p;
-    auto *dS = (mifsk_stream_state *)S.p, *dR = (mifsk_stream_state *)Rr.p;
-    auto *dcnt = (uint32_t *)cnt.p, *drcnt = (uint32_t *)rcnt.p;
-    float *drows = (float *)rows.p;
-    const auto *dstreams = (const StreamRef *)streams.p;
-    const auto *drowref = (const RowRef *)rowref.p;
-
-    HIP_OK(hipMemsetAsync(cnt.p, 0, 4 * (size_t)nrows * sizeof(uint32_t), st));
-    HIP_OK(hipMemsetAsync(mark.p, 0, nrows, st));
-    HIP_OK(hipMemcpyAsync(streams.p, hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(rowref.p, hrow.data(), nrows * sizeof(RowRef), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(ns.p, hns.data(), nrows * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    gather_rows(src, dim3(blocks_for(rstride), (unsigned)std::min(R, 65535)), st, dstreams, drowref, drows,
-		rstride, L, R);
-
-    // pass A: rows 1 .. R-1, W samples each, from a zeroed state (a stream's row 0 is skipped)
-    const unsigned tb = 256, gb = (unsigned)( ( nrows + tb - 1 ) / tb );
-    hipLaunchKernelGGL(ts_guess_init, dim3(gb), dim3(tb), 0, st, dX, drowref, R);
-    mifsk_demod_io a = base;
-    a.d_samples = drows + rstride;
-    a.stream_stride = rstride;
-    a.nsamples = (uint32_t)W;
-    a.nstreams = R - 1;
-    if ( ( rc = mifsk_demod_slab(ctx, cfg, &a, dX + 1, nullptr, 0, stream) ) )
-	return rc;
-    hipLaunchKernelGGL(ts_prepare, dim3(gb), dim3(tb), 0, st, dX, dI, dS, drowref, R);
-
-    // pass B: every row up to W samples into its stream's next chunk (a stream's last one to the
-    // end; it stays a non-final slab: the tail below finishes it)
-    mifsk_demod_io b = base;
-    b.d_samples = drows;
-    b.stream_stride = rstride;
-    b.d_nsamples = (const uint32_t *)ns.p;
-    b.nsamples = (uint32_t)( L + W );
-    b.d_frames = (mifsk_frame *)rframes.p;
-    b.d_bytes = (uint8_t *)rbytes.p;
-    b.frames_cap = fcap;
-    b.d_episodes = (mifsk_episode *)reps.p;
-    b.episodes_cap = ecap;
-    b = rows_of(b, dcnt, nrows, 0, R);
-    if ( ( rc = mifsk_demod_slab(ctx, cfg, &b, dS, nullptr, 0, stream) ) )
-	return rc;
-
-    // Verify, and re-run what was rejected, in rounds.  Row k of a stream is CONSISTENT when the
-    // state it started from agrees in control with the state row k-1 of that stream paused in;
-    // a stream's settled rows are its consistent prefix.  A round re-runs every inconsistent row
-    // of every stream at once from its predecessor's current state (settled or not: a row whose
-    // predecessor changes again is simply inconsistent again), so the rounds follow the longest
-    // run of rejections in any one stream, not their number and not the sum over the streams.
-    std::vector<uint8_t> settled(nrows, 0), drop(nrows, 0), hmark(nrows, 0), ran(nrows, 0);
-    std::vector<uint32_t> hcode(nrows, 0);
-    for ( int m = 0; m < M; m++ )
-	settled[hs[m].rowbase] = 1;
-    uint32_t rounds = 0;
-    for ( ;; ) {
-	// (MIFSK_TIME_SPLIT_REJECT_ALL: every guess of pass A is rejected)
-	const int reject = rounds == 0 && ( flags & MIFSK_TIME_SPLIT_REJECT_ALL );
-	hipLaunchKernelGGL(ts_verify, dim3(gb), dim3(tb), 0, st, (const mifsk_stream_state *)dI,
-			   (const mifsk_stream_state *)dS, drowref, (uint32_t *)code.p, R, L, reject);
-	HIP_OK(hipMemcpyAsync(hcode.data(), code.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-	HIP_OK(hipStreamSynchronize(st));
-	int lo, hi;
-	settle_round(hcode, hs, hns, settled, drop, ran, ps, hmark, lo, hi);
-	if ( lo < 0 )
-	    break;
-	HIP_OK(hipMemcpyAsync(mark.p, hmark.data(), nrows, hipMemcpyHostToDevice, st));
-	const int nr = hi - lo + 1;
-	const unsigned gm = (unsigned)( ( nr + tb - 1 ) / tb );
-	hipLaunchKernelGGL(ts_seed, dim3(gm), dim3(tb), 0, st, dS, (const uint8_t *)mark.p, drowref, dR, dI,
-			   lo, hi, L);
-	const mifsk_demod_io r = rows_of(b, drcnt, nrows, lo, nr);
-	if ( ( rc = mifsk_demod_slab(ctx, cfg, &r, dR + lo, nullptr, 0, stream) ) )
-	    return rc;
-	hipLaunchKernelGGL(ts_merge, dim3(gm), dim3(tb), 0, st, (const mifsk_stream_state *)dR,
-			   (const uint8_t *)mark.p, (const uint32_t *)drcnt, dS, dcnt, lo, hi, nrows);
-	rounds++;
-    }
-
-    // the tails: every stream's last chunk finished as a final slab from its paused state, all of
-    // them one batch over a small buffer of their own (they do not sit at one stride in the rows)
-    std::vector<mifsk_stream_state> last(M);
-    hipLaunchKernelGGL(ts_last_states, dim3((unsigned)( ( M + tb - 1 ) / tb )), dim3(tb), 0, st,
-		       (const mifsk_stream_state *)dS, dstreams, dR + R, M);
-    HIP_OK(hipMemcpyAsync(last.data(), dR + R, M * stsz, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    uint64_t longest_tail = 0;
-    bool live = false;
-    for ( int m = 0; m < M; m++ ) {
-	const uint64_t K = hs[m].K;
-	if ( drop[hs[m].rowbase + K - 1] || ( last[m].flags & MIFSK_STATE_FINISHED ) ) {
-	    drop[R + m] = 1;
-	    hs[m].tail_off = nsamples[m];
-	    std::memset(&last[m], 0, stsz);
-	    last[m].flags = MIFSK_STATE_STARTED | MIFSK_STATE_FINISHED;
-	    continue;
-	}
-	const uint64_t rel = last[m].base & ~3ull;	// (rows start 16-byte aligned)
-	hs[m].tail_off = ( K - 1 ) * L + rel;
-	last[m] = reset_book(last[m], rel);
-	hns[R + m] = (uint32_t)( nsamples[m] - hs[m].tail_off );
-	longest_tail = std::max<uint64_t>(longest_tail, hns[R + m]);
-	live = true;
-    }
-    HIP_OK(hipMemcpyAsync(streams.p, hs.data(), M * sizeof(StreamRef), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dI + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(dS + R, last.data(), M * stsz, hipMemcpyHostToDevice, st));
-    if ( live ) {
-	const uint64_t tstride = std::max<uint64_t>(4, ( longest_tail + 3u ) & ~3ull);
-	if ( ( rc = tails.alloc((size_t)M * tstride * sizeof(float)) ) )
-	    return rc;
-	HIP_OK(hipMemcpyAsync((uint32_t *)ns.p + R, hns.data() + R, M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-	gather_tails(src, dim3(blocks_for(tstride), (unsigned)std::min(M, 65535)), st, dstreams, (float *)tails.p,
-		     tstride, M);
-	mifsk_demod_io t = rows_of(b, dcnt, nrows, R, M);
-	t.d_samples = (const float *)tails.p;
-	t.stream_stride = tstride;
-	t.nsamples = (uint32_t)longest_tail;
-	if ( ( rc = mifsk_demod_slab(ctx, cfg, &t, dS + R, nullptr, 1, stream) ) )
-	    return rc;
-    }
-    HIP_OK(hipMemcpyAsync(mark.p, drop.data(), nrows, hipMemcpyHostToDevice, st));
-
-    // stitch
-    StitchArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.I = dI;
-    sa.S = dS;
-    sa.cnt = dcnt;
-    sa.drop = (const uint8_t *)mark.p;
-    sa.streams = dstreams;
-    sa.rowref = drowref;
-    sa.nrows = nrows;
-    sa.R = R;
-    sa.rframes = b.d_frames;
-    sa.rbytes = b.d_bytes;
-    sa.reps = b.d_episodes;
-    sa.fcap = fcap;
-    sa.ecap = ecap;
-    sa.L = L;
-    sa.pref = (Agg *)pref.p;
-    sa.out = *io_out;
-    sa.autodetect = cfg->auto_carrier_threshold > 0.0f;
-    hipLaunchKernelGGL(ts_scan, dim3(M), dim3(kScanThreads), 0, st, sa);
-    if ( io_out->d_frames || io_out->d_bits || io_out->d_bytes )
-	hipLaunchKernelGGL(ts_scatter, dim3(nrows), dim3(256), 0, st, sa);
-    if ( io_out->d_episodes )
-	hipLaunchKernelGGL(ts_episodes, dim3(nrows), dim3(64), 0, st, sa);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(st));
     if ( stats )
-	std::copy(ps.begin(), ps.end(), stats);
+	std::copy(j.ps.begin(), j.ps.end(), stats);
     return 0;
 }
 
 } // namespace
-
-extern "C" int mifsk_time_split_plan_get( const mifsk_rx_config *cfg, uint64_t nsamples,
-	const mifsk_time_split *params, mifsk_time_split_stats *out )
-{
-    return plan(cfg, &nsamples, 1, params, 0, out);
-}
-
-extern "C" int mifsk_time_split_plan_batch_get( const mifsk_rx_config *cfg, const uint64_t *nsamples,
-	int nstreams, const mifsk_time_split *params, mifsk_time_split_stats *out )
-{
-    return plan(cfg, nsamples, nstreams, params, 0, out);
-}
 
 extern "C" int mifsk_demod_long( mifsk_ctx *ctx, const mifsk_rx_config *cfg, const float *d_samples,
 	uint64_t nsamples, const mifsk_time_split *params, const mifsk_demod_io *io_out,

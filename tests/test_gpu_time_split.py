@@ -12,6 +12,7 @@ import pytest
 
 import _golden as G
 import _oracle as O
+from _timesplit import _lattice  # noqa: F401  (the other time-split modules take it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +26,6 @@ def gpu():
     ctx = M.Context()
     yield M, torch, ctx
     ctx.close()
-
-
-def _lattice(cfg):
-    half = cfg.samplebuf_size // 2
-    return half * 4 // math.gcd(half, 4)
 
 
 def _single(M, torch, ctx, cfg, x, engine=None):

@@ -1,24 +1,15 @@
 """The planner of mifsk_demod_long_batch (a small batch of long recordings cut in time by one chunk
 and one warmup; DESIGN.md "cutting a stream in time", "Several recordings"): host only, no GPU."""
 import ctypes as C
-import math
 import time
 
 import pytest
 
 import minimodem_amd as M
 from minimodem_amd import _lib
+from _timesplit import _default_warmup, _lattice
 
 GIB4 = 4 << 30
-
-
-def _lattice(cfg):
-    half = cfg.samplebuf_size // 2
-    return half * 4 // math.gcd(half, 4)
-
-
-def _default_warmup(cfg):
-    return max(int(10.0 * cfg.sample_rate), 2 * cfg.samplebuf_size)
 
 
 def _raw(cfg, lens, chunk=None, warmup=None, chunks=None, engine=None, flags=0):

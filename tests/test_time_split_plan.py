@@ -1,7 +1,6 @@
 """The planner of mifsk_demod_long (one long recording cut in time; DESIGN.md "cutting a stream
 in time"): host only, no GPU."""
 import ctypes as C
-import math
 import os
 import subprocess
 import sys
@@ -10,13 +9,9 @@ import pytest
 
 import minimodem_amd as M
 from minimodem_amd import _lib
+from _timesplit import _lattice
 
 MODES = ["1200", "300", "rtty", "tdd", "same", "12000", "uic-train", "callerid"]
-
-
-def _lattice(cfg):
-    half = cfg.samplebuf_size // 2
-    return half * 4 // math.gcd(half, 4)
 
 
 @pytest.mark.parametrize("mode", MODES)
