@@ -201,6 +201,10 @@ int mifsk_selftest_mag( mifsk_ctx *ctx, const double *re, const double *im, floa
 int mifsk_selftest_confidence( mifsk_ctx *ctx, int variant, uint32_t n_bits, uint64_t req_mask,
 	uint64_t req_val, const float *mags, uint64_t ncases, float *conf_out, float *ampl_out,
 	uint64_t *bits_out, uint32_t *fell_back_out );
+/* _gauss: the transform of the channel model's noise field (mifsk_impair_batch below;
+ * csrc/mifsk_gauss.h) for chosen words, which cannot be steered through Philox: z_out[i] =
+ * { R(words[i][0]) C(words[i][1]), R(words[i][0]) S(words[i][1]) }, words [n][2], z_out [n][2]. */
+int mifsk_selftest_gauss( mifsk_ctx *ctx, const uint32_t *words, uint64_t n, double *z_out );
 
 /* Diagnostics, wave-wide routines (csrc/mifsk_devlib.h) on HOST arrays, synchronous, like the
  * three above; tests/test_gpu_correlators.py and tests/test_gpu_scans.py compare them with the
@@ -1207,6 +1211,91 @@ int  mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, 
 /* host only, no context: G as the plan makes it, [ntaps][2] doubles.  -EINVAL for what
  * mifsk_mux_plan_create refuses of params, or a NULL g_out. */
 int  mifsk_mux_table( const mifsk_mux_params *params, double *g_out );
+
+/* ---- channel model: reproducible AWGN, gain and DC offset for a batch ---- */
+
+/* The stage between transmitter and receiver: out = gain x + dc + sigma z for a batch of rows, z a
+ * standard normal NOISE FIELD that is a pure function of (seed, stream index, sample index), made
+ * of integer arithmetic and IEEE double operations only -- so a batch cut into pieces, sharded over
+ * ranks or fed in slabs gets the noise of the whole batch, and a host can regenerate any noisy row
+ * from a handful of numbers (tools/impair_ref.c restates all of this; the device equals it bit for
+ * bit).
+ *   The field z(seed, S, n), for a 64-bit seed, stream index S and sample index n.  Philox4x32-10
+ * (Salmon et al., SC'11) supplies the words: key (k0, k1) = (lo32(seed), hi32(seed)), counter
+ * (c0, c1, c2, c3) = (lo32(j), hi32(j), lo32(S), hi32(S)) with j = n >> 2; ten rounds, each
+ *   p0 = 0xD2511F53 * c0,  p1 = 0xCD9E8D57 * c2                       (64-bit products)
+ *   c = ( hi32(p1) ^ c1 ^ k0,  lo32(p1),  hi32(p0) ^ c3 ^ k1,  lo32(p0) )
+ *   k0 += 0x9E3779B9,  k1 += 0xBB67AE85
+ * (counter 0,0,0,0 under key 0,0 gives 6627e8d5 e169c58d bc57ac4c 9b00dbd8).  The four words
+ * w0 .. w3 of block j are the four normals of samples 4 j .. 4 j + 3, by Box-Muller:
+ *   z[4j] = R(w0) C(w1),  z[4j+1] = R(w0) S(w1),  z[4j+2] = R(w2) C(w3),  z[4j+3] = R(w2) S(w3)
+ * Every operation below is ONE IEEE double operation, rounded once; every a * b + c written fma is
+ * one fused operation and nothing else is fused (both sides compile with -ffp-contract=off).
+ *   R(w) = sqrt(-2 ln u), u = (w + 1) / 2^32:
+ *     t = w + 1 (a 64-bit integer);  e = floor(log2 t);  m = (double)t * 2^-e (exact, in [1, 2))
+ *     if m > 0x1.6a09e667f3bcdp+0:  m = m * 0.5,  e = e + 1
+ *     f = m - 1.0;  s = f / (2.0 + f);  y = s * s
+ *     p = 1.0 / 23.0;  for k = 10 down to 0:  p = fma(p, y, 1.0 / (2 k + 1))
+ *     lnm = (2.0 * s) * p;  ln = fma((double)(e - 32), 0x1.62e42fefa39efp-1, lnm)
+ *     R = sqrt(-2.0 * ln)
+ *   (w = 0xFFFFFFFF gives -0.0; signs of zero are whatever the expressions give.)
+ *   C(w), S(w) = cos, sin of 2 pi w / 2^32, by octant:
+ *     q = w >> 29;  fr = w & 0x1FFFFFFF;  a = fr for even q, 0x20000000 - fr for odd q
+ *     phi = 0x1.921fb54442d18p-1 * ((double)a * 2^-29);  y = phi * phi
+ *     ps = -1.0 / 19!;  for k = 8 down to 0:  ps = fma(ps, y, (-1)^k / (2 k + 1)!);  sn = phi * ps
+ *     pc = 1.0 / 20!;   for k = 9 down to 0:  pc = fma(pc, y, (-1)^k / (2 k)!);      cs = pc
+ *     (every constant is one double division of +-1.0 by the factorial, an exact double)
+ *     (C, S) for q = 0 .. 7:  (cs, sn) (sn, cs) (-sn, cs) (-cs, sn) (-cs, -sn) (-sn, -cs) (sn, -cs) (cs, -sn)
+ *   z(0, 0, 0 .. 3) = 0x1.fb7665db1b649p-1, -0x1.d96d5ff0aec98p-1, -0x1.3c373dd6d9558p-1,
+ * -0x1.eda3633cd971p-2.  |z| <= sqrt(64 ln 2) < 6.67.
+ *   The element.  Row s, element i < W_s, with x the input scalar widened to double (PCM16:
+ * (float)v / 32768.0f, mifsk_ingest_s16's expression without the --Xrxnoise term; 0.0 when d_samples
+ * is NULL) and g, sg, d row s's gain, sigma and dc -- d_gain[s] / d_sigma[s] / d_dc[s] where that
+ * array is given, else the scalar; floats widened to double:
+ *   v = fma(g, x, d);  v = fma(sg, z(seed, first_stream + s, first_sample + i), v);  out = (float)v
+ * (the index sums wrap in 64 bits).  For PCM16 output the float goes through the multiplexer's write
+ * conversion: * 32767.0f, clamp to [-32768, 32767], lrintf to nearest even, NaN -> 0.
+ * W_s = min(nsamples[s], stream_stride, out_stride), or min(nsamples[s], out_stride) without input
+ * rows; elements from W_s to out_stride are written as zero.  Parameters are data, finite or not:
+ * NaN and Inf propagate as the arithmetic says, and nothing is skipped for sigma == 0 (fma(1, -0.0,
+ * 0) = +0.0: the arithmetic decides).
+ *   IN PLACE -- d_out == d_samples with out_kind == kind and out_stride == stream_stride -- is
+ * legal; any other overlap of the two arrays is undefined.
+ *   mifsk_impair_batch checks, in this order and before any HIP call: -EINVAL for a NULL ctx, io or
+ * d_out; for nstreams <= 0; for a kind or out_kind that is neither MIFSK_FEED_F32 nor
+ * MIFSK_FEED_S16; for flags != 0; for first_sample % 4 != 0; when d_samples is given, for an input
+ * base that is not 16-byte aligned or a stream_stride that is not whole 16-byte vectors of `kind`
+ * (4 floats, 8 PCM16); for an output base that is not 16-byte aligned, out_stride == 0, out_stride
+ * not whole 16-byte vectors of out_kind, or above 2^32 - 8.  Asynchronous on `stream`; it
+ * allocates nothing and synchronises nothing.  Whatever the arguments hold, nothing outside nstreams
+ * * stream_stride input elements is read and nothing outside nstreams * out_stride output elements
+ * is written; nothing written is read back, and the outputs are plain vector stores. */
+typedef struct mifsk_impair_io {
+    const void		*d_samples;	/* nstreams rows of `kind`, or NULL: x = 0 (noise rows)  */
+    size_t		stream_stride;	/* elements between input rows                           */
+    const uint32_t	*d_nsamples;	/* per stream; NULL -> all = nsamples                    */
+    uint32_t		nsamples;
+    int			nstreams;
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16: the input scalars    */
+    uint32_t		out_kind;	/* ... the output scalars                                */
+    void		*d_out;		/* [nstreams][out_stride]                                */
+    size_t		out_stride;	/* elements between output rows, whole 16-byte vectors   */
+    uint64_t		seed;
+    uint64_t		first_stream;	/* the field's stream index of row 0 (a rank's shard)    */
+    uint64_t		first_sample;	/* the field's sample index of column 0, % 4 == 0 (a piece) */
+    const float		*d_gain;	/* [nstreams] device arrays, or NULL: the scalars below  */
+    const float		*d_sigma;
+    const float		*d_dc;
+    float		gain;
+    float		sigma;
+    float		dc;
+    uint32_t		flags;		/* 0 */
+} mifsk_impair_io;			/* 120 bytes */
+
+int   mifsk_impair_batch( mifsk_ctx *ctx, const mifsk_impair_io *io, void *stream );
+/* host only: the sigma of a signal-to-noise ratio, (float)sqrt((a * a / 2) / 10^(snr_db / 10)) in
+ * double: the power of a tone of amplitude a is a^2 / 2. */
+float mifsk_impair_sigma( float amplitude, double snr_db );
 
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 

@@ -17,12 +17,14 @@ import numpy as np
 from . import _lib
 from ._lib import ModemArgs, RxConfig  # noqa: F401
 from ._lib import MUX_COMPLEX, MuxIO, MuxParams  # noqa: F401
+from ._lib import ImpairIO  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
            "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones",
            "channel_taps", "ChannelPlan", "channelize",
-           "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table"]
+           "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table",
+           "ImpairIO", "impair", "snr_sigma"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -132,6 +134,17 @@ class Context(_Handle):
         if rc != 0:
             raise RuntimeError("mifsk_selftest_rcp failed: %d" % rc)
         return rc_out, q
+
+    def selftest_gauss(self, words):
+        """mifsk_selftest_gauss: uint32 words [n, 2] -> float64 [n, 2], the device's R(w[0]) C(w[1]) and
+        R(w[0]) S(w[1]) of the channel model's noise field."""
+        words = np.ascontiguousarray(words, np.uint32)
+        assert words.ndim == 2 and words.shape[1] == 2
+        z = np.empty(words.shape, np.float64)
+        rc = self._lib.mifsk_selftest_gauss(self.handle, words.ctypes.data, words.shape[0], z.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_gauss failed: %d" % rc)
+        return z
 
     def selftest_mag(self, re, im, scalar=1.0):
         """mifsk_selftest_mag: double arrays re, im -> (sqrt_sumsq(s), sqrt_newton1(s)'s g, its
@@ -769,6 +782,93 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     rc = lib.mifsk_multiplex_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_multiplex_batch failed: %d" % rc)
+    return out
+
+
+def snr_sigma(amplitude, snr_db):
+    """mifsk_impair_sigma: the noise sigma that puts a tone of `amplitude` (power amplitude^2 / 2) at
+    snr_db; float("inf") gives 0.0."""
+    return float(_lib.load().mifsk_impair_sigma(C.c_float(amplitude), C.c_double(snr_db)))
+
+
+def impair(ctx, samples, nsamples=None, seed=0, sigma=0.0, gain=1.0, dc=0.0, first_stream=0, first_sample=0,
+           s16_out=None, out=None, stream=None):
+    """mifsk_impair_batch, the channel model: out = gain * x + dc + sigma * z, z the library's noise field,
+    a pure function of (seed, first_stream + row, first_sample + column).
+
+    samples : CUDA tensor [nstreams, stride] (or 1-D for one stream), float32 or int16 (PCM16); rows are
+              16-byte aligned and a whole number of 16-byte vectors apart.  None (with out=) or a shape
+              (nstreams, width) gives noise rows: x = 0.
+    nsamples: None (the rows' width), an int, or a torch.int32/uint32 CUDA tensor [nstreams]
+    sigma, gain, dc: each a number or a float32 CUDA tensor [nstreams], one value per row
+    first_stream, first_sample: where row 0 and column 0 lie in the field (a shard of the rows, a piece
+              of the columns; first_sample % 4 == 0)
+    s16_out : PCM16 output; None: out's kind, else the input's (float32 for noise rows)
+    out     : the output tensor [nstreams, out_stride], float32 or int16, its rows filling their stride (every
+              element up to the stride is written); out=samples is in place.  None: a new tensor, the width rounded up to whole 16-byte vectors, made on the launch stream.
+    Returns out; a row is zero behind its length.  No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    shape = None
+    if samples is not None and not torch.is_tensor(samples):
+        shape, samples = tuple(int(v) for v in samples), None
+        assert len(shape) == 2, "a shape is (nstreams, width)"
+    if samples is not None:
+        assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
+        if samples.dim() == 1:
+            samples = samples[None, :]
+            if out is not None and out.dim() == 1:
+                out = out[None, :]
+        assert samples.dim() == 2 and samples.stride(1) == 1
+        nstreams, width = samples.shape
+        in_s16 = samples.dtype == torch.int16
+        row_stride = samples.stride(0) if nstreams > 1 else int(width)
+        device = samples.device
+    else:
+        assert out is not None or shape is not None, "noise rows want out= or a shape"
+        nstreams, width = shape if shape is not None else out.shape
+        in_s16, row_stride = False, 0
+        device = out.device if out is not None else torch.device("cuda")
+    if out is None:
+        out_s16 = in_s16 if s16_out is None else bool(s16_out)
+        vec = 8 if out_s16 else 4
+        with _on(torch, stream):
+            out = torch.empty((nstreams, max(vec, (int(width) + vec - 1) // vec * vec)),
+                              dtype=torch.int16 if out_s16 else torch.float32, device=device)
+        if stream is not None:
+            out.record_stream(torch.cuda.current_stream())      # (see _torch_outputs)
+    else:
+        assert out.is_cuda and out.dtype in (torch.float32, torch.int16)
+        assert out.dim() == 2 and out.shape[0] == nstreams and out.stride(1) == 1
+        # (every element of a row up to the stride is written: a view narrower than its stride is refused)
+        assert nstreams == 1 or out.stride(0) == out.shape[1], "out's rows must fill their stride"
+        out_s16 = out.dtype == torch.int16
+        assert s16_out is None or bool(s16_out) == out_s16, "out is not of the kind s16_out asks for"
+    out_stride = out.stride(0) if nstreams > 1 else int(out.shape[1])
+    nsamples_t = nsamples if torch.is_tensor(nsamples) else None
+    _check_nsamples(torch, nsamples_t, nstreams)
+
+    io = _lib.ImpairIO()
+    io.d_samples = samples.data_ptr() if samples is not None else None
+    io.stream_stride = row_stride
+    io.d_nsamples = nsamples_t.data_ptr() if nsamples_t is not None else None
+    io.nsamples = int(width) if nsamples is None or nsamples_t is not None else int(nsamples)
+    io.nstreams = nstreams
+    io.kind = _lib.FEED_S16 if in_s16 else _lib.FEED_F32
+    io.out_kind = _lib.FEED_S16 if out_s16 else _lib.FEED_F32
+    io.d_out = out.data_ptr()
+    io.out_stride = out_stride
+    io.seed, io.first_stream, io.first_sample = int(seed), int(first_stream), int(first_sample)
+    for name, v in (("gain", gain), ("sigma", sigma), ("dc", dc)):
+        if torch.is_tensor(v):
+            assert v.is_cuda and v.dtype == torch.float32 and v.shape == (nstreams,) and v.is_contiguous(), \
+                "%s: a float32 CUDA tensor [nstreams]" % name
+            setattr(io, "d_" + name, v.data_ptr())
+        else:
+            setattr(io, name, float(v))
+    rc = lib.mifsk_impair_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_impair_batch failed: %d" % rc)
     return out
 
 

@@ -290,7 +290,17 @@ class MuxIO(C.Structure):
                 ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
 
 
+class ImpairIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("out_kind", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("seed", C.c_uint64),
+                ("first_stream", C.c_uint64), ("first_sample", C.c_uint64), ("d_gain", C.c_void_p),
+                ("d_sigma", C.c_void_p), ("d_dc", C.c_void_p), ("gain", C.c_float), ("sigma", C.c_float),
+                ("dc", C.c_float), ("flags", C.c_uint32)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
+assert C.sizeof(ImpairIO) == 120 and ImpairIO.d_out.offset == 40 and ImpairIO.d_gain.offset == 80
 assert C.sizeof(MuxParams) == 56 and MuxParams.centres.offset == 32 and MuxParams.gains.offset == 48
 assert C.sizeof(MuxIO) == 64 and MuxIO.d_out.offset == 32 and MuxIO.d_nout.offset == 56
 assert C.sizeof(ChannelParams) == 48 and ChannelParams.centres.offset == 32
@@ -336,6 +346,7 @@ EXPORTS = [
     "mifsk_channel_plan_create", "mifsk_channel_plan_destroy", "mifsk_channelize_batch",
     "mifsk_channel_table", "mifsk_channel_taps",
     "mifsk_mux_plan_create", "mifsk_mux_plan_destroy", "mifsk_multiplex_batch", "mifsk_mux_table",
+    "mifsk_impair_batch", "mifsk_impair_sigma", "mifsk_selftest_gauss",
 ]
 
 _lib = None
@@ -586,5 +597,11 @@ def load():
     lib.mifsk_multiplex_batch.argtypes = [C.c_void_p, C.POINTER(MuxIO), C.c_void_p]
     lib.mifsk_mux_table.restype = C.c_int
     lib.mifsk_mux_table.argtypes = [C.POINTER(MuxParams), C.c_void_p]
+    lib.mifsk_impair_batch.restype = C.c_int
+    lib.mifsk_impair_batch.argtypes = [C.c_void_p, C.POINTER(ImpairIO), C.c_void_p]
+    lib.mifsk_impair_sigma.restype = C.c_float
+    lib.mifsk_impair_sigma.argtypes = [C.c_float, C.c_double]
+    lib.mifsk_selftest_gauss.restype = C.c_int
+    lib.mifsk_selftest_gauss.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = lib
     return lib

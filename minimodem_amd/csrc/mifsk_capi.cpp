@@ -73,6 +73,7 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_channel_io);
     MIFSK_SIZEOF(mifsk_mux_params);
     MIFSK_SIZEOF(mifsk_mux_io);
+    MIFSK_SIZEOF(mifsk_impair_io);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;

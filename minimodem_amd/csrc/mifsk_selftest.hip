@@ -1,6 +1,7 @@
 // mifsk_selftest.hip -- the device arithmetic of mifsk_devlib.h / mifsk_devmath.h, one value or
 // one frame per thread, for the host to compare with an independent reference
-// (mifsk_selftest_rcp / _mag / _confidence in include/mifsk.h; tests/test_gpu_devmath.py), and the
+// (mifsk_selftest_rcp / _mag / _confidence in include/mifsk.h; tests/test_gpu_devmath.py; _gauss:
+// the noise field's transform of mifsk_gauss.h, tests/test_gpu_impair.py), and the
 // wave-wide routines -- the correlators, the replay's lane scans, the wave maximum -- one window
 // or one frame per LANE of whole waves (mifsk_selftest_corr / _scan / _wave_max;
 // tests/test_gpu_correlators.py, tests/test_gpu_scans.py).
@@ -20,6 +21,7 @@
 #include "mifsk_ctx.h"
 #include "mifsk_hostmem.h"
 #include "mifsk_devlib.h"
+#include "mifsk_gauss.h"
 
 namespace mifsk {
 
@@ -34,6 +36,19 @@ void selftest_rcp_kernel( const float *__restrict__ c, const float *__restrict__
     const double rc = rcp_of_float(c[i]);
     rc_out[i] = rc;
     q_out[i] = div_by_rcp(x[i], rc);
+}
+
+// z[i] = { R(w[i].x) C(w[i].y), R(w[i].x) S(w[i].y) } (mifsk_gauss.h)
+__global__ __launch_bounds__(256)
+void selftest_gauss_kernel( const uint2 *__restrict__ w, uint64_t n, double2 *__restrict__ z_out )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n )
+	return;
+    const uint2 wi = w[i];
+    double z0, z1;
+    mifsk_gauss_pair(wi.x, wi.y, &z0, &z1);
+    z_out[i] = double2{z0, z1};
 }
 
 // s as band_mag() builds it from (re[i], im[i]); root[i] = sqrt_sumsq(s); g[i], unsafe[i] =
@@ -287,6 +302,25 @@ extern "C" int mifsk_selftest_rcp( mifsk_ctx *ctx, const float *c, const float *
     if ( int rc = mifsk::finish() )
 	return rc;
     return d_rc.get(rcp_out, n * sizeof(double)) && d_q.get(quot_out, n * sizeof(float)) ? 0 : -EIO;
+}
+
+extern "C" int mifsk_selftest_gauss( mifsk_ctx *ctx, const uint32_t *words, uint64_t n, double *z_out )
+{
+    if ( !ctx || !words || !z_out || n > mifsk::kMaxValues )
+	return -EINVAL;
+    if ( n == 0 )
+	return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    TestBuf d_w, d_z;
+    if ( !d_w.make(n * sizeof(uint2)) || !d_z.make(n * sizeof(double2)) )
+	return -ENOMEM;
+    if ( !d_w.put(words, n * sizeof(uint2)) )
+	return -EIO;
+    hipLaunchKernelGGL(mifsk::selftest_gauss_kernel, dim3((unsigned)( ( n + 255u ) / 256u )), dim3(256), 0, nullptr,
+	    (const uint2 *)d_w.p, n, (double2 *)d_z.p);
+    if ( int rc = mifsk::finish() )
+	return rc;
+    return d_z.get(z_out, n * sizeof(double2)) ? 0 : -EIO;
 }
 
 extern "C" int mifsk_selftest_mag( mifsk_ctx *ctx, const double *re, const double *im, float scalar, uint64_t n,
