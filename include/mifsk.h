@@ -889,9 +889,10 @@ size_t mifsk_session_pending( const mifsk_session *s, int stream );
  *                            d_samples[i][0 .. nsamples[i]) is read, until the call returns.
  * -EINVAL: a session without the flag, an unknown kind, a count without its pointer (d_samples ==
  * NULL with any count non-zero), a stride smaller than a count, a feed after the final one.
- * A FAILED FEED leaves the session as it was before the call -- the rows it built are in the
- * other buffer, and the host's integers change only after the loop has run -- so the caller may
- * repeat it.  A stream whose loop has FINISHED (--rx-one after its carrier loss, an aborted
+ * A FAILED FEED, refused or broken off, leaves a session of EITHER kind as it was before the call
+ * -- the rows it built are in the other buffer (host-tail: in the staging rows), and what the
+ * session holds of a stream changes only after the loop has run -- so the caller may repeat it.
+ * A stream whose loop has FINISHED (--rx-one after its carrier loss, an aborted
  * loop) holds nothing from then on: later samples for it are ignored, its pending is 0 and its
  * results are empty; so a live stream's row stays below about two samplebufs plus the piece.
  * (The host-tail session keeps appending to such a stream's tail.) */

@@ -1840,35 +1840,14 @@ class SlabSession:
             d = torch.from_numpy(host).cuda()
             dl = torch.from_numpy(lens).cuda()
             do = torch.from_numpy(self.origin.view(np.int64).copy()).cuda()
-            fc = max_frames(self.cfg, width)
-            dev = d.device
-            out = {"nframes": torch.zeros(self.n, dtype=torch.int32, device=dev),
-                   "status": torch.zeros(self.n, dtype=torch.int32, device=dev),
-                   "bytes": torch.zeros((self.n, fc), dtype=torch.uint8, device=dev),
-                   "nbytes": torch.zeros(self.n, dtype=torch.int32, device=dev),
-                   "bits": torch.zeros((self.n, fc), dtype=torch.int64, device=dev),
-                   "frames": torch.zeros((self.n, fc, FRAME_DTYPE.itemsize), dtype=torch.uint8, device=dev),
-                   "episodes": torch.zeros((self.n, self.episodes_cap, EPISODE_DTYPE.itemsize),
-                                           dtype=torch.uint8, device=dev),
-                   "nepisodes": torch.zeros(self.n, dtype=torch.int32, device=dev),
-                   "carrier_band": torch.full((self.n,), -1, dtype=torch.int32, device=dev)}
-        io = _lib.DemodIO()
+        fc = max_frames(self.cfg, width)
+        out = _torch_outputs(torch, self.cfg, d.device, self.n, ("bytes", "bits", "frames", "episodes", "carrier_band"),
+                             fc, self.episodes_cap, stream)
+        io = _result_io(out, self.n, fc, self.episodes_cap, _tensor_address)
         io.d_samples = d.data_ptr()
         io.stream_stride = d.stride(0) if self.n > 1 else width
         io.d_nsamples = dl.data_ptr()
         io.nsamples = width
-        io.nstreams = self.n
-        io.d_bytes = out["bytes"].data_ptr()
-        io.d_nbytes = out["nbytes"].data_ptr()
-        io.d_bits = out["bits"].data_ptr()
-        io.d_frames = out["frames"].data_ptr()
-        io.d_nframes = out["nframes"].data_ptr()
-        io.frames_cap = fc
-        io.d_episodes = out["episodes"].data_ptr()
-        io.d_nepisodes = out["nepisodes"].data_ptr()
-        io.episodes_cap = self.episodes_cap
-        io.d_status = out["status"].data_ptr()
-        io.d_carrier_band = out["carrier_band"].data_ptr()
         io.flags = _io_flags(False, self.engine)
         if self.ring is not None:
             io.flags = _lib.IO_RING_EXACT

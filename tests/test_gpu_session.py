@@ -137,3 +137,22 @@ def test_argument_errors(gpu):
         s.feed([None, None], final=True)                                   # the final piece has been fed
     assert not lib.mifsk_session_get(s.handle, 2) and lib.mifsk_session_pending(s.handle, -1) == 0
     s.close()
+
+
+def test_a_refused_feed_leaves_a_host_tail_session_as_it_was(gpu):
+    """stream 0's five samples come before the count without its pointer: they must not stay behind"""
+    M, torch, ctx = gpu
+    from minimodem_amd import _lib
+    lib = _lib.load()
+    cfg = M.rx_config("1200")
+    s = M.Session(ctx, cfg, 2)
+    x = M.synthesize(cfg, np.arange(40, 80, dtype=np.uint8))
+    ptrs = (C.c_void_p * 2)(x.ctypes.data, None)
+    cnt = (C.c_uint32 * 2)(5, 5)
+    assert lib.mifsk_session_feed(s.handle, ptrs, cnt, 0) == -22
+    assert [lib.mifsk_session_pending(s.handle, i) for i in range(2)] == [0, 0]
+    assert s.info()["feeds"] == 0
+    cut = len(x) // 2 | 1
+    got = s.feed([x[:cut], None])[0]["bytes"] + s.feed([x[cut:], None], final=True)[0]["bytes"]
+    assert got == bytes(range(40, 80))
+    s.close()
