@@ -35,6 +35,8 @@
  *   mifsk_demod_files_long        ... long recordings: every group cut in time across the chip
  *   mifsk_frame_softbits          fsk_bit_analyze on every bit window of the frames found  fsk.c:107-169
  *   mifsk_detect_carrier_batch    fsk_detect_carrier     fsk.c:543-581 (windows of every stream)
+ *   mifsk_fm_demod_batch          (none: the FM receiver in front of the audio input) I/Q rows -> audio rows
+ *   mifsk_fm_modulate_batch       (none: the FM transmitter behind the audio output)  audio rows -> I/Q rows
  */
 #ifndef MIFSK_H
 #define MIFSK_H
@@ -205,6 +207,9 @@ int mifsk_selftest_confidence( mifsk_ctx *ctx, int variant, uint32_t n_bits, uin
  * csrc/mifsk_gauss.h) for chosen words, which cannot be steered through Philox: z_out[i] =
  * { R(words[i][0]) C(words[i][1]), R(words[i][0]) S(words[i][1]) }, words [n][2], z_out [n][2]. */
 int mifsk_selftest_gauss( mifsk_ctx *ctx, const uint32_t *words, uint64_t n, double *z_out );
+/* _turn: the FM stage's angle (mifsk_fm_demod_batch below; csrc/mifsk_angle.h) for chosen pairs,
+ * most of which no pair of float samples reaches: out[i] = mifsk_turn(y[i], x[i]). */
+int mifsk_selftest_turn( mifsk_ctx *ctx, const double *y, const double *x, uint64_t n, double *out );
 
 /* Diagnostics, wave-wide routines (csrc/mifsk_devlib.h) on HOST arrays, synchronous, like the
  * three above; tests/test_gpu_correlators.py and tests/test_gpu_scans.py compare them with the
@@ -1297,6 +1302,117 @@ int   mifsk_impair_batch( mifsk_ctx *ctx, const mifsk_impair_io *io, void *strea
 /* host only: the sigma of a signal-to-noise ratio, (float)sqrt((a * a / 2) / 10^(snr_db / 10)) in
  * double: the power of a tone of amplitude a is a^2 / 2. */
 float mifsk_impair_sigma( float amplitude, double snr_db );
+
+/* ---- FM stage: batched NBFM discriminator and phase-exact FM modulator ---- */
+
+/* Audio FSK on the air (Bell-202 as APRS, SAME, UIC-751-3) sits inside a narrow-band FM channel.
+ * These two entries are the FM receiver in front of mifsk_demod_batch and the FM transmitter behind
+ * mifsk_tx_synthesize_batch, for a batch of rows, made of integer arithmetic and IEEE double
+ * operations only (tools/fm_ref.c restates all of this; the device equals it bit for bit).  Every
+ * operation below is ONE IEEE double operation, rounded once; every a * b + c written fma is one
+ * fused operation and nothing else is fused (both sides compile with -ffp-contract=off).
+ *   The angle turn(y, x): the argument of x + i y in TURNS, [-0.5, 0.5] (csrc/mifsk_angle.h):
+ *     ax = |x|;  ay = |y|;  sw = ay > ax;  mx = sw ? ay : ax;  mn = sw ? ax : ay
+ *     if mx == 0.0:  a = 0.0
+ *     else:
+ *       big = mn > mx * 0x1.a827999fcef32p-2                          (tan(pi/8))
+ *       u = big ? (mn - mx) / (mn + mx) : mn / mx                     (one division; |u| <= tan(pi/8))
+ *       v = u * u;  p = -1.0 / 23.0;  for k = 10 down to 0:  p = fma(p, v, (-1)^k / (2 k + 1))
+ *       r = u * p
+ *       a = fma(r, 0x1.45f306dc9c883p-3, big ? 0.125 : 0.0)           (1 / (2 pi))
+ *     if sw:  a = 0.25 - a
+ *     if x < 0.0:  a = 0.5 - a
+ *     if y < 0.0:  a = -a
+ *   (every constant of the series is one double division of +-1.0 by the odd number.)  The series
+ * stops at u^23: at u = tan(pi/8) the next term is 1.7e-12 turns.  Nothing is special-cased: a NaN
+ * on either side gives a NaN, and so does Inf / Inf, because the arithmetic says so -- but for y a
+ * NaN beside x = +-0.0, where the comparisons make mx = 0.0 and the answer 0.0.  turn(0, 1) = 0,
+ * turn(1, 0) = 0.25, turn(0, -1) = 0.5, turn(-1, 0) = -0.25, turn(0, 0) = 0 (a zero of either sign on either side).
+ *   THE DISCRIMINATOR.  Rows are interleaved I, Q, float32 (MIFSK_FEED_F32) or PCM16
+ * (MIFSK_FEED_S16, a scalar is (float)v / 32768.0f); an element is one complex sample and strides
+ * count elements, as in the channelizer.  Row s, n < W_s = min(nsamples[s], stream_stride,
+ * out_stride), with (a, b) = (I[n], Q[n]) and (c, d) = (I[n - 1], Q[n - 1]) widened to double:
+ *   re = fma(a, c, b * d);  im = fma(b, c, -(a * d));  out[n] = (float)((double)gain * turn(im, re))
+ * For n = 0 the sample before is d_prev[s] (two floats) where that array is given, else (0, 0),
+ * which gives 0.0.  d_last[s] (may be NULL) receives the row's last valid sample as two floats --
+ * d_prev[s], or (0, 0), when W_s = 0 -- so a recording demodulated in pieces with one call's d_last
+ * as the next call's d_prev is the whole recording's output, bit for bit.  d_last must not overlap
+ * d_prev or the rows.  Elements from W_s to out_stride are written as zero.  mifsk_fm_gain's gain
+ * puts full deviation at +-1.0.
+ *   mifsk_fm_demod_batch checks, in this order and before any HIP call: -EINVAL for a NULL ctx, io,
+ * d_samples or d_out; for nstreams <= 0; for a kind that is neither MIFSK_FEED_F32 nor
+ * MIFSK_FEED_S16; for flags != 0; for an input base that is not 16-byte aligned or a stream_stride
+ * that is not whole 16-byte vectors of complex elements (2 of float32, 4 of PCM16); for an output
+ * base that is not 16-byte aligned, out_stride == 0, out_stride % 4 != 0, or above 2^32 - 8.
+ * Asynchronous on `stream`; it allocates nothing and synchronises nothing.  Whatever the arguments
+ * hold, nothing outside nstreams * stream_stride input elements (and d_prev) is read and nothing
+ * outside nstreams * out_stride output elements and d_last is written; nothing written is read
+ * back, and the outputs are plain vector stores. */
+typedef struct mifsk_fm_demod_io {
+    const void		*d_samples;	/* nstreams rows of interleaved I, Q of `kind`           */
+    size_t		stream_stride;	/* complex elements between input rows                   */
+    const uint32_t	*d_nsamples;	/* per stream; NULL -> all = nsamples                    */
+    uint32_t		nsamples;
+    int			nstreams;
+    uint32_t		kind;		/* MIFSK_FEED_F32 / MIFSK_FEED_S16: the input scalars    */
+    uint32_t		flags;		/* 0 */
+    float		*d_out;		/* [nstreams][out_stride]                                */
+    size_t		out_stride;	/* floats between output rows, % 4 == 0                  */
+    const float		*d_prev;	/* [nstreams][2]: the sample before each row, or NULL: (0, 0) */
+    float		*d_last;	/* [nstreams][2]: each row's last valid sample, or NULL  */
+    float		gain;
+    uint32_t		reserved;
+} mifsk_fm_demod_io;			/* 80 bytes */
+
+int   mifsk_fm_demod_batch( mifsk_ctx *ctx, const mifsk_fm_demod_io *io, void *stream );
+/* host only: (float)(sample_rate / deviation_hz), the gain that puts +-deviation_hz at +-1.0 */
+float mifsk_fm_gain( double sample_rate, double deviation_hz );
+
+/*   THE MODULATOR.  The phase is an INTEGER, 2^48 to the turn, summed mod 2^64: a sum of integers
+ * does not depend on its order, so the device scans it in parallel and still equals a serial loop.
+ * Input rows are real float32, what mifsk_tx_synthesize_batch writes; output rows are interleaved
+ * I, Q, float32 or PCM16 (out_kind).  Row s, i < W_s = min(nsamples[s], stream_stride, out_stride):
+ *   d = fma((double)x[i], deviation, centre)            (turns per sample; both are doubles)
+ *   q[i] = |d| < 16384.0 ? (int64)rint(d * 2^48) : 0    (to nearest even; false for a NaN)
+ *   phase[n] = phase0[s] + q[0] + ... + q[n]  mod 2^64  (phase0 = 0 without d_phase0)
+ *   w = (uint32)(phase[n] >> 16);  (C, S) = C(w), S(w) of the channel model above
+ *   I = (float)(A * C),  Q = (float)(A * S),  A = (double)amplitude
+ * For PCM16 output each float goes through the multiplexer's write conversion.  Elements from W_s
+ * to out_stride are written as zero.  d_phase_out[s] (may be NULL) receives phase[W_s - 1], or
+ * phase0[s] when W_s = 0, so pieces continue exactly; d_phase_out may be d_phase0.  mifsk_fm_step
+ * gives `deviation` (and `centre`) from Hertz.
+ *   mifsk_fm_modulate_batch checks, in this order and before any HIP call: -EINVAL for a NULL ctx,
+ * io, d_samples or d_out; for nstreams <= 0; for an out_kind that is neither MIFSK_FEED_F32 nor
+ * MIFSK_FEED_S16; for flags != 0; for an input base that is not 16-byte aligned or a stream_stride
+ * % 4 != 0; for an output base that is not 16-byte aligned, out_stride == 0, out_stride not whole
+ * 16-byte vectors of complex elements of out_kind (2 of float32, 4 of PCM16), or above 2^32 - 8.
+ * Asynchronous on `stream`: three launches (sums of tiles of 2048 samples, one wave per row over the
+ * sums, the tiles' outputs) around nstreams * ceil(out_stride / 2048) * 8 bytes of stream-ordered
+ * scratch (-ENOMEM when there is none); it synchronises nothing, and no workgroup waits for another.
+ * Nothing outside nstreams * stream_stride input elements (and d_phase0) is read and nothing
+ * outside nstreams * out_stride output elements and d_phase_out is written; the outputs are plain
+ * vector stores. */
+typedef struct mifsk_fm_mod_io {
+    const float		*d_samples;	/* nstreams rows of float32                              */
+    size_t		stream_stride;	/* floats between input rows, % 4 == 0                   */
+    const uint32_t	*d_nsamples;	/* per stream; NULL -> all = nsamples                    */
+    uint32_t		nsamples;
+    int			nstreams;
+    uint32_t		out_kind;	/* MIFSK_FEED_F32 / MIFSK_FEED_S16: the output scalars   */
+    uint32_t		flags;		/* 0 */
+    void		*d_out;		/* [nstreams][out_stride] interleaved I, Q               */
+    size_t		out_stride;	/* complex elements between output rows, whole 16-byte vectors */
+    double		deviation;	/* turns per sample at x = 1.0                           */
+    double		centre;		/* turns per sample at x = 0.0                           */
+    const uint64_t	*d_phase0;	/* [nstreams]: the phase before each row, or NULL: 0     */
+    uint64_t		*d_phase_out;	/* [nstreams]: each row's last phase, or NULL            */
+    float		amplitude;
+    uint32_t		reserved;
+} mifsk_fm_mod_io;			/* 96 bytes */
+
+int    mifsk_fm_modulate_batch( mifsk_ctx *ctx, const mifsk_fm_mod_io *io, void *stream );
+/* host only: deviation_hz / sample_rate, Hertz as turns per sample */
+double mifsk_fm_step( double deviation_hz, double sample_rate );
 
 /* ---- several GPUs (SURVEY 8 e) -------------------------------------------- */
 

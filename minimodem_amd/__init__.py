@@ -18,13 +18,15 @@ from . import _lib
 from ._lib import ModemArgs, RxConfig  # noqa: F401
 from ._lib import MUX_COMPLEX, MuxIO, MuxParams  # noqa: F401
 from ._lib import ImpairIO  # noqa: F401
+from ._lib import FmDemodIO, FmModIO  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
            "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones",
            "channel_taps", "ChannelPlan", "channelize",
            "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table",
-           "ImpairIO", "impair", "snr_sigma"]
+           "ImpairIO", "impair", "snr_sigma",
+           "FmDemodIO", "FmModIO", "fm_demod", "fm_modulate", "fm_gain", "fm_step"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -145,6 +147,18 @@ class Context(_Handle):
         if rc != 0:
             raise RuntimeError("mifsk_selftest_gauss failed: %d" % rc)
         return z
+
+    def selftest_turn(self, y, x):
+        """mifsk_selftest_turn: float64 arrays y, x [n] -> float64 [n], the device's mifsk_turn(y, x) of the
+        FM stage: the angle of x + i y in turns."""
+        y = np.ascontiguousarray(y, np.float64)
+        x = np.ascontiguousarray(x, np.float64)
+        assert y.shape == x.shape and y.ndim == 1
+        out = np.empty(y.shape, np.float64)
+        rc = self._lib.mifsk_selftest_turn(self.handle, y.ctypes.data, x.ctypes.data, y.size, out.ctypes.data)
+        if rc != 0:
+            raise RuntimeError("mifsk_selftest_turn failed: %d" % rc)
+        return out
 
     def selftest_mag(self, re, im, scalar=1.0):
         """mifsk_selftest_mag: double arrays re, im -> (sqrt_sumsq(s), sqrt_newton1(s)'s g, its
@@ -869,6 +883,127 @@ def impair(ctx, samples, nsamples=None, seed=0, sigma=0.0, gain=1.0, dc=0.0, fir
     rc = lib.mifsk_impair_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
     if rc != 0:
         raise RuntimeError("mifsk_impair_batch failed: %d" % rc)
+    return out
+
+
+def fm_gain(sample_rate, deviation_hz):
+    """mifsk_fm_gain: the discriminator gain that puts +-deviation_hz at +-1.0."""
+    return float(_lib.load().mifsk_fm_gain(C.c_double(sample_rate), C.c_double(deviation_hz)))
+
+
+def fm_step(deviation_hz, sample_rate):
+    """mifsk_fm_step: Hertz as turns per sample, the modulator's `deviation` and `centre`."""
+    return float(_lib.load().mifsk_fm_step(C.c_double(deviation_hz), C.c_double(sample_rate)))
+
+
+def _fm_out(torch, out, shape, dtype, device, stream):
+    """the output rows of an FM entry: `out` checked (its rows fill their stride: every element up to the
+    stride is written), or a new tensor of `shape` made on the launch stream -> (out, elements between rows)"""
+    if out is None:
+        with _on(torch, stream):
+            out = torch.empty(shape, dtype=dtype, device=device)
+        if stream is not None:
+            out.record_stream(torch.cuda.current_stream())      # (see _torch_outputs)
+    else:
+        assert out.is_cuda and out.dtype == dtype and out.dim() == len(shape) and out.shape[0] == shape[0]
+        assert out.shape[2:] == tuple(shape[2:]) and out.is_contiguous(), "out's rows must fill their stride"
+    return out, int(out.shape[1])
+
+
+def _fm_lengths(torch, io, nsamples, width, nstreams):
+    nsamples_t = nsamples if torch.is_tensor(nsamples) else None
+    _check_nsamples(torch, nsamples_t, nstreams)
+    io.d_nsamples = nsamples_t.data_ptr() if nsamples_t is not None else None
+    io.nsamples = int(width) if nsamples is None or nsamples_t is not None else int(nsamples)
+    io.nstreams = nstreams
+
+
+def fm_demod(ctx, iq, nsamples=None, gain=1.0, prev=None, last=None, stream=None, out=None):
+    """mifsk_fm_demod_batch, the NBFM discriminator: out[n] = gain * turn(z[n] * conj(z[n - 1])), the angle
+    in turns by the library's own arithmetic (reproducible bit for bit; tools/fm_ref.c).
+
+    iq      : CUDA tensor [nstreams, stride, 2] of interleaved I, Q, float32 or int16 (PCM16); rows are 16-byte
+              aligned and a whole number of 16-byte vectors apart
+    nsamples: None (the rows' width), an int, or a torch.int32/uint32 CUDA tensor [nstreams]
+    gain    : fm_gain(sample_rate, deviation_hz) puts full deviation at +-1.0
+    prev    : None ((0, 0): out[0] = 0), or a float32 CUDA tensor [nstreams, 2]: the sample before each row
+    last    : None, or a float32 CUDA tensor [nstreams, 2] (not `prev`) that receives each row's last valid
+              sample: the next piece's `prev`
+    out     : the output tensor, float32 [nstreams, out_stride], out_stride % 4 == 0, its rows filling their
+              stride.  None: a new tensor, the width rounded up to 4, made on the launch stream.
+    Returns out; a row is zero behind its length.  No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert iq.is_cuda and iq.dtype in (torch.float32, torch.int16) and iq.dim() == 3 and iq.shape[2] == 2
+    assert iq.stride(2) == 1 and iq.stride(1) == 2 and iq.stride(0) % 2 == 0, "complex rows are interleaved I, Q"
+    nstreams, width = int(iq.shape[0]), int(iq.shape[1])
+    s16 = iq.dtype == torch.int16
+    row_stride = iq.stride(0) // 2 if nstreams > 1 else width
+    out, out_stride = _fm_out(torch, out, (nstreams, max(4, (width + 3) // 4 * 4)), torch.float32, iq.device, stream)
+    io = _lib.FmDemodIO()
+    io.d_samples, io.stream_stride = iq.data_ptr(), row_stride
+    _fm_lengths(torch, io, nsamples, width, nstreams)
+    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    io.d_out, io.out_stride, io.gain = out.data_ptr(), out_stride, float(gain)
+    for name, t in (("d_prev", prev), ("d_last", last)):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == (nstreams, 2) and t.is_contiguous(), \
+                "%s: a float32 CUDA tensor [nstreams, 2]" % name[2:]
+            setattr(io, name, t.data_ptr())
+    assert prev is None or last is None or prev.data_ptr() != last.data_ptr(), "last must not be prev"
+    rc = lib.mifsk_fm_demod_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_fm_demod_batch failed: %d" % rc)
+    return out
+
+
+def fm_modulate(ctx, samples, nsamples=None, deviation=None, centre=0.0, amplitude=1.0, phase0=None, phase_out=None,
+                s16=False, stream=None, out=None):
+    """mifsk_fm_modulate_batch, the FM modulator: I, Q = amplitude * cos, sin of an INTEGER phase that advances
+    by rint((x * deviation + centre) * 2^48) per sample (2^48 to the turn), so pieces and the parallel scan on
+    the device equal one serial loop bit for bit (tools/fm_ref.c).
+
+    samples : float32 CUDA tensor [nstreams, stride] (or 1-D for one stream), what synthesize_batch returns;
+              rows are 16-byte aligned, stride % 4 == 0
+    nsamples: None (the rows' width), an int, or a torch.int32/uint32 CUDA tensor [nstreams]
+    deviation, centre: turns per sample at x = 1.0 and at x = 0.0: fm_step(hertz, sample_rate)
+    phase0  : None (0), or an int64/uint64 CUDA tensor [nstreams]: the phase before each row
+    phase_out: None, or an int64/uint64 CUDA tensor [nstreams] that receives each row's last phase, the next
+              piece's phase0 (it may be `phase0` itself)
+    s16     : PCM16 output (when out is None)
+    out     : the output tensor [nstreams, out_stride, 2], float32 or int16, its rows filling their stride.
+              None: a new tensor, the width rounded up to whole 16-byte vectors, made on the launch stream.
+    Returns out; a row is zero behind its length.  No synchronisation is performed."""
+    torch = _torch()
+    lib = _lib.load()
+    assert deviation is not None, "deviation: turns per sample at x = 1.0 (fm_step)"
+    assert samples.is_cuda and samples.dtype == torch.float32
+    if samples.dim() == 1:
+        samples = samples[None, :]
+    assert samples.dim() == 2 and samples.stride(1) == 1
+    nstreams, width = int(samples.shape[0]), int(samples.shape[1])
+    row_stride = samples.stride(0) if nstreams > 1 else width
+    assert nstreams > 1 or width % 4 == 0, "a lone row must be padded to a multiple of 4 floats"
+    if out is not None:
+        assert out.dtype in (torch.float32, torch.int16)
+        s16 = out.dtype == torch.int16
+    vec = 4 if s16 else 2
+    out, out_stride = _fm_out(torch, out, (nstreams, max(vec, (width + vec - 1) // vec * vec), 2),
+                              torch.int16 if s16 else torch.float32, samples.device, stream)
+    io = _lib.FmModIO()
+    io.d_samples, io.stream_stride = samples.data_ptr(), row_stride
+    _fm_lengths(torch, io, nsamples, width, nstreams)
+    io.out_kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    io.d_out, io.out_stride = out.data_ptr(), out_stride
+    io.deviation, io.centre, io.amplitude = float(deviation), float(centre), float(amplitude)
+    for name, t in (("d_phase0", phase0), ("d_phase_out", phase_out)):
+        if t is not None:
+            assert t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.shape == (nstreams,) and t.is_contiguous(), \
+                "%s: an int64/uint64 CUDA tensor [nstreams]" % name[2:]
+            setattr(io, name, t.data_ptr())
+    rc = lib.mifsk_fm_modulate_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
+    if rc != 0:
+        raise RuntimeError("mifsk_fm_modulate_batch failed: %d" % rc)
     return out
 
 

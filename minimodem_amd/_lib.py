@@ -299,7 +299,24 @@ class ImpairIO(C.Structure):
                 ("dc", C.c_float), ("flags", C.c_uint32)]
 
 
+class FmDemodIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("flags", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("d_prev", C.c_void_p), ("d_last", C.c_void_p),
+                ("gain", C.c_float), ("reserved", C.c_uint32)]
+
+
+class FmModIO(C.Structure):
+    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("out_kind", C.c_uint32), ("flags", C.c_uint32),
+                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("deviation", C.c_double), ("centre", C.c_double),
+                ("d_phase0", C.c_void_p), ("d_phase_out", C.c_void_p), ("amplitude", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
+assert C.sizeof(FmDemodIO) == 80 and FmDemodIO.d_out.offset == 40 and FmDemodIO.gain.offset == 72
+assert C.sizeof(FmModIO) == 96 and FmModIO.d_out.offset == 40 and FmModIO.amplitude.offset == 88
 assert C.sizeof(ImpairIO) == 120 and ImpairIO.d_out.offset == 40 and ImpairIO.d_gain.offset == 80
 assert C.sizeof(MuxParams) == 56 and MuxParams.centres.offset == 32 and MuxParams.gains.offset == 48
 assert C.sizeof(MuxIO) == 64 and MuxIO.d_out.offset == 32 and MuxIO.d_nout.offset == 56
@@ -347,6 +364,7 @@ EXPORTS = [
     "mifsk_channel_table", "mifsk_channel_taps",
     "mifsk_mux_plan_create", "mifsk_mux_plan_destroy", "mifsk_multiplex_batch", "mifsk_mux_table",
     "mifsk_impair_batch", "mifsk_impair_sigma", "mifsk_selftest_gauss",
+    "mifsk_fm_demod_batch", "mifsk_fm_modulate_batch", "mifsk_fm_gain", "mifsk_fm_step", "mifsk_selftest_turn",
 ]
 
 _lib = None
@@ -603,5 +621,15 @@ def load():
     lib.mifsk_impair_sigma.argtypes = [C.c_float, C.c_double]
     lib.mifsk_selftest_gauss.restype = C.c_int
     lib.mifsk_selftest_gauss.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.mifsk_fm_demod_batch.restype = C.c_int
+    lib.mifsk_fm_demod_batch.argtypes = [C.c_void_p, C.POINTER(FmDemodIO), C.c_void_p]
+    lib.mifsk_fm_modulate_batch.restype = C.c_int
+    lib.mifsk_fm_modulate_batch.argtypes = [C.c_void_p, C.POINTER(FmModIO), C.c_void_p]
+    lib.mifsk_fm_gain.restype = C.c_float
+    lib.mifsk_fm_gain.argtypes = [C.c_double, C.c_double]
+    lib.mifsk_fm_step.restype = C.c_double
+    lib.mifsk_fm_step.argtypes = [C.c_double, C.c_double]
+    lib.mifsk_selftest_turn.restype = C.c_int
+    lib.mifsk_selftest_turn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = lib
     return lib

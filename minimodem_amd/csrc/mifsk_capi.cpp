@@ -74,6 +74,8 @@ extern "C" size_t mifsk_abi_sizeof( const char *name )
     MIFSK_SIZEOF(mifsk_mux_params);
     MIFSK_SIZEOF(mifsk_mux_io);
     MIFSK_SIZEOF(mifsk_impair_io);
+    MIFSK_SIZEOF(mifsk_fm_demod_io);
+    MIFSK_SIZEOF(mifsk_fm_mod_io);
     MIFSK_SIZEOF(fsk_plan);
 #undef MIFSK_SIZEOF
     return 0;

@@ -1,7 +1,8 @@
 // mifsk_selftest.hip -- the device arithmetic of mifsk_devlib.h / mifsk_devmath.h, one value or
 // one frame per thread, for the host to compare with an independent reference
 // (mifsk_selftest_rcp / _mag / _confidence in include/mifsk.h; tests/test_gpu_devmath.py; _gauss:
-// the noise field's transform of mifsk_gauss.h, tests/test_gpu_impair.py), and the
+// the noise field's transform of mifsk_gauss.h, tests/test_gpu_impair.py; _turn: the FM stage's
+// angle of mifsk_angle.h, tests/test_gpu_fm.py), and the
 // wave-wide routines -- the correlators, the replay's lane scans, the wave maximum -- one window
 // or one frame per LANE of whole waves (mifsk_selftest_corr / _scan / _wave_max;
 // tests/test_gpu_correlators.py, tests/test_gpu_scans.py).
@@ -22,6 +23,7 @@
 #include "mifsk_hostmem.h"
 #include "mifsk_devlib.h"
 #include "mifsk_gauss.h"
+#include "mifsk_angle.h"
 
 namespace mifsk {
 
@@ -49,6 +51,17 @@ void selftest_gauss_kernel( const uint2 *__restrict__ w, uint64_t n, double2 *__
     double z0, z1;
     mifsk_gauss_pair(wi.x, wi.y, &z0, &z1);
     z_out[i] = double2{z0, z1};
+}
+
+// t[i] = mifsk_turn(y[i], x[i]) (mifsk_angle.h)
+__global__ __launch_bounds__(256)
+void selftest_turn_kernel( const double *__restrict__ y, const double *__restrict__ x, uint64_t n,
+	double *__restrict__ t_out )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if ( i >= n )
+	return;
+    t_out[i] = mifsk_turn(y[i], x[i]);
 }
 
 // s as band_mag() builds it from (re[i], im[i]); root[i] = sqrt_sumsq(s); g[i], unsafe[i] =
@@ -321,6 +334,25 @@ extern "C" int mifsk_selftest_gauss( mifsk_ctx *ctx, const uint32_t *words, uint
     if ( int rc = mifsk::finish() )
 	return rc;
     return d_z.get(z_out, n * sizeof(double2)) ? 0 : -EIO;
+}
+
+extern "C" int mifsk_selftest_turn( mifsk_ctx *ctx, const double *y, const double *x, uint64_t n, double *out )
+{
+    if ( !ctx || !y || !x || !out || n > mifsk::kMaxValues )
+	return -EINVAL;
+    if ( n == 0 )
+	return 0;
+    HIP_OK(hipSetDevice(ctx->device));
+    TestBuf d_y, d_x, d_t;
+    if ( !d_y.make(n * sizeof(double)) || !d_x.make(n * sizeof(double)) || !d_t.make(n * sizeof(double)) )
+	return -ENOMEM;
+    if ( !d_y.put(y, n * sizeof(double)) || !d_x.put(x, n * sizeof(double)) )
+	return -EIO;
+    hipLaunchKernelGGL(mifsk::selftest_turn_kernel, dim3((unsigned)( ( n + 255u ) / 256u )), dim3(256), 0, nullptr,
+	    (const double *)d_y.p, (const double *)d_x.p, n, (double *)d_t.p);
+    if ( int rc = mifsk::finish() )
+	return rc;
+    return d_t.get(out, n * sizeof(double)) ? 0 : -EIO;
 }
 
 extern "C" int mifsk_selftest_mag( mifsk_ctx *ctx, const double *re, const double *im, float scalar, uint64_t n,
