@@ -7,6 +7,7 @@ used by the tests, the benchmark and Python callers: it marshals arguments,
 uses PyTorch only for device memory / streams / torch.distributed, and raises
 if the native library is missing -- there is no fallback implementation.
 """
+import collections
 import contextlib
 import ctypes as C
 import os
@@ -263,14 +264,134 @@ def _stream_ptr(torch, stream):
     return C.c_void_p(stream.cuda_stream)
 
 
-def _check_nsamples(torch, nsamples, nstreams):
-    """Per-stream lengths cross the C ABI as a raw uint32 pointer: reject what the
-    kernels would silently misread (a CPU tensor, int64 lengths, a wrong shape)."""
+_HOST = object()       # _call: the function takes no stream
+
+
+def _call(name, *args, stream=_HOST, errors=None):
+    """libmifsk's `name`(*args), and the handle of torch stream `stream` (None: the current one) behind
+    them where one is given; raises where it returns non-zero: what errors[rc] makes of the message if
+    there is one, else errors[None], else RuntimeError."""
+    if stream is not _HOST:
+        args += (_stream_ptr(_torch(), stream),)
+    rc = getattr(_lib.load(), name)(*args)
+    if rc != 0:
+        errors = errors or {}
+        raise errors.get(rc, errors.get(None, RuntimeError))("%s failed: %d" % (name, rc))
+
+
+_EINVAL_IS_VALUE = {-22: ValueError}
+
+
+# ---------------------------------------------------------------------------
+# a batch of rows: what the batch entries' wrappers below share (csrc/mifsk_batch.h is the C++ side's)
+# ---------------------------------------------------------------------------
+
+_RowView = collections.namedtuple("_RowView", "t nstreams width stride s16 vec")
+
+
+def _row_view(torch, t, cx=False, dtypes=None, one_row=True, whole=True, unit="samples", cuda=True):
+    """A batch of rows as the C ABI takes it, from tensor `t` and what the entry accepts -> (the tensor as
+    used, nstreams, width, elements between rows, PCM16?, elements of 16 bytes).  An element is a scalar,
+    or with `cx` an I, Q pair.
+
+    cx     : complex rows, interleaved: a last dimension of 2, or complex64 where `dtypes` names it
+    dtypes : what the entry takes (default: float32 and int16)
+    one_row: a 1-D tensor (complex: [w, 2]) is one row
+    whole  : the kernels read whole 16-byte vectors: a lone row must hold them
+    cuda   : refuse a tensor that is not on the device (the rest is a function of shape, strides and dtype)"""
+    assert not cuda or t.is_cuda
+    assert t.dtype in (dtypes or (torch.float32, torch.int16)), "the rows are not of the kind the entry takes"
+    if t.dtype == torch.complex64:
+        t = torch.view_as_real(t)
+    per = 2 if cx else 1                    # scalars of an element
+    if cx:
+        assert t.shape[-1] == 2 and t.stride(-1) == 1, "complex rows are interleaved I, Q"
+    if one_row and t.dim() == (2 if cx else 1):
+        t = t[None]
+    assert t.dim() == (3 if cx else 2) and t.stride(1) == per
+    nstreams, width = int(t.shape[0]), int(t.shape[1])
+    assert nstreams <= 1 or t.stride(0) % per == 0, "complex rows are interleaved I, Q"
+    vec = 16 // (t.element_size() * per)
+    # (a lone row's stride is arbitrary in torch -- numpy's x[None, :] has stride 0 -- so its width stands
+    # in for it, and the row must hold the whole vectors that the kernels read)
+    assert not whole or nstreams > 1 or width % vec == 0, \
+        "a lone row must be padded to a multiple of %d %s" % (vec, unit)
+    return _RowView(t, nstreams, width, t.stride(0) // per if nstreams > 1 else width, t.dtype == torch.int16, vec)
+
+
+def _row_lengths(torch, nsamples, nstreams, width, allow_int=False, cuda=True):
+    """The rows' lengths as the C ABI takes them -> (the address of [nstreams] uint32 or None, the length of
+    every row then).  nsamples: None (the rows' width), an int where the entry allows one, or an
+    int32/uint32 tensor [nstreams].  The address crosses as a raw pointer: what the kernels would silently
+    misread (a CPU tensor, int64 lengths, a wrong shape) is refused."""
     if nsamples is None:
-        return
-    assert nsamples.is_cuda and nsamples.dtype in (torch.int32, torch.uint32), \
-        "nsamples must be a CUDA int32/uint32 tensor"
+        return None, int(width)
+    if allow_int and not torch.is_tensor(nsamples):
+        return None, int(nsamples)
+    assert torch.is_tensor(nsamples) and (nsamples.is_cuda or not cuda) \
+        and nsamples.dtype in (torch.int32, torch.uint32), "nsamples must be a CUDA int32/uint32 tensor"
     assert nsamples.dim() == 1 and nsamples.shape[0] == nstreams and nsamples.is_contiguous()
+    return nsamples.data_ptr(), int(width)
+
+
+def _rows_io(io, v, lens, nstreams=None):
+    """the rows at the head of every io (_lib.ROWS_FIELDS) from a view and its lengths -> io"""
+    io.d_samples, io.stream_stride = (v.t.data_ptr() if v.t is not None else None), v.stride
+    io.d_nsamples, io.nsamples = lens
+    io.nstreams = v.nstreams if nstreams is None else nstreams
+    return io
+
+
+def _kind(s16):
+    return _lib.FEED_S16 if s16 else _lib.FEED_F32
+
+
+def _whole(n, vec):
+    """n rounded up to whole vectors of `vec`, one at least"""
+    return max(vec, (int(n) + vec - 1) // vec * vec)
+
+
+def _new_outputs(torch, spec, device, stream):
+    """New tensors {name: (shape, dtype, fill)} (fill None: not filled) for a launch on `stream`."""
+    # (allocated and filled ON the launch stream: a fill queued on torch's current stream would race a
+    # kernel launched on another one)
+    with _on(torch, stream):
+        out = {}
+        for name, (shape, dtype, fill) in spec.items():
+            if fill is None:
+                out[name] = torch.empty(shape, dtype=dtype, device=device)
+            elif fill == 0:
+                out[name] = torch.zeros(shape, dtype=dtype, device=device)
+            else:
+                out[name] = torch.full(shape, fill, dtype=dtype, device=device)
+    if stream is not None:
+        # The tensors belong to `stream` in torch's caching allocator.  Whoever reads them on
+        # another stream must order that read behind `stream` (an event, wait_stream); marking
+        # them used on the current stream as well keeps the allocator from handing a dropped
+        # tensor's block back out -- and its zero-fill onto `stream` -- under such a reader.
+        cur = torch.cuda.current_stream()
+        for t in out.values():
+            t.record_stream(cur)
+    return out
+
+
+def _check_out_rows(torch, out, dtypes, nrows, tail=()):
+    """What every entry asks of output rows that the caller brings: on the device, of one of `dtypes`,
+    [nrows, stride, *tail], the rows filling their stride (every element up to the stride is written) -> out"""
+    assert out.is_cuda and out.dtype in dtypes and out.dim() == 2 + len(tail)
+    assert out.shape[0] == nrows and tuple(out.shape[2:]) == tuple(tail)
+    assert out.is_contiguous(), "out's rows must fill their stride"
+    return out
+
+
+def _out_rows(torch, out, shape, dtype, device, stream, dtypes=None):
+    """An entry's one tensor of output rows -> (it, elements between its rows): new, of `shape` and `dtype`,
+    or the caller's `out` if it is of one of `dtypes` (default: `dtype`)."""
+    if out is None:
+        out = _new_outputs(torch, {"out": (shape, dtype, None)}, device, stream)["out"]
+    else:
+        _check_out_rows(torch, out, dtypes or (dtype,), shape[0], shape[2:])
+    return out, int(out.shape[1])
 
 
 def max_frames(cfg, nsamples):
@@ -297,39 +418,23 @@ def _struct_dict(st, drop_reserved=False):
     return {k: getattr(st, k) for k, _ in st._fields_ if not (drop_reserved and k == "reserved")}
 
 
-def _torch_outputs(torch, cfg, dev, nstreams, want, frames_cap, episodes_cap, stream, counters=False):
+def _demod_outputs(torch, cfg, dev, nstreams, want, frames_cap, episodes_cap, stream, counters=False):
     """demod_batch's output tensors; "counters" only where the caller can get them (demod_batch)."""
-    # (allocated and zero-filled ON the launch stream: a fill queued on torch's current
-    # stream would race a kernel launched on another one)
-    with _on(torch, stream):
-        out = {}
-        out["nframes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-        out["status"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-        if "bytes" in want:
-            out["bytes"] = torch.zeros((nstreams, frames_cap), dtype=torch.uint8, device=dev)
-            out["nbytes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-        if "bits" in want:
-            out["bits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=dev)
-        if "frames" in want:
-            out["frames"] = torch.zeros((nstreams, frames_cap, FRAME_DTYPE.itemsize),
-                                        dtype=torch.uint8, device=dev)
-        if counters and "counters" in want:
-            out["counters"] = torch.zeros((nstreams, NCOUNTERS), dtype=torch.int64, device=dev)
-        if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
-            out["carrier_band"] = torch.full((nstreams,), -1, dtype=torch.int32, device=dev)
-        if "episodes" in want:
-            out["episodes"] = torch.zeros((nstreams, episodes_cap, EPISODE_DTYPE.itemsize),
-                                          dtype=torch.uint8, device=dev)
-            out["nepisodes"] = torch.zeros(nstreams, dtype=torch.int32, device=dev)
-    if stream is not None:
-        # The tensors belong to `stream` in torch's caching allocator.  Whoever reads them on
-        # another stream must order that read behind `stream` (an event, wait_stream); marking
-        # them used on the current stream as well keeps the allocator from handing a dropped
-        # tensor's block back out -- and its zero-fill onto `stream` -- under such a reader.
-        cur = torch.cuda.current_stream()
-        for t in out.values():
-            t.record_stream(cur)
-    return out
+    n, u8, i32, i64 = nstreams, torch.uint8, torch.int32, torch.int64
+    spec = {"nframes": ((n,), i32, 0), "status": ((n,), i32, 0)}
+    if "bytes" in want:
+        spec.update(bytes=((n, frames_cap), u8, 0), nbytes=((n,), i32, 0))
+    if "bits" in want:
+        spec["bits"] = ((n, frames_cap), i64, 0)
+    if "frames" in want:
+        spec["frames"] = ((n, frames_cap, FRAME_DTYPE.itemsize), u8, 0)
+    if counters and "counters" in want:
+        spec["counters"] = ((n, NCOUNTERS), i64, 0)
+    if "carrier_band" in want or cfg.auto_carrier_threshold > 0:
+        spec["carrier_band"] = ((n,), i32, -1)
+    if "episodes" in want:
+        spec.update(episodes=((n, episodes_cap, EPISODE_DTYPE.itemsize), u8, 0), nepisodes=((n,), i32, 0))
+    return _new_outputs(torch, spec, dev, stream)
 
 
 def _numpy_outputs(nstreams, want, frames_cap, episodes_cap):
@@ -387,32 +492,18 @@ def demod_batch(ctx, cfg, samples, nsamples=None, want=("bytes", "episodes"),
     MIFSK_IO_ENGINE_WORKGROUP); force_engine=True makes None mean "wave".
     """
     torch = _torch()
-    lib = _lib.load()
-    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2
-    assert samples.stride(1) == 1
-    nstreams, width = samples.shape
-    _check_nsamples(torch, nsamples, nstreams)     # (the kernels clamp lengths to the row width)
-    # (a lone row's stride is arbitrary in torch -- numpy's x[None, :] has stride 0 -- so its
-    # width stands in for it: the kernels read whole float4s, the row must hold them)
-    assert nstreams > 1 or width % 4 == 0, "a lone row must be padded to a multiple of 4 samples"
-    stride = samples.stride(0) if nstreams > 1 else int(width)
-    n_uniform = int(width)
+    v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False)
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)      # (the kernels clamp lengths to the row width)
     if frames_cap is None:
-        frames_cap = max_frames(cfg, n_uniform)
+        frames_cap = max_frames(cfg, v.width)
     if out is None:
-        out = _torch_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream,
+        out = _demod_outputs(torch, cfg, samples.device, v.nstreams, want, frames_cap, episodes_cap, stream,
                              counters=True)
-    io = _result_io(out, nstreams, frames_cap, episodes_cap, _tensor_address)
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = stride
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = n_uniform
+    io = _rows_io(_result_io(out, v.nstreams, frames_cap, episodes_cap, _tensor_address), v, lens)
     if engine is None and force_engine:
         engine = "wave"
     io.flags = _io_flags(ring_exact, engine)
-    rc = lib.mifsk_demod_batch(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_demod_batch failed: %d" % rc)
+    _call("mifsk_demod_batch", ctx.handle, C.byref(cfg), C.byref(io), stream=stream)
     return out
 
 
@@ -432,16 +523,9 @@ def frame_softbits(ctx, cfg, samples, out, nsamples=None, origin=None, rxnoise=0
     allocated on the launch stream; entries at or beyond a stream's frame count are 0.  No
     synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
-    assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
-    if samples.dim() == 1:
-        samples = samples[None, :]
-    assert samples.dim() == 2 and samples.stride(1) == 1
-    s16 = samples.dtype == torch.int16
-    vec = 8 if s16 else 4
-    nstreams, width = samples.shape
-    _check_nsamples(torch, nsamples, nstreams)
-    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d samples" % vec
+    v = _row_view(torch, samples)
+    nstreams = v.nstreams
+    lens = _row_lengths(torch, nsamples, nstreams, v.width)
     frames, nframes = out["frames"], out["nframes"]
     assert frames.is_cuda and frames.is_contiguous() and frames.dim() == 3 and frames.shape[0] == nstreams \
         and frames.shape[2] == FRAME_DTYPE.itemsize, "out must hold the frames of these streams"
@@ -450,22 +534,12 @@ def frame_softbits(ctx, cfg, samples, out, nsamples=None, origin=None, rxnoise=0
         assert origin.is_cuda and origin.dtype == torch.int64 and origin.is_contiguous() \
             and origin.shape == (nstreams,)
     frames_cap = int(frames.shape[1])
-    with _on(torch, stream):
-        res = {"mag": torch.zeros((nstreams, frames_cap, int(cfg.expect_n_bits), 2), dtype=torch.float32,
-                                  device=samples.device)}
-        if rawbits:
-            res["rawbits"] = torch.zeros((nstreams, frames_cap), dtype=torch.int64, device=samples.device)
-    if stream is not None:
-        cur = torch.cuda.current_stream()       # (see _torch_outputs)
-        for t in res.values():
-            t.record_stream(cur)
-    io = _lib.SoftbitsIO()
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = samples.stride(0) if nstreams > 1 else int(width)
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = int(width)
-    io.nstreams = nstreams
-    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    spec = {"mag": ((nstreams, frames_cap, int(cfg.expect_n_bits), 2), torch.float32, 0)}
+    if rawbits:
+        spec["rawbits"] = ((nstreams, frames_cap), torch.int64, 0)
+    res = _new_outputs(torch, spec, v.t.device, stream)
+    io = _rows_io(_lib.SoftbitsIO(), v, lens)
+    io.kind = _kind(v.s16)
     io.rxnoise = float(rxnoise)
     io.d_origin = origin.data_ptr() if origin is not None else None
     io.d_frames = frames.data_ptr()
@@ -473,9 +547,7 @@ def frame_softbits(ctx, cfg, samples, out, nsamples=None, origin=None, rxnoise=0
     io.frames_cap = frames_cap
     io.d_mag = res["mag"].data_ptr()
     io.d_rawbits = res["rawbits"].data_ptr() if rawbits else None
-    rc = lib.mifsk_frame_softbits(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_frame_softbits failed: %d" % rc)
+    _call("mifsk_frame_softbits", ctx.handle, C.byref(cfg), C.byref(io), stream=stream)
     return res
 
 
@@ -491,11 +563,9 @@ def carrier_tones(cfg, band):
     configuration without a shift, IndexError where the space band falls outside 1 .. nbands-1 (the
     receive loop drops such a detection)."""
     bm, bs, fm, fs = C.c_uint(0), C.c_uint(0), C.c_float(0), C.c_float(0)
-    rc = _lib.load().mifsk_carrier_tones(C.byref(cfg), int(band), C.byref(bm), C.byref(bs), C.byref(fm), C.byref(fs))
-    if rc == -34:
-        raise IndexError("band %d: the space band falls outside 1 .. %d" % (band, cfg.nbands - 1))
-    if rc != 0:
-        raise ValueError("mifsk_carrier_tones failed: %d" % rc)
+    outside = IndexError("band %d: the space band falls outside 1 .. %d" % (band, cfg.nbands - 1))
+    _call("mifsk_carrier_tones", C.byref(cfg), int(band), C.byref(bm), C.byref(bs), C.byref(fm), C.byref(fs),
+          errors={-34: lambda _: outside, None: ValueError})
     return {"b_mark": bm.value, "b_space": bs.value, "mark_f": fm.value, "space_f": fs.value}
 
 
@@ -523,43 +593,25 @@ def carrier_survey(ctx, cfg, samples, nsamples=None, window=None, hop=None, firs
     float32 [nstreams, nwindows, nbands] with spectrum=True, "window", "hop"}, allocated on the launch
     stream.  No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
-    assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
-    if samples.dim() == 1:
-        samples = samples[None, :]
-    assert samples.dim() == 2 and samples.stride(1) == 1
-    s16 = samples.dtype == torch.int16
-    vec = 8 if s16 else 4
-    nstreams, width = samples.shape
-    _check_nsamples(torch, nsamples, nstreams)
-    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d samples" % vec
+    v = _row_view(torch, samples)
+    nstreams = v.nstreams
+    lens = _row_lengths(torch, nsamples, nstreams, v.width)
     window = carrier_window_default(cfg) if window is None else int(window)
     hop = window if not hop else int(hop)
     if nwindows is None:
-        nwindows = max(1, carrier_windows(width, window, hop, first))
+        nwindows = max(1, carrier_windows(v.width, window, hop, first))
     nwindows = int(nwindows)
     if out is None:
-        with _on(torch, stream):
-            out = {"band": torch.full((nstreams, nwindows), _lib.CARRIER_NO_WINDOW, dtype=torch.int32,
-                                      device=samples.device),
-                   "mag": torch.zeros((nstreams, nwindows), dtype=torch.float32, device=samples.device)}
-            if spectrum:
-                out["spectrum"] = torch.zeros((nstreams, nwindows, int(cfg.nbands)), dtype=torch.float32,
-                                              device=samples.device)
-        if stream is not None:
-            cur = torch.cuda.current_stream()       # (see _torch_outputs)
-            for t in out.values():
-                t.record_stream(cur)
+        spec = {"band": ((nstreams, nwindows), torch.int32, _lib.CARRIER_NO_WINDOW),
+                "mag": ((nstreams, nwindows), torch.float32, 0)}
+        if spectrum:
+            spec["spectrum"] = ((nstreams, nwindows, int(cfg.nbands)), torch.float32, 0)
+        out = _new_outputs(torch, spec, v.t.device, stream)
     else:
         assert out["band"].shape == (nstreams, nwindows) and out["band"].is_contiguous()
         assert (not spectrum) or out["spectrum"].shape == (nstreams, nwindows, int(cfg.nbands))
-    io = _lib.CarrierIO()
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = samples.stride(0) if nstreams > 1 else int(width)
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = int(width)
-    io.nstreams = nstreams
-    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    io = _rows_io(_lib.CarrierIO(), v, lens)
+    io.kind = _kind(v.s16)
     io.rxnoise = float(rxnoise)
     io.first = int(first)
     io.window = window
@@ -569,9 +621,7 @@ def carrier_survey(ctx, cfg, samples, nsamples=None, window=None, hop=None, firs
     io.d_band = out["band"].data_ptr()
     io.d_mag = out["mag"].data_ptr()
     io.d_spectrum = out["spectrum"].data_ptr() if spectrum else None
-    rc = lib.mifsk_detect_carrier_batch(ctx.handle, C.byref(cfg), C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_detect_carrier_batch failed: %d" % rc)
+    _call("mifsk_detect_carrier_batch", ctx.handle, C.byref(cfg), C.byref(io), stream=stream)
     out["window"], out["hop"] = window, hop
     return out
 
@@ -580,9 +630,8 @@ def channel_taps(ntaps, cutoff, sample_rate, gain=1.0):
     """mifsk_channel_taps: `ntaps` Hamming-windowed sinc taps with a cutoff of `cutoff` Hz at
     `sample_rate`, scaled to sum to `gain`, as a float32 numpy array (a real input wants gain 2)."""
     out = np.empty(int(ntaps), np.float32)
-    rc = _lib.load().mifsk_channel_taps(int(ntaps), float(cutoff), float(sample_rate), float(gain), out.ctypes.data)
-    if rc != 0:
-        raise ValueError("mifsk_channel_taps failed: %d" % rc)
+    _call("mifsk_channel_taps", int(ntaps), float(cutoff), float(sample_rate), float(gain), out.ctypes.data,
+          errors={None: ValueError})
     return out
 
 
@@ -608,9 +657,7 @@ def channel_table(taps, centres, k, phase_steps):
     """mifsk_channel_table: channel k's G as a plan makes it, float64 [ntaps, 2] (host only)."""
     p, _keep = _channel_params(taps, 1, centres, 0, phase_steps, False, False)
     g = np.empty((p.ntaps, 2), np.float64)
-    rc = _lib.load().mifsk_channel_table(C.byref(p), int(k), g.ctypes.data)
-    if rc != 0:
-        raise ValueError("mifsk_channel_table failed: %d" % rc)
+    _call("mifsk_channel_table", C.byref(p), int(k), g.ctypes.data, errors={None: ValueError})
     return g
 
 
@@ -621,9 +668,7 @@ class _PhasePlan(_Handle):
         self._lib, self._destroy = _lib.load(), destroy
         p, _keep = params
         h = C.c_void_p()
-        rc = getattr(self._lib, create)(ctx.handle, C.byref(p), C.byref(h))
-        if rc != 0:
-            raise (ValueError if rc == -22 else RuntimeError)("%s failed: %d" % (create, rc))
+        _call(create, ctx.handle, C.byref(p), C.byref(h), errors=_EINVAL_IS_VALUE)
         self.handle = h
         self.ctx = ctx                      # the plan must not outlive its context
         self.ntaps, self.nchannels, self.s16 = p.ntaps, p.nchannels, p.kind == _lib.FEED_S16
@@ -636,30 +681,18 @@ def _row_outputs(torch, nrows, full, vec, dtype, tail, device, stream, out):
     `full` (one at least), or `out`, a dict of a former call, when its tensors are of that kind (`full`
     is not looked at then)."""
     if out is None:
-        out_stride = max(vec, (full + vec - 1) // vec * vec)
-        with _on(torch, stream):
-            out = {"rows": torch.empty((nrows, out_stride) + tail, dtype=dtype, device=device),
-                   "nsamples": torch.empty((nrows,), dtype=torch.int32, device=device)}
-        if stream is not None:
-            cur = torch.cuda.current_stream()       # (see _torch_outputs)
-            for t in out.values():
-                t.record_stream(cur)
-    else:
-        rows, counts = out["rows"], out["nsamples"]
-        assert rows.dim() == 2 + len(tail) and rows.shape[0] == nrows and tuple(rows.shape[2:]) == tail
-        assert rows.dtype == dtype and rows.is_contiguous()
-        assert counts.shape == (nrows,) and counts.dtype == torch.int32 and counts.is_contiguous()
+        return _new_outputs(torch, {"rows": ((nrows, _whole(full, vec)) + tail, dtype, None),
+                                    "nsamples": ((nrows,), torch.int32, None)}, device, stream)
+    _check_out_rows(torch, out["rows"], (dtype,), nrows, tail)
+    counts = out["nsamples"]
+    assert counts.shape == (nrows,) and counts.dtype == torch.int32 and counts.is_contiguous()
     return out
 
 
-def _phase_io(io, rows_field, samples, row_stride, width, nsamples, nstreams, out, nout_cap):
+def _phase_io(io, rows_field, v, lens, nstreams, out, nout_cap):
     """the fields mifsk_channel_io and mifsk_mux_io share (the output rows are `rows_field`) -> io"""
     out_stride = out["rows"].shape[1]
-    io.d_samples = samples.data_ptr()
-    io.stream_stride = row_stride
-    io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-    io.nsamples = int(width)
-    io.nstreams = nstreams
+    _rows_io(io, v, lens, nstreams)
     setattr(io, rows_field, out["rows"].data_ptr())
     io.out_stride = out_stride
     io.nout_cap = out_stride if nout_cap is None else min(int(nout_cap), out_stride)
@@ -695,34 +728,13 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     row s * nchannels + k is channel k of stream s, zero behind its count.  Allocated on the launch
     stream.  No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
-    assert samples.is_cuda
-    if plan.complex_input:
-        if samples.dtype == torch.complex64:
-            samples = torch.view_as_real(samples)
-        assert samples.shape[-1] == 2 and samples.stride(-1) == 1, "complex rows are interleaved I, Q"
-        if samples.dim() == 2:
-            samples = samples[None]
-        assert samples.dim() == 3 and samples.stride(1) == 2
-        nstreams, width = samples.shape[0], samples.shape[1]
-        row_stride = samples.stride(0) // 2 if nstreams > 1 else int(width)
-        assert nstreams == 1 or samples.stride(0) % 2 == 0
-    else:
-        if samples.dim() == 1:
-            samples = samples[None, :]
-        assert samples.dim() == 2 and samples.stride(1) == 1
-        nstreams, width = samples.shape
-        row_stride = samples.stride(0) if nstreams > 1 else int(width)
-    assert samples.dtype == (torch.int16 if plan.s16 else torch.float32), "the rows are not of the plan's kind"
-    vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_input else 1))
-    assert nstreams > 1 or width % vec == 0, "a lone row must be padded to a multiple of %d elements" % vec
-    _check_nsamples(torch, nsamples, nstreams)
-    full = out is None and (carrier_windows(width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap))
-    out = _row_outputs(torch, nstreams * plan.nchannels, full, 4, torch.float32, (), samples.device, stream, out)
-    io = _phase_io(_lib.ChannelIO(), "d_rows", samples, row_stride, width, nsamples, nstreams, out, nout_cap)
-    rc = lib.mifsk_channelize_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_channelize_batch failed: %d" % rc)
+    kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
+    v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
+    full = out is None and (carrier_windows(v.width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap))
+    out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 4, torch.float32, (), v.t.device, stream, out)
+    io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, nout_cap)
+    _call("mifsk_channelize_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
 
@@ -742,9 +754,7 @@ def mux_table(taps, in_centre, phase_steps):
     """mifsk_mux_table: G as a multiplexer plan makes it, float64 [ntaps, 2] (host only)."""
     p, _keep = _mux_params(taps, 1, [0], in_centre, phase_steps, False, False, None)
     g = np.empty((p.ntaps, 2), np.float64)
-    rc = _lib.load().mifsk_mux_table(C.byref(p), g.ctypes.data)
-    if rc != 0:
-        raise ValueError("mifsk_mux_table failed: %d" % rc)
+    _call("mifsk_mux_table", C.byref(p), g.ctypes.data, errors={None: ValueError})
     return g
 
 
@@ -778,24 +788,17 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     "nsamples": int32 [nstreams]}; a row is zero behind its count.  Allocated on the launch stream.
     No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
-    assert samples.is_cuda and samples.dtype == torch.float32
-    assert samples.dim() == 2 and samples.stride(1) == 1
-    nrows, width = samples.shape
+    v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
     K = plan.nchannels
-    assert nrows > 0 and nrows % K == 0, "samples holds nchannels rows per stream"
-    nstreams = nrows // K
-    row_stride = samples.stride(0) if nrows > 1 else int(width)
-    assert nrows > 1 or width % 4 == 0, "a lone row must be padded to a multiple of 4 floats"
-    _check_nsamples(torch, nsamples, nrows)
+    assert v.nstreams > 0 and v.nstreams % K == 0, "samples holds nchannels rows per stream"
+    nstreams = v.nstreams // K
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
     dtype = torch.int16 if plan.s16 else torch.float32
     vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
-    full = out is None and ((int(width) - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap))
+    full = out is None and ((v.width - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap))
     out = _row_outputs(torch, nstreams, full, vec, dtype, (2,) if plan.complex_output else (), samples.device, stream, out)
-    io = _phase_io(_lib.MuxIO(), "d_out", samples, row_stride, width, nsamples, nstreams, out, nout_cap)
-    rc = lib.mifsk_multiplex_batch(plan.handle, C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_multiplex_batch failed: %d" % rc)
+    io = _phase_io(_lib.MuxIO(), "d_out", v, lens, nstreams, out, nout_cap)
+    _call("mifsk_multiplex_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
 
@@ -822,67 +825,39 @@ def impair(ctx, samples, nsamples=None, seed=0, sigma=0.0, gain=1.0, dc=0.0, fir
               element up to the stride is written); out=samples is in place.  None: a new tensor, the width rounded up to whole 16-byte vectors, made on the launch stream.
     Returns out; a row is zero behind its length.  No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
     shape = None
     if samples is not None and not torch.is_tensor(samples):
-        shape, samples = tuple(int(v) for v in samples), None
+        shape, samples = tuple(int(n) for n in samples), None
         assert len(shape) == 2, "a shape is (nstreams, width)"
     if samples is not None:
-        assert samples.is_cuda and samples.dtype in (torch.float32, torch.int16)
-        if samples.dim() == 1:
-            samples = samples[None, :]
-            if out is not None and out.dim() == 1:
-                out = out[None, :]
-        assert samples.dim() == 2 and samples.stride(1) == 1
-        nstreams, width = samples.shape
-        in_s16 = samples.dtype == torch.int16
-        row_stride = samples.stride(0) if nstreams > 1 else int(width)
+        if samples.dim() == 1 and out is not None and out.dim() == 1:
+            out = out[None, :]
+        v = _row_view(torch, samples)
         device = samples.device
     else:
         assert out is not None or shape is not None, "noise rows want out= or a shape"
-        nstreams, width = shape if shape is not None else out.shape
-        in_s16, row_stride = False, 0
+        n, w = shape if shape is not None else out.shape
+        v = _RowView(None, int(n), int(w), 0, False, 4)             # no rows: x = 0
         device = out.device if out is not None else torch.device("cuda")
-    if out is None:
-        out_s16 = in_s16 if s16_out is None else bool(s16_out)
-        vec = 8 if out_s16 else 4
-        with _on(torch, stream):
-            out = torch.empty((nstreams, max(vec, (int(width) + vec - 1) // vec * vec)),
-                              dtype=torch.int16 if out_s16 else torch.float32, device=device)
-        if stream is not None:
-            out.record_stream(torch.cuda.current_stream())      # (see _torch_outputs)
-    else:
-        assert out.is_cuda and out.dtype in (torch.float32, torch.int16)
-        assert out.dim() == 2 and out.shape[0] == nstreams and out.stride(1) == 1
-        # (every element of a row up to the stride is written: a view narrower than its stride is refused)
-        assert nstreams == 1 or out.stride(0) == out.shape[1], "out's rows must fill their stride"
-        out_s16 = out.dtype == torch.int16
-        assert s16_out is None or bool(s16_out) == out_s16, "out is not of the kind s16_out asks for"
-    out_stride = out.stride(0) if nstreams > 1 else int(out.shape[1])
-    nsamples_t = nsamples if torch.is_tensor(nsamples) else None
-    _check_nsamples(torch, nsamples_t, nstreams)
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width, allow_int=True)
+    out_s16 = out.dtype == torch.int16 if out is not None else v.s16 if s16_out is None else bool(s16_out)
+    out, out_stride = _out_rows(torch, out, (v.nstreams, _whole(v.width, 8 if out_s16 else 4)),
+                                torch.int16 if out_s16 else torch.float32, device, stream,
+                                dtypes=(torch.float32, torch.int16))
+    assert s16_out is None or bool(s16_out) == out_s16, "out is not of the kind s16_out asks for"
 
-    io = _lib.ImpairIO()
-    io.d_samples = samples.data_ptr() if samples is not None else None
-    io.stream_stride = row_stride
-    io.d_nsamples = nsamples_t.data_ptr() if nsamples_t is not None else None
-    io.nsamples = int(width) if nsamples is None or nsamples_t is not None else int(nsamples)
-    io.nstreams = nstreams
-    io.kind = _lib.FEED_S16 if in_s16 else _lib.FEED_F32
-    io.out_kind = _lib.FEED_S16 if out_s16 else _lib.FEED_F32
-    io.d_out = out.data_ptr()
-    io.out_stride = out_stride
+    io = _rows_io(_lib.ImpairIO(), v, lens)
+    io.kind, io.out_kind = _kind(v.s16), _kind(out_s16)
+    io.d_out, io.out_stride = out.data_ptr(), out_stride
     io.seed, io.first_stream, io.first_sample = int(seed), int(first_stream), int(first_sample)
-    for name, v in (("gain", gain), ("sigma", sigma), ("dc", dc)):
-        if torch.is_tensor(v):
-            assert v.is_cuda and v.dtype == torch.float32 and v.shape == (nstreams,) and v.is_contiguous(), \
+    for name, val in (("gain", gain), ("sigma", sigma), ("dc", dc)):
+        if torch.is_tensor(val):
+            assert val.is_cuda and val.dtype == torch.float32 and val.shape == (v.nstreams,) and val.is_contiguous(), \
                 "%s: a float32 CUDA tensor [nstreams]" % name
-            setattr(io, "d_" + name, v.data_ptr())
+            setattr(io, "d_" + name, val.data_ptr())
         else:
-            setattr(io, name, float(v))
-    rc = lib.mifsk_impair_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_impair_batch failed: %d" % rc)
+            setattr(io, name, float(val))
+    _call("mifsk_impair_batch", ctx.handle, C.byref(io), stream=stream)
     return out
 
 
@@ -894,28 +869,6 @@ def fm_gain(sample_rate, deviation_hz):
 def fm_step(deviation_hz, sample_rate):
     """mifsk_fm_step: Hertz as turns per sample, the modulator's `deviation` and `centre`."""
     return float(_lib.load().mifsk_fm_step(C.c_double(deviation_hz), C.c_double(sample_rate)))
-
-
-def _fm_out(torch, out, shape, dtype, device, stream):
-    """the output rows of an FM entry: `out` checked (its rows fill their stride: every element up to the
-    stride is written), or a new tensor of `shape` made on the launch stream -> (out, elements between rows)"""
-    if out is None:
-        with _on(torch, stream):
-            out = torch.empty(shape, dtype=dtype, device=device)
-        if stream is not None:
-            out.record_stream(torch.cuda.current_stream())      # (see _torch_outputs)
-    else:
-        assert out.is_cuda and out.dtype == dtype and out.dim() == len(shape) and out.shape[0] == shape[0]
-        assert out.shape[2:] == tuple(shape[2:]) and out.is_contiguous(), "out's rows must fill their stride"
-    return out, int(out.shape[1])
-
-
-def _fm_lengths(torch, io, nsamples, width, nstreams):
-    nsamples_t = nsamples if torch.is_tensor(nsamples) else None
-    _check_nsamples(torch, nsamples_t, nstreams)
-    io.d_nsamples = nsamples_t.data_ptr() if nsamples_t is not None else None
-    io.nsamples = int(width) if nsamples is None or nsamples_t is not None else int(nsamples)
-    io.nstreams = nstreams
 
 
 def fm_demod(ctx, iq, nsamples=None, gain=1.0, prev=None, last=None, stream=None, out=None):
@@ -933,17 +886,12 @@ def fm_demod(ctx, iq, nsamples=None, gain=1.0, prev=None, last=None, stream=None
               stride.  None: a new tensor, the width rounded up to 4, made on the launch stream.
     Returns out; a row is zero behind its length.  No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
-    assert iq.is_cuda and iq.dtype in (torch.float32, torch.int16) and iq.dim() == 3 and iq.shape[2] == 2
-    assert iq.stride(2) == 1 and iq.stride(1) == 2 and iq.stride(0) % 2 == 0, "complex rows are interleaved I, Q"
-    nstreams, width = int(iq.shape[0]), int(iq.shape[1])
-    s16 = iq.dtype == torch.int16
-    row_stride = iq.stride(0) // 2 if nstreams > 1 else width
-    out, out_stride = _fm_out(torch, out, (nstreams, max(4, (width + 3) // 4 * 4)), torch.float32, iq.device, stream)
-    io = _lib.FmDemodIO()
-    io.d_samples, io.stream_stride = iq.data_ptr(), row_stride
-    _fm_lengths(torch, io, nsamples, width, nstreams)
-    io.kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    v = _row_view(torch, iq, cx=True, one_row=False, unit="elements")
+    nstreams = v.nstreams
+    lens = _row_lengths(torch, nsamples, nstreams, v.width, allow_int=True)
+    out, out_stride = _out_rows(torch, out, (nstreams, _whole(v.width, 4)), torch.float32, iq.device, stream)
+    io = _rows_io(_lib.FmDemodIO(), v, lens)
+    io.kind = _kind(v.s16)
     io.d_out, io.out_stride, io.gain = out.data_ptr(), out_stride, float(gain)
     for name, t in (("d_prev", prev), ("d_last", last)):
         if t is not None:
@@ -951,9 +899,7 @@ def fm_demod(ctx, iq, nsamples=None, gain=1.0, prev=None, last=None, stream=None
                 "%s: a float32 CUDA tensor [nstreams, 2]" % name[2:]
             setattr(io, name, t.data_ptr())
     assert prev is None or last is None or prev.data_ptr() != last.data_ptr(), "last must not be prev"
-    rc = lib.mifsk_fm_demod_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_fm_demod_batch failed: %d" % rc)
+    _call("mifsk_fm_demod_batch", ctx.handle, C.byref(io), stream=stream)
     return out
 
 
@@ -975,25 +921,17 @@ def fm_modulate(ctx, samples, nsamples=None, deviation=None, centre=0.0, amplitu
               None: a new tensor, the width rounded up to whole 16-byte vectors, made on the launch stream.
     Returns out; a row is zero behind its length.  No synchronisation is performed."""
     torch = _torch()
-    lib = _lib.load()
     assert deviation is not None, "deviation: turns per sample at x = 1.0 (fm_step)"
-    assert samples.is_cuda and samples.dtype == torch.float32
-    if samples.dim() == 1:
-        samples = samples[None, :]
-    assert samples.dim() == 2 and samples.stride(1) == 1
-    nstreams, width = int(samples.shape[0]), int(samples.shape[1])
-    row_stride = samples.stride(0) if nstreams > 1 else width
-    assert nstreams > 1 or width % 4 == 0, "a lone row must be padded to a multiple of 4 floats"
+    v = _row_view(torch, samples, dtypes=(torch.float32,), unit="floats")
+    nstreams = v.nstreams
+    lens = _row_lengths(torch, nsamples, nstreams, v.width, allow_int=True)
     if out is not None:
-        assert out.dtype in (torch.float32, torch.int16)
         s16 = out.dtype == torch.int16
-    vec = 4 if s16 else 2
-    out, out_stride = _fm_out(torch, out, (nstreams, max(vec, (width + vec - 1) // vec * vec), 2),
-                              torch.int16 if s16 else torch.float32, samples.device, stream)
-    io = _lib.FmModIO()
-    io.d_samples, io.stream_stride = samples.data_ptr(), row_stride
-    _fm_lengths(torch, io, nsamples, width, nstreams)
-    io.out_kind = _lib.FEED_S16 if s16 else _lib.FEED_F32
+    out, out_stride = _out_rows(torch, out, (nstreams, _whole(v.width, 4 if s16 else 2), 2),
+                                torch.int16 if s16 else torch.float32, samples.device, stream,
+                                dtypes=(torch.float32, torch.int16))
+    io = _rows_io(_lib.FmModIO(), v, lens)
+    io.out_kind = _kind(s16)
     io.d_out, io.out_stride = out.data_ptr(), out_stride
     io.deviation, io.centre, io.amplitude = float(deviation), float(centre), float(amplitude)
     for name, t in (("d_phase0", phase0), ("d_phase_out", phase_out)):
@@ -1001,9 +939,7 @@ def fm_modulate(ctx, samples, nsamples=None, deviation=None, centre=0.0, amplitu
             assert t.is_cuda and t.dtype in (torch.int64, torch.uint64) and t.shape == (nstreams,) and t.is_contiguous(), \
                 "%s: an int64/uint64 CUDA tensor [nstreams]" % name[2:]
             setattr(io, name, t.data_ptr())
-    rc = lib.mifsk_fm_modulate_batch(ctx.handle, C.byref(io), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_fm_modulate_batch failed: %d" % rc)
+    _call("mifsk_fm_modulate_batch", ctx.handle, C.byref(io), stream=stream)
     return out
 
 
@@ -1127,7 +1063,7 @@ def _demod_long(torch, ctx, cfg, samples, stride, lens, rxnoise, want, frames_ca
     lib = _lib.load()
     nstreams = len(lens)
     frames_cap, episodes_cap = _default_caps(cfg, max(lens), frames_cap, episodes_cap)
-    out = _torch_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream)
+    out = _demod_outputs(torch, cfg, samples.device, nstreams, want, frames_cap, episodes_cap, stream)
     io = _result_io(out, nstreams, frames_cap, episodes_cap, _tensor_address)
     arr = (C.c_uint64 * nstreams)(*lens)
     st = (_lib.TimeSplitStats * nstreams)()
@@ -1373,16 +1309,8 @@ class Pipeline(_Handle):
         """`after`: the torch stream the batch was produced on ("current": torch's current
         stream), or None when nothing has to be waited for."""
         torch = _torch()
-        assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2 and samples.stride(1) == 1
-        nstreams, width = samples.shape
-        _check_nsamples(torch, nsamples, nstreams)
-        assert nstreams > 1 or width % 4 == 0
-        io = _lib.DemodIO()
-        io.d_samples = samples.data_ptr()
-        io.stream_stride = samples.stride(0) if nstreams > 1 else int(width)
-        io.d_nsamples = nsamples.data_ptr() if nsamples is not None else None
-        io.nsamples = int(width)
-        io.nstreams = nstreams
+        v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False)
+        io = _rows_io(_lib.DemodIO(), v, _row_lengths(torch, nsamples, v.nstreams, v.width))
         io.flags = _io_flags(ring_exact, engine)
         if after == "current":
             after = torch.cuda.current_stream()
@@ -1669,33 +1597,23 @@ def ingest_s16(ctx, pcm, nsamples=None, rxnoise=0.0, stride=None, stream=None):
     pcm is a torch.int16 CUDA tensor [nstreams, width]; returns float32
     [nstreams, stride] (stride defaults to width rounded up to a multiple of 4)."""
     torch = _torch()
-    assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.dim() == 2 and pcm.stride(1) == 1
-    nstreams, width = pcm.shape
-    _check_nsamples(torch, nsamples, nstreams)
+    v = _row_view(torch, pcm, dtypes=(torch.int16,), one_row=False, whole=False)
+    d_nsamples, width = _row_lengths(torch, nsamples, v.nstreams, v.width)
     if stride is None:
         stride = (width + 3) & ~3
-    out = torch.empty((nstreams, stride), dtype=torch.float32, device=pcm.device)
-    rc = _lib.load().mifsk_ingest_s16(
-        ctx.handle, C.c_void_p(pcm.data_ptr()), pcm.stride(0) if nstreams > 1 else width,
-        C.c_void_p(out.data_ptr()), stride,
-        C.c_void_p(nsamples.data_ptr()) if nsamples is not None else None, int(width), nstreams,
-        C.c_float(rxnoise), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_ingest_s16 -> %d" % rc)
+    out, stride = _out_rows(torch, None, (v.nstreams, stride), torch.float32, pcm.device, stream)
+    _call("mifsk_ingest_s16", ctx.handle, C.c_void_p(pcm.data_ptr()), v.stride, C.c_void_p(out.data_ptr()), stride,
+          C.c_void_p(d_nsamples), width, v.nstreams, C.c_float(rxnoise), stream=stream)
     return out
 
 
 def ingest_rxnoise(ctx, samples, rxnoise, nsamples=None, stream=None):
     """The --Xrxnoise term applied in place to float32 CUDA samples [nstreams, stride]."""
     torch = _torch()
-    assert samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 2
-    _check_nsamples(torch, nsamples, samples.shape[0])
-    rc = _lib.load().mifsk_ingest_rxnoise_f32(
-        ctx.handle, C.c_void_p(samples.data_ptr()), samples.stride(0),
-        C.c_void_p(nsamples.data_ptr()) if nsamples is not None else None, int(samples.shape[1]),
-        samples.shape[0], C.c_float(rxnoise), _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_ingest_rxnoise_f32 -> %d" % rc)
+    v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, whole=False)
+    d_nsamples, width = _row_lengths(torch, nsamples, v.nstreams, v.width)
+    _call("mifsk_ingest_rxnoise_f32", ctx.handle, C.c_void_p(samples.data_ptr()), v.stride, C.c_void_p(d_nsamples),
+          width, v.nstreams, C.c_float(rxnoise), stream=stream)
     return samples
 
 
@@ -1706,31 +1624,23 @@ def synthesize_batch(ctx, cfg, words, nwords=None, lut=4096, amplitude=1.0, lead
     may be int32 CUDA tensors [nstreams] or scalars.  Returns (samples float32
     [nstreams, stride], lengths int32 [nstreams]); rows are zero after their length."""
     torch = _torch()
-    assert words.is_cuda and words.dtype == torch.uint8 and words.dim() == 2
-    nstreams, width = words.shape
-    nw_t = nwords if torch.is_tensor(nwords) else None
-    nw_u = int(width if nwords is None else (0 if nw_t is not None else nwords))
-    ls_t = leading_silence if torch.is_tensor(leading_silence) else None
-    ls_u = 0 if ls_t is not None else int(leading_silence)
+    v = _row_view(torch, words, dtypes=(torch.uint8,), one_row=False, whole=False)
+    nstreams = v.nstreams
+    d_nwords, nw_u = _row_lengths(torch, nwords, nstreams, v.width, allow_int=True)
+    d_lead, ls_u = _row_lengths(torch, leading_silence, nstreams, 0, allow_int=True)
     if stride is None:
-        max_lead = int(ls_t.max()) if ls_t is not None and nstreams else ls_u
-        max_words = int(nw_t.max()) if nw_t is not None and nstreams else nw_u
+        max_lead = int(leading_silence.max()) if d_lead and nstreams else ls_u
+        max_words = int(nwords.max()) if d_nwords and nstreams else nw_u
         one = np.zeros(max(1, max_words), np.uint8)
         n = _lib.load().mifsk_tx_synthesize(C.byref(cfg), one.ctypes.data, max_words, lut,
                                             C.c_float(amplitude), max_lead, 0, None, 0)
         stride = (max(int(n), 4) + 3) & ~3
-    with _on(_torch(), stream):
-        out = torch.empty((nstreams, stride), dtype=torch.float32, device=words.device)
-        lens = torch.zeros(nstreams, dtype=torch.int32, device=words.device)
-    rc = _lib.load().mifsk_tx_synthesize_batch(
-        ctx.handle, C.byref(cfg), C.c_void_p(words.data_ptr()),
-        words.stride(0) if nstreams > 1 else width,
-        C.c_void_p(nw_t.data_ptr()) if nw_t is not None else None, nw_u, nstreams, int(lut),
-        C.c_float(amplitude), C.c_void_p(ls_t.data_ptr()) if ls_t is not None else None, ls_u,
-        1 if s16 else 0, C.c_void_p(out.data_ptr()), stride, C.c_void_p(lens.data_ptr()),
-        _stream_ptr(torch, stream))
-    if rc != 0:
-        raise RuntimeError("mifsk_tx_synthesize_batch -> %d" % rc)
+    res = _new_outputs(torch, {"out": ((nstreams, stride), torch.float32, None), "lens": ((nstreams,), torch.int32, 0)},
+                       words.device, stream)
+    out, lens = res["out"], res["lens"]
+    _call("mifsk_tx_synthesize_batch", ctx.handle, C.byref(cfg), C.c_void_p(words.data_ptr()), v.stride,
+          C.c_void_p(d_nwords), nw_u, nstreams, int(lut), C.c_float(amplitude), C.c_void_p(d_lead), ls_u,
+          1 if s16 else 0, C.c_void_p(out.data_ptr()), stride, C.c_void_p(lens.data_ptr()), stream=stream)
     return out, lens
 
 
@@ -1956,7 +1866,6 @@ class SlabSession:
 
     def feed(self, new, final=False, stream=None):
         torch = _torch()
-        lib = _lib.load()
         assert len(new) == self.n
         for i, x in enumerate(new):
             if x is not None and len(x):
@@ -1975,27 +1884,19 @@ class SlabSession:
             d = torch.from_numpy(host).cuda()
             dl = torch.from_numpy(lens).cuda()
             do = torch.from_numpy(self.origin.view(np.int64).copy()).cuda()
+        v = _row_view(torch, d, dtypes=(torch.float32,), one_row=False)
         fc = max_frames(self.cfg, width)
-        out = _torch_outputs(torch, self.cfg, d.device, self.n, ("bytes", "bits", "frames", "episodes", "carrier_band"),
+        out = _demod_outputs(torch, self.cfg, d.device, self.n, ("bytes", "bits", "frames", "episodes", "carrier_band"),
                              fc, self.episodes_cap, stream)
-        io = _result_io(out, self.n, fc, self.episodes_cap, _tensor_address)
-        io.d_samples = d.data_ptr()
-        io.stream_stride = d.stride(0) if self.n > 1 else width
-        io.d_nsamples = dl.data_ptr()
-        io.nsamples = width
+        io = _rows_io(_result_io(out, self.n, fc, self.episodes_cap, _tensor_address), v,
+                      _row_lengths(torch, dl, self.n, width))
         io.flags = _io_flags(False, self.engine)
+        args = (self.ctx.handle, C.byref(self.cfg), C.byref(io), C.c_void_p(self.state.data_ptr()), C.c_void_p(do.data_ptr()))
         if self.ring is not None:
             io.flags = _lib.IO_RING_EXACT
-            rc = lib.mifsk_demod_slab_ring(self.ctx.handle, C.byref(self.cfg), C.byref(io),
-                                           C.c_void_p(self.state.data_ptr()), C.c_void_p(do.data_ptr()),
-                                           C.c_void_p(self.ring.data_ptr()), 1 if final else 0,
-                                           _stream_ptr(torch, stream))
+            _call("mifsk_demod_slab_ring", *args, C.c_void_p(self.ring.data_ptr()), 1 if final else 0, stream=stream)
         else:
-            rc = lib.mifsk_demod_slab(self.ctx.handle, C.byref(self.cfg), C.byref(io),
-                                      C.c_void_p(self.state.data_ptr()), C.c_void_p(do.data_ptr()),
-                                      1 if final else 0, _stream_ptr(torch, stream))
-        if rc != 0:
-            raise RuntimeError("mifsk_demod_slab failed: %d" % rc)
+            _call("mifsk_demod_slab", *args, 1 if final else 0, stream=stream)
         torch.cuda.synchronize()
         res = results_to_host(out)
         st = self.state.cpu().numpy().view(STATE_DTYPE).reshape(self.n)

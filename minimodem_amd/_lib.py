@@ -113,13 +113,14 @@ class SearchResult(C.Structure):
     ]
 
 
+# what every io of a batch entry begins with: the rows (base, elements between them, per-row
+# lengths or NULL, the length of every row then) and their number
+ROWS_FIELDS = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
+               ("nsamples", C.c_uint32), ("nstreams", C.c_int)]
+
+
 class DemodIO(C.Structure):
-    _fields_ = [
-        ("d_samples", C.c_void_p),
-        ("stream_stride", C.c_size_t),
-        ("d_nsamples", C.c_void_p),
-        ("nsamples", C.c_uint32),
-        ("nstreams", C.c_int),
+    _fields_ = ROWS_FIELDS + [
         ("d_bytes", C.c_void_p),
         ("d_nbytes", C.c_void_p),
         ("d_bits", C.c_void_p),
@@ -243,21 +244,19 @@ TIME_SPLIT_REJECT_ALL = 0x10000
 
 
 class SoftbitsIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("rxnoise", C.c_float),
-                ("d_origin", C.c_void_p), ("d_frames", C.c_void_p), ("d_nframes", C.c_void_p),
-                ("frames_cap", C.c_size_t), ("d_mag", C.c_void_p), ("d_rawbits", C.c_void_p)]
+    _fields_ = ROWS_FIELDS + [("kind", C.c_uint32), ("rxnoise", C.c_float),
+                              ("d_origin", C.c_void_p), ("d_frames", C.c_void_p), ("d_nframes", C.c_void_p),
+                              ("frames_cap", C.c_size_t), ("d_mag", C.c_void_p), ("d_rawbits", C.c_void_p)]
 
 
 CARRIER_NONE, CARRIER_NO_WINDOW = -1, -2
 
 
 class CarrierIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("rxnoise", C.c_float),
-                ("first", C.c_uint64), ("window", C.c_uint32), ("hop", C.c_uint32), ("nwindows", C.c_uint32),
-                ("threshold", C.c_float), ("d_band", C.c_void_p), ("d_mag", C.c_void_p),
-                ("d_spectrum", C.c_void_p)]
+    _fields_ = ROWS_FIELDS + [("kind", C.c_uint32), ("rxnoise", C.c_float),
+                              ("first", C.c_uint64), ("window", C.c_uint32), ("hop", C.c_uint32), ("nwindows", C.c_uint32),
+                              ("threshold", C.c_float), ("d_band", C.c_void_p), ("d_mag", C.c_void_p),
+                              ("d_spectrum", C.c_void_p)]
 
 
 CHANNEL_COMPLEX = 1
@@ -270,9 +269,8 @@ class ChannelParams(C.Structure):
 
 
 class ChannelIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("d_rows", C.c_void_p),
-                ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
+    _fields_ = ROWS_FIELDS + [("d_rows", C.c_void_p),
+                              ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
 
 
 MUX_COMPLEX = 1
@@ -285,33 +283,29 @@ class MuxParams(C.Structure):
 
 
 class MuxIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("d_out", C.c_void_p),
-                ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
+    _fields_ = ROWS_FIELDS + [("d_out", C.c_void_p),
+                              ("out_stride", C.c_size_t), ("nout_cap", C.c_uint32), ("d_nout", C.c_void_p)]
 
 
 class ImpairIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("out_kind", C.c_uint32),
-                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("seed", C.c_uint64),
-                ("first_stream", C.c_uint64), ("first_sample", C.c_uint64), ("d_gain", C.c_void_p),
-                ("d_sigma", C.c_void_p), ("d_dc", C.c_void_p), ("gain", C.c_float), ("sigma", C.c_float),
-                ("dc", C.c_float), ("flags", C.c_uint32)]
+    _fields_ = ROWS_FIELDS + [("kind", C.c_uint32), ("out_kind", C.c_uint32),
+                              ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("seed", C.c_uint64),
+                              ("first_stream", C.c_uint64), ("first_sample", C.c_uint64), ("d_gain", C.c_void_p),
+                              ("d_sigma", C.c_void_p), ("d_dc", C.c_void_p), ("gain", C.c_float), ("sigma", C.c_float),
+                              ("dc", C.c_float), ("flags", C.c_uint32)]
 
 
 class FmDemodIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("kind", C.c_uint32), ("flags", C.c_uint32),
-                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("d_prev", C.c_void_p), ("d_last", C.c_void_p),
-                ("gain", C.c_float), ("reserved", C.c_uint32)]
+    _fields_ = ROWS_FIELDS + [("kind", C.c_uint32), ("flags", C.c_uint32),
+                              ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("d_prev", C.c_void_p), ("d_last", C.c_void_p),
+                              ("gain", C.c_float), ("reserved", C.c_uint32)]
 
 
 class FmModIO(C.Structure):
-    _fields_ = [("d_samples", C.c_void_p), ("stream_stride", C.c_size_t), ("d_nsamples", C.c_void_p),
-                ("nsamples", C.c_uint32), ("nstreams", C.c_int), ("out_kind", C.c_uint32), ("flags", C.c_uint32),
-                ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("deviation", C.c_double), ("centre", C.c_double),
-                ("d_phase0", C.c_void_p), ("d_phase_out", C.c_void_p), ("amplitude", C.c_float),
-                ("reserved", C.c_uint32)]
+    _fields_ = ROWS_FIELDS + [("out_kind", C.c_uint32), ("flags", C.c_uint32),
+                              ("d_out", C.c_void_p), ("out_stride", C.c_size_t), ("deviation", C.c_double), ("centre", C.c_double),
+                              ("d_phase0", C.c_void_p), ("d_phase_out", C.c_void_p), ("amplitude", C.c_float),
+                              ("reserved", C.c_uint32)]
 
 
 assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40

@@ -1,6 +1,8 @@
 // mifsk_batch.h -- the host side that the batch entries share (mifsk_carrier.hip, mifsk_softbits.hip,
-// mifsk_channel.hip, mifsk_mux.hip): what they refuse of a batch of rows, how a batch of any number
-// of rows becomes launches, and how a kernel with dynamic LDS is launched.  Host only.
+// mifsk_channel.hip, mifsk_mux.hip, mifsk_impair.hip, mifsk_fm.hip): what a batch of rows is (RowsIn),
+// what they refuse of one, how a batch of any number of rows becomes launches, and how a kernel with
+// dynamic LDS is launched.  Host only, but for RowsIn::len (mifsk_rows.h); the checks call no HIP
+// (tools/rows_check.cpp runs them on a CPU).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,15 +52,45 @@ inline bool rows_aligned( const void *rows, size_t stride, uint32_t vec )
     return ( (uintptr_t)rows & 15u ) == 0 && stride % vec == 0;
 }
 
+// a kind of scalars that the entries know
+inline int kind_check( uint32_t kind ) { return kind == MIFSK_FEED_F32 || kind == MIFSK_FEED_S16 ? 0 : -EINVAL; }
+
+// what the entries refuse of their output rows: `vec` elements are 16 bytes, a row is 1 .. out_max elements
+inline int out_rows_check( const void *d_out, size_t out_stride, uint32_t vec, uint64_t out_max )
+{
+    return rows_aligned(d_out, out_stride, vec) && out_stride != 0 && out_stride <= out_max ? 0 : -EINVAL;
+}
+
 // what the entries that read a feed of real rows refuse of it
 inline int feed_rows_check( uint32_t kind, float rxnoise, const void *d_samples, size_t stride )
 {
-    if ( kind != MIFSK_FEED_F32 && kind != MIFSK_FEED_S16 )
-	return -EINVAL;
+    if ( int rc = kind_check(kind) )
+	return rc;
     const bool s16 = kind == MIFSK_FEED_S16;
     if ( !s16 && !( rxnoise == 0.0f ) )
 	return -EINVAL;
     return rows_aligned(d_samples, stride, rows_vec(false, s16)) ? 0 : -EINVAL;
+}
+
+// The input rows of a batch as the row stages' kernels take them.  28 bytes, so that the 32-bit member
+// behind it in a kernel's arguments lies where it lay behind four loose members: grouping them moves
+// no kernel argument and changes no kernel's code.
+struct __attribute__((packed, aligned(4))) RowsIn {
+    const void		*x;		// NULL where the entry allows it
+    size_t		stride;		// elements between rows
+    const uint32_t	*nsamples_v;	// [rows] or NULL
+    uint32_t		nsamples_u;	// ... then every row's length
+    // row s's length, no more than the stride (`to_stride`) and than out_stride (mifsk_rows.h)
+    __device__ uint64_t len( size_t s, bool to_stride = true, uint64_t out_stride = ~0ull ) const;
+};
+
+static_assert(sizeof(RowsIn) == 28, "three pointers and a count");
+
+// ... of any io that begins with d_samples, stream_stride, d_nsamples, nsamples
+template <class IO>
+inline RowsIn rows_in( const IO *io )
+{
+    return RowsIn{io->d_samples, io->stream_stride, io->d_nsamples, io->nsamples};
 }
 
 // f(complex rows, PCM16 scalars) with both as compile-time constants

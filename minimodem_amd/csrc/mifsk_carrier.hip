@@ -42,10 +42,7 @@ constexpr uint32_t kCarBigTable = 40u * 1024u;		// a table beyond this: one work
 
 struct CarrierArgs {
     const double	*cs;		// the context's spectrum table, [N][2]
-    const void		*x;		// rows of float or int16_t
-    size_t		stride;		// elements
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// rows of float or int16_t
     uint32_t		s16;		// the rows hold PCM16
     float		dc;		// rxnoise_term(): PCM16 only
     uint64_t		first;
@@ -121,10 +118,10 @@ void carrier_survey_kernel( const CarrierArgs A )
     }
 
     const uint32_t s = A.s0 + blockIdx.y;
-    const uint32_t n_row = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
-    const uint32_t nv = n_row < A.stride ? n_row : (uint32_t)A.stride;	// samples the row holds
-    const float *rowf = reinterpret_cast<const float *>(A.x) + (size_t)s * A.stride;
-    const int16_t *rowh = reinterpret_cast<const int16_t *>(A.x) + (size_t)s * A.stride;
+    const uint32_t n_row = A.in.nsamples_v ? A.in.nsamples_v[s] : A.in.nsamples_u;
+    const uint32_t nv = n_row < A.in.stride ? n_row : (uint32_t)A.in.stride;	// samples the row holds
+    const float *rowf = reinterpret_cast<const float *>(A.in.x) + (size_t)s * A.in.stride;
+    const int16_t *rowh = reinterpret_cast<const int16_t *>(A.in.x) + (size_t)s * A.in.stride;
     // windows that lie wholly inside the row, of those the outputs have room for: window w < nuse
     // reads x[first + w * hop + n] with n < window, all below nv
     uint64_t nfit = 0;
@@ -337,10 +334,7 @@ extern "C" int mifsk_detect_carrier_batch( mifsk_ctx *ctx, const mifsk_rx_config
 
     CarrierArgs A = {};
     A.cs = d_cs;
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.s16 = s16 ? 1u : 0u;
     A.dc = s16 ? rxnoise_term(io->rxnoise) : 0.0f;
     A.first = io->first;

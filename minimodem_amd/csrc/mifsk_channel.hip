@@ -39,6 +39,7 @@
 #include "mifsk.h"
 #include "mifsk_ctx.h"
 #include "mifsk_phase.h"
+#include "mifsk_rows.h"
 
 namespace mifsk {
 
@@ -54,10 +55,7 @@ struct ChannelArgs {
     const double2	*gt;		// G transposed, [T][K]
     const double2	*w;		// [P]: cos, sin
     const uint32_t	*dq;		// [K]: (r - q[k]) mod P
-    const void		*x;
-    size_t		stride;		// elements
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// elements
     uint32_t		T, D, K, P;
     uint32_t		s0;		// first stream of this launch
     uint32_t		cwshift;	// cw = 1 << cwshift channel lanes of a wave
@@ -76,14 +74,14 @@ __device__ __forceinline__ auto channel_sample( const void *row, uint64_t at )
     if constexpr ( CX ) {
 	if constexpr ( S16 ) {
 	    const short2 v = reinterpret_cast<const short2 *>(row)[at];
-	    return double2{(double)( (float)v.x / 32768.0f ), (double)( (float)v.y / 32768.0f )};
+	    return double2{(double)rows_f32(v.x), (double)rows_f32(v.y)};
 	} else {
 	    const float2 v = reinterpret_cast<const float2 *>(row)[at];
 	    return double2{(double)v.x, (double)v.y};
 	}
     } else {
 	if constexpr ( S16 )
-	    return (double)( (float)reinterpret_cast<const int16_t *>(row)[at] / 32768.0f );
+	    return (double)rows_f32(reinterpret_cast<const int16_t *>(row)[at]);
 	else
 	    return (double)reinterpret_cast<const float *>(row)[at];
     }
@@ -108,10 +106,12 @@ void channelize_kernel( const ChannelArgs A )
     const uint32_t R = ( OB - 1u ) * ss + tt;
 
     const uint32_t s = A.s0 + blockIdx.y, k0 = blockIdx.z * C;
-    const uint32_t n_row = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
-    const uint32_t nv = n_row < A.stride ? n_row : (uint32_t)A.stride;	// elements the row holds
-    const char *row = reinterpret_cast<const char *>(A.x)
-	+ (size_t)s * A.stride * ( ( S16 ? 2u : 4u ) * ( CX ? 2u : 1u ) );
+    // (RowsIn::len(s), written out: with the member this kernel's code comes out three instructions
+    // shorter, and it is to stay as it is)
+    const uint32_t n_row = A.in.nsamples_v ? A.in.nsamples_v[s] : A.in.nsamples_u;
+    const uint32_t nv = n_row < A.in.stride ? n_row : (uint32_t)A.in.stride;	// elements the row holds
+    const char *row = reinterpret_cast<const char *>(A.in.x)
+	+ (size_t)s * A.in.stride * ( ( S16 ? 2u : 4u ) * ( CX ? 2u : 1u ) );
     // outputs that exist, of those the rows have room for: output m < cnt reads x[m D + t], t < T,
     // all below nv
     const uint32_t fit = nv >= T ? ( nv - T ) / D + 1u : 0u;
@@ -321,10 +321,7 @@ extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mif
     A.gt = plan->gt.p;
     A.w = plan->w.p;
     A.dq = plan->dq.p;
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.T = plan->T;
     A.D = plan->D;
     A.K = plan->K;

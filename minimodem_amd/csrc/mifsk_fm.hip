@@ -32,6 +32,7 @@
 #include "mifsk_ctx.h"
 #include "mifsk_gauss.h"
 #include "mifsk_hostmem.h"
+#include "mifsk_rows.h"
 
 namespace mifsk {
 
@@ -39,27 +40,11 @@ constexpr uint32_t kFmThreads = 256u;
 constexpr uint32_t kFmPer = 8u;					// the modulator's samples per thread
 constexpr uint32_t kFmTile = kFmThreads * kFmPer;		// ... and per workgroup
 
-struct alignas(16) FmS16x8 { int16_t v[8]; };
-
-// the float as the PCM16 write conversion stores it (mifsk_mux.hip's)
-__device__ __forceinline__ int16_t fm_s16( float v )
-{
-    float t = v * 32767.0f;
-    if ( t > 32767.0f )
-	t = 32767.0f;
-    if ( t < -32768.0f )
-	t = -32768.0f;
-    return t != t ? (int16_t)0 : (int16_t)(int)rintf(t);
-}
-
 // ---------------------------------------------------------------------------
 // the discriminator
 // ---------------------------------------------------------------------------
 struct FmDemodArgs {
-    const void		*x;		// interleaved I, Q
-    size_t		stride;		// complex elements between input rows
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// interleaved I, Q: complex elements
     uint32_t		s0;		// first row of this launch
     float		*out;
     size_t		out_stride;
@@ -76,9 +61,11 @@ void fm_demod_kernel( const FmDemodArgs A )
     const uint64_t i0 = (uint64_t)( blockIdx.x * kFmThreads + threadIdx.x ) * 4u;
     if ( i0 >= A.out_stride )
 	return;
-    uint64_t W = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
-    if ( W > A.stride )
-	W = A.stride;
+    // (RowsIn::len(s, true, A.out_stride), written out: through the member the compiler orders this
+    // kernel's argument loads differently, and its code is to stay as it is)
+    uint64_t W = A.in.nsamples_v ? A.in.nsamples_v[s] : A.in.nsamples_u;
+    if ( W > A.in.stride )
+	W = A.in.stride;
     if ( W > A.out_stride )
 	W = A.out_stride;
 
@@ -91,19 +78,19 @@ void fm_demod_kernel( const FmDemodArgs A )
 	// its stride (a multiple of the vector)
 	float zr[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, zi[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
 	if constexpr ( S16 ) {
-	    const int16_t *row = reinterpret_cast<const int16_t *>(A.x) + ( (size_t)s * A.stride + i0 ) * 2u;
-	    const FmS16x8 p = *reinterpret_cast<const FmS16x8 *>(row);
+	    const int16_t *row = reinterpret_cast<const int16_t *>(A.in.x) + ( (size_t)s * A.in.stride + i0 ) * 2u;
+	    const S16x8 p = *reinterpret_cast<const S16x8 *>(row);
 #pragma unroll
 	    for ( uint32_t u = 0; u < 4u; u++ ) {
-		zr[u] = (float)p.v[2u * u] / 32768.0f;
-		zi[u] = (float)p.v[2u * u + 1u] / 32768.0f;
+		zr[u] = rows_f32(p.v[2u * u]);
+		zi[u] = rows_f32(p.v[2u * u + 1u]);
 	    }
 	    if ( i0 > 0u ) {
 		const short2 b = *reinterpret_cast<const short2 *>(row - 2);
-		before = float2{(float)b.x / 32768.0f, (float)b.y / 32768.0f};
+		before = float2{rows_f32(b.x), rows_f32(b.y)};
 	    }
 	} else {
-	    const float *row = reinterpret_cast<const float *>(A.x) + ( (size_t)s * A.stride + i0 ) * 2u;
+	    const float *row = reinterpret_cast<const float *>(A.in.x) + ( (size_t)s * A.in.stride + i0 ) * 2u;
 #pragma unroll
 	    for ( uint32_t h = 0; h < 2u; h++ ) {
 		if ( i0 + 2u * h < W ) {
@@ -142,10 +129,7 @@ void fm_demod_kernel( const FmDemodArgs A )
 // the modulator
 // ---------------------------------------------------------------------------
 struct FmModArgs {
-    const float		*x;
-    size_t		stride;		// floats between input rows
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// floats
     uint32_t		s0;		// first row of this launch
     uint32_t		nrows;		// all rows (the row scan)
     uint32_t		ntiles;		// tiles of a row: up to out_stride
@@ -157,14 +141,6 @@ struct FmModArgs {
     uint64_t		*tiles;		// scratch [nstreams][ntiles]: sums, then the phase before each tile
 };
 
-__device__ __forceinline__ uint64_t fm_row_len( const FmModArgs &A, uint32_t s )
-{
-    uint64_t W = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
-    if ( W > A.stride )
-	W = A.stride;
-    return W > A.out_stride ? A.out_stride : W;
-}
-
 // the phase step of one sample
 __device__ __forceinline__ uint64_t fm_step( float x, double deviation, double centre )
 {
@@ -175,7 +151,7 @@ __device__ __forceinline__ uint64_t fm_step( float x, double deviation, double c
 // q[0 .. 8): the steps of the thread's samples i0 .. i0 + 7 of row s, zero from W on
 __device__ __forceinline__ void fm_steps( const FmModArgs &A, uint32_t s, uint64_t i0, uint64_t W, uint64_t q[kFmPer] )
 {
-    const float *row = A.x + (size_t)s * A.stride + i0;
+    const float *row = reinterpret_cast<const float *>(A.in.x) + (size_t)s * A.in.stride + i0;
 #pragma unroll
     for ( uint32_t h = 0; h < kFmPer; h += 4u ) {
 	float4 p = float4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -207,7 +183,7 @@ void fm_tile_sums_kernel( const FmModArgs A )
 {
     __shared__ uint64_t wave_sum[kFmThreads / 64u];
     const uint32_t s = A.s0 + blockIdx.y, tid = threadIdx.x, lane = tid & 63u;
-    const uint64_t t0 = (uint64_t)blockIdx.x * kFmTile, W = fm_row_len(A, s);
+    const uint64_t t0 = (uint64_t)blockIdx.x * kFmTile, W = A.in.len(s, true, A.out_stride);
     uint64_t mine = 0ull;
     if ( t0 < W ) {						// (the whole workgroup)
 	uint64_t q[kFmPer];
@@ -253,7 +229,7 @@ void fm_tile_write_kernel( const FmModArgs A )
 {
     __shared__ uint64_t wave_sum[kFmThreads / 64u];
     const uint32_t s = A.s0 + blockIdx.y, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t t0 = (uint64_t)blockIdx.x * kFmTile, i0 = t0 + (uint64_t)tid * kFmPer, W = fm_row_len(A, s);
+    const uint64_t t0 = (uint64_t)blockIdx.x * kFmTile, i0 = t0 + (uint64_t)tid * kFmPer, W = A.in.len(s, true, A.out_stride);
     float oi[kFmPer], oq[kFmPer];
 #pragma unroll
     for ( uint32_t u = 0; u < kFmPer; u++ ) {
@@ -291,13 +267,13 @@ void fm_tile_write_kernel( const FmModArgs A )
 #pragma unroll
 	for ( uint32_t h = 0; h < kFmPer; h += 4u ) {
 	    if ( i0 + h < A.out_stride ) {
-		FmS16x8 p;
+		S16x8 p;
 #pragma unroll
 		for ( uint32_t u = 0; u < 4u; u++ ) {
-		    p.v[2u * u] = i0 + h + u < W ? fm_s16(oi[h + u]) : (int16_t)0;
-		    p.v[2u * u + 1u] = i0 + h + u < W ? fm_s16(oq[h + u]) : (int16_t)0;
+		    p.v[2u * u] = i0 + h + u < W ? rows_s16(oi[h + u]) : (int16_t)0;
+		    p.v[2u * u + 1u] = i0 + h + u < W ? rows_s16(oq[h + u]) : (int16_t)0;
 		}
-		*reinterpret_cast<FmS16x8 *>(row + 2u * h) = p;
+		*reinterpret_cast<S16x8 *>(row + 2u * h) = p;
 	    }
 	}
     } else {
@@ -322,21 +298,18 @@ extern "C" int mifsk_fm_demod_batch( mifsk_ctx *ctx, const mifsk_fm_demod_io *io
 	return -EINVAL;
     if ( io->nstreams <= 0 )
 	return -EINVAL;
-    if ( io->kind != MIFSK_FEED_F32 && io->kind != MIFSK_FEED_S16 )
-	return -EINVAL;
+    if ( int rc = kind_check(io->kind) )
+	return rc;
     if ( io->flags != 0u )
 	return -EINVAL;
     const bool s16 = io->kind == MIFSK_FEED_S16;
     if ( !rows_aligned(io->d_samples, io->stream_stride, rows_vec(true, s16)) )
 	return -EINVAL;
-    if ( !rows_aligned(io->d_out, io->out_stride, 4u) || io->out_stride == 0 || io->out_stride > 0xFFFFFFF8ull )
-	return -EINVAL;
+    if ( int rc = out_rows_check(io->d_out, io->out_stride, 4u, 0xFFFFFFF8ull) )
+	return rc;
 
     FmDemodArgs A = {};
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.out = io->d_out;
     A.out_stride = io->out_stride;
     A.prev = reinterpret_cast<const float2 *>(io->d_prev);
@@ -364,22 +337,18 @@ extern "C" int mifsk_fm_modulate_batch( mifsk_ctx *ctx, const mifsk_fm_mod_io *i
 	return -EINVAL;
     if ( io->nstreams <= 0 )
 	return -EINVAL;
-    if ( io->out_kind != MIFSK_FEED_F32 && io->out_kind != MIFSK_FEED_S16 )
-	return -EINVAL;
+    if ( int rc = kind_check(io->out_kind) )
+	return rc;
     if ( io->flags != 0u )
 	return -EINVAL;
     const bool s16 = io->out_kind == MIFSK_FEED_S16;
     if ( !rows_aligned(io->d_samples, io->stream_stride, rows_vec(false, false)) )
 	return -EINVAL;
-    if ( !rows_aligned(io->d_out, io->out_stride, rows_vec(true, s16)) || io->out_stride == 0
-	    || io->out_stride > 0xFFFFFFF8ull )
-	return -EINVAL;
+    if ( int rc = out_rows_check(io->d_out, io->out_stride, rows_vec(true, s16), 0xFFFFFFF8ull) )
+	return rc;
 
     FmModArgs A = {};
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.nrows = (uint32_t)io->nstreams;
     A.ntiles = (uint32_t)( ( io->out_stride + kFmTile - 1u ) / kFmTile );
     A.out = io->d_out;

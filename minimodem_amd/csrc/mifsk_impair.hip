@@ -24,16 +24,14 @@
 #include "mifsk_batch.h"
 #include "mifsk_ctx.h"
 #include "mifsk_gauss.h"
+#include "mifsk_rows.h"
 
 namespace mifsk {
 
 constexpr uint32_t kImThreads = 256u;
 
 struct ImpairArgs {
-    const void		*x;		// NULL: x = 0
-    size_t		stride;		// elements between input rows
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// x NULL: x = 0
     uint32_t		s0;		// first row of this launch
     void		*out;
     size_t		out_stride;	// elements
@@ -41,19 +39,6 @@ struct ImpairArgs {
     const float		*gain_v, *sigma_v, *dc_v;
     float		gain, sigma, dc;
 };
-
-// the float as the PCM16 write conversion stores it (mifsk_mux.hip's)
-__device__ __forceinline__ int16_t impair_s16( float v )
-{
-    float t = v * 32767.0f;
-    if ( t > 32767.0f )
-	t = 32767.0f;
-    if ( t < -32768.0f )
-	t = -32768.0f;
-    return t != t ? (int16_t)0 : (int16_t)(int)rintf(t);
-}
-
-struct alignas(16) S16x8 { int16_t v[8]; };
 
 // IN_S16 / OUT_S16: PCM16 scalars on that side
 template <bool IN_S16, bool OUT_S16>
@@ -65,9 +50,11 @@ void impair_kernel( const ImpairArgs A )
     const uint64_t i0 = (uint64_t)( blockIdx.x * kImThreads + threadIdx.x ) * V;
     if ( i0 >= A.out_stride )
 	return;
-    uint64_t W = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
-    if ( A.x && W > A.stride )
-	W = A.stride;
+    // (RowsIn::len(s, A.in.x, A.out_stride), written out: through the member the compiler orders this
+    // kernel's argument loads differently, and its code is to stay as it is)
+    uint64_t W = A.in.nsamples_v ? A.in.nsamples_v[s] : A.in.nsamples_u;
+    if ( A.in.x && W > A.in.stride )
+	W = A.in.stride;
     if ( W > A.out_stride )
 	W = A.out_stride;
 
@@ -82,15 +69,15 @@ void impair_kernel( const ImpairArgs A )
 #pragma unroll
 	for ( uint32_t u = 0; u < V; u++ )
 	    x[u] = 0.0f;
-	if ( A.x ) {
+	if ( A.in.x ) {
 	    if constexpr ( IN_S16 ) {
 		const S16x8 p = *reinterpret_cast<const S16x8 *>(
-			reinterpret_cast<const int16_t *>(A.x) + (size_t)s * A.stride + i0);
+			reinterpret_cast<const int16_t *>(A.in.x) + (size_t)s * A.in.stride + i0);
 #pragma unroll
 		for ( uint32_t u = 0; u < 8u; u++ )
-		    x[u] = (float)p.v[u] / 32768.0f;
+		    x[u] = rows_f32(p.v[u]);
 	    } else {
-		const float *row = reinterpret_cast<const float *>(A.x) + (size_t)s * A.stride + i0;
+		const float *row = reinterpret_cast<const float *>(A.in.x) + (size_t)s * A.in.stride + i0;
 #pragma unroll
 		for ( uint32_t h = 0; h < V; h += 4u ) {
 		    if ( i0 + h < W ) {
@@ -123,7 +110,7 @@ void impair_kernel( const ImpairArgs A )
 	S16x8 p;
 #pragma unroll
 	for ( uint32_t u = 0; u < 8u; u++ )
-	    p.v[u] = i0 + u < W ? impair_s16(o[u]) : (int16_t)0;
+	    p.v[u] = i0 + u < W ? rows_s16(o[u]) : (int16_t)0;
 	*reinterpret_cast<S16x8 *>(reinterpret_cast<int16_t *>(A.out) + (size_t)s * A.out_stride + i0) = p;
     } else {
 	float *row = reinterpret_cast<float *>(A.out) + (size_t)s * A.out_stride + i0;
@@ -149,8 +136,7 @@ extern "C" int mifsk_impair_batch( mifsk_ctx *ctx, const mifsk_impair_io *io, vo
 	return -EINVAL;
     if ( io->nstreams <= 0 )
 	return -EINVAL;
-    if ( ( io->kind != MIFSK_FEED_F32 && io->kind != MIFSK_FEED_S16 )
-	    || ( io->out_kind != MIFSK_FEED_F32 && io->out_kind != MIFSK_FEED_S16 ) )
+    if ( kind_check(io->kind) || kind_check(io->out_kind) )
 	return -EINVAL;
     if ( io->flags != 0u )
 	return -EINVAL;
@@ -160,15 +146,11 @@ extern "C" int mifsk_impair_batch( mifsk_ctx *ctx, const mifsk_impair_io *io, vo
     if ( io->d_samples )
 	if ( int rc = feed_rows_check(io->kind, 0.0f, io->d_samples, io->stream_stride) )
 	    return rc;
-    if ( !rows_aligned(io->d_out, io->out_stride, rows_vec(false, out_s16)) || io->out_stride == 0
-	    || io->out_stride > 0xFFFFFFF8ull )
-	return -EINVAL;
+    if ( int rc = out_rows_check(io->d_out, io->out_stride, rows_vec(false, out_s16), 0xFFFFFFF8ull) )
+	return rc;
 
     ImpairArgs A = {};
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.out = io->d_out;
     A.out_stride = io->out_stride;
     A.seed = io->seed;

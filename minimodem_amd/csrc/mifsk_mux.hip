@@ -38,6 +38,7 @@
 #include "mifsk.h"
 #include "mifsk_ctx.h"
 #include "mifsk_phase.h"
+#include "mifsk_rows.h"
 
 namespace mifsk {
 
@@ -52,10 +53,7 @@ struct MuxArgs {
     const uint32_t	*dq;		// [K]: (q[k] - r) mod P
     const uint32_t	*ps;		// [K]: (dq[k] * (L mod P)) mod P
     const float		*gains;		// [K] or NULL
-    const float		*x;
-    size_t		stride;		// floats between input rows
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// floats
     uint32_t		T, L, K, P;
     uint32_t		jmax;		// ceil(T / L): tap steps of phase 0
     uint32_t		span;		// samples staged per channel, at most
@@ -83,17 +81,6 @@ __device__ __forceinline__ uint32_t mux_mulmod( uint32_t a, uint32_t b, uint32_t
     return (uint32_t)r;
 }
 
-// the float as the PCM16 write conversion stores it
-__device__ __forceinline__ int16_t mux_s16( float v )
-{
-    float t = v * 32767.0f;
-    if ( t > 32767.0f )
-	t = 32767.0f;
-    if ( t < -32768.0f )
-	t = -32768.0f;
-    return t != t ? (int16_t)0 : (int16_t)(int)rintf(t);
-}
-
 // CX: complex rows.  S16: PCM16 scalars.
 template <bool CX, bool S16>
 __global__ __launch_bounds__(256)
@@ -108,10 +95,7 @@ void multiplex_kernel( const MuxArgs A )
 
     const uint32_t s = A.s0 + blockIdx.y;
     const size_t row0 = (size_t)s * K;
-    auto row_len = [&]( uint32_t k ) {
-	const uint32_t n = A.nsamples_v ? A.nsamples_v[row0 + k] : A.nsamples_u;
-	return n < A.stride ? n : (uint32_t)A.stride;
-    };
+    auto row_len = [&]( uint32_t k ) { return (uint32_t)A.in.len(row0 + k); };
     if ( tid == 0 )
 	nmax_sh = 0u;
     __syncthreads();
@@ -160,7 +144,7 @@ void multiplex_kernel( const MuxArgs A )
 	    // a wave per channel: the row and its length are the wave's, the lanes read along the row
 	    for ( uint32_t c = tid >> 6; c < cbn; c += kMxThreads / 64u ) {
 		const int64_t nk = row_len(k0 + c);
-		const float *xr = A.x + ( row0 + k0 + c ) * A.stride;
+		const float *xr = reinterpret_cast<const float *>(A.in.x) + ( row0 + k0 + c ) * A.in.stride;
 		double *xc = xs + (size_t)c * A.spanp;
 		for ( uint32_t e = tid & 63u; e < span; e += 64u ) {
 		    const int64_t i = lo + e;
@@ -270,12 +254,12 @@ void multiplex_kernel( const MuxArgs A )
 	const float vr = n < cnt ? (float)o[u] : 0.0f, vi = n < cnt ? (float)oi[u] : 0.0f;
 	if constexpr ( CX ) {
 	    if constexpr ( S16 )
-		reinterpret_cast<short2 *>(out)[n] = short2{n < cnt ? mux_s16(vr) : (int16_t)0, n < cnt ? mux_s16(vi) : (int16_t)0};
+		reinterpret_cast<short2 *>(out)[n] = short2{n < cnt ? rows_s16(vr) : (int16_t)0, n < cnt ? rows_s16(vi) : (int16_t)0};
 	    else
 		reinterpret_cast<float2 *>(out)[n] = float2{vr, vi};
 	} else {
 	    if constexpr ( S16 )
-		reinterpret_cast<int16_t *>(out)[n] = n < cnt ? mux_s16(vr) : (int16_t)0;
+		reinterpret_cast<int16_t *>(out)[n] = n < cnt ? rows_s16(vr) : (int16_t)0;
 	    else
 		reinterpret_cast<float *>(out)[n] = vr;
 	}
@@ -366,10 +350,7 @@ extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mu
     A.dq = plan->dq.p;
     A.ps = plan->ps.p;
     A.gains = plan->gains.p;
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.T = plan->T;
     A.L = plan->L;
     A.K = plan->K;

@@ -152,8 +152,8 @@ int phase_check_io( const PhasePlanCommon &plan, const IO *io, const void *d_out
 	return -EINVAL;
     if ( !rows_aligned(io->d_samples, io->stream_stride, in_vec) )
 	return -EINVAL;
-    if ( !rows_aligned(d_out, io->out_stride, out_vec) || io->out_stride == 0 || io->out_stride > out_max )
-	return -EINVAL;
+    if ( int rc = out_rows_check(d_out, io->out_stride, out_vec, out_max) )
+	return rc;
     if ( io->nout_cap > io->out_stride || (uint64_t)io->nstreams * plan.K > 0x7FFFFFFFull )
 	return -EINVAL;
     return 0;

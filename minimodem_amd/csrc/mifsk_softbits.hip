@@ -42,10 +42,7 @@ constexpr uint32_t kSoftMaxLdsFloats = 12288u;		// 48 KiB of the 64 a workgroup 
 struct SoftArgs {
     const DevCfg	*cfg;
     const double	*tw;
-    const void		*x;		// rows of Src
-    size_t		stride;		// elements
-    const uint32_t	*nsamples_v;
-    uint32_t		nsamples_u;
+    RowsIn		in;		// rows of Src
     float		dc;		// rxnoise_term(): PCM16 only
     const uint64_t	*origin;
     const mifsk_frame	*frames;
@@ -216,7 +213,7 @@ void softbits_kernel( const SoftArgs A )
     const uint64_t start_s = A.frames[(size_t)s * A.frames_cap + js].start;
     const uint32_t off_s = cfg.bit_offset[ks];
     const uint32_t nfr = A.nframes[s];
-    const uint32_t n = A.nsamples_v ? A.nsamples_v[s] : A.nsamples_u;
+    const uint32_t n = A.in.nsamples_v ? A.in.nsamples_v[s] : A.in.nsamples_u;
     const uint64_t origin = A.origin ? A.origin[s] : 0u;
     const uint32_t total = ( nfr < A.frames_cap ? nfr : A.frames_cap ) * nb;
     if ( c0 >= total )
@@ -231,8 +228,8 @@ void softbits_kernel( const SoftArgs A )
     const uint64_t start = active ? start_s : start0;
     const uint32_t off = active ? off_s : off0;
 
-    const uint32_t nv = n < A.stride ? n : (uint32_t)A.stride;	// samples the row holds
-    const Src *row = reinterpret_cast<const Src *>(A.x) + (size_t)s * A.stride;
+    const uint32_t nv = n < A.in.stride ? n : (uint32_t)A.in.stride;	// samples the row holds
+    const Src *row = reinterpret_cast<const Src *>(A.in.x) + (size_t)s * A.in.stride;
     const bool before = start < origin;				// samples the caller no longer holds
     const uint64_t rel = start - origin;
     // the window's start inside the row, nv for a window that lies wholly beyond it: a in [0, nv]
@@ -405,10 +402,7 @@ extern "C" int mifsk_frame_softbits( mifsk_ctx *ctx, const mifsk_rx_config *cfg,
     SoftArgs A = {};
     A.cfg = d_cfg;
     A.tw = d_tw;
-    A.x = io->d_samples;
-    A.stride = io->stream_stride;
-    A.nsamples_v = io->d_nsamples;
-    A.nsamples_u = io->nsamples;
+    A.in = rows_in(io);
     A.dc = s16 ? rxnoise_term(io->rxnoise) : 0.0f;
     A.origin = io->d_origin;
     A.frames = io->d_frames;
