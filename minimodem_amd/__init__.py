@@ -1836,6 +1836,9 @@ STATE_DTYPE = np.dtype([("base", "<u8"), ("rp", "<u8"), ("carrier_nsamples", "<u
                         ("nepisodes_total", "<u4"), ("status", "<u4")])
 assert STATE_DTYPE.itemsize == 96
 STATE_FINISHED = 4
+# C struct name -> the numpy dtype that mirrors it (the ctypes mirrors: _lib.STRUCTS)
+DTYPES = {"mifsk_frame": FRAME_DTYPE, "mifsk_episode": EPISODE_DTYPE, "mifsk_stream_state": STATE_DTYPE,
+          "mifsk_search": SEARCH_DTYPE, "mifsk_search_result": RESULT_DTYPE}
 
 
 class SlabSession:

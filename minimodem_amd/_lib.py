@@ -308,58 +308,162 @@ class FmModIO(C.Structure):
                               ("reserved", C.c_uint32)]
 
 
-assert C.sizeof(FskPlan) == 64 and FskPlan.fftplan.offset == 40
-assert C.sizeof(FmDemodIO) == 80 and FmDemodIO.d_out.offset == 40 and FmDemodIO.gain.offset == 72
-assert C.sizeof(FmModIO) == 96 and FmModIO.d_out.offset == 40 and FmModIO.amplitude.offset == 88
-assert C.sizeof(ImpairIO) == 120 and ImpairIO.d_out.offset == 40 and ImpairIO.d_gain.offset == 80
-assert C.sizeof(MuxParams) == 56 and MuxParams.centres.offset == 32 and MuxParams.gains.offset == 48
-assert C.sizeof(MuxIO) == 64 and MuxIO.d_out.offset == 32 and MuxIO.d_nout.offset == 56
-assert C.sizeof(ChannelParams) == 48 and ChannelParams.centres.offset == 32
-assert C.sizeof(ChannelIO) == 64 and ChannelIO.d_rows.offset == 32 and ChannelIO.d_nout.offset == 56
-assert C.sizeof(CarrierIO) == 88 and CarrierIO.first.offset == 40 and CarrierIO.d_band.offset == 64
-assert C.sizeof(Search) == 32 and C.sizeof(SearchResult) == 24
-assert C.sizeof(SessionInfo) == 56 and SessionInfo.h2d_bytes_last.offset == 24
+# C struct name -> its mirror, for every struct of include/*.h that has one here (mifsk_frame, mifsk_episode
+# and mifsk_stream_state are numpy dtypes only: DTYPES in __init__.py)
+STRUCTS = {
+    "fsk_plan": FskPlan, "mifsk_modem_args": ModemArgs, "mifsk_rx_config": RxConfig, "mifsk_search": Search,
+    "mifsk_search_result": SearchResult, "mifsk_demod_io": DemodIO, "mifsk_pipeline_info": PipelineInfo,
+    "mifsk_gather_info": GatherInfo, "mifsk_launch_info": LaunchInfo, "mifsk_scan_plan": ScanPlan,
+    "mifsk_host_stats": HostStats, "mifsk_time_split": TimeSplit, "mifsk_time_split_stats": TimeSplitStats,
+    "mifsk_session_result": SessionResult, "mifsk_session_info": SessionInfo, "mifsk_softbits_io": SoftbitsIO,
+    "mifsk_carrier_io": CarrierIO, "mifsk_channel_params": ChannelParams, "mifsk_channel_io": ChannelIO,
+    "mifsk_mux_params": MuxParams, "mifsk_mux_io": MuxIO, "mifsk_impair_io": ImpairIO,
+    "mifsk_fm_demod_io": FmDemodIO, "mifsk_fm_mod_io": FmModIO, "mifsk_wav_info": WavInfo,
+    "mifsk_file_result": FileResult,
+}
 
-# every symbol include/*.h declares
-EXPORTS = [
-    "fsk_plan_new", "fsk_plan_destroy", "fsk_find_frame", "fsk_detect_carrier",
-    "fsk_set_tones_by_bandshift",
-    "mifsk_modem_args_default", "mifsk_rx_config_init", "mifsk_max_frames",
-    "mifsk_stream_padding", "mifsk_ctx_create", "mifsk_ctx_destroy",
-    "mifsk_ctx_device_name", "mifsk_abi_version", "mifsk_abi_sizeof", "mifsk_find_frame_batch", "mifsk_demod_plan_ex",
-    "mifsk_demod_batch", "mifsk_demod_batch_host",
-    "mifsk_tx_synthesize",
-    "mifsk_databits_create", "mifsk_databits_destroy", "mifsk_databits_reset",
-    "mifsk_databits_decode", "mifsk_databits_encode", "mifsk_shard_range",
-    "mifsk_demod_batch_host_multi", "mifsk_demod_plan", "mifsk_stream_text",
-    "mifsk_wav_parse", "mifsk_ingest_s16", "mifsk_ingest_rxnoise_f32",
-    "mifsk_tx_synthesize_batch",
-    "mifsk_demod_batch_host_ex", "mifsk_host_alloc", "mifsk_host_free", "mifsk_max_episodes",
-    "mifsk_demod_files", "mifsk_files_count", "mifsk_files_get", "mifsk_files_stats",
-    "mifsk_files_free", "mifsk_demod_slab", "mifsk_scan_plan_get",
-    "mifsk_demod_slab_ring", "mifsk_ring_floats", "mifsk_selftest_sqrt",
-    "mifsk_selftest_rcp", "mifsk_selftest_mag", "mifsk_selftest_confidence",
-    "mifsk_selftest_corr", "mifsk_selftest_scan", "mifsk_selftest_wave_max",
-    "mifsk_pipeline_create", "mifsk_pipeline_destroy", "mifsk_pipeline_info_get",
-    "mifsk_pipeline_outputs_alloc", "mifsk_pipeline_outputs_get", "mifsk_pipeline_submit",
-    "mifsk_pipeline_next_ticket", "mifsk_pipeline_wait", "mifsk_pipeline_join",
-    "mifsk_pipeline_drain", "mifsk_pipeline_stream", "mifsk_pipeline_ctx",
-    "mifsk_gather_unique_id", "mifsk_gather_create", "mifsk_gather_destroy", "mifsk_gather_info_get",
-    "mifsk_gather_start", "mifsk_gather_received",
-    "mifsk_session_create", "mifsk_session_destroy", "mifsk_session_feed", "mifsk_session_get",
-    "mifsk_session_pending", "mifsk_time_split_plan_get", "mifsk_demod_long",
-    "mifsk_time_split_plan_batch_get", "mifsk_demod_long_batch",
-    "mifsk_demod_long_batch_s16", "mifsk_demod_long_batch_host", "mifsk_demod_files_long",
-    "mifsk_files_time_split",
-    "mifsk_session_feed_ex", "mifsk_session_feed_device", "mifsk_session_info_get",
-    "mifsk_frame_softbits",
-    "mifsk_detect_carrier_batch", "mifsk_carrier_windows", "mifsk_carrier_tones",
-    "mifsk_channel_plan_create", "mifsk_channel_plan_destroy", "mifsk_channelize_batch",
-    "mifsk_channel_table", "mifsk_channel_taps",
-    "mifsk_mux_plan_create", "mifsk_mux_plan_destroy", "mifsk_multiplex_batch", "mifsk_mux_table",
-    "mifsk_impair_batch", "mifsk_impair_sigma", "mifsk_selftest_gauss",
-    "mifsk_fm_demod_batch", "mifsk_fm_modulate_batch", "mifsk_fm_gain", "mifsk_fm_step", "mifsk_selftest_turn",
-]
+_P = C.POINTER
+_vp, _str, _int, _uint, _f32, _f64 = C.c_void_p, C.c_char_p, C.c_int, C.c_uint, C.c_float, C.c_double
+_sz, _u32, _u64 = C.c_size_t, C.c_uint32, C.c_uint64
+_cfg, _io, _split, _split_stats = _P(RxConfig), _P(DemodIO), _P(TimeSplit), _P(TimeSplitStats)
+
+# every function include/*.h declares, in the headers' order: name -> (restype, argtypes); None: void
+SIGNATURES = {
+    # include/fsk.h
+    "fsk_plan_new": (_P(FskPlan), [_f32, _f32, _f32, _f32]),
+    "fsk_plan_destroy": (None, [_vp]),
+    "fsk_find_frame": (_f32, [_vp, _vp, _uint, _uint, _uint, _uint, _f32, _str, _P(C.c_ulonglong), _P(_f32),
+                              _P(_uint)]),
+    "fsk_detect_carrier": (_int, [_vp, _vp, _uint, _f32]),
+    "fsk_set_tones_by_bandshift": (None, [_vp, _uint, _int]),
+    # include/mifsk.h: the configuration
+    "mifsk_modem_args_default": (None, [_P(ModemArgs)]),
+    "mifsk_rx_config_init": (_int, [_cfg, _P(ModemArgs)]),
+    "mifsk_max_frames": (_sz, [_cfg, _sz]),
+    "mifsk_stream_padding": (_sz, [_cfg]),
+    # device context
+    "mifsk_ctx_create": (_int, [_P(_vp), _int]),
+    "mifsk_ctx_destroy": (None, [_vp]),
+    "mifsk_ctx_device_name": (_str, [_vp]),
+    "mifsk_abi_version": (_int, []),
+    "mifsk_abi_sizeof": (_sz, [_str]),
+    # diagnostics (declared with the device context)
+    "mifsk_selftest_sqrt": (_int, [_vp, _u64, _u64, _P(_u64)]),
+    "mifsk_selftest_rcp": (_int, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "mifsk_selftest_mag": (_int, [_vp, _vp, _vp, _f32, _u64, _vp, _vp, _vp, _vp]),
+    "mifsk_selftest_confidence": (_int, [_vp, _int, _u32, _u64, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "mifsk_selftest_gauss": (_int, [_vp, _vp, _u64, _vp]),
+    "mifsk_selftest_turn": (_int, [_vp, _vp, _vp, _u64, _vp]),
+    "mifsk_selftest_corr": (_int, [_vp, _cfg, _int, _int, _vp, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "mifsk_selftest_scan": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "mifsk_selftest_wave_max": (_int, [_vp, _vp, _u32, _vp]),
+    # N independent fsk_find_frame() problems; the whole-stream receive loop
+    "mifsk_find_frame_batch": (_int, [_vp, _cfg, _vp, _vp, _vp, _int, _vp]),
+    "mifsk_demod_batch": (_int, [_vp, _cfg, _io, _vp]),
+    # several batches in flight
+    "mifsk_pipeline_create": (_int, [_P(_vp), _int, _int]),
+    "mifsk_pipeline_destroy": (None, [_vp]),
+    "mifsk_pipeline_info_get": (_int, [_vp, _P(PipelineInfo)]),
+    "mifsk_pipeline_outputs_alloc": (_int, [_vp, _int, _sz, _sz, _uint]),
+    "mifsk_pipeline_outputs_get": (_int, [_vp, _u64, _io]),
+    "mifsk_pipeline_submit": (_int, [_vp, _cfg, _io, _vp, _P(_u64)]),
+    "mifsk_pipeline_next_ticket": (_u64, [_vp]),
+    "mifsk_pipeline_wait": (_int, [_vp, _u64]),
+    "mifsk_pipeline_join": (_int, [_vp, _u64, _vp]),
+    "mifsk_pipeline_drain": (_int, [_vp]),
+    "mifsk_pipeline_stream": (_vp, [_vp, _u64]),
+    "mifsk_pipeline_ctx": (_vp, [_vp, _u64]),
+    # one process per GPU: decoded bytes to one rank
+    "mifsk_gather_unique_id": (_int, [_vp]),
+    "mifsk_gather_create": (_int, [_P(_vp), _vp, _int, _int, _int, _int, _uint]),
+    "mifsk_gather_destroy": (None, [_vp]),
+    "mifsk_gather_info_get": (_int, [_vp, _P(GatherInfo)]),
+    "mifsk_gather_start": (_int, [_vp, _vp, _sz, _vp, _int, _int, _P(_int), _vp, _P(_u64)]),
+    "mifsk_gather_received": (_int, [_vp, _u64, _int, _P(_vp), _P(_vp), _P(_int), _P(_int)]),
+    # what a batch would launch
+    "mifsk_demod_plan": (_int, [_vp, _cfg, _int, _uint, _P(LaunchInfo)]),
+    "mifsk_demod_plan_ex": (_int, [_vp, _cfg, _int, _u32, _uint, _P(LaunchInfo)]),
+    "mifsk_scan_plan_get": (_int, [_cfg, _int, _P(ScanPlan)]),
+    # streams that start in host memory
+    "mifsk_demod_batch_host": (_int, [_vp, _cfg, _io]),
+    "mifsk_demod_batch_host_ex": (_int, [_vp, _cfg, _io, _f32, _P(HostStats)]),
+    "mifsk_host_alloc": (_vp, [_sz]),
+    "mifsk_host_free": (None, [_vp]),
+    "mifsk_max_episodes": (_sz, [_cfg, _sz]),
+    # streams that arrive in pieces
+    "mifsk_demod_slab": (_int, [_vp, _cfg, _io, _vp, _vp, _int, _vp]),
+    "mifsk_ring_floats": (_sz, [_cfg]),
+    "mifsk_demod_slab_ring": (_int, [_vp, _cfg, _io, _vp, _vp, _vp, _int, _vp]),
+    # one long recording across the whole chip
+    "mifsk_time_split_plan_get": (_int, [_cfg, _u64, _split, _split_stats]),
+    "mifsk_demod_long": (_int, [_vp, _cfg, _vp, _u64, _split, _io, _split_stats, _vp]),
+    "mifsk_time_split_plan_batch_get": (_int, [_cfg, _P(_u64), _int, _split, _split_stats]),
+    "mifsk_demod_long_batch": (_int, [_vp, _cfg, _vp, _sz, _P(_u64), _int, _split, _io, _split_stats, _vp]),
+    "mifsk_demod_long_batch_s16": (_int, [_vp, _cfg, _vp, _sz, _P(_u64), _int, _f32, _split, _io, _split_stats,
+                                          _vp]),
+    "mifsk_demod_long_batch_host": (_int, [_vp, _cfg, _P(_vp), _P(_u64), _int, _uint, _f32, _split, _io,
+                                           _split_stats, _P(HostStats)]),
+    # streams fed in pieces from host memory; the resident session
+    "mifsk_session_create": (_int, [_P(_vp), _vp, _cfg, _int, _uint]),
+    "mifsk_session_destroy": (None, [_vp]),
+    "mifsk_session_feed": (_int, [_vp, _P(_vp), _P(_u32), _int]),
+    "mifsk_session_get": (_P(SessionResult), [_vp, _int]),
+    "mifsk_session_pending": (_sz, [_vp, _int]),
+    "mifsk_session_feed_ex": (_int, [_vp, _P(_vp), _P(_u32), _uint, _f32, _int]),
+    "mifsk_session_feed_device": (_int, [_vp, _vp, _sz, _P(_u32), _uint, _f32, _int, _vp]),
+    "mifsk_session_info_get": (_int, [_vp, _P(SessionInfo)]),
+    # soft bits; a batch of fsk_detect_carrier() problems
+    "mifsk_frame_softbits": (_int, [_vp, _cfg, _P(SoftbitsIO), _vp]),
+    "mifsk_detect_carrier_batch": (_int, [_vp, _cfg, _P(CarrierIO), _vp]),
+    "mifsk_carrier_windows": (_u64, [_u64, _u64, _u32, _u32]),
+    "mifsk_carrier_tones": (_int, [_cfg, _int, _P(_uint), _P(_uint), _P(_f32), _P(_f32)]),
+    # channelizer
+    "mifsk_channel_plan_create": (_int, [_vp, _P(ChannelParams), _P(_vp)]),
+    "mifsk_channel_plan_destroy": (None, [_vp]),
+    "mifsk_channelize_batch": (_int, [_vp, _P(ChannelIO), _vp]),
+    "mifsk_channel_table": (_int, [_P(ChannelParams), _u32, _vp]),
+    "mifsk_channel_taps": (_int, [_u32, _f64, _f64, _f64, _vp]),
+    # multiplexer
+    "mifsk_mux_plan_create": (_int, [_vp, _P(MuxParams), _P(_vp)]),
+    "mifsk_mux_plan_destroy": (None, [_vp]),
+    "mifsk_multiplex_batch": (_int, [_vp, _P(MuxIO), _vp]),
+    "mifsk_mux_table": (_int, [_P(MuxParams), _vp]),
+    # channel model
+    "mifsk_impair_batch": (_int, [_vp, _P(ImpairIO), _vp]),
+    "mifsk_impair_sigma": (_f32, [_f32, _f64]),
+    # FM stage
+    "mifsk_fm_demod_batch": (_int, [_vp, _P(FmDemodIO), _vp]),
+    "mifsk_fm_gain": (_f32, [_f64, _f64]),
+    "mifsk_fm_modulate_batch": (_int, [_vp, _P(FmModIO), _vp]),
+    "mifsk_fm_step": (_f64, [_f64, _f64]),
+    # several GPUs
+    "mifsk_shard_range": (None, [_int, _int, _int, _P(_int), _P(_int)]),
+    "mifsk_demod_batch_host_multi": (_int, [_P(_vp), _int, _cfg, _io]),
+    # host post-pass: frame bits -> text
+    "mifsk_databits_create": (_int, [_P(_vp), _int]),
+    "mifsk_databits_destroy": (None, [_vp]),
+    "mifsk_databits_reset": (None, [_vp]),
+    "mifsk_databits_decode": (_uint, [_vp, _str, _uint, C.c_ulonglong, _uint]),
+    "mifsk_databits_encode": (_uint, [_vp, _P(_uint), C.c_char]),
+    "mifsk_stream_text": (_int, [_cfg, _vp, _u32, _vp, _u32, _uint, _str, _sz, _P(_sz), _str, _sz, _P(_sz)]),
+    # input side: the step before the path
+    "mifsk_wav_parse": (_int, [_str, _sz, _P(WavInfo)]),
+    "mifsk_ingest_s16": (_int, [_vp, _vp, _sz, _vp, _sz, _vp, _u32, _int, _f32, _vp]),
+    "mifsk_ingest_rxnoise_f32": (_int, [_vp, _vp, _sz, _vp, _u32, _int, _f32, _vp]),
+    # a list of audio files -> one batch
+    "mifsk_demod_files": (_int, [_vp, _P(ModemArgs), _P(_str), _int, _f32, _uint, _P(_vp)]),
+    "mifsk_demod_files_long": (_int, [_vp, _P(ModemArgs), _P(_str), _int, _f32, _uint, _split, _P(_vp)]),
+    "mifsk_files_time_split": (_split_stats, [_vp, _int]),
+    "mifsk_files_count": (_int, [_vp]),
+    "mifsk_files_get": (_P(FileResult), [_vp, _int]),
+    "mifsk_files_stats": (_P(HostStats), [_vp]),
+    "mifsk_files_free": (None, [_vp]),
+    # transmit side
+    "mifsk_tx_synthesize": (C.c_long, [_cfg, _vp, _sz, _uint, _f32, _uint, _int, _vp, _sz]),
+    "mifsk_tx_synthesize_batch": (_int, [_vp, _cfg, _vp, _sz, _vp, _u32, _int, _uint, _f32, _vp, _u32, _int, _vp,
+                                         _sz, _vp, _vp]),
+}
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -373,257 +477,8 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.mifsk_modem_args_default.argtypes = [C.POINTER(ModemArgs)]
-    lib.mifsk_rx_config_init.restype = C.c_int
-    lib.mifsk_rx_config_init.argtypes = [C.POINTER(RxConfig), C.POINTER(ModemArgs)]
-    lib.mifsk_max_frames.restype = C.c_size_t
-    lib.mifsk_max_frames.argtypes = [C.POINTER(RxConfig), C.c_size_t]
-    lib.mifsk_stream_padding.restype = C.c_size_t
-    lib.mifsk_stream_padding.argtypes = [C.POINTER(RxConfig)]
-    lib.mifsk_ctx_create.restype = C.c_int
-    lib.mifsk_ctx_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    lib.mifsk_ctx_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_ctx_device_name.restype = C.c_char_p
-    lib.mifsk_ctx_device_name.argtypes = [C.c_void_p]
-    lib.mifsk_abi_version.restype = C.c_int
-    lib.mifsk_abi_sizeof.restype = C.c_size_t
-    lib.mifsk_abi_sizeof.argtypes = [C.c_char_p]
-    lib.mifsk_find_frame_batch.restype = C.c_int
-    lib.mifsk_find_frame_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.mifsk_demod_batch.restype = C.c_int
-    lib.mifsk_demod_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO),
-                                      C.c_void_p]
-    lib.mifsk_demod_batch_host.restype = C.c_int
-    lib.mifsk_demod_batch_host.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO)]
-    lib.fsk_plan_new.restype = C.POINTER(FskPlan)
-    lib.fsk_plan_new.argtypes = [C.c_float] * 4
-    lib.fsk_plan_destroy.argtypes = [C.c_void_p]
-    lib.fsk_find_frame.restype = C.c_float
-    lib.fsk_find_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_uint,
-                                   C.c_uint, C.c_float, C.c_char_p,
-                                   C.POINTER(C.c_ulonglong), C.POINTER(C.c_float),
-                                   C.POINTER(C.c_uint)]
-    lib.fsk_detect_carrier.restype = C.c_int
-    lib.fsk_detect_carrier.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_float]
-    lib.fsk_set_tones_by_bandshift.argtypes = [C.c_void_p, C.c_uint, C.c_int]
-    lib.mifsk_tx_synthesize.restype = C.c_long
-    lib.mifsk_tx_synthesize.argtypes = [C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
-                                        C.c_uint, C.c_float, C.c_uint, C.c_int,
-                                        C.c_void_p, C.c_size_t]
-    lib.mifsk_databits_create.restype = C.c_int
-    lib.mifsk_databits_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    lib.mifsk_databits_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_databits_reset.argtypes = [C.c_void_p]
-    lib.mifsk_databits_decode.restype = C.c_uint
-    lib.mifsk_databits_decode.argtypes = [C.c_void_p, C.c_char_p, C.c_uint, C.c_ulonglong, C.c_uint]
-    lib.mifsk_stream_text.restype = C.c_int
-    lib.mifsk_stream_text.argtypes = [C.POINTER(RxConfig), C.c_void_p, C.c_uint32, C.c_void_p,
-                                      C.c_uint32, C.c_uint, C.c_char_p, C.c_size_t,
-                                      C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t,
-                                      C.POINTER(C.c_size_t)]
-    lib.mifsk_wav_parse.restype = C.c_int
-    lib.mifsk_wav_parse.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(WavInfo)]
-    lib.mifsk_ingest_s16.restype = C.c_int
-    lib.mifsk_ingest_s16.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                     C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_void_p]
-    lib.mifsk_ingest_rxnoise_f32.restype = C.c_int
-    lib.mifsk_ingest_rxnoise_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
-                                             C.c_uint32, C.c_int, C.c_float, C.c_void_p]
-    lib.mifsk_tx_synthesize_batch.restype = C.c_int
-    lib.mifsk_tx_synthesize_batch.argtypes = [
-        C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int,
-        C.c_uint, C.c_float, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
-        C.c_void_p]
-    lib.mifsk_demod_plan.restype = C.c_int
-    lib.mifsk_demod_plan.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_int, C.c_uint,
-                                     C.POINTER(LaunchInfo)]
-    lib.mifsk_demod_plan_ex.restype = C.c_int
-    lib.mifsk_demod_plan_ex.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_int, C.c_uint32, C.c_uint,
-                                        C.POINTER(LaunchInfo)]
-    lib.mifsk_demod_batch_host_multi.restype = C.c_int
-    lib.mifsk_demod_batch_host_multi.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(RxConfig),
-                                                 C.POINTER(DemodIO)]
-    lib.mifsk_databits_encode.restype = C.c_uint
-    lib.mifsk_databits_encode.argtypes = [C.c_void_p, C.POINTER(C.c_uint), C.c_char]
-    lib.mifsk_shard_range.restype = None
-    lib.mifsk_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.mifsk_demod_batch_host_ex.restype = C.c_int
-    lib.mifsk_demod_batch_host_ex.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO),
-                                              C.c_float, C.POINTER(HostStats)]
-    lib.mifsk_host_alloc.restype = C.c_void_p
-    lib.mifsk_host_alloc.argtypes = [C.c_size_t]
-    lib.mifsk_host_free.restype = None
-    lib.mifsk_host_free.argtypes = [C.c_void_p]
-    lib.mifsk_max_episodes.restype = C.c_size_t
-    lib.mifsk_max_episodes.argtypes = [C.POINTER(RxConfig), C.c_size_t]
-    lib.mifsk_demod_files.restype = C.c_int
-    lib.mifsk_demod_files.argtypes = [C.c_void_p, C.POINTER(ModemArgs), C.POINTER(C.c_char_p), C.c_int,
-                                      C.c_float, C.c_uint, C.POINTER(C.c_void_p)]
-    lib.mifsk_files_count.restype = C.c_int
-    lib.mifsk_files_count.argtypes = [C.c_void_p]
-    lib.mifsk_files_get.restype = C.POINTER(FileResult)
-    lib.mifsk_files_get.argtypes = [C.c_void_p, C.c_int]
-    lib.mifsk_files_stats.restype = C.POINTER(HostStats)
-    lib.mifsk_files_stats.argtypes = [C.c_void_p]
-    lib.mifsk_files_free.restype = None
-    lib.mifsk_files_free.argtypes = [C.c_void_p]
-    lib.mifsk_scan_plan_get.restype = C.c_int
-    lib.mifsk_scan_plan_get.argtypes = [C.POINTER(RxConfig), C.c_int, C.POINTER(ScanPlan)]
-    lib.mifsk_demod_slab.restype = C.c_int
-    lib.mifsk_demod_slab.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO), C.c_void_p,
-                                     C.c_void_p, C.c_int, C.c_void_p]
-    lib.mifsk_demod_slab_ring.restype = C.c_int
-    lib.mifsk_demod_slab_ring.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO), C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.mifsk_ring_floats.restype = C.c_size_t
-    lib.mifsk_ring_floats.argtypes = [C.POINTER(RxConfig)]
-    lib.mifsk_pipeline_create.restype = C.c_int
-    lib.mifsk_pipeline_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int]
-    lib.mifsk_pipeline_destroy.restype = None
-    lib.mifsk_pipeline_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_pipeline_info_get.restype = C.c_int
-    lib.mifsk_pipeline_info_get.argtypes = [C.c_void_p, C.POINTER(PipelineInfo)]
-    lib.mifsk_pipeline_outputs_alloc.restype = C.c_int
-    lib.mifsk_pipeline_outputs_alloc.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_uint]
-    lib.mifsk_pipeline_outputs_get.restype = C.c_int
-    lib.mifsk_pipeline_outputs_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(DemodIO)]
-    lib.mifsk_pipeline_submit.restype = C.c_int
-    lib.mifsk_pipeline_submit.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(DemodIO), C.c_void_p,
-                                          C.POINTER(C.c_uint64)]
-    lib.mifsk_pipeline_next_ticket.restype = C.c_uint64
-    lib.mifsk_pipeline_next_ticket.argtypes = [C.c_void_p]
-    lib.mifsk_pipeline_wait.restype = C.c_int
-    lib.mifsk_pipeline_wait.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mifsk_pipeline_join.restype = C.c_int
-    lib.mifsk_pipeline_join.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.mifsk_pipeline_drain.restype = C.c_int
-    lib.mifsk_pipeline_drain.argtypes = [C.c_void_p]
-    lib.mifsk_pipeline_stream.restype = C.c_void_p
-    lib.mifsk_pipeline_stream.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mifsk_pipeline_ctx.restype = C.c_void_p
-    lib.mifsk_pipeline_ctx.argtypes = [C.c_void_p, C.c_uint64]
-    lib.mifsk_gather_unique_id.restype = C.c_int
-    lib.mifsk_gather_unique_id.argtypes = [C.c_void_p]
-    lib.mifsk_gather_create.restype = C.c_int
-    lib.mifsk_gather_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]
-    lib.mifsk_gather_destroy.restype = None
-    lib.mifsk_gather_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_gather_info_get.restype = C.c_int
-    lib.mifsk_gather_info_get.argtypes = [C.c_void_p, C.POINTER(GatherInfo)]
-    lib.mifsk_gather_start.restype = C.c_int
-    lib.mifsk_gather_start.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
-                                       C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.mifsk_gather_received.restype = C.c_int
-    lib.mifsk_gather_received.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p),
-                                          C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.mifsk_session_create.restype = C.c_int
-    lib.mifsk_session_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(RxConfig), C.c_int, C.c_uint]
-    lib.mifsk_session_destroy.restype = None
-    lib.mifsk_session_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_session_feed.restype = C.c_int
-    lib.mifsk_session_feed.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_int]
-    lib.mifsk_session_get.restype = C.POINTER(SessionResult)
-    lib.mifsk_session_get.argtypes = [C.c_void_p, C.c_int]
-    lib.mifsk_session_pending.restype = C.c_size_t
-    lib.mifsk_session_pending.argtypes = [C.c_void_p, C.c_int]
-    lib.mifsk_session_feed_ex.restype = C.c_int
-    lib.mifsk_session_feed_ex.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_uint,
-                                          C.c_float, C.c_int]
-    lib.mifsk_session_feed_device.restype = C.c_int
-    lib.mifsk_session_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint,
-                                              C.c_float, C.c_int, C.c_void_p]
-    lib.mifsk_session_info_get.restype = C.c_int
-    lib.mifsk_session_info_get.argtypes = [C.c_void_p, C.POINTER(SessionInfo)]
-    lib.mifsk_selftest_sqrt.restype = C.c_int
-    lib.mifsk_selftest_sqrt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
-    lib.mifsk_selftest_rcp.restype = C.c_int
-    lib.mifsk_selftest_rcp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mifsk_selftest_mag.restype = C.c_int
-    lib.mifsk_selftest_mag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_uint64,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mifsk_selftest_confidence.restype = C.c_int
-    lib.mifsk_selftest_confidence.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64,
-                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                              C.c_void_p, C.c_void_p]
-    lib.mifsk_selftest_corr.restype = C.c_int
-    lib.mifsk_selftest_corr.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_int, C.c_int, C.c_void_p, C.c_uint32,
-                                        C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.mifsk_selftest_scan.restype = C.c_int
-    lib.mifsk_selftest_scan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-    lib.mifsk_selftest_wave_max.restype = C.c_int
-    lib.mifsk_selftest_wave_max.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.mifsk_time_split_plan_get.restype = C.c_int
-    lib.mifsk_time_split_plan_get.argtypes = [C.POINTER(RxConfig), C.c_uint64, C.POINTER(TimeSplit),
-                                              C.POINTER(TimeSplitStats)]
-    lib.mifsk_demod_long.restype = C.c_int
-    lib.mifsk_demod_long.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_uint64,
-                                     C.POINTER(TimeSplit), C.POINTER(DemodIO), C.POINTER(TimeSplitStats),
-                                     C.c_void_p]
-    lib.mifsk_time_split_plan_batch_get.restype = C.c_int
-    lib.mifsk_time_split_plan_batch_get.argtypes = [C.POINTER(RxConfig), C.POINTER(C.c_uint64), C.c_int,
-                                                    C.POINTER(TimeSplit), C.POINTER(TimeSplitStats)]
-    lib.mifsk_demod_long_batch.restype = C.c_int
-    lib.mifsk_demod_long_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
-                                           C.POINTER(C.c_uint64), C.c_int, C.POINTER(TimeSplit),
-                                           C.POINTER(DemodIO), C.POINTER(TimeSplitStats), C.c_void_p]
-    lib.mifsk_demod_long_batch_s16.restype = C.c_int
-    lib.mifsk_demod_long_batch_s16.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.c_void_p, C.c_size_t,
-                                               C.POINTER(C.c_uint64), C.c_int, C.c_float, C.POINTER(TimeSplit),
-                                               C.POINTER(DemodIO), C.POINTER(TimeSplitStats), C.c_void_p]
-    lib.mifsk_demod_long_batch_host.restype = C.c_int
-    lib.mifsk_demod_long_batch_host.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(C.c_void_p),
-                                                C.POINTER(C.c_uint64), C.c_int, C.c_uint, C.c_float,
-                                                C.POINTER(TimeSplit), C.POINTER(DemodIO),
-                                                C.POINTER(TimeSplitStats), C.POINTER(HostStats)]
-    lib.mifsk_demod_files_long.restype = C.c_int
-    lib.mifsk_demod_files_long.argtypes = [C.c_void_p, C.POINTER(ModemArgs), C.POINTER(C.c_char_p), C.c_int,
-                                           C.c_float, C.c_uint, C.POINTER(TimeSplit), C.POINTER(C.c_void_p)]
-    lib.mifsk_files_time_split.restype = C.POINTER(TimeSplitStats)
-    lib.mifsk_files_time_split.argtypes = [C.c_void_p, C.c_int]
-    lib.mifsk_frame_softbits.restype = C.c_int
-    lib.mifsk_frame_softbits.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(SoftbitsIO), C.c_void_p]
-    lib.mifsk_detect_carrier_batch.restype = C.c_int
-    lib.mifsk_detect_carrier_batch.argtypes = [C.c_void_p, C.POINTER(RxConfig), C.POINTER(CarrierIO), C.c_void_p]
-    lib.mifsk_carrier_windows.restype = C.c_uint64
-    lib.mifsk_carrier_windows.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.mifsk_carrier_tones.restype = C.c_int
-    lib.mifsk_carrier_tones.argtypes = [C.POINTER(RxConfig), C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
-                                        C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    lib.mifsk_channel_plan_create.restype = C.c_int
-    lib.mifsk_channel_plan_create.argtypes = [C.c_void_p, C.POINTER(ChannelParams), C.POINTER(C.c_void_p)]
-    lib.mifsk_channel_plan_destroy.restype = None
-    lib.mifsk_channel_plan_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_channelize_batch.restype = C.c_int
-    lib.mifsk_channelize_batch.argtypes = [C.c_void_p, C.POINTER(ChannelIO), C.c_void_p]
-    lib.mifsk_channel_table.restype = C.c_int
-    lib.mifsk_channel_table.argtypes = [C.POINTER(ChannelParams), C.c_uint32, C.c_void_p]
-    lib.mifsk_channel_taps.restype = C.c_int
-    lib.mifsk_channel_taps.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p]
-    lib.mifsk_mux_plan_create.restype = C.c_int
-    lib.mifsk_mux_plan_create.argtypes = [C.c_void_p, C.POINTER(MuxParams), C.POINTER(C.c_void_p)]
-    lib.mifsk_mux_plan_destroy.restype = None
-    lib.mifsk_mux_plan_destroy.argtypes = [C.c_void_p]
-    lib.mifsk_multiplex_batch.restype = C.c_int
-    lib.mifsk_multiplex_batch.argtypes = [C.c_void_p, C.POINTER(MuxIO), C.c_void_p]
-    lib.mifsk_mux_table.restype = C.c_int
-    lib.mifsk_mux_table.argtypes = [C.POINTER(MuxParams), C.c_void_p]
-    lib.mifsk_impair_batch.restype = C.c_int
-    lib.mifsk_impair_batch.argtypes = [C.c_void_p, C.POINTER(ImpairIO), C.c_void_p]
-    lib.mifsk_impair_sigma.restype = C.c_float
-    lib.mifsk_impair_sigma.argtypes = [C.c_float, C.c_double]
-    lib.mifsk_selftest_gauss.restype = C.c_int
-    lib.mifsk_selftest_gauss.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    lib.mifsk_fm_demod_batch.restype = C.c_int
-    lib.mifsk_fm_demod_batch.argtypes = [C.c_void_p, C.POINTER(FmDemodIO), C.c_void_p]
-    lib.mifsk_fm_modulate_batch.restype = C.c_int
-    lib.mifsk_fm_modulate_batch.argtypes = [C.c_void_p, C.POINTER(FmModIO), C.c_void_p]
-    lib.mifsk_fm_gain.restype = C.c_float
-    lib.mifsk_fm_gain.argtypes = [C.c_double, C.c_double]
-    lib.mifsk_fm_step.restype = C.c_double
-    lib.mifsk_fm_step.argtypes = [C.c_double, C.c_double]
-    lib.mifsk_selftest_turn.restype = C.c_int
-    lib.mifsk_selftest_turn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib

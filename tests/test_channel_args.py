@@ -1,11 +1,9 @@
-"""The channelizer (include/mifsk.h, minimodem_amd/csrc/mifsk_channel.hip) without a device: the ABI,
+"""The channelizer (include/mifsk.h, minimodem_amd/csrc/mifsk_channel.hip) without a device:
 what mifsk_channel_plan_create and mifsk_channelize_batch refuse before any HIP call (the context is
 a block of zeroed host memory, the device pointers are numbers), the two host helpers, the host
 restatement tools/channel_ref.c against a float64 evaluation of the definition, and the condition
 the GPU test's end-to-end cases rely on: the restatement's rows decode through the oracle."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,49 +11,15 @@ import pytest
 import _channel as Ch
 import _oracle as O
 import minimodem_amd as M
+from _abi import EINVAL, fake_ctx, lib  # noqa: F401
 from minimodem_amd import _lib
 
-EINVAL = -22
 F32 = np.float32
 
 
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def fake_ctx():
-    buf = C.create_string_buffer(1 << 16)
-    return C.cast(buf, C.c_void_p), buf
-
-
-def test_the_symbols_resolve_the_abi_version_stays_8_and_the_mirrors_fit(lib):
-    assert lib.mifsk_abi_version() == 8
-    for name in ("mifsk_channel_plan_create", "mifsk_channel_plan_destroy", "mifsk_channelize_batch",
-                 "mifsk_channel_table", "mifsk_channel_taps"):
-        assert hasattr(lib, name) and name in _lib.EXPORTS, name
-    assert lib.mifsk_abi_sizeof(b"mifsk_channel_params") == C.sizeof(_lib.ChannelParams) == 48
-    assert lib.mifsk_abi_sizeof(b"mifsk_channel_io") == C.sizeof(_lib.ChannelIO) == 64
-    assert _lib.CHANNEL_COMPLEX == 1 and (_lib.FEED_F32, _lib.FEED_S16) == (0, 1)
-    # no struct beside them moved
-    for name, t, size in (("mifsk_demod_io", _lib.DemodIO, None), ("mifsk_softbits_io", _lib.SoftbitsIO, 88),
-                          ("mifsk_carrier_io", _lib.CarrierIO, 88), ("mifsk_session_info", _lib.SessionInfo, 56)):
-        assert lib.mifsk_abi_sizeof(name.encode()) == C.sizeof(t), name
-        assert size is None or C.sizeof(t) == size, name
+def test_the_python_names_are_public():
     for name in ("channel_taps", "ChannelPlan", "channelize"):
         assert name in M.__all__ and callable(getattr(M, name)), name
-
-
-def test_the_header_declares_the_structs_in_the_mirrors_order():
-    text = open(os.path.join(Ch.ROOT, "include", "mifsk.h")).read()
-    for name, mirror in (("mifsk_channel_params", _lib.ChannelParams), ("mifsk_channel_io", _lib.ChannelIO)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        assert re.findall(r"\**(\w+)\s*;", body) == [f[0] for f in mirror._fields_], name
-    assert re.search(r"#define\s+MIFSK_CHANNEL_COMPLEX\s+1u", text)
-    assert re.search(r"#define\s+MIFSK_ABI_VERSION\s+8\b", text)
-    assert sorted(re.findall(r"#define\s+(MIFSK_FEED_\w+)", text)) == ["MIFSK_FEED_F32", "MIFSK_FEED_S16"]
 
 
 def _params(keep, **kw):

@@ -1,70 +1,22 @@
-"""mifsk_fm_demod_batch, mifsk_fm_modulate_batch and their host helpers (include/mifsk.h): the ABI, and what
+"""mifsk_fm_demod_batch, mifsk_fm_modulate_batch and their host helpers (include/mifsk.h): what
 the entries refuse -- before any HIP call, so every code below comes back on a machine without a device:
 the context is a block of zeroed host memory and the device pointers are numbers."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
-import pytest
 
 import minimodem_amd as M
 from minimodem_amd import _lib
 
 import _fm as Fm
-
-EINVAL = -22
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
+from _abi import BASE, EINVAL, fake_ctx, ladder, lib  # noqa: F401
 
 
-@pytest.fixture(scope="module")
-def fake_ctx():
-    buf = C.create_string_buffer(1 << 16)
-    return C.cast(buf, C.c_void_p), buf
-
-
-def test_the_symbols_resolve_the_abi_version_stays_8_and_the_mirrors_fit(lib):
-    assert lib.mifsk_abi_version() == 8
-    for name in ("mifsk_fm_demod_batch", "mifsk_fm_modulate_batch", "mifsk_fm_gain", "mifsk_fm_step",
-                 "mifsk_selftest_turn"):
-        assert hasattr(lib, name) and name in _lib.EXPORTS, name
-    assert lib.mifsk_abi_sizeof(b"mifsk_fm_demod_io") == C.sizeof(_lib.FmDemodIO) == 80
-    assert lib.mifsk_abi_sizeof(b"mifsk_fm_mod_io") == C.sizeof(_lib.FmModIO) == 96
-    t = _lib.FmDemodIO
-    assert (t.kind.offset, t.flags.offset, t.d_out.offset, t.out_stride.offset) == (32, 36, 40, 48)
-    assert (t.d_prev.offset, t.d_last.offset, t.gain.offset, t.reserved.offset) == (56, 64, 72, 76)
-    t = _lib.FmModIO
-    assert (t.out_kind.offset, t.flags.offset, t.d_out.offset, t.out_stride.offset) == (32, 36, 40, 48)
-    assert (t.deviation.offset, t.centre.offset, t.d_phase0.offset, t.d_phase_out.offset) == (56, 64, 72, 80)
-    assert (t.amplitude.offset, t.reserved.offset) == (88, 92)
-    assert (_lib.FEED_F32, _lib.FEED_S16) == (Fm.F32K, Fm.S16K) == (0, 1)
-    # no struct beside them moved
-    for name, t, size in (("mifsk_impair_io", _lib.ImpairIO, 120), ("mifsk_mux_io", _lib.MuxIO, 64),
-                          ("mifsk_channel_io", _lib.ChannelIO, 64), ("mifsk_demod_io", _lib.DemodIO, None)):
-        assert lib.mifsk_abi_sizeof(name.encode()) == C.sizeof(t), name
-        assert size is None or C.sizeof(t) == size, name
+def test_the_python_names_are_public_and_the_kinds_are_the_restatements():
+    assert (_lib.FEED_F32, _lib.FEED_S16) == (Fm.F32K, Fm.S16K)
     for name in ("FmDemodIO", "FmModIO", "fm_demod", "fm_modulate", "fm_gain", "fm_step"):
         assert name in M.__all__ and hasattr(M, name), name
     assert M.FmDemodIO is _lib.FmDemodIO and M.FmModIO is _lib.FmModIO and hasattr(M.Context, "selftest_turn")
-
-
-def test_the_header_declares_the_structs_in_the_mirrors_order():
-    text = open(os.path.join(Fm.ROOT, "include", "mifsk.h")).read()
-    for name, mirror in (("mifsk_fm_demod_io", _lib.FmDemodIO), ("mifsk_fm_mod_io", _lib.FmModIO)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        assert re.findall(r"\**(\w+)\s*[;,]", body) == [f[0] for f in mirror._fields_], name
-    assert re.search(r"int\s+mifsk_fm_demod_batch\(", text) and re.search(r"int\s+mifsk_fm_modulate_batch\(", text)
-    assert re.search(r"float\s+mifsk_fm_gain\(", text) and re.search(r"double\s+mifsk_fm_step\(", text)
-    assert re.search(r"int\s+mifsk_selftest_turn\(", text)
-    assert re.search(r"#define\s+MIFSK_ABI_VERSION\s+8\b", text)
-
-
-BASE = 1 << 20                                      # 16-byte aligned; never dereferenced
 
 
 def _demod_io(**kw):
@@ -87,16 +39,6 @@ def _mod_io(**kw):
     for k, v in kw.items():
         setattr(io, k, v)
     return io
-
-
-def _ladder(rc, late, order):
-    """the earlier checks win over the later ones: with `late` as the one late violation, each earlier one
-    alone still refuses, and so does every pair in the stated order"""
-    for i, early in enumerate(order):
-        assert rc(**dict(late, **early)) == EINVAL, early
-        for later in order[i + 1:]:
-            assert rc(**dict(late, **dict(later, **early))) == EINVAL, (early, later)
-    assert rc(ctx=None, **late) == EINVAL
 
 
 def test_the_discriminators_argument_checks_come_back_without_a_device(lib, fake_ctx):
@@ -128,9 +70,9 @@ def test_the_discriminators_argument_checks_come_back_without_a_device(lib, fake
     assert rc(out_stride=96002) == EINVAL and rc(out_stride=95999) == EINVAL
     assert rc(out_stride=(1 << 32) - 4) == EINVAL and rc(out_stride=1 << 32) == EINVAL
     assert rc(out_stride=1 << 40) == EINVAL
-    _ladder(rc, dict(out_stride=96002),
-            [dict(d_samples=None), dict(nstreams=0), dict(kind=9), dict(flags=2), dict(d_samples=BASE + 8),
-             dict(stream_stride=96001), dict(d_out=BASE + 4)])
+    ladder(rc, dict(out_stride=96002),
+           [dict(d_samples=None), dict(nstreams=0), dict(kind=9), dict(flags=2), dict(d_samples=BASE + 8),
+            dict(stream_stride=96001), dict(d_out=BASE + 4)])
     # gain, d_prev and d_last are data and not among the checks
     for v in (0.0, -1.0, float("inf"), float("nan")):
         assert rc(out_stride=96002, gain=v) == EINVAL
@@ -163,9 +105,9 @@ def test_the_modulators_argument_checks_come_back_without_a_device(lib, fake_ctx
     assert rc(out_stride=96001) == EINVAL and rc(out_kind=_lib.FEED_S16, out_stride=96002) == EINVAL
     assert rc(out_stride=(1 << 32) - 6) == EINVAL and rc(out_stride=1 << 32) == EINVAL
     assert rc(out_stride=1 << 40) == EINVAL
-    _ladder(rc, dict(out_stride=96001),
-            [dict(d_out=None), dict(nstreams=0), dict(out_kind=9), dict(flags=2), dict(d_samples=BASE + 8),
-             dict(stream_stride=96002), dict(d_out=BASE + 4)])
+    ladder(rc, dict(out_stride=96001),
+           [dict(d_out=None), dict(nstreams=0), dict(out_kind=9), dict(flags=2), dict(d_samples=BASE + 8),
+            dict(stream_stride=96002), dict(d_out=BASE + 4)])
     # deviation, centre, amplitude and the phase arrays are data and not among the checks
     for v in (0.0, -1.0, float("inf"), float("nan"), 1e30):
         for name in ("deviation", "centre", "amplitude"):

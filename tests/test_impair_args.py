@@ -1,64 +1,22 @@
-"""mifsk_impair_batch and its host helper (include/mifsk.h): the ABI, and what the entry refuses --
+"""mifsk_impair_batch and its host helper (include/mifsk.h): what the entry refuses --
 before any HIP call, so every code below comes back on a machine without a device: the context is a
 block of zeroed host memory and the device pointers are numbers."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
-import pytest
 
 import minimodem_amd as M
 from minimodem_amd import _lib
 
 import _impair as Im
-
-EINVAL = -22
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
+from _abi import BASE, EINVAL, fake_ctx, ladder, lib  # noqa: F401
 
 
-@pytest.fixture(scope="module")
-def fake_ctx():
-    buf = C.create_string_buffer(1 << 16)
-    return C.cast(buf, C.c_void_p), buf
-
-
-def test_the_symbols_resolve_the_abi_version_stays_8_and_the_mirror_fits(lib):
-    assert lib.mifsk_abi_version() == 8
-    for name in ("mifsk_impair_batch", "mifsk_impair_sigma", "mifsk_selftest_gauss"):
-        assert hasattr(lib, name) and name in _lib.EXPORTS, name
-    assert lib.mifsk_abi_sizeof(b"mifsk_impair_io") == C.sizeof(_lib.ImpairIO) == 120
-    t = _lib.ImpairIO
-    assert (t.kind.offset, t.out_kind.offset, t.d_out.offset, t.seed.offset, t.first_sample.offset) == (32, 36, 40, 56, 72)
-    assert (t.d_gain.offset, t.gain.offset, t.flags.offset) == (80, 104, 116)
-    assert (_lib.FEED_F32, _lib.FEED_S16) == (Im.F32K, Im.S16K) == (0, 1)
-    # no struct beside it moved
-    for name, t, size in (("mifsk_mux_params", _lib.MuxParams, 56), ("mifsk_mux_io", _lib.MuxIO, 64),
-                          ("mifsk_channel_params", _lib.ChannelParams, 48), ("mifsk_channel_io", _lib.ChannelIO, 64),
-                          ("mifsk_softbits_io", _lib.SoftbitsIO, 88), ("mifsk_carrier_io", _lib.CarrierIO, 88),
-                          ("mifsk_session_info", _lib.SessionInfo, 56), ("mifsk_demod_io", _lib.DemodIO, None)):
-        assert lib.mifsk_abi_sizeof(name.encode()) == C.sizeof(t), name
-        assert size is None or C.sizeof(t) == size, name
+def test_the_python_names_are_public_and_the_kinds_are_the_restatements():
+    assert (_lib.FEED_F32, _lib.FEED_S16) == (Im.F32K, Im.S16K)
     for name in ("ImpairIO", "impair", "snr_sigma"):
         assert name in M.__all__ and hasattr(M, name), name
     assert M.ImpairIO is _lib.ImpairIO
-
-
-def test_the_header_declares_the_struct_in_the_mirrors_order():
-    text = open(os.path.join(Im.ROOT, "include", "mifsk.h")).read()
-    body = re.search(r"typedef struct mifsk_impair_io \{(.*?)\} mifsk_impair_io;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    assert re.findall(r"\**(\w+)\s*[;,]", body) == [f[0] for f in _lib.ImpairIO._fields_]
-    assert re.search(r"int\s+mifsk_impair_batch\(", text) and re.search(r"float\s+mifsk_impair_sigma\(", text)
-    assert re.search(r"int\s+mifsk_selftest_gauss\(", text)
-    assert re.search(r"#define\s+MIFSK_ABI_VERSION\s+8\b", text)
-
-
-BASE = 1 << 20                                      # 16-byte aligned; never dereferenced
 
 
 def _io(**kw):
@@ -107,14 +65,9 @@ def test_argument_checks_come_back_without_a_device(lib, fake_ctx):
     assert rc(d_samples=None, stream_stride=3, d_out=BASE + 4) == EINVAL
     # the earlier checks win over the later ones: with the output stride as the one late violation,
     # each earlier one alone still refuses, and so does every pair in the stated order
-    late = dict(out_stride=96002)
-    order = [dict(d_out=None), dict(nstreams=0), dict(out_kind=9), dict(flags=2), dict(first_sample=2),
-             dict(stream_stride=96001)]
-    for i, early in enumerate(order):
-        assert rc(**dict(late, **early)) == EINVAL, early
-        for later in order[i + 1:]:
-            assert rc(**dict(late, **dict(later, **early))) == EINVAL, (early, later)
-    assert rc(ctx=None, **late) == EINVAL
+    ladder(rc, dict(out_stride=96002),
+           [dict(d_out=None), dict(nstreams=0), dict(out_kind=9), dict(flags=2), dict(first_sample=2),
+            dict(stream_stride=96001)])
 
 
 def test_parameters_are_data_and_not_among_the_checks(lib, fake_ctx):

@@ -2,51 +2,16 @@
 code below comes back on a machine without a device.  The context is a block of zeroed host
 memory and the device pointers are numbers: nothing looks into either before the call is refused."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
 import minimodem_amd as M
+from _abi import EINVAL, ENOTSUP, fake_ctx, lib  # noqa: F401
 from minimodem_amd import _lib
 
-EINVAL, ENOTSUP = -22, -95
 
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def fake_ctx():
-    buf = C.create_string_buffer(1 << 16)
-    return C.cast(buf, C.c_void_p), buf
-
-
-def test_the_symbol_resolves_the_abi_version_stays_8_and_the_mirror_fits(lib):
-    assert lib.mifsk_abi_version() == 8
-    assert hasattr(lib, "mifsk_frame_softbits") and "mifsk_frame_softbits" in _lib.EXPORTS
-    assert lib.mifsk_abi_sizeof(b"mifsk_softbits_io") == C.sizeof(_lib.SoftbitsIO) == 88
-    names = [f[0] for f in _lib.SoftbitsIO._fields_]
-    assert names == ["d_samples", "stream_stride", "d_nsamples", "nsamples", "nstreams", "kind", "rxnoise",
-                     "d_origin", "d_frames", "d_nframes", "frames_cap", "d_mag", "d_rawbits"]
-    assert _lib.SoftbitsIO.kind.offset == 32 and _lib.SoftbitsIO.d_origin.offset == 40
-    # no struct beside it moved
-    for name, t in (("mifsk_demod_io", _lib.DemodIO), ("mifsk_session_info", _lib.SessionInfo),
-                    ("mifsk_time_split", _lib.TimeSplit)):
-        assert lib.mifsk_abi_sizeof(name.encode()) == C.sizeof(t), name
-    assert "frame_softbits" in M.__all__
-
-
-def test_the_header_declares_the_struct_in_the_mirrors_order():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "mifsk.h")).read()
-    body = re.search(r"typedef struct mifsk_softbits_io \{(.*?)\} mifsk_softbits_io;", text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = re.findall(r"\**(\w+)\s*;", body)
-    assert fields == [f[0] for f in _lib.SoftbitsIO._fields_]
-    assert re.search(r"int\s+mifsk_frame_softbits\(", text)
+def test_the_python_name_is_public():
+    assert "frame_softbits" in M.__all__ and callable(M.frame_softbits)
 
 
 def _io(**kw):

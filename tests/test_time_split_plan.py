@@ -77,13 +77,6 @@ def test_invalid_parameters():
         M.time_split_plan(cfg, n, chunk=lat + 4)
 
 
-def test_abi_sizeof_of_the_new_structs():
-    lib = _lib.load()
-    assert lib.mifsk_abi_sizeof(b"mifsk_time_split") == C.sizeof(_lib.TimeSplit) == 24
-    assert lib.mifsk_abi_sizeof(b"mifsk_time_split_stats") == C.sizeof(_lib.TimeSplitStats) == 64
-    assert lib.mifsk_abi_version() == 8
-
-
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 _LONG_PLANS = r"""

@@ -8,39 +8,14 @@ import ctypes as C
 import pytest
 
 import minimodem_amd as M
+from _abi import EINVAL, ENOTSUP, fake_ctx, lib  # noqa: F401
 from minimodem_amd import _lib
-
-EINVAL, ENOTSUP = -22, -95
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib.load()
-
-
-@pytest.fixture(scope="module")
-def fake_ctx():
-    buf = C.create_string_buffer(1 << 16)
-    return C.cast(buf, C.c_void_p), buf
 
 
 def _params(flags=0, chunk=0, warmup=0):
     p = _lib.TimeSplit()
     p.chunk, p.warmup, p.flags = chunk, warmup, flags
     return p
-
-
-def test_abi_version_stays_8_and_the_new_symbols_resolve(lib):
-    assert lib.mifsk_abi_version() == 8
-    for name in ("mifsk_demod_long_batch_s16", "mifsk_demod_long_batch_host", "mifsk_demod_files_long",
-                 "mifsk_files_time_split"):
-        assert hasattr(lib, name), name
-        assert name in _lib.EXPORTS
-    # no public struct changed size
-    for name, t in (("mifsk_demod_io", _lib.DemodIO), ("mifsk_time_split", _lib.TimeSplit),
-                    ("mifsk_time_split_stats", _lib.TimeSplitStats), ("mifsk_host_stats", _lib.HostStats)):
-        n = lib.mifsk_abi_sizeof(name.encode())
-        assert n in (0, C.sizeof(t)), (name, n)
 
 
 def test_pcm16_entry_argument_checks_in_order(lib, fake_ctx):
