@@ -321,7 +321,7 @@ struct WaveAuto {
 // empty.  Cut in time instead -- G groups of streams x K chunks of every stream, each (group,
 // chunk) one launch of the resumable kernel, a group's chunks in order on the group's own HIP
 // stream -- the dispatcher fills those slots with the other groups' next chunk, and the idle
-// tail shrinks to that of one chunk.  The context owns what this needs (mifsk_capi.cpp).
+// tail shrinks to that of one chunk.  The context owns what this needs (mifsk_ctx.cpp).
 struct WaveChain {
     enum { kMaxGroups = 3 };
     void		*streams[kMaxGroups];	// hipStream_t, non-blocking
@@ -424,7 +424,7 @@ int launch_detect_carrier( const float *d_samples, unsigned nsamples,
 // self-test of the short square root of band_mag2() (mifsk_kernels.hip); d_out: four counters
 int launch_selftest_sqrt( uint64_t seed, uint32_t blocks, uint32_t per_thread, unsigned long long *d_out, void *stream );
 
-// the HIP device a context is bound to (mifsk_capi.cpp)
+// the HIP device a context is bound to (mifsk_ctx.cpp)
 int ctx_device( const mifsk_ctx *ctx );
 
 // What --Xrxnoise really adds to every sample: (0 - 0.5f) * (factor * 2), in float as at

@@ -1,9 +1,12 @@
-// mifsk_hostmem.h -- who owns a device or page-locked allocation on the host side of libmifsk.so.
+// mifsk_hostmem.h -- who owns a device resource on the host side of libmifsk.so.
 //
-// Three move-only owners, each with a destructor that frees: DevMem<T> (hipMalloc), PinMem<T>
-// (hipHostMalloc) and StreamMem (hipMallocAsync, freed in the order of the stream it was made
-// for).  What is not here keeps its explicit frees on purpose: the context's cached tables, whose
-// lifetime the collector in mifsk_capi.cpp decides, and LegacyPlan.
+// Move-only owners, each with a destructor that gives back what it holds: DevMem<T> (hipMalloc),
+// PinMem<T> (hipHostMalloc), StreamMem (hipMallocAsync, freed in the order of the stream it was made
+// for), HipStream (a non-blocking stream, synchronised before it is destroyed) and HipEvent (an
+// event without timing).  Every allocation, stream and event the library keeps is a member of one
+// of these -- the context's cached tables and its chain, the host pipeline's work, a pipeline's
+// lanes, a session, the legacy plan -- so dropping the struct that holds it frees it, once.  The one
+// exception hands memory to the caller: mifsk_host_alloc / mifsk_host_free (mifsk_hostpipe.cpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -107,5 +110,52 @@ struct StreamMem {
 	return 0;
     }
 };
+
+// a stream or an event: make() keeps what is already held, so a creation that failed half-way
+// through a set of them is finished by calling make() on the whole set again
+struct StreamKind {
+    using handle = hipStream_t;
+    static hipError_t make( handle *h ) { return hipStreamCreateWithFlags(h, hipStreamNonBlocking); }
+    static void drop( handle h ) { (void)hipStreamSynchronize(h); (void)hipStreamDestroy(h); }
+};
+
+struct EventKind {
+    using handle = hipEvent_t;
+    static hipError_t make( handle *h ) { return hipEventCreateWithFlags(h, hipEventDisableTiming); }
+    static void drop( handle h ) { (void)hipEventDestroy(h); }
+};
+
+template <class Kind>
+struct OwnedHandle {
+    typename Kind::handle	h = nullptr;
+
+    OwnedHandle() = default;
+    OwnedHandle( OwnedHandle &&o ) noexcept : h(std::exchange(o.h, nullptr)) {}
+    OwnedHandle &operator=( OwnedHandle &&o ) noexcept
+    {
+	if ( this != &o ) {
+	    reset();
+	    h = std::exchange(o.h, nullptr);
+	}
+	return *this;
+    }
+    ~OwnedHandle() { reset(); }
+
+    void reset() { if ( h ) Kind::drop(h); h = nullptr; }
+    int make()
+    {
+	if ( h )
+	    return 0;
+	if ( Kind::make(&h) != hipSuccess ) {
+	    h = nullptr;
+	    return -EIO;
+	}
+	return 0;
+    }
+    operator typename Kind::handle() const { return h; }
+};
+
+using HipStream = OwnedHandle<StreamKind>;	// non-blocking; synchronised, then destroyed
+using HipEvent = OwnedHandle<EventKind>;	// timing disabled
 
 } // namespace mifsk

@@ -47,30 +47,6 @@ namespace mifsk {
 // wav header of a file of which only the first `have` bytes are in memory (mifsk_ingest.hip)
 int wav_parse_sized( const void *file, size_t have, size_t file_size, mifsk_wav_info *info );
 
-struct HostWork {
-    std::mutex	lock;			// one host call at a time per context
-    hipStream_t	s_in = nullptr, s_comp = nullptr, s_out = nullptr;
-    hipEvent_t	ev_in[2] = { nullptr, nullptr }, ev_comp[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
-    PinMem<uint8_t>	pin[2];		// staging for sources that are not page-locked
-    PinMem<uint32_t>	pin_n[2];	// per-chunk stream lengths
-    bool	ready = false;
-};
-
-void host_work_destroy( HostWork *w )
-{
-    if ( !w )
-	return;
-    for ( int i = 0; i < 2; i++ ) {
-	if ( w->ev_in[i] ) (void)hipEventDestroy(w->ev_in[i]);
-	if ( w->ev_comp[i] ) (void)hipEventDestroy(w->ev_comp[i]);
-	if ( w->ev_out[i] ) (void)hipEventDestroy(w->ev_out[i]);
-    }
-    if ( w->s_in ) (void)hipStreamDestroy(w->s_in);
-    if ( w->s_comp ) (void)hipStreamDestroy(w->s_comp);
-    if ( w->s_out ) (void)hipStreamDestroy(w->s_out);
-    delete w;
-}
-
 namespace {
 
 constexpr size_t kChunkBytes = 64u << 20;	// of input per chunk: ~1 ms of PCIe gen5 x16
@@ -84,31 +60,10 @@ int host_work_get( mifsk_ctx *ctx, HostWork **out )
 {
     std::lock_guard<std::mutex> g(ctx->lock);
     if ( !ctx->host )
-	ctx->host = new (std::nothrow) HostWork();
+	ctx->host.reset(new (std::nothrow) HostWork());
     if ( !ctx->host )
 	return -ENOMEM;
-    *out = ctx->host;
-    return 0;
-}
-
-// `overlapped`: the job has more than one chunk, i.e. something to overlap: the copy streams and
-// the events that order the three are made then.  A job of one chunk -- a file, a few files: the
-// reference's own use -- runs on s_comp alone (a stream costs ~10 ms to make: a third of what
-// such a call spent inside the library).
-int host_work_init( HostWork *w, bool overlapped )
-{
-    if ( w->ready || !overlapped )
-	return 0;
-    if ( !w->s_comp )
-	HIP_OK(hipStreamCreateWithFlags(&w->s_comp, hipStreamNonBlocking));
-    HIP_OK(hipStreamCreateWithFlags(&w->s_in, hipStreamNonBlocking));
-    HIP_OK(hipStreamCreateWithFlags(&w->s_out, hipStreamNonBlocking));
-    for ( int i = 0; i < 2; i++ ) {
-	HIP_OK(hipEventCreateWithFlags(&w->ev_in[i], hipEventDisableTiming));
-	HIP_OK(hipEventCreateWithFlags(&w->ev_comp[i], hipEventDisableTiming));
-	HIP_OK(hipEventCreateWithFlags(&w->ev_out[i], hipEventDisableTiming));
-    }
-    w->ready = true;
+    *out = ctx->host.get();
     return 0;
 }
 

@@ -31,9 +31,9 @@ namespace {
 
 struct Lane {
     mifsk_ctx	*ctx = nullptr;
-    hipStream_t	stream = nullptr;
-    hipEvent_t	done = nullptr;		// behind the last pass submitted on this lane
-    hipEvent_t	after = nullptr;	// the producer's stream at submit time
+    mifsk::HipStream	stream;
+    mifsk::HipEvent	done;		// behind the last pass submitted on this lane
+    mifsk::HipEvent	after;		// the producer's stream at submit time
     uint64_t	last = 0;		// ticket of that pass
     bool	used = false;
     mifsk::OutMirror	set;	// its output arrays (io.nstreams: the batch size they were made for)
@@ -56,12 +56,9 @@ extern "C" void mifsk_pipeline_destroy( mifsk_pipeline *p )
 	return;
     (void)hipSetDevice(p->device);
     for ( Lane &l : p->lanes ) {
-	if ( l.stream )
-	    (void)hipStreamSynchronize(l.stream);
+	// (in this order: the stream synchronised, then the output set, then the lane's context)
+	l.stream.reset();
 	l.set.reset();
-	if ( l.done ) (void)hipEventDestroy(l.done);
-	if ( l.after ) (void)hipEventDestroy(l.after);
-	if ( l.stream ) (void)hipStreamDestroy(l.stream);
 	if ( l.ctx ) mifsk_ctx_destroy(l.ctx);
     }
     delete p;
@@ -100,10 +97,7 @@ extern "C" int mifsk_pipeline_create( mifsk_pipeline **out, int device, int dept
 	if ( i == 0 )
 	    p->device = mifsk::ctx_device(l.ctx);
 	device = p->device;			// (device < 0: every lane on the one the first lane got)
-	if ( hipSetDevice(p->device) != hipSuccess
-		|| hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) != hipSuccess
-		|| hipEventCreateWithFlags(&l.done, hipEventDisableTiming) != hipSuccess
-		|| hipEventCreateWithFlags(&l.after, hipEventDisableTiming) != hipSuccess )
+	if ( hipSetDevice(p->device) != hipSuccess || l.stream.make() || l.done.make() || l.after.make() )
 	    rc = -EIO;
     }
     if ( rc != 0 ) {

@@ -74,7 +74,6 @@ struct mifsk_session {
     int			n;
     unsigned		flags = 0;
     bool		want_frames = false, ring = false, resident;
-    hipStream_t		stream = nullptr;
     // per stream: where what is held starts in the stream, how much is held, who is done
     mifsk::SessionBook	book;
     mifsk::FeedPlan	plan;				// (of the feed that runs)
@@ -104,7 +103,9 @@ struct mifsk_session {
     int				cur = 0;
     PinMem<uint8_t>		h_stage;		// a feed's table, then its new pieces
     DevMem<uint8_t>		d_stage;
-    hipEvent_t			ev_producer = nullptr;	// feed_device: the producer's stream at the call
+    mifsk::HipEvent		ev_producer;		// feed_device: the producer's stream at the call
+    // (the last member: synchronised and destroyed before any buffer above is freed)
+    mifsk::HipStream		stream;
 
     mifsk_session( int n_, bool resident_ )		// (may throw std::bad_alloc)
 	: n(n_), resident(resident_), book((size_t)n_, resident_ ? mifsk::kResidentPolicy : mifsk::kHostTailPolicy),
@@ -360,12 +361,7 @@ extern "C" void mifsk_session_destroy( mifsk_session *s )
 	return;
     if ( s->ctx )
 	(void)hipSetDevice(s->ctx->device);
-    if ( s->stream ) {
-	(void)hipStreamSynchronize(s->stream);
-	(void)hipStreamDestroy(s->stream);
-    }
-    if ( s->ev_producer ) (void)hipEventDestroy(s->ev_producer);
-    delete s;					// (its buffers free themselves)
+    delete s;					// (the stream first, then the buffers: they free themselves)
 }
 
 extern "C" int mifsk_session_create( mifsk_session **out, mifsk_ctx *ctx, const mifsk_rx_config *cfg,
@@ -399,7 +395,7 @@ extern "C" int mifsk_session_create( mifsk_session **out, mifsk_ctx *ctx, const 
     s->ring = ( flags & MIFSK_IO_RING_EXACT ) != 0;
     rc = -EIO;
     if ( hipSetDevice(ctx->device) == hipSuccess
-	    && hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) == hipSuccess ) {
+	    && s->stream.make() == 0 ) {
 	rc = s->d_state.fit((size_t)nstreams);
 	if ( rc == 0 && hipMemsetAsync(s->d_state.p, 0, (size_t)nstreams * sizeof(mifsk_stream_state), s->stream) != hipSuccess )
 	    rc = -EIO;				// (all zero: a new stream)
@@ -409,9 +405,8 @@ extern "C" int mifsk_session_create( mifsk_session **out, mifsk_ctx *ctx, const 
 	    if ( rc == 0 && hipMemsetAsync(s->d_ring.p, 0, nf * sizeof(float), s->stream) != hipSuccess )
 		rc = -EIO;
 	}
-	if ( rc == 0 && s->resident
-		&& hipEventCreateWithFlags(&s->ev_producer, hipEventDisableTiming) != hipSuccess )
-	    rc = -EIO;
+	if ( rc == 0 && s->resident )
+	    rc = s->ev_producer.make();
     }
     if ( rc != 0 ) {
 	mifsk_session_destroy(s);

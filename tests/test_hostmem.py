@@ -20,6 +20,7 @@ def checker(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("hostmem") / "hostmem_check")
     subprocess.run(["g++", "-std=c++17", "-g", "-D__HIP_PLATFORM_AMD__", "-I" + ROCM_INCLUDE,
                     "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "minimodem_amd", "csrc"),
+                    "-I" + os.path.join(ROOT, "tools"),         # (fake_hip.h: the runtime made of malloc())
                     "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     "-static-libasan", "-static-libubsan",     # (the runtimes in the program: nothing to load first)
                     "-o", exe,

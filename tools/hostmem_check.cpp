@@ -1,92 +1,19 @@
 // hostmem_check.cpp -- the host-side owners and the output table of libmifsk.so without a device:
 // minimodem_amd/csrc/mifsk_hostmem.h, mifsk_outputs.h and mifsk_gather_sets.h over a HIP made of
-// malloc(), whose N-th allocation can be made to fail.
+// malloc() (tools/fake_hip.h), whose N-th allocation can be made to fail.
 //
-//   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iminimodem_amd/csrc
+//   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iminimodem_amd/csrc -Itools
 //       -fsanitize=address,undefined -o hostmem_check tools/hostmem_check.cpp && ./hostmem_check
 //
 // A leak or a double free is the sanitizer's to report; what a scenario leaves allocated is also
 // counted here (g_live).  Exit status 0 and "hostmem_check: N checks, 0 failed" when all is well.
 // (tests/test_hostmem.py)
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <utility>
 
+#include "fake_hip.h"
 #include "mifsk_gather_sets.h"
 #include "mifsk_hostmem.h"
 #include "mifsk_outputs.h"
-
-// ---- the runtime: malloc, a count of what is held, and a countdown to the allocation that fails
-
-static long g_live = 0, g_allocs = 0, g_fail_at = 0;		// g_fail_at: 1-based, 0 = never
-static long g_syncs = 0;
-
-static hipError_t fake_alloc( void **p, size_t bytes )
-{
-    g_allocs++;
-    if ( g_allocs == g_fail_at ) {
-	*p = (void *)(uintptr_t)0xDEAD;			// (an owner must not keep what a failed call left)
-	return hipErrorOutOfMemory;
-    }
-    *p = std::malloc(bytes ? bytes : 1);
-    std::memset(*p, 0xA5, bytes);
-    g_live++;
-    return hipSuccess;
-}
-
-static hipError_t fake_free( void *p )
-{
-    if ( p ) {
-	g_live--;
-	std::free(p);
-    }
-    return hipSuccess;
-}
-
-hipError_t hipMalloc( void **p, size_t bytes ) { return fake_alloc(p, bytes); }
-hipError_t hipFree( void *p ) { return fake_free(p); }
-hipError_t hipHostMalloc( void **p, size_t bytes, unsigned ) { return fake_alloc(p, bytes); }
-hipError_t hipHostFree( void *p ) { return fake_free(p); }
-hipError_t hipMallocAsync( void **p, size_t bytes, hipStream_t ) { return fake_alloc(p, bytes); }
-hipError_t hipFreeAsync( void *p, hipStream_t ) { return fake_free(p); }
-hipError_t hipMemset( void *p, int v, size_t bytes ) { std::memset(p, v, bytes); return hipSuccess; }
-hipError_t hipMemcpyAsync( void *d, const void *s, size_t bytes, hipMemcpyKind, hipStream_t )
-{
-    std::memcpy(d, s, bytes);
-    return hipSuccess;
-}
-hipError_t hipStreamSynchronize( hipStream_t ) { g_syncs++; return hipSuccess; }
-hipError_t hipDeviceSynchronize() { g_syncs++; return hipSuccess; }
-const char *hipGetErrorString( hipError_t ) { return "error"; }
-
-static long g_checks = 0, g_failed = 0;
-
-#define CHECK(cond)	do { g_checks++; if ( !( cond ) ) { g_failed++; \
-	std::fprintf(stderr, "%s:%d: %s (fail_at %ld)\n", __FILE__, __LINE__, #cond, g_fail_at); } } while (0)
-
-// a scenario with allocation `fail_at` failing (0: none): returns how many allocations it made
-template <class F>
-static long run( long fail_at, F scenario )
-{
-    g_allocs = 0;
-    g_fail_at = fail_at;
-    scenario();
-    g_fail_at = 0;
-    CHECK(g_live == 0);					// everything a scenario made is gone behind it
-    return g_allocs;
-}
-
-// a scenario once clean, then once for every allocation it makes, that one failing
-template <class F>
-static void every_failure( F scenario )
-{
-    const long n = run(0, scenario);
-    CHECK(n > 0);
-    for ( long k = 1; k <= n; k++ )
-	run(k, scenario);
-}
 
 using namespace mifsk;
 
@@ -202,14 +129,14 @@ static void gather_scenario()
 	CHECK(rc == -ENOMEM && rx_empty(s));
 	CHECK(g_live == 0);				// (what the half-built set held is gone already)
     }
-    g_fail_at = 0;
+    g_alloc.fail_at = 0;
     CHECK(fit_rx(s, 3, 0, rows, 0, 7) == 0);		// allocates again after a failure
     CHECK(rx_whole(s, 3, 0, rows, 7));
     // the same shape once more: nothing moves, nothing is allocated
     const uint8_t *was = s.bytes[1].p;
-    const long before = g_allocs;
+    const long before = g_alloc.n;
     s.filled = true;
-    CHECK(fit_rx(s, 3, 0, rows, 0, 7) == 0 && s.bytes[1].p == was && g_allocs == before && s.filled);
+    CHECK(fit_rx(s, 3, 0, rows, 0, 7) == 0 && s.bytes[1].p == was && g_alloc.n == before && s.filled);
 }
 
 // a slot reused with another shape and back (loopback: one peer, which sends; also no rows at all):
@@ -376,13 +303,13 @@ static void mirror_scenario()
 
 int main()
 {
-    every_failure(owner_scenario<DevMem<float>>);
-    every_failure(owner_scenario<PinMem<uint64_t>>);
-    every_failure(owner_scenario<DevMem<uint8_t>>);
-    every_failure(stream_scenario);
-    every_failure(gather_scenario);
-    every_failure(gather_reuse_scenario);
-    every_failure(mirror_scenario);
+    every_failure(g_alloc, owner_scenario<DevMem<float>>);
+    every_failure(g_alloc, owner_scenario<PinMem<uint64_t>>);
+    every_failure(g_alloc, owner_scenario<DevMem<uint8_t>>);
+    every_failure(g_alloc, stream_scenario);
+    every_failure(g_alloc, gather_scenario);
+    every_failure(g_alloc, gather_reuse_scenario);
+    every_failure(g_alloc, mirror_scenario);
     table_checks();
     CHECK(g_live == 0);
     std::printf("hostmem_check: %ld checks, %ld failed\n", g_checks, g_failed);
