@@ -63,7 +63,11 @@ enum mifsk_decoder {
     MIFSK_DECODE_UIC_TRAIN = 5
 };
 
-/* The --rx command line, as data.  Zero / negative means "not given". */
+/* The --rx command line, as data.  Zero / negative means "not given".
+ * confidence_threshold, search_limit: the reference takes a negative -c or -l
+ * literally (below every confidence: each search result counts); passed on in
+ * this struct it would silently mean 1.5 / 2.3.  A caller that parses a command
+ * line refuses a negative value, as the batch program (mifsk_cli.c) does. */
 typedef struct mifsk_modem_args {
     const char	*baudmode;	/* "1200" "300" "rtty" "tdd" "same" "callerid"
 				   "uic-train" "uic-ground" "V.21" or a number */

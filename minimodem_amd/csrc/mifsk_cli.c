@@ -260,8 +260,21 @@ int main( int argc, char *argv[] )
 	switch ( c ) {
 	case 't': tx_mode = 1; break;
 	case 'r': tx_mode = 0; break;
-	case 'c': a.confidence_threshold = (float)atof(optarg); break;
-	case 'l': a.search_limit = (float)atof(optarg); break;
+	case 'c':
+	case 'l': {
+	    /* negative means "not given" in mifsk_modem_args: the reference would take it literally */
+	    const float v = (float)atof(optarg);
+	    if ( v < 0.0f ) {
+		fprintf(stderr, "E: %s %s: a negative value is not supported\n",
+			c == 'c' ? "--confidence" : "--limit", optarg);
+		return 1;
+	    }
+	    if ( c == 'c' )
+		a.confidence_threshold = v;
+	    else
+		a.search_limit = v;
+	    break;
+	}
 	case 'a': a.auto_carrier_threshold = 0.001f; break;
 	case 'i': a.inverted_freqs = 1; break;
 	case 'f':

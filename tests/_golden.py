@@ -15,7 +15,8 @@ def names():
 
 
 _INT_KEYS = {"sample_rate", "n_data_bits", "nstartbits", "binary_output", "inverted_freqs", "rx_one"}
-_FLOAT_KEYS = {"mark_f", "space_f", "band_width", "nstopbits", "auto_carrier_threshold"}
+_FLOAT_KEYS = {"mark_f", "space_f", "band_width", "nstopbits", "auto_carrier_threshold", "confidence_threshold",
+               "search_limit"}
 
 
 def load(name):

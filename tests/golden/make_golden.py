@@ -149,6 +149,22 @@ CASES = [
      dict(baudmode="1200", auto_carrier_threshold=0.001),
      dict(compose=[("noise", 4000, 0.004, 3), ("tx", ["1200"], ASCII_PAYLOAD[:30]), ("noise", 9000, 0.004, 4),
                    ("tx", ["1200", "-M", "1600", "-S", "2600"], ASCII_PAYLOAD[30:60]), ("silence", 2500)])),
+    # --confidence / --limit (minimodem.c:519-530): the two values every decision of the receive loop
+    # compares against, on transmissions under seeded noise (noise=(sigma, seed): Gaussian noise added
+    # to the reference's S16 file, 4000 samples of it in front and behind).  The payloads are as long
+    # as 64 KiB a file allow: noise does not compress.
+    ("t95_c0_l0_1200", ASCII_PAYLOAD[:40], ["1200"], ["-c", "0", "-l", "0", "1200"],
+     dict(baudmode="1200", confidence_threshold=0.0, search_limit=0.0), dict(noise=(0.25, 9501))),
+    ("t95_c4_l20_1200", ASCII_PAYLOAD[:40], ["1200"], ["-c", "4", "-l", "20", "1200"],
+     dict(baudmode="1200", confidence_threshold=4.0, search_limit=20.0), dict(noise=(0.25, 9502))),
+    ("t95_linf_12000", ASCII_PAYLOAD[:40], ["12000"], ["-l", "inf", "12000"],
+     dict(baudmode="12000", search_limit=float("inf")), dict(noise=(0.15, 9503))),
+    ("t95_c0p5_300", ASCII_PAYLOAD[:14], ["300"], ["-c", "0.5", "300"],
+     dict(baudmode="300", confidence_threshold=0.5), dict(noise=(0.3, 9504))),
+    ("t95_c12_same", ASCII_PAYLOAD[:16], ["same"], ["-c", "12", "same"],
+     dict(baudmode="same", confidence_threshold=12.0), dict(noise=(0.3, 9505))),
+    ("t95_c4_rtty", BAUDOT_PAYLOAD[:1], ["rtty"], ["-c", "4", "rtty"],
+     dict(baudmode="rtty", confidence_threshold=4.0), dict(noise=(0.35, 9506))),
 ]
 
 
@@ -240,6 +256,15 @@ def main():
                     body = np.concatenate([np.zeros(extra["lead"], "<i2"),
                                            np.frombuffer(raw0[44:], dtype="<i2")])
                 O.write_wav(wav, body, sr0, "--float-samples" not in tx)
+            if extra.get("noise"):      # seeded noise over the reference's S16 file, and in front and behind
+                sigma, seed = extra["noise"]
+                assert "--float-samples" not in tx
+                with open(wav, "rb") as f:
+                    raw0 = f.read()
+                sr0, _ = O.read_wav(wav)
+                body = np.concatenate([np.zeros(4000), np.frombuffer(raw0[44:], dtype="<i2") / 32768.0, np.zeros(4000)])
+                body = body + np.random.default_rng(seed).normal(0, sigma, body.shape)
+                O.write_wav(wav, np.clip(np.rint(body * 32768), -32768, 32767).astype("<i2"), sr0, True)
             out, err = O.ref_rx(wav, rx)
             with open(wav, "rb") as f:
                 raw = f.read()

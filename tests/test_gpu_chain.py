@@ -63,7 +63,8 @@ def test_chained_launches_give_the_oracles_streams_on_goldens(gpu, monkeypatch, 
 
 
 @pytest.mark.parametrize("engine", ["wave", "workgroup"])
-@pytest.mark.parametrize("mode,opts", [("rtty", {}), ("300", {}), ("same", {}), ("110", {}), ("1200", {}), ("2400", {})])
+@pytest.mark.parametrize("mode,opts", [("rtty", {}), ("300", {}), ("same", {}), ("110", {}), ("1200", {}), ("2400", {}),
+                                       ("1200", dict(confidence_threshold=3.0, search_limit=8.0))])
 def test_chained_equals_single_launch_on_noisy_ragged_batch(gpu, monkeypatch, mode, opts, engine):
     M, torch, ctx = gpu
     if engine == "workgroup" and mode in ("rtty", "same"):

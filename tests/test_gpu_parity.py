@@ -352,7 +352,8 @@ def test_auto_carrier_batch_with_different_tones_per_stream(gpu, mode, tones, ri
 
 
 @pytest.mark.parametrize("mode,kw", [("1200", {}), ("same", {}),
-                                     ("300", dict(auto_carrier_threshold=0.001))])
+                                     ("300", dict(auto_carrier_threshold=0.001)),
+                                     ("1200", dict(confidence_threshold=3.0, search_limit=8.0))])
 @pytest.mark.parametrize("ring", [False, True], ids=["flat", "ring"])
 def test_demod_batch_host_entry_point(gpu, mode, kw, ring):
     """mifsk_demod_batch_host: host pointers in, host results out (ragged rows whose

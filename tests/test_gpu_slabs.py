@@ -126,15 +126,15 @@ def test_any_golden_fed_in_slabs_prints_what_the_reference_prints(gpu, name):
 
 @pytest.mark.parametrize("mode,kw", [("1200", {}), ("300", {}), ("12000", {}), ("same", {}), ("rtty", {}),
                                      ("1200", dict(auto_carrier_threshold=0.001)), ("uic-ground", {}),
-                                     ("5", {})],
-                         ids=["1200", "300", "12000", "same", "rtty", "1200-auto", "uic", "5baud"])
+                                     ("5", {}), ("1200", dict(confidence_threshold=3.0, search_limit=8.0))],
+                         ids=["1200", "300", "12000", "same", "rtty", "1200-auto", "uic", "5baud", "1200-c3-l8"])
 @pytest.mark.parametrize("engine", ["wave", "workgroup", "alternate"])
 def test_batch_of_streams_fed_in_many_ragged_slabs(gpu, mode, kw, engine):
     """A batch whose streams are cut at different places, seven slabs each (some empty, some a
     few samples): noisy, with gaps between bursts (episodes that end inside one slab and are
     reported by a later call), ragged lengths."""
     M, torch, ctx = gpu
-    if engine != "wave" and kw:
+    if engine != "wave" and "auto_carrier_threshold" in kw:
         pytest.skip("--auto-carrier runs on the wavefront engine")
     cfg = M.rx_config(mode, **kw)
     ocfg = O.oracle_config(mode, **kw)

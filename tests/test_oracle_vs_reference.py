@@ -223,3 +223,58 @@ def test_restatement_equals_reference_program_at_other_frame_shapes(shape, rate,
             if kw.get("binary_raw_nbits") != 64:
                 text, _err = M.stream_text(mcfg, r["frames"]["bits"], r["episodes"], quiet=True)
                 assert text == out
+
+
+# --confidence / --limit as the reference's command line takes them: (threshold, limit), None = not given
+CONFIDENCE_OPTIONS = [(None, None), (0, None), (0, 0), (0.5, None), (1.5, 1.5), (None, 8), (None, "inf"), (4, None),
+                      (4, 20), (12, None), (30, None), (3, 1)]
+# (mode, payload file, bytes of it, sigma)
+CONFIDENCE_MODES = [("1200", "testdata-ascii.txt", 40, 0.25), ("300", "testdata-ascii.txt", 24, 0.3),
+                    ("rtty", "testdata-baudot.txt", 6, 0.35), ("12000", "testdata-ascii.txt", 40, 0.15),
+                    ("same", "testdata-ascii.txt", 40, 0.3)]
+
+
+@pytest.mark.parametrize("mode,payload_file,nbytes,sigma", CONFIDENCE_MODES, ids=[m[0] for m in CONFIDENCE_MODES])
+def test_restatement_equals_reference_program_under_confidence_options(mode, payload_file, nbytes, sigma, tmp_path):
+    """-c and -l drive every decision of the receive loop (minimodem.c:1265-1321,1357: a search ends
+    at the first candidate that reaches the limit, a frame counts only above the threshold, the
+    limit is lifted to the threshold); the GPU sweeps of tests/test_gpu_thresholds.py take the
+    restatement's word for them.  Here the reference program transmits, seeded noise is added in
+    front of, over and behind the signal, and it receives with twelve settings -- not given, 0, 0 / 0,
+    0.5, 1.5 / 1.5, -l 8, -l inf, 4, 4 / 20, 12, 30, 3 / 1: the restatement with the same two values
+    must print the reference's NOCARRIER lines, and its bytes where the decoder is ASCII, in ring
+    and flat mode.  (Behind the noise the file ends with a buffer's length of silence, as in
+    test_restatement_equals_reference_program_at_other_frame_shapes: with -c 0 the noise itself is
+    decoded, and a frame that reaches past the end of a file reads the reference's stale buffer
+    cells, which ring mode alone replicates -- 0.873 against flat mode's 0.874 in the last line
+    at 1200 baud.)"""
+    wav = str(tmp_path / "c.wav")
+    O.ref_tx(ref_payload(payload_file)[:nbytes], [mode], wav)
+    sr, x = O.read_wav(wav)
+    rng = np.random.default_rng([95, CONFIDENCE_MODES.index((mode, payload_file, nbytes, sigma))])
+    x = np.concatenate([np.zeros(4000), x.astype(np.float64), np.zeros(4000)])
+    x = np.concatenate([x + rng.normal(0, sigma, x.shape), np.zeros(int(O.oracle_config(mode).samplebuf_size))])
+    O.write_wav(wav, np.clip(np.rint(x * 32768), -32768, 32767).astype("<i2"), sr, True)
+    sr, x = O.read_wav(wav)
+    outcomes = set()
+    for thr, lim in CONFIDENCE_OPTIONS:
+        args, kw = [], {}
+        if thr is not None:
+            args += ["-c", str(thr)]
+            kw["confidence_threshold"] = float(thr)
+        if lim is not None:
+            args += ["-l", str(lim)]
+            kw["search_limit"] = float(lim)
+        out, err = O.ref_rx(wav, args + [mode])
+        ref_lines = [l for l in err.splitlines() if l.startswith("### NOCARRIER")]
+        cfg = O.oracle_config(mode, **kw)
+        assert sr == cfg.sample_rate
+        for ring in (True, False):
+            r = O.oracle_rx_stream(cfg, x, ring_mode=ring)
+            assert [O.format_nocarrier(cfg, e) for e in r["episodes"]] == ref_lines, (mode, thr, lim, ring)
+            if cfg.decoder == 0:
+                assert r["bytes"] == out, (mode, thr, lim, ring)
+        outcomes.add((out, tuple(ref_lines)))
+    # (the settings do something -- frames out of the noise at 0, the default's, fewer or none at 30: the
+    # reference itself prints at least three different things)
+    assert len(outcomes) >= 3, len(outcomes)
