@@ -715,8 +715,10 @@ class ChannelPlan(_PhasePlan):
         self.decim, self.complex_input = p.decim, bool(complex_input)
 
 
-def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
-    """mifsk_channelize_batch: every channel of every row as a row demod_batch takes.
+def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None, iq=False):
+    """mifsk_channelize_batch: every channel of every row as a row demod_batch takes; with iq=True
+    mifsk_channelize_iq_batch: every channel as a row of I, Q pairs, which fm_demod takes (plan the
+    channelizer with out_centre=0 for the complex envelope).
 
     samples : CUDA tensor [nstreams, stride] (or 1-D for one stream) of the plan's kind: float32 or
               int16 (PCM16) for real rows; for complex rows complex64, or float32 / int16 with a last
@@ -726,15 +728,19 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     out     : a dict a former call with the same shapes returned, to reuse its tensors
     Returns {"rows": float32 [nstreams * nchannels, out_stride], "nsamples": int32 [nstreams * nchannels]}:
     row s * nchannels + k is channel k of stream s, zero behind its count.  Allocated on the launch
-    stream.  No synchronisation is performed."""
+    stream.  No synchronisation is performed.
+    iq=True : "rows" is float32 [nstreams * nchannels, out_stride, 2], element m of a row (I, Q); out_stride
+              and nout_cap count such elements (None: what a full row gives, at least 2, rounded up to 2);
+              "rows" and "nsamples" are what fm_demod takes as iq and nsamples."""
     torch = _torch()
     kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
     v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
     lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
     full = out is None and (carrier_windows(v.width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap))
-    out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 4, torch.float32, (), v.t.device, stream, out)
+    out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 2 if iq else 4, torch.float32, (2,) if iq else (),
+                       v.t.device, stream, out)
     io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, nout_cap)
-    _call("mifsk_channelize_batch", plan.handle, C.byref(io), stream=stream)
+    _call("mifsk_channelize_iq_batch" if iq else "mifsk_channelize_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
 

@@ -1,5 +1,5 @@
 """ctypes binding of libmifsk.so (the C ABI declared in include/fsk.h and
-include/mifsk.h).  The library is built in-tree by `minimodem_amd.build()` /
+include/mifsk.h, and the extension headers under include/mifsk/).  The library is built in-tree by `minimodem_amd.build()` /
 `__graft_entry__.build()`; if it is missing or cannot be loaded this module
 raises -- there is no Python or CPU fallback for the signal path."""
 import ctypes as C
@@ -465,6 +465,13 @@ SIGNATURES = {
 }
 EXPORTS = list(SIGNATURES)
 
+# what the extension headers under include/mifsk/ declare, bound like SIGNATURES: additions that leave the
+# ABI of include/*.h (its prototypes, structs and MIFSK_ABI_VERSION) as it is
+EXT_SIGNATURES = {
+    # include/mifsk/channel_iq.h
+    "mifsk_channelize_iq_batch": (_int, [_vp, _P(ChannelIO), _vp]),
+}
+
 _lib = None
 
 
@@ -477,7 +484,7 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib

@@ -1,5 +1,7 @@
 // mifsk_channel.hip -- the channelizer (include/mifsk.h): mifsk_channel_plan_create / _destroy,
-// mifsk_channelize_batch, and the host helpers mifsk_channel_table and mifsk_channel_taps.
+// mifsk_channelize_batch, the host helpers mifsk_channel_table and mifsk_channel_taps, and
+// mifsk_channelize_iq_batch (include/mifsk/channel_iq.h): the same kernel body with the epilogue that
+// keeps both halves of the rotated sum.
 //
 // One output sample is a window sum of carrier_survey_kernel's kind -- the complex sum kept, the
 // rectangle replaced by a filter's taps, then rotated to the output tone -- so the kernel is laid
@@ -37,6 +39,7 @@
 #include <type_traits>
 
 #include "mifsk.h"
+#include "mifsk/channel_iq.h"
 #include "mifsk_ctx.h"
 #include "mifsk_phase.h"
 #include "mifsk_rows.h"
@@ -87,11 +90,16 @@ __device__ __forceinline__ auto channel_sample( const void *row, uint64_t at )
     }
 }
 
-// NC: channels per lane.  CX: complex rows.  S16: PCM16 scalars.
-template <int NC, bool CX, bool S16>
+// NC: channels per lane.  CX: complex rows.  S16: PCM16 scalars.  IQ: the epilogue of
+// mifsk_channelize_iq_batch (include/mifsk/channel_iq.h): rows are [out_stride] (I, Q) pairs, I the
+// real entry's output, Q the other half of the same rotation, one 8-byte store for both.  (A fourth
+// parameter of this kernel, not a body shared by two kernels: inlined into a wrapper the IQ = false
+// code comes out nine instructions longer, and it is to stay as it is.)
+template <int NC, bool CX, bool S16, bool IQ>
 __global__ __launch_bounds__(256)
 void channelize_kernel( const ChannelArgs A )
 {
+    using OT = std::conditional_t<IQ, float2, float>;
     using XT = std::conditional_t<CX, double2, double>;
     extern __shared__ double2 ch_lds[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -197,15 +205,19 @@ void channelize_kernel( const ChannelArgs A )
 	const uint32_t dq = A.dq[k[j]];
 	uint32_t p = (uint32_t)( ( (uint64_t)dq * md0 ) % P );
 	const uint32_t pstep = (uint32_t)( ( (uint64_t)dq * mdstep ) % P );
-	float *out = A.rows + ( (size_t)s * K + k[j] ) * A.out_stride;
+	OT *out = reinterpret_cast<OT *>(A.rows) + ( (size_t)s * K + k[j] ) * A.out_stride;
 #pragma unroll
 	for ( int o = 0; o < kChO; o++ ) {
 	    const uint64_t m = m0 + ol + (uint32_t)o * NOG;
 	    if ( m < A.out_stride ) {
-		float v = 0.0f;
+		OT v = {};
 		if ( m < cnt ) {
 		    const double2 w = A.w[p];
-		    v = (float)fma(re[o][j], w.x, -( im[o][j] * w.y ));
+		    if constexpr ( IQ ) {
+			v.x = (float)fma(re[o][j], w.x, -( im[o][j] * w.y ));
+			v.y = (float)fma(re[o][j], w.y, im[o][j] * w.x);
+		    } else
+			v = (float)fma(re[o][j], w.x, -( im[o][j] * w.y ));
 		}
 		out[m] = v;
 	    }
@@ -309,12 +321,16 @@ extern "C" int mifsk_channel_plan_create( mifsk_ctx *ctx, const mifsk_channel_pa
 
 extern "C" void mifsk_channel_plan_destroy( mifsk_channel_plan *plan ) { mifsk::phase_plan_destroy(plan); }
 
-extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream )
+// Both batch entries: their checks, then the one launch path.  An output element is a float, or with
+// `iq` an (I, Q) pair: out_vec of them are 16 bytes, a row is out_max of them at most.
+static int channelize_rows( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream, bool iq )
 {
     using namespace mifsk;
     if ( !plan || !io )
 	return -EINVAL;
-    if ( int rc = phase_check_io(*plan, io, io->d_rows, rows_vec(plan->cx, plan->s16), 4u, 0xFFFFFFFCull) )
+    const uint32_t out_vec = iq ? 2u : 4u;
+    const uint64_t out_max = iq ? 0x7FFFFFFEull : 0xFFFFFFFCull;
+    if ( int rc = phase_check_io(*plan, io, io->d_rows, rows_vec(plan->cx, plan->s16), out_vec, out_max) )
 	return rc;
 
     ChannelArgs A = {};
@@ -370,10 +386,22 @@ extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mif
 	const dim3 grid(nchunks, rows, gz), block(64u * kChWaves);
 	auto launch = [&]( auto per_lane ) {
 	    return dispatch_kind(plan->cx, plan->s16, [&]( auto cx, auto s16 ) {
-		return launch_lds(channelize_kernel<decltype(per_lane)::value, decltype(cx)::value, decltype(s16)::value>,
+		constexpr int NC = decltype(per_lane)::value;
+		constexpr bool CX = decltype(cx)::value, S16 = decltype(s16)::value;
+		return launch_lds(iq ? channelize_kernel<NC, CX, S16, true> : channelize_kernel<NC, CX, S16, false>,
 				  grid, block, lds, st, A);
 	    });
 	};
 	return nc == 2u ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
     });
+}
+
+extern "C" int mifsk_channelize_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream )
+{
+    return channelize_rows(plan, io, stream, false);
+}
+
+extern "C" int mifsk_channelize_iq_batch( const mifsk_channel_plan *plan, const mifsk_channel_io *io, void *stream )
+{
+    return channelize_rows(plan, io, stream, true);
 }

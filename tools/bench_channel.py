@@ -15,10 +15,23 @@ plus the outputs written once.
 
     python tools/bench_channel.py [--out profiles/channelize.json]
 
+--iq times the I/Q entry (mifsk_channelize_iq_batch) on the same shapes, next to the real
+entry: one process per shape holds one plan and one input, and its rounds alternate a window of the real
+entry with a window of the I/Q entry.  The result (profiles/channelize_iq.json) holds both times, their
+ratio and the windows' spread; --parent FILE ... adds the real entry's time from results that the tool
+of another commit wrote on the same machine (its own profiles/channelize.json), and what this commit's
+real entry takes against each.
+
+    python tools/bench_channel.py --iq [--parent FILE ... --parent-commit HASH] [--out profiles/channelize_iq.json]
+
 Needs the GPU: there is no other path.
 """
+import argparse
 import json
+import os
+import statistics
 import sys
+import time
 
 import _benchsteps as B
 
@@ -30,13 +43,43 @@ WORKLOADS = {
     "iq-1.92M": (8, 19200000, 1920000.0, True, True, 64, 513, 9000.0, 40, 19200),
 }
 LIMIT = 300                 # seconds a workload step may take
+IQ = "+iq"                  # a step name's tail: both entries, alternating
+
+
+def alternating_windows(calls, rounds, window_ms, preheat_ms):
+    """B.timed_windows for several calls at once: each preheated and its K chosen alone, then `rounds`
+    rounds of one window of each, in turn -> [(K, {"median", "min", "max"} ms per call)] in calls' order"""
+    import torch
+
+    def timed(call, k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(k):
+            call()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / k
+
+    ks = []
+    for call in calls:
+        t0 = time.perf_counter()
+        while (time.perf_counter() - t0) * 1e3 < preheat_ms:
+            call()
+            torch.cuda.synchronize()
+        ks.append(max(2, int(window_ms / max(timed(call, 2), 1e-3))))
+    ms = [[] for _ in calls]
+    for _ in range(rounds):
+        for i, call in enumerate(calls):
+            ms[i].append(timed(call, ks[i]))
+    return [(k, {"median": statistics.median(m), "min": min(m), "max": max(m)}) for k, m in zip(ks, ms)]
 
 
 def step_workload(name, rounds, window_ms, preheat_ms):
     import numpy as np
     import torch
     import minimodem_amd as M
-    rows, n, fs, cx, s16, K, T, cutoff, D, P = WORKLOADS[name]
+    both = name.endswith(IQ)
+    rows, n, fs, cx, s16, K, T, cutoff, D, P = WORKLOADS[name[:-len(IQ)] if both else name]
     ctx = M.Context()
     g = torch.Generator(device="cuda")
     g.manual_seed(1)
@@ -56,24 +99,40 @@ def step_workload(name, rounds, window_ms, preheat_ms):
     def call():
         M.channelize(plan, d, out=out)
 
-    k, ms = B.timed_windows(call, rounds, window_ms, preheat_ms)
     nout = M.carrier_windows(n, T, D)
-    counts = out["nsamples"].cpu().numpy()
-    assert counts.shape == (rows * K,) and (counts == nout).all(), (counts[:4], nout)
-    assert bool(torch.isfinite(out["rows"][::max(1, rows * K // 8), :4096]).all())
-    med = ms["median"]
     outputs = rows * K * nout
     fma = outputs * T * (4 if cx else 2)
     read = rows * n * (2 if s16 else 4) * (2 if cx else 1)
-    written = outputs * 4
+
+    def figures(k, ms, o, bytes_per_output):
+        counts = o["nsamples"].cpu().numpy()
+        assert counts.shape == (rows * K,) and (counts == nout).all(), (counts[:4], nout)
+        assert bool(torch.isfinite(o["rows"][::max(1, rows * K // 8), :4096]).all())
+        med, written = ms["median"], outputs * bytes_per_output
+        return {"launches_per_window": k, "rounds": rounds, "ms": ms,
+                "outputs_per_s": outputs / med * 1e3, "fma_per_s": fma / med * 1e3,
+                "input_seconds_per_s": rows * n / fs / med * 1e3,
+                "bytes_read": read, "bytes_written": written,
+                "read_bytes_per_s": read / med * 1e3, "written_bytes_per_s": written / med * 1e3}
+
     res = {"workload": {"rows": rows, "elements_per_row": n, "input_rate": fs, "complex": cx, "pcm16": s16,
                         "channels": K, "taps": T, "decimation": D, "phase_steps": P, "outputs": outputs},
-           "device": ctx.device_name, "launches_per_window": k, "rounds": rounds,
-           "ms": ms,
-           "outputs_per_s": outputs / med * 1e3, "fma_per_s": fma / med * 1e3,
-           "input_seconds_per_s": rows * n / fs / med * 1e3,
-           "bytes_read": read, "bytes_written": written,
-           "read_bytes_per_s": read / med * 1e3, "written_bytes_per_s": written / med * 1e3}
+           "device": ctx.device_name}
+    if both:
+        out_iq = M.channelize(plan, d, iq=True)
+        torch.cuda.synchronize()
+        # the I plane of the I/Q entry is the real entry's output, here too
+        assert torch.equal(out_iq["rows"][::max(1, rows * K // 8), :4096, 0], out["rows"][::max(1, rows * K // 8), :4096])
+
+        def call_iq():
+            M.channelize(plan, d, out=out_iq, iq=True)
+
+        (k, ms), (k_iq, ms_iq) = alternating_windows([call, call_iq], rounds, window_ms, preheat_ms)
+        res.update(figures(k, ms, out, 4))
+        res["iq"] = figures(k_iq, ms_iq, out_iq, 8)
+        res["iq_over_real"] = ms_iq["median"] / ms["median"]
+    else:
+        res.update(figures(*B.timed_windows(call, rounds, window_ms, preheat_ms), out, 4))
     plan.close()
     ctx.close()
     print(json.dumps(res))
@@ -83,8 +142,40 @@ def show(name, r, peak):
     print("%-10s %9.3f ms  %.3e outputs/s  %.2f TFMA/s (%.0f %% of %.2f)  %.0f s of input per s" % (
         name, r["ms"]["median"], r["outputs_per_s"], r["fma_per_s"] * 1e-12,
         100 * r["share_of_measured_fma64"], peak * 1e-12, r["input_seconds_per_s"]), flush=True)
+    if "iq" in r:
+        print("%-10s %9.3f ms  I/Q entry: %.4f of the real entry's time (real windows %.3f .. %.3f ms)" % (
+            "", r["iq"]["ms"]["median"], r["iq_over_real"], r["ms"]["min"], r["ms"]["max"]), flush=True)
+
+
+def add_parents(paths, commit):
+    """finish() of an --iq run: the real entry's time of other commits' results beside this one's"""
+    def finish(result, _step):
+        if commit:
+            result["parent_commit"] = commit
+        result["parents"] = []
+        for path in paths:
+            with open(path) as f:
+                theirs = json.load(f)["workloads"]
+            entry = {"file": os.path.basename(path), "workloads": {}}
+            for name, r in result["workloads"].items():
+                p = theirs[name[:-len(IQ)]]
+                assert p["workload"] == r["workload"], name
+                entry["workloads"][name] = {"ms": p["ms"], "this_over_parent": r["ms"]["median"] / p["ms"]["median"]}
+            result["parents"].append(entry)
+    return finish
 
 
 if __name__ == "__main__":
-    B.main(__file__, __doc__, "channelize.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
-           WORKLOADS, LIMIT, step_workload, show)
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--iq", action="store_true")
+    ap.add_argument("--parent", nargs="*", default=[])
+    ap.add_argument("--parent-commit", default=None)
+    mine, rest = ap.parse_known_args()
+    sys.argv[1:] = rest
+    if mine.iq:
+        B.main(__file__, __doc__, "channelize_iq.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
+               {name + IQ: w for name, w in WORKLOADS.items()}, LIMIT, step_workload, show,
+               finish=add_parents(mine.parent, mine.parent_commit))
+    else:
+        B.main(__file__, __doc__, "channelize.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
+               WORKLOADS, LIMIT, step_workload, show)

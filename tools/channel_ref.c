@@ -2,7 +2,8 @@
  * host as three nested loops with explicit fma() and sincos(): the yardstick of
  * tests/test_channel_args.py and tests/test_gpu_channel.py, which compile it into a temporary
  * shared object with -O2 -ffp-contract=off.  Never linked into libmifsk.so: the library has no
- * host channelizer.
+ * host channelizer.  channel_ref_iq restates the I/Q entry (include/mifsk/channel_iq.h) the same
+ * way, for tests/test_channel_iq_args.py and tests/test_gpu_channel_iq.py.
  *
  *   cc -O2 -ffp-contract=off -shared -fPIC -o channel_ref.so tools/channel_ref.c -lm
  */
@@ -72,6 +73,45 @@ uint64_t channel_ref( const void *x, uint64_t N, int kind, uint32_t P, uint32_t 
 	    double S, C;
 	    sincos(two_pi * (double)p / (double)P, &S, &C);
 	    out[(uint64_t)k * out_stride + m] = (float)fma(re, C, -( im * S ));
+	}
+    }
+    return M;
+}
+
+/* The I/Q entry's definition (include/mifsk/channel_iq.h), written out again from it: the same sums,
+ * then both halves of the rotation.  out is [K][out_stride][2]: (I, Q) of output m of channel k at
+ * out[(k * out_stride + m) * 2]; otherwise as channel_ref. */
+uint64_t channel_ref_iq( const void *x, uint64_t N, int kind, uint32_t P, uint32_t T, const float *h,
+	uint32_t D, uint32_t K, const int32_t *q, int32_t r, float *out, uint64_t out_stride, double *g )
+{
+    const int cx = kind & CHANNEL_REF_COMPLEX, s16 = kind & CHANNEL_REF_S16;
+    const uint64_t M = N >= T ? ( N - T ) / D + 1 : 0;
+    for ( uint32_t k = 0; k < K; k++ ) {
+	channel_ref_table(P, T, h, q[k], g);
+	const int64_t dq = reduce((int64_t)r - reduce(q[k], P), P);
+	for ( uint64_t m = 0; m < M && m < out_stride; m++ ) {
+	    double re = 0.0, im = 0.0;
+	    for ( uint32_t t = 0; t < T; t++ ) {
+		const uint64_t n = m * D + t;
+		if ( cx ) {
+		    const double xr = scalar(x, s16, 2 * n), xi = scalar(x, s16, 2 * n + 1);
+		    re = fma(xr, g[2 * t], re);
+		    re = fma(-xi, g[2 * t + 1], re);
+		    im = fma(xr, g[2 * t + 1], im);
+		    im = fma(xi, g[2 * t], im);
+		} else {
+		    const double v = scalar(x, s16, n);
+		    re = fma(v, g[2 * t], re);
+		    im = fma(v, g[2 * t + 1], im);
+		}
+	    }
+	    const int64_t p = ( dq * (int64_t)( ( m * D ) % P ) ) % (int64_t)P;
+	    double S, C;
+	    sincos(two_pi * (double)p / (double)P, &S, &C);
+	    const double neg = -( im * S ), pos = im * C;
+	    float *o = out + ( (uint64_t)k * out_stride + m ) * 2;
+	    o[0] = (float)fma(re, C, neg);
+	    o[1] = (float)fma(re, S, pos);
 	}
     }
     return M;
