@@ -773,7 +773,10 @@ class MuxPlan(_PhasePlan):
     centres    : where each channel goes, in steps of fs_out / phase_steps Hz, negative allowed
     in_centre  : the input rows' tone centre, same unit: the band the filter keeps
     complex_output: rows are interleaved I, Q; s16: the scalars are PCM16
-    gains      : None, or one float per channel"""
+    gains      : None, or one float per channel
+    For multiplex(..., iq=True) the input rows are complex envelopes: in_centre is the envelope's centre
+    (0 for fm_modulate with centre=0), and unit gain wants taps that sum to interp,
+    channel_taps(T, fc, fs_out, interp): a complex row is one-sided already."""
 
     def __init__(self, ctx, taps, interp, centres, in_centre, phase_steps, complex_output=False, s16=False,
                  gains=None):
@@ -782,8 +785,9 @@ class MuxPlan(_PhasePlan):
         self.interp, self.complex_output = p.interp, bool(complex_output)
 
 
-def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None):
-    """mifsk_multiplex_batch: the channels of every stream summed into one wideband row.
+def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None, iq=False):
+    """mifsk_multiplex_batch: the channels of every stream summed into one wideband row; with iq=True
+    mifsk_multiplex_iq_batch: the same from rows of I, Q pairs, what fm_modulate writes.
 
     samples : float32 CUDA tensor [nstreams * nchannels, stride], what synthesize_batch returns: row
               s * nchannels + k is channel k of stream s.  Rows are 16-byte aligned, stride % 4 == 0.
@@ -792,9 +796,15 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     out     : a dict a former call with the same shapes returned, to reuse its tensors
     Returns {"rows": [nstreams, out_stride] (complex plans: [nstreams, out_stride, 2]) float32 or int16,
     "nsamples": int32 [nstreams]}; a row is zero behind its count.  Allocated on the launch stream.
-    No synchronisation is performed."""
+    No synchronisation is performed.
+    iq=True : samples is float32 [nstreams * nchannels, stride, 2] (I, Q) or complex64 [nstreams * nchannels,
+              stride], stride % 2 == 0; nsamples counts such elements.  fm_modulate's float32 result goes in
+              as it is, and so do "rows" and "nsamples" of channelize(..., iq=True).  The outputs are as above."""
     torch = _torch()
-    v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
+    if iq:
+        v = _row_view(torch, samples, cx=True, dtypes=(torch.float32, torch.complex64), one_row=False, unit="elements")
+    else:
+        v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
     K = plan.nchannels
     assert v.nstreams > 0 and v.nstreams % K == 0, "samples holds nchannels rows per stream"
     nstreams = v.nstreams // K
@@ -804,7 +814,7 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     full = out is None and ((v.width - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap))
     out = _row_outputs(torch, nstreams, full, vec, dtype, (2,) if plan.complex_output else (), samples.device, stream, out)
     io = _phase_io(_lib.MuxIO(), "d_out", v, lens, nstreams, out, nout_cap)
-    _call("mifsk_multiplex_batch", plan.handle, C.byref(io), stream=stream)
+    _call("mifsk_multiplex_iq_batch" if iq else "mifsk_multiplex_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
 

@@ -466,10 +466,16 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 
 # what the extension headers under include/mifsk/ declare, bound like SIGNATURES: additions that leave the
-# ABI of include/*.h (its prototypes, structs and MIFSK_ABI_VERSION) as it is
+# ABI of include/*.h (its prototypes, structs and MIFSK_ABI_VERSION) as it is.  EXT_SIGNATURES is the first
+# such header's table; EXTENSIONS below holds one per header, and load() binds them all.
 EXT_SIGNATURES = {
     # include/mifsk/channel_iq.h
     "mifsk_channelize_iq_batch": (_int, [_vp, _P(ChannelIO), _vp]),
+}
+# one table per extension header, by the header's path under include/
+EXTENSIONS = {
+    "mifsk/channel_iq.h": EXT_SIGNATURES,
+    "mifsk/mux_iq.h": {"mifsk_multiplex_iq_batch": (_int, [_vp, _P(MuxIO), _vp])},
 }
 
 _lib = None
@@ -484,8 +490,9 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in [SIGNATURES] + list(EXTENSIONS.values()):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib

@@ -1,5 +1,6 @@
 // mifsk_mux.hip -- the multiplexer (include/mifsk.h): mifsk_mux_plan_create / _destroy,
-// mifsk_multiplex_batch, and the host helper mifsk_mux_table.
+// mifsk_multiplex_batch, and the host helper mifsk_mux_table; mifsk_multiplex_iq_batch
+// (include/mifsk/mux_iq.h): the same kernel with I/Q rows in (IQIN, at the kernel).
 //
 // One output n = m L + phi of one channel is a polyphase sum: the taps phi, phi + L, ... against the
 // samples x[m], x[m - 1], ...  The kernel is laid out around what feeds the FP64 pipe:
@@ -36,6 +37,7 @@
 #include <new>
 
 #include "mifsk.h"
+#include "mifsk/mux_iq.h"
 #include "mifsk_ctx.h"
 #include "mifsk_phase.h"
 #include "mifsk_rows.h"
@@ -53,7 +55,7 @@ struct MuxArgs {
     const uint32_t	*dq;		// [K]: (q[k] - r) mod P
     const uint32_t	*ps;		// [K]: (dq[k] * (L mod P)) mod P
     const float		*gains;		// [K] or NULL
-    RowsIn		in;		// floats
+    RowsIn		in;		// floats; IQIN: (I, Q) pairs of floats
     uint32_t		T, L, K, P;
     uint32_t		jmax;		// ceil(T / L): tap steps of phase 0
     uint32_t		span;		// samples staged per channel, at most
@@ -81,8 +83,14 @@ __device__ __forceinline__ uint32_t mux_mulmod( uint32_t a, uint32_t b, uint32_t
     return (uint32_t)r;
 }
 
-// CX: complex rows.  S16: PCM16 scalars.
-template <bool CX, bool S16>
+// CX: complex rows.  S16: PCM16 scalars.  IQIN: the input rows of mifsk_multiplex_iq_batch
+// (include/mifsk/mux_iq.h), (I, Q) pairs of floats.  A sample is staged as it is read, one 8-byte cell
+// of two floats where a real row's sample is one double, so that the padding, the spans and the LDS
+// sizing are the same and one ds_read_b64 per tap step still brings the new sample; both halves are
+// widened at the read (exact, so where it happens does not matter) and the window holds 8 (I, Q) pairs
+// of doubles: a tap step is 4 * kMxO FMAs.  A parameter of this kernel, not a body shared by two
+// kernels (mifsk_channel.hip says why): what the IQIN = false instantiations execute is the text it was.
+template <bool CX, bool S16, bool IQIN>
 __global__ __launch_bounds__(256)
 void multiplex_kernel( const MuxArgs A )
 {
@@ -144,11 +152,20 @@ void multiplex_kernel( const MuxArgs A )
 	    // a wave per channel: the row and its length are the wave's, the lanes read along the row
 	    for ( uint32_t c = tid >> 6; c < cbn; c += kMxThreads / 64u ) {
 		const int64_t nk = row_len(k0 + c);
+		if constexpr ( IQIN ) {
+		    const float2 *xr = reinterpret_cast<const float2 *>(A.in.x) + ( row0 + k0 + c ) * A.in.stride;
+		    float2 *xc = reinterpret_cast<float2 *>(xs) + (size_t)c * A.spanp;
+		    for ( uint32_t e = tid & 63u; e < span; e += 64u ) {
+			const int64_t i = lo + e;
+			xc[mux_pad(e)] = i >= 0 && i < nk ? xr[i] : float2{0.0f, 0.0f};
+		    }
+		} else {
 		const float *xr = reinterpret_cast<const float *>(A.in.x) + ( row0 + k0 + c ) * A.in.stride;
 		double *xc = xs + (size_t)c * A.spanp;
 		for ( uint32_t e = tid & 63u; e < span; e += 64u ) {
 		    const int64_t i = lo + e;
 		    xc[mux_pad(e)] = i >= 0 && i < nk ? (double)xr[i] : 0.0;
+		}
 		}
 	    }
 	    __syncthreads();
@@ -176,6 +193,63 @@ void multiplex_kernel( const MuxArgs A )
 		    re[u] = 0.0;
 		    im[u] = 0.0;
 		}
+		if constexpr ( IQIN ) {
+		    const float2 *xq = reinterpret_cast<const float2 *>(xs) + (size_t)c * A.spanp;
+		    if ( lo >= 0 && hi < nk ) {
+			// the window path of real rows below, a slot (I, Q) as two doubles
+			double wa[kMxO], wb[kMxO];
+#pragma unroll
+			for ( int u = 0; u < kMxO; u++ ) {
+			    const float2 v = xq[mux_pad(xb + (uint32_t)u)];
+			    wa[u] = (double)v.x;
+			    wb[u] = (double)v.y;
+			}
+			uint32_t t = phi;
+			double2 gn = gl[t < T ? t : T - 1u];
+			float2 xn = float2{0.0f, 0.0f};
+			for ( uint32_t j0 = 0; j0 < jmax; j0 += (uint32_t)kMxO ) {
+#pragma unroll
+			    for ( int r = 0; r < kMxO; r++ ) {
+				const uint32_t j = j0 + (uint32_t)r, tn = t + L;
+				const double2 gt = gn;
+				if ( r > 0 || j0 > 0u ) {
+				    wa[( kMxO - r ) & 7] = (double)xn.x;		// x[m0 - j]
+				    wb[( kMxO - r ) & 7] = (double)xn.y;
+				}
+				gn = gl[tn < T ? tn : T - 1u];
+				xn = xq[mux_pad(xb - ( j + 1u < jmax ? j + 1u : jmax - 1u ))];
+				if ( t < T ) {
+#pragma unroll
+				    for ( int u = 0; u < kMxO; u++ ) {
+					const double a = wa[( u - r ) & 7], b = wb[( u - r ) & 7];
+					re[u] = fma(a, gt.x, re[u]);
+					re[u] = fma(-b, gt.y, re[u]);
+					im[u] = fma(a, gt.y, im[u]);
+					im[u] = fma(b, gt.x, im[u]);
+				    }
+				}
+				t = tn;
+			    }
+			}
+		    } else if ( lo < nk ) {
+			uint32_t t = phi;
+			for ( uint32_t j = 0; j < jmax && t < T; j++, t += L ) {
+			    const double2 gt = gl[t];
+#pragma unroll
+			    for ( int u = 0; u < kMxO; u++ ) {
+				const int64_t i = m0 + u - (int64_t)j;
+				if ( i >= 0 && i < nk ) {
+				    const float2 v = xq[mux_pad(xb + (uint32_t)u - j)];
+				    const double a = (double)v.x, b = (double)v.y;
+				    re[u] = fma(a, gt.x, re[u]);
+				    re[u] = fma(-b, gt.y, re[u]);
+				    im[u] = fma(a, gt.y, im[u]);
+				    im[u] = fma(b, gt.x, im[u]);
+				}
+			    }
+			}
+		    }
+		} else
 		if ( lo >= 0 && hi < nk ) {
 		    // every term of every lane exists: the window in registers, slot (v & 7) holds
 		    // x[m0 + v] for the 8 values of v in use
@@ -336,12 +410,14 @@ extern "C" int mifsk_mux_plan_create( mifsk_ctx *ctx, const mifsk_mux_params *pa
 
 extern "C" void mifsk_mux_plan_destroy( mifsk_mux_plan *plan ) { mifsk::phase_plan_destroy(plan); }
 
-extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream )
+// Both entries.  `iq`: the input rows are (I, Q) pairs of floats, 2 of them 16 bytes, and the kernel is
+// the IQIN one; everything else is a function of the plan and the io alone.
+static int multiplex_rows( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream, bool iq )
 {
     using namespace mifsk;
     if ( !plan || !io )
 	return -EINVAL;
-    if ( int rc = phase_check_io(*plan, io, io->d_out, 4u, rows_vec(plan->cx, plan->s16), 0xFFFFFFF8ull) )
+    if ( int rc = phase_check_io(*plan, io, io->d_out, iq ? 2u : 4u, rows_vec(plan->cx, plan->s16), 0xFFFFFFF8ull) )
 	return rc;
 
     MuxArgs A = {};
@@ -380,8 +456,19 @@ extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mu
     return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	A.s0 = s0;
 	return dispatch_kind(plan->cx, plan->s16, [&]( auto cx, auto s16 ) {
-	    return launch_lds(multiplex_kernel<decltype(cx)::value, decltype(s16)::value>, dim3(nblocks, rows, 1),
+	    constexpr bool CX = decltype(cx)::value, S16 = decltype(s16)::value;
+	    return launch_lds(iq ? multiplex_kernel<CX, S16, true> : multiplex_kernel<CX, S16, false>, dim3(nblocks, rows, 1),
 			      dim3(kMxThreads), lds, st, A);
 	});
     });
+}
+
+extern "C" int mifsk_multiplex_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream )
+{
+    return multiplex_rows(plan, io, stream, false);
+}
+
+extern "C" int mifsk_multiplex_iq_batch( const mifsk_mux_plan *plan, const mifsk_mux_io *io, void *stream )
+{
+    return multiplex_rows(plan, io, stream, true);
 }

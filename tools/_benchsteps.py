@@ -51,6 +51,34 @@ def timed_windows(call, rounds, window_ms, preheat_ms):
     return k, {"median": statistics.median(ms), "min": min(ms), "max": max(ms)}
 
 
+def alternating_windows(calls, rounds, window_ms, preheat_ms):
+    """timed_windows for several calls at once: each preheated and its K chosen alone, then `rounds`
+    rounds of one window of each, in turn -> [(K, {"median", "min", "max"} ms per call)] in calls' order"""
+    import torch
+
+    def timed(call, k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(k):
+            call()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / k
+
+    ks = []
+    for call in calls:
+        t0 = time.perf_counter()
+        while (time.perf_counter() - t0) * 1e3 < preheat_ms:
+            call()
+            torch.cuda.synchronize()
+        ks.append(max(2, int(window_ms / max(timed(call, 2), 1e-3))))
+    ms = [[] for _ in calls]
+    for _ in range(rounds):
+        for i, call in enumerate(calls):
+            ms[i].append(timed(call, ks[i]))
+    return [(k, {"median": statistics.median(m), "min": min(m), "max": max(m)}) for k, m in zip(ks, ms)]
+
+
 def step_fma64():
     """the fma64 step (built first where it is missing) -> what goes under "fma64" of the result"""
     ub = os.path.join(ROOT, "tools", "ubench", "fma64_rate")
@@ -101,3 +129,22 @@ def main(script, doc, out_name, window_ms, fma_count, workloads, limit, step_wor
         json.dump(result, f, indent=1)
         f.write("\n")
     print(json.dumps(result))
+
+
+def add_parents(paths, commit, tail):
+    """finish() of an --iq run, whose workloads are named NAME + `tail`: the real entry's time of other
+    commits' results (their plain runs: workloads named NAME) beside this one's"""
+    def finish(result, _step):
+        if commit:
+            result["parent_commit"] = commit
+        result["parents"] = []
+        for path in paths:
+            with open(path) as f:
+                theirs = json.load(f)["workloads"]
+            entry = {"file": os.path.basename(path), "workloads": {}}
+            for name, r in result["workloads"].items():
+                p = theirs[name[:-len(tail)]]
+                assert p["workload"] == r["workload"], name
+                entry["workloads"][name] = {"ms": p["ms"], "this_over_parent": r["ms"]["median"] / p["ms"]["median"]}
+            result["parents"].append(entry)
+    return finish

@@ -28,10 +28,7 @@ Needs the GPU: there is no other path.
 """
 import argparse
 import json
-import os
-import statistics
 import sys
-import time
 
 import _benchsteps as B
 
@@ -44,34 +41,6 @@ WORKLOADS = {
 }
 LIMIT = 300                 # seconds a workload step may take
 IQ = "+iq"                  # a step name's tail: both entries, alternating
-
-
-def alternating_windows(calls, rounds, window_ms, preheat_ms):
-    """B.timed_windows for several calls at once: each preheated and its K chosen alone, then `rounds`
-    rounds of one window of each, in turn -> [(K, {"median", "min", "max"} ms per call)] in calls' order"""
-    import torch
-
-    def timed(call, k):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(k):
-            call()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / k
-
-    ks = []
-    for call in calls:
-        t0 = time.perf_counter()
-        while (time.perf_counter() - t0) * 1e3 < preheat_ms:
-            call()
-            torch.cuda.synchronize()
-        ks.append(max(2, int(window_ms / max(timed(call, 2), 1e-3))))
-    ms = [[] for _ in calls]
-    for _ in range(rounds):
-        for i, call in enumerate(calls):
-            ms[i].append(timed(call, ks[i]))
-    return [(k, {"median": statistics.median(m), "min": min(m), "max": max(m)}) for k, m in zip(ks, ms)]
 
 
 def step_workload(name, rounds, window_ms, preheat_ms):
@@ -127,7 +96,7 @@ def step_workload(name, rounds, window_ms, preheat_ms):
         def call_iq():
             M.channelize(plan, d, out=out_iq, iq=True)
 
-        (k, ms), (k_iq, ms_iq) = alternating_windows([call, call_iq], rounds, window_ms, preheat_ms)
+        (k, ms), (k_iq, ms_iq) = B.alternating_windows([call, call_iq], rounds, window_ms, preheat_ms)
         res.update(figures(k, ms, out, 4))
         res["iq"] = figures(k_iq, ms_iq, out_iq, 8)
         res["iq_over_real"] = ms_iq["median"] / ms["median"]
@@ -147,24 +116,6 @@ def show(name, r, peak):
             "", r["iq"]["ms"]["median"], r["iq_over_real"], r["ms"]["min"], r["ms"]["max"]), flush=True)
 
 
-def add_parents(paths, commit):
-    """finish() of an --iq run: the real entry's time of other commits' results beside this one's"""
-    def finish(result, _step):
-        if commit:
-            result["parent_commit"] = commit
-        result["parents"] = []
-        for path in paths:
-            with open(path) as f:
-                theirs = json.load(f)["workloads"]
-            entry = {"file": os.path.basename(path), "workloads": {}}
-            for name, r in result["workloads"].items():
-                p = theirs[name[:-len(IQ)]]
-                assert p["workload"] == r["workload"], name
-                entry["workloads"][name] = {"ms": p["ms"], "this_over_parent": r["ms"]["median"] / p["ms"]["median"]}
-            result["parents"].append(entry)
-    return finish
-
-
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--iq", action="store_true")
@@ -175,7 +126,7 @@ if __name__ == "__main__":
     if mine.iq:
         B.main(__file__, __doc__, "channelize_iq.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
                {name + IQ: w for name, w in WORKLOADS.items()}, LIMIT, step_workload, show,
-               finish=add_parents(mine.parent, mine.parent_commit))
+               finish=B.add_parents(mine.parent, mine.parent_commit, IQ))
     else:
         B.main(__file__, __doc__, "channelize.json", 600.0, "outputs x taps x 2 (real rows) or 4 (complex rows)",
                WORKLOADS, LIMIT, step_workload, show)

@@ -2,7 +2,8 @@
  * as plain nested loops with explicit fma(), sincos() and lrintf(): the yardstick of
  * tests/test_mux_args.py and tests/test_gpu_mux.py, which compile it into a temporary shared
  * object with -O2 -ffp-contract=off.  Never linked into libmifsk.so: the library has no host
- * multiplexer.
+ * multiplexer.  mux_ref_iq at the end is the same for the I/Q entry (include/mifsk/mux_iq.h, DESIGN.md
+ * 4.19; tests/test_mux_iq_args.py and tests/test_gpu_mux_iq.py).
  *
  *   cc -O2 -ffp-contract=off -shared -fPIC -o mux_ref.so tools/mux_ref.c -lm
  */
@@ -79,6 +80,79 @@ uint64_t mux_ref( const float *x, uint64_t stride, const uint32_t *len, int kind
 		    const double v = (double)x[(uint64_t)k * stride + i];
 		    re = fma(v, g[2 * t], re);
 		    im = fma(v, g[2 * t + 1], im);
+		}
+	    }
+	    if ( gains ) {
+		re = re * (double)gains[k];
+		im = im * (double)gains[k];
+	    }
+	    const int64_t dq = reduce(reduce(q[k], P) - rr, P);
+	    const int64_t p = ( dq * (int64_t)( n % P ) ) % (int64_t)P;
+	    double S, C;
+	    sincos(two_pi * (double)p / (double)P, &S, &C);
+	    o = fma(re, C, o);
+	    o = fma(-im, S, o);
+	    if ( cx ) {
+		oi = fma(re, S, oi);
+		oi = fma(im, C, oi);
+	    }
+	}
+	const float vr = n < M ? (float)o : 0.0f, vi = n < M ? (float)oi : 0.0f;
+	if ( s16 ) {
+	    int16_t *o16 = (int16_t *)out;
+	    if ( cx ) {
+		o16[2 * n] = n < M ? mux_ref_s16(vr) : 0;
+		o16[2 * n + 1] = n < M ? mux_ref_s16(vi) : 0;
+	    } else
+		o16[n] = n < M ? mux_ref_s16(vr) : 0;
+	} else {
+	    float *of = (float *)out;
+	    if ( cx ) {
+		of[2 * n] = vr;
+		of[2 * n + 1] = vi;
+	    } else
+		of[n] = vr;
+	}
+    }
+    return M;
+}
+
+/* mux_ref with I/Q rows in (include/mifsk/mux_iq.h): x is [K][stride][2] floats, len
+ * and stride count (I, Q) elements.  The tap step is the product of the complex sample and the
+ * complex table entry, four fma()s; everything else is mux_ref's, written out again. */
+uint64_t mux_ref_iq( const float *x, uint64_t stride, const uint32_t *len, int kind, uint32_t P, uint32_t T,
+	const float *h, uint32_t L, uint32_t K, const int32_t *q, int32_t r, const float *gains,
+	void *out, uint64_t out_stride, uint64_t nout_cap, double *g )
+{
+    const int cx = kind & MUX_REF_COMPLEX, s16 = kind & MUX_REF_S16;
+    const int64_t rr = reduce(r, P);
+    uint64_t nmax = 0;
+    for ( uint32_t k = 0; k < K; k++ ) {
+	const uint64_t n = len[k] < stride ? len[k] : stride;
+	if ( n > nmax )
+	    nmax = n;
+    }
+    uint64_t M = nmax ? ( nmax - 1 ) * L + T : 0;
+    if ( M > nout_cap )
+	M = nout_cap;
+    mux_ref_table(P, T, h, r, g);
+    for ( uint64_t n = 0; n < out_stride; n++ ) {
+	double o = 0.0, oi = 0.0;
+	for ( uint32_t k = 0; k < K && n < M; k++ ) {
+	    const int64_t nk = len[k] < stride ? len[k] : stride;
+	    const int64_t m = n / L;
+	    const uint64_t phi = n % L;
+	    double re = 0.0, im = 0.0;
+	    for ( uint64_t j = 0; phi + j * L < T; j++ ) {
+		const uint64_t t = phi + j * L;
+		const int64_t i = m - (int64_t)j;
+		if ( i >= 0 && i < nk ) {
+		    const double a = (double)x[2 * ( (uint64_t)k * stride + i )];
+		    const double b = (double)x[2 * ( (uint64_t)k * stride + i ) + 1];
+		    re = fma(a, g[2 * t], re);
+		    re = fma(-b, g[2 * t + 1], re);
+		    im = fma(a, g[2 * t + 1], im);
+		    im = fma(b, g[2 * t], im);
 		}
 	    }
 	    if ( gains ) {
