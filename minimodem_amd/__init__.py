@@ -24,7 +24,7 @@ from ._lib import FmDemodIO, FmModIO  # noqa: F401
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
            "gather_bytes", "shard_range", "carrier_survey", "carrier_windows", "carrier_tones",
-           "channel_taps", "ChannelPlan", "channelize",
+           "channel_taps", "ChannelPlan", "channelize", "ChannelStream", "channel_stream_outputs",
            "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table",
            "ImpairIO", "impair", "snr_sigma",
            "FmDemodIO", "FmModIO", "fm_demod", "fm_modulate", "fm_gain", "fm_step"]
@@ -742,6 +742,64 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, nout_cap)
     _call("mifsk_channelize_iq_batch" if iq else "mifsk_channelize_batch", plan.handle, C.byref(io), stream=stream)
     return out
+
+
+def channel_stream_outputs(ntaps, decim, seen, k):
+    """mifsk_channel_stream_outputs: the outputs a ChannelStream that has seen `seen` elements delivers for `k`
+    more, M(seen + k) - M(seen) with M(n) = (n - ntaps) // decim + 1 for n >= ntaps, else 0 (host only)."""
+    return int(_lib.load().mifsk_channel_stream_outputs(int(ntaps), int(decim), int(seen), int(k)))
+
+
+class ChannelStream(_Handle):
+    """mifsk_channel_stream (include/mifsk/channel_stream.h): `plan`'s channelizer fed in pieces.  The concatenated
+    outputs of the feeds are channelize's on the concatenated capture, bit for bit; every output comes with the
+    feed that brings its last element.  Counters and tails of `nstreams` streams live on the plan's device.
+    Feeds of one object are ordered by the caller: one stream, or events."""
+    _destroy = "mifsk_channel_stream_destroy"
+
+    def __init__(self, plan, nstreams):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _call("mifsk_channel_stream_create", plan.handle, int(nstreams), C.byref(h), errors=_EINVAL_IS_VALUE)
+        self.handle = h
+        self.plan, self.nstreams = plan, int(nstreams)      # the object must not outlive its plan
+
+    def feed(self, samples, nsamples=None, stream=None, out=None, iq=False):
+        """mifsk_channel_stream_feed: the next piece of every stream, as channelize takes a batch: `samples`
+        [nstreams, stride] of the plan's kind, `nsamples` None (the rows' width) or a CUDA int32/uint32 tensor
+        [nstreams] of new elements (0: the stream stays as it is).  Returns channelize's dict, {"rows",
+        "nsamples"}: what THIS piece completes, zero behind the counts.  The default out_stride is
+        ceil(width / decim) rounded up to 4 (iq=True: to 2), which no piece of that width exceeds; `out`, a dict
+        of a former feed, is reused when its tensors are of that kind.  No synchronisation is performed."""
+        torch = _torch()
+        plan = self.plan
+        kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
+        v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
+        lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
+        full = out is None and -(-v.width // plan.decim)
+        out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 2 if iq else 4, torch.float32, (2,) if iq else (),
+                           v.t.device, stream, out)
+        io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, None)
+        _call("mifsk_channel_stream_feed", self.handle, C.byref(io), _lib.CHANNEL_STREAM_IQ if iq else 0,
+              stream=stream, errors=_EINVAL_IS_VALUE)
+        return out
+
+    def seek(self, seen=None, stream=None):
+        """mifsk_channel_stream_seek: every stream has seen seen[s] elements (None: 0, the reset) and holds no
+        tail: the next output is the first m with m * decim >= seen[s].  Waits for `stream`."""
+        arr = None
+        if seen is not None:
+            arr = np.ascontiguousarray(seen, np.uint64).reshape(-1)
+            assert arr.size == self.nstreams, "one count per stream"
+        _call("mifsk_channel_stream_seek", self.handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint64)),
+              stream=stream, errors=_EINVAL_IS_VALUE)
+
+    def seen(self, stream=None):
+        """mifsk_channel_stream_seen: the elements every stream has seen, numpy uint64 [nstreams].  Waits for
+        `stream` (None: the current one)."""
+        out = np.empty(self.nstreams, np.uint64)
+        _call("mifsk_channel_stream_seen", self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), stream=stream)
+        return out
 
 
 def _mux_params(taps, interp, centres, in_centre, phase_steps, complex_output, s16, gains):

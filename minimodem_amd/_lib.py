@@ -478,6 +478,19 @@ EXTENSIONS = {
     "mifsk/mux_iq.h": {"mifsk_multiplex_iq_batch": (_int, [_vp, _P(MuxIO), _vp])},
 }
 
+# include/mifsk/channel_stream.h, the channelizer fed in pieces: a third extension header.  Its table is a name
+# of its own (EXTENSIONS stays the two stateless entries' headers), which load() binds as well.
+CHANNEL_STREAM_IQ = 1
+STREAM_HEADER = "mifsk/channel_stream.h"
+STREAM_SIGNATURES = {
+    "mifsk_channel_stream_create": (_int, [_vp, _int, _P(_vp)]),
+    "mifsk_channel_stream_destroy": (None, [_vp]),
+    "mifsk_channel_stream_feed": (_int, [_vp, _P(ChannelIO), _u32, _vp]),
+    "mifsk_channel_stream_seek": (_int, [_vp, _P(_u64), _vp]),
+    "mifsk_channel_stream_seen": (_int, [_vp, _P(_u64), _vp]),
+    "mifsk_channel_stream_outputs": (_u64, [_u32, _u32, _u64, _u64]),
+}
+
 _lib = None
 
 
@@ -490,7 +503,7 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in [SIGNATURES] + list(EXTENSIONS.values()):
+    for table in [SIGNATURES] + list(EXTENSIONS.values()) + [STREAM_SIGNATURES]:
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

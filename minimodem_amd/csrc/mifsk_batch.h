@@ -93,6 +93,24 @@ inline RowsIn rows_in( const IO *io )
     return RowsIn{io->d_samples, io->stream_stride, io->d_nsamples, io->nsamples};
 }
 
+// What the channelizer's and the multiplexer's entries refuse of an io (mifsk_channel_io, mifsk_mux_io:
+// rows in, d_nout, out_stride, nout_cap; `d_out` its output rows), in the headers' order: `in_vec` and
+// `out_vec` elements are 16 bytes of an input and an output row, an output row is out_max elements at
+// most, K rows go out per stream.
+template <class IO>
+inline int rows_io_check( uint32_t K, const IO *io, const void *d_out, uint32_t in_vec, uint32_t out_vec, uint64_t out_max )
+{
+    if ( !io->d_samples || !d_out || !io->d_nout || io->nstreams <= 0 )
+	return -EINVAL;
+    if ( !rows_aligned(io->d_samples, io->stream_stride, in_vec) )
+	return -EINVAL;
+    if ( int rc = out_rows_check(d_out, io->out_stride, out_vec, out_max) )
+	return rc;
+    if ( io->nout_cap > io->out_stride || (uint64_t)io->nstreams * K > 0x7FFFFFFFull )
+	return -EINVAL;
+    return 0;
+}
+
 // f(complex rows, PCM16 scalars) with both as compile-time constants
 template <class F>
 inline int dispatch_kind( bool cx, bool s16, F &&f )

@@ -1,7 +1,8 @@
 // mifsk_channel.hip -- the channelizer (include/mifsk.h): mifsk_channel_plan_create / _destroy,
 // mifsk_channelize_batch, the host helpers mifsk_channel_table and mifsk_channel_taps, and
 // mifsk_channelize_iq_batch (include/mifsk/channel_iq.h): the same kernel body with the epilogue that
-// keeps both halves of the rotated sum.
+// keeps both halves of the rotated sum.  The plan, the kernel's arguments and the geometry of a launch
+// are in mifsk_channel_plan.h, which mifsk_channel_stream.hip (rows fed in pieces) shares.
 //
 // One output sample is a window sum of carrier_survey_kernel's kind -- the complex sum kept, the
 // rectangle replaced by a filter's taps, then rotated to the output tone -- so the kernel is laid
@@ -40,55 +41,10 @@
 
 #include "mifsk.h"
 #include "mifsk/channel_iq.h"
+#include "mifsk_channel_plan.h"
 #include "mifsk_ctx.h"
-#include "mifsk_phase.h"
-#include "mifsk_rows.h"
 
 namespace mifsk {
-
-constexpr int kChO = 8;					// outputs per lane
-constexpr uint32_t kChWaves = 4u;			// waves of a workgroup
-constexpr uint32_t kChTile = 64u;			// taps staged at a time, at most
-constexpr uint32_t kChLdsTwo = 64u * 1024u;		// two workgroups per CU up to here
-constexpr uint32_t kChLdsMax = 144u * 1024u;
-constexpr uint32_t kChMaxD = 65535u;
-constexpr uint64_t kChMaxKT = 1ull << 22;
-
-struct ChannelArgs {
-    const double2	*gt;		// G transposed, [T][K]
-    const double2	*w;		// [P]: cos, sin
-    const uint32_t	*dq;		// [K]: (r - q[k]) mod P
-    RowsIn		in;		// elements
-    uint32_t		T, D, K, P;
-    uint32_t		s0;		// first stream of this launch
-    uint32_t		cwshift;	// cw = 1 << cwshift channel lanes of a wave
-    uint32_t		tt;		// taps per tile, a power of two
-    uint32_t		ss;		// LDS samples between neighbouring outputs: D, or tt + 1
-    float		*rows;
-    size_t		out_stride;
-    uint32_t		nout_cap;
-    uint32_t		*nout;
-};
-
-// element `at` of a row as the definition widens it
-template <bool CX, bool S16>
-__device__ __forceinline__ auto channel_sample( const void *row, uint64_t at )
-{
-    if constexpr ( CX ) {
-	if constexpr ( S16 ) {
-	    const short2 v = reinterpret_cast<const short2 *>(row)[at];
-	    return double2{(double)rows_f32(v.x), (double)rows_f32(v.y)};
-	} else {
-	    const float2 v = reinterpret_cast<const float2 *>(row)[at];
-	    return double2{(double)v.x, (double)v.y};
-	}
-    } else {
-	if constexpr ( S16 )
-	    return (double)rows_f32(reinterpret_cast<const int16_t *>(row)[at]);
-	else
-	    return (double)reinterpret_cast<const float *>(row)[at];
-    }
-}
 
 // NC: channels per lane.  CX: complex rows.  S16: PCM16 scalars.  IQ: the epilogue of
 // mifsk_channelize_iq_batch (include/mifsk/channel_iq.h): rows are [out_stride] (I, Q) pairs, I the
@@ -251,11 +207,6 @@ void channel_table( const mifsk_channel_params *p, uint32_t k, double2 *g, size_
 } // namespace
 } // namespace mifsk
 
-struct mifsk_channel_plan : mifsk::PhasePlanCommon {
-    uint32_t			D;
-    mifsk::DevMem<double2>	gt;
-};
-
 extern "C" int mifsk_channel_table( const mifsk_channel_params *params, uint32_t k, double *g_out )
 {
     if ( int rc = mifsk::channel_check_params(params) )
@@ -333,53 +284,13 @@ static int channelize_rows( const mifsk_channel_plan *plan, const mifsk_channel_
     if ( int rc = phase_check_io(*plan, io, io->d_rows, rows_vec(plan->cx, plan->s16), out_vec, out_max) )
 	return rc;
 
-    ChannelArgs A = {};
-    A.gt = plan->gt.p;
-    A.w = plan->w.p;
-    A.dq = plan->dq.p;
-    A.in = rows_in(io);
-    A.T = plan->T;
-    A.D = plan->D;
-    A.K = plan->K;
-    A.P = plan->P;
-    A.rows = io->d_rows;
-    A.out_stride = io->out_stride;
-    A.nout_cap = io->nout_cap;
-    A.nout = io->d_nout;
-
-    // two channels per lane as soon as there are two; cw channel lanes, the rest of a wave's lanes
-    // are groups of outputs
-    const uint32_t nc = plan->K > 1u ? 2u : 1u;
-    const uint32_t ncl = ( plan->K + nc - 1u ) / nc;
-    while ( ( 1u << A.cwshift ) < ncl && A.cwshift < 6u )
-	A.cwshift++;
-    const uint32_t C = ( 1u << A.cwshift ) * nc;
-    const uint32_t OB = kChWaves * ( 64u >> A.cwshift ) * (uint32_t)kChO;
-    // the tile of taps: the largest power of two with which table and samples fit, two workgroups
-    // per CU down to 16 taps
-    const size_t esz = plan->cx ? 16u : 8u;
-    auto lds_of = [&]( uint32_t tt ) {
-	const uint32_t ss = A.D < tt ? A.D : tt + 1u;
-	return (size_t)tt * C * sizeof(double2) + ( (size_t)( OB - 1u ) * ss + tt ) * esz;
-    };
-    uint32_t tt = kChTile;
-    while ( tt / 2u >= A.T )
-	tt /= 2u;
-    uint32_t two = tt;
-    while ( two > 16u && lds_of(two) > kChLdsTwo )
-	two /= 2u;
-    if ( lds_of(two) <= kChLdsTwo )
-	tt = two;
-    while ( tt > 1u && lds_of(tt) > kChLdsMax )
-	tt /= 2u;
-    A.tt = tt;
-    A.ss = A.D < tt ? A.D : tt + 1u;
-    const size_t lds = lds_of(tt);
+    const ChannelGeometry g = channel_geometry(*plan);
+    ChannelArgs A = channel_args(*plan, io, g);
 
     if ( hipSetDevice(plan->device) != hipSuccess )
 	return -EIO;
-    const uint32_t nchunks = (uint32_t)( ( io->out_stride + OB - 1u ) / OB );
-    const uint32_t gz = ( plan->K + C - 1u ) / C;
+    const uint32_t nchunks = (uint32_t)( ( io->out_stride + g.OB - 1u ) / g.OB );
+    const uint32_t gz = ( plan->K + g.C - 1u ) / g.C;
     const hipStream_t st = (hipStream_t)stream;
     return for_row_blocks((uint32_t)io->nstreams, [&]( uint32_t s0, uint32_t rows ) {
 	A.s0 = s0;
@@ -389,10 +300,10 @@ static int channelize_rows( const mifsk_channel_plan *plan, const mifsk_channel_
 		constexpr int NC = decltype(per_lane)::value;
 		constexpr bool CX = decltype(cx)::value, S16 = decltype(s16)::value;
 		return launch_lds(iq ? channelize_kernel<NC, CX, S16, true> : channelize_kernel<NC, CX, S16, false>,
-				  grid, block, lds, st, A);
+				  grid, block, g.lds, st, A);
 	    });
 	};
-	return nc == 2u ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
+	return g.nc == 2u ? launch(std::integral_constant<int, 2>{}) : launch(std::integral_constant<int, 1>{});
     });
 }
 

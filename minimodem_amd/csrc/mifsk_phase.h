@@ -142,21 +142,12 @@ void phase_plan_destroy( Plan *plan )
     delete plan;
 }
 
-// What both batch entries refuse of their rows: `in_vec` and `out_vec` elements are 16 bytes of an
-// input and an output row, an output row is out_max elements at most.
+// What both batch entries refuse of their rows (rows_io_check of mifsk_batch.h, K the plan's)
 template <class IO>
 int phase_check_io( const PhasePlanCommon &plan, const IO *io, const void *d_out, uint32_t in_vec, uint32_t out_vec,
 	uint64_t out_max )
 {
-    if ( !io->d_samples || !d_out || !io->d_nout || io->nstreams <= 0 )
-	return -EINVAL;
-    if ( !rows_aligned(io->d_samples, io->stream_stride, in_vec) )
-	return -EINVAL;
-    if ( int rc = out_rows_check(d_out, io->out_stride, out_vec, out_max) )
-	return rc;
-    if ( io->nout_cap > io->out_stride || (uint64_t)io->nstreams * plan.K > 0x7FFFFFFFull )
-	return -EINVAL;
-    return 0;
+    return rows_io_check(plan.K, io, d_out, in_vec, out_vec, out_max);
 }
 
 } // namespace mifsk
