@@ -715,6 +715,19 @@ class ChannelPlan(_PhasePlan):
         self.decim, self.complex_input = p.decim, bool(complex_input)
 
 
+def _channel_io(plan, samples, nsamples, full, nout_cap, stream, out, iq):
+    """What channelize and ChannelStream.feed do in front of their entry: `samples` and `nsamples` checked
+    against the plan's kind, the outputs made (full(width): the outputs a row of that width needs room for)
+    or `out` taken over -> (the outputs' dict, the mifsk_channel_io of the call)."""
+    torch = _torch()
+    kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
+    v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
+    out = _row_outputs(torch, v.nstreams * plan.nchannels, out is None and full(v.width), 2 if iq else 4, torch.float32,
+                       (2,) if iq else (), v.t.device, stream, out)
+    return out, _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, nout_cap)
+
+
 def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None, iq=False):
     """mifsk_channelize_batch: every channel of every row as a row demod_batch takes; with iq=True
     mifsk_channelize_iq_batch: every channel as a row of I, Q pairs, which fm_demod takes (plan the
@@ -732,14 +745,9 @@ def channelize(plan, samples, nsamples=None, nout_cap=None, stream=None, out=Non
     iq=True : "rows" is float32 [nstreams * nchannels, out_stride, 2], element m of a row (I, Q); out_stride
               and nout_cap count such elements (None: what a full row gives, at least 2, rounded up to 2);
               "rows" and "nsamples" are what fm_demod takes as iq and nsamples."""
-    torch = _torch()
-    kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
-    v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
-    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
-    full = out is None and (carrier_windows(v.width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap))
-    out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 2 if iq else 4, torch.float32, (2,) if iq else (),
-                       v.t.device, stream, out)
-    io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, nout_cap)
+    def full(width):
+        return carrier_windows(width, plan.ntaps, plan.decim) if nout_cap is None else int(nout_cap)
+    out, io = _channel_io(plan, samples, nsamples, full, nout_cap, stream, out, iq)
     _call("mifsk_channelize_iq_batch" if iq else "mifsk_channelize_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
@@ -771,15 +779,7 @@ class ChannelStream(_Handle):
         "nsamples"}: what THIS piece completes, zero behind the counts.  The default out_stride is
         ceil(width / decim) rounded up to 4 (iq=True: to 2), which no piece of that width exceeds; `out`, a dict
         of a former feed, is reused when its tensors are of that kind.  No synchronisation is performed."""
-        torch = _torch()
-        plan = self.plan
-        kinds = (torch.int16,) if plan.s16 else (torch.float32, torch.complex64) if plan.complex_input else (torch.float32,)
-        v = _row_view(torch, samples, cx=plan.complex_input, dtypes=kinds, unit="elements")
-        lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
-        full = out is None and -(-v.width // plan.decim)
-        out = _row_outputs(torch, v.nstreams * plan.nchannels, full, 2 if iq else 4, torch.float32, (2,) if iq else (),
-                           v.t.device, stream, out)
-        io = _phase_io(_lib.ChannelIO(), "d_rows", v, lens, v.nstreams, out, None)
+        out, io = _channel_io(self.plan, samples, nsamples, lambda width: -(-width // self.plan.decim), None, stream, out, iq)
         _call("mifsk_channel_stream_feed", self.handle, C.byref(io), _lib.CHANNEL_STREAM_IQ if iq else 0,
               stream=stream, errors=_EINVAL_IS_VALUE)
         return out

@@ -93,6 +93,15 @@ inline RowsIn rows_in( const IO *io )
     return RowsIn{io->d_samples, io->stream_stride, io->d_nsamples, io->nsamples};
 }
 
+// An output element of the channelizer is a float, or with `iq` an (I, Q) pair: `vec` of them are 16
+// bytes, a row is `max` of them at most
+struct OutKind {
+    uint32_t	vec;
+    uint64_t	max;
+};
+
+constexpr OutKind channel_out_kind( bool iq ) { return iq ? OutKind{2u, 0x7FFFFFFEull} : OutKind{4u, 0xFFFFFFFCull}; }
+
 // What the channelizer's and the multiplexer's entries refuse of an io (mifsk_channel_io, mifsk_mux_io:
 // rows in, d_nout, out_stride, nout_cap; `d_out` its output rows), in the headers' order: `in_vec` and
 // `out_vec` elements are 16 bytes of an input and an output row, an output row is out_max elements at

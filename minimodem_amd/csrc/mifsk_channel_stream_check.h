@@ -78,9 +78,8 @@ inline uint64_t stream_kmax( const IO *io )
 // M(seen + k) - M(seen) <= ceil(k / D) outputs per row, and dropping one would break the continuation.
 inline int stream_feed_check( const StreamShape &sh, const mifsk_channel_io *io, uint32_t flags )
 {
-    const bool iq = ( flags & MIFSK_CHANNEL_STREAM_IQ ) != 0u;
-    if ( int rc = rows_io_check(sh.K, io, io->d_rows, rows_vec(sh.cx, sh.s16), iq ? 2u : 4u,
-				iq ? 0x7FFFFFFEull : 0xFFFFFFFCull) )
+    const OutKind ok = channel_out_kind(( flags & MIFSK_CHANNEL_STREAM_IQ ) != 0u);
+    if ( int rc = rows_io_check(sh.K, io, io->d_rows, rows_vec(sh.cx, sh.s16), ok.vec, ok.max) )
 	return rc;
     if ( io->nstreams != sh.nstreams )
 	return -EINVAL;
