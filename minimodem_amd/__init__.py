@@ -876,6 +876,72 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     return out
 
 
+def mux_stream_drain(ntaps, interp):
+    """mifsk_mux_stream_drain: H = ceil(ntaps / interp) - 1, the samples of +0.0 that, fed behind the last piece
+    of a MuxStream, bring out the rest of the filter's tail; 0 for interp == 0 (host only)."""
+    return int(_lib.load().mifsk_mux_stream_drain(int(ntaps), int(interp)))
+
+
+class MuxStream(_Handle):
+    """mifsk_mux_stream (include/mifsk/mux_stream.h): `plan`'s multiplexer fed in pieces.  The concatenated outputs
+    of the feeds are multiplex's on the concatenated rows, bit for bit, on the first N * interp elements (N: the
+    rows' length); mux_stream_drain(ntaps, interp) more samples of 0.0 bring out the filter's tail.  iq=True: the
+    input rows are (I, Q) pairs, as multiplex(..., iq=True) takes them; the kind is fixed at creation.  Counters
+    and tails of `nstreams` streams live on the plan's device.  Feeds of one object are ordered by the caller: one
+    stream, or events."""
+    _destroy = "mifsk_mux_stream_destroy"
+
+    def __init__(self, plan, nstreams, iq=False):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _call("mifsk_mux_stream_create", plan.handle, int(nstreams), _lib.MUX_STREAM_IQ if iq else 0, C.byref(h),
+              errors=_EINVAL_IS_VALUE)
+        self.handle = h
+        self.plan, self.nstreams, self.iq = plan, int(nstreams), bool(iq)   # the object must not outlive its plan
+
+    def feed(self, samples, nsamples=None, stream=None, out=None):
+        """mifsk_mux_stream_feed: the next piece of every row, as multiplex takes a batch: `samples`
+        [nstreams * nchannels, stride] float32 (iq: [.., stride, 2] or complex64), `nsamples` None (the rows'
+        width) or a CUDA int32/uint32 tensor [nstreams * nchannels] of new samples.  A stream advances by the
+        longest of its rows, k; shorter rows are continued with 0.0 (all 0: the stream stays as it is).  Returns
+        multiplex's dict, {"rows", "nsamples"}: the k * interp outputs of THIS piece, zero behind the counts.  The
+        default out_stride is width * interp rounded up to the output kind's vector, which no piece of that
+        width exceeds; `out`, a dict of a former feed, is reused when its tensors are of that kind.  No
+        synchronisation is performed."""
+        torch = _torch()
+        plan = self.plan
+        if self.iq:
+            v = _row_view(torch, samples, cx=True, dtypes=(torch.float32, torch.complex64), one_row=False, unit="elements")
+        else:
+            v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
+        assert v.nstreams == self.nstreams * plan.nchannels, "samples holds nchannels rows per stream"
+        lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
+        dtype = torch.int16 if plan.s16 else torch.float32
+        vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
+        out = _row_outputs(torch, self.nstreams, out is None and v.width * plan.interp, vec, dtype,
+                           (2,) if plan.complex_output else (), samples.device, stream, out)
+        io = _phase_io(_lib.MuxIO(), "d_out", v, lens, self.nstreams, out, None)
+        _call("mifsk_mux_stream_feed", self.handle, C.byref(io), stream=stream, errors=_EINVAL_IS_VALUE)
+        return out
+
+    def seek(self, seen=None, stream=None):
+        """mifsk_mux_stream_seek: every stream has taken seen[s] samples (None: 0, the reset) and nothing in front
+        of them exists: the next feed delivers the outputs from seen[s] * interp on.  Waits for `stream`."""
+        arr = None
+        if seen is not None:
+            arr = np.ascontiguousarray(seen, np.uint64).reshape(-1)
+            assert arr.size == self.nstreams, "one count per stream"
+        _call("mifsk_mux_stream_seek", self.handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint64)),
+              stream=stream, errors=_EINVAL_IS_VALUE)
+
+    def seen(self, stream=None):
+        """mifsk_mux_stream_seen: the samples every stream has taken, numpy uint64 [nstreams].  Waits for
+        `stream` (None: the current one)."""
+        out = np.empty(self.nstreams, np.uint64)
+        _call("mifsk_mux_stream_seen", self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), stream=stream)
+        return out
+
+
 def snr_sigma(amplitude, snr_db):
     """mifsk_impair_sigma: the noise sigma that puts a tone of `amplitude` (power amplitude^2 / 2) at
     snr_db; float("inf") gives 0.0."""

@@ -491,6 +491,19 @@ STREAM_SIGNATURES = {
     "mifsk_channel_stream_outputs": (_u64, [_u32, _u32, _u64, _u64]),
 }
 
+# include/mifsk/mux_stream.h, the multiplexer fed in pieces: the fourth extension header, bound like the third
+# from a table of its own (SIGNATURES, EXPORTS, EXT_SIGNATURES, EXTENSIONS and STREAM_SIGNATURES stay as they are).
+MUX_STREAM_IQ = 1
+MUX_STREAM_HEADER = "mifsk/mux_stream.h"
+MUX_STREAM_SIGNATURES = {
+    "mifsk_mux_stream_create": (_int, [_vp, _int, _u32, _P(_vp)]),
+    "mifsk_mux_stream_destroy": (None, [_vp]),
+    "mifsk_mux_stream_feed": (_int, [_vp, _P(MuxIO), _vp]),
+    "mifsk_mux_stream_seek": (_int, [_vp, _P(_u64), _vp]),
+    "mifsk_mux_stream_seen": (_int, [_vp, _P(_u64), _vp]),
+    "mifsk_mux_stream_drain": (_u32, [_u32, _u32]),
+}
+
 _lib = None
 
 
@@ -503,7 +516,7 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in [SIGNATURES] + list(EXTENSIONS.values()) + [STREAM_SIGNATURES]:
+    for table in [SIGNATURES] + list(EXTENSIONS.values()) + [STREAM_SIGNATURES, MUX_STREAM_SIGNATURES]:
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes
