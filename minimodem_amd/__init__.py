@@ -20,6 +20,7 @@ from ._lib import ModemArgs, RxConfig  # noqa: F401
 from ._lib import MUX_COMPLEX, MuxIO, MuxParams  # noqa: F401
 from ._lib import ImpairIO  # noqa: F401
 from ._lib import FmDemodIO, FmModIO  # noqa: F401
+from ._lib import FmSquelchIO  # noqa: F401
 
 __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "find_frame_batch",
            "LegacyPlan", "synthesize", "FRAME_DTYPE", "EPISODE_DTYPE",
@@ -27,7 +28,8 @@ __all__ = ["build", "rx_config", "Context", "demod_batch", "frame_softbits", "fi
            "channel_taps", "ChannelPlan", "channelize", "ChannelStream", "channel_stream_outputs",
            "MUX_COMPLEX", "MuxParams", "MuxIO", "MuxPlan", "multiplex", "mux_table",
            "ImpairIO", "impair", "snr_sigma",
-           "FmDemodIO", "FmModIO", "fm_demod", "fm_modulate", "fm_gain", "fm_step"]
+           "FmDemodIO", "FmModIO", "fm_demod", "fm_modulate", "fm_gain", "fm_step",
+           "FmSquelchIO", "fm_squelch", "squelch_level"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -1081,6 +1083,78 @@ def fm_modulate(ctx, samples, nsamples=None, deviation=None, centre=0.0, amplitu
             setattr(io, name, t.data_ptr())
     _call("mifsk_fm_modulate_batch", ctx.handle, C.byref(io), stream=stream)
     return out
+
+
+def squelch_level(dbfs, window):
+    """mifsk_fm_squelch_level: the energy of a window of `window` samples at dbfs (0 dBFS: |z| = 1), the
+    unit of fm_squelch's levels."""
+    return int(_lib.load().mifsk_fm_squelch_level(C.c_double(dbfs), C.c_uint32(window)))
+
+
+def fm_squelch(ctx, iq, nsamples=None, window=None, open_db=None, close_db=None, hang=0, state=None, audio=None,
+               span_cap=8, stream=None, out=None):
+    """mifsk_fm_squelch_batch, the FM stage's power squelch (include/mifsk/squelch.h): the energy of every
+    window of `window` samples of the I/Q rows as an integer, a gate with hysteresis and a hang time over the
+    windows, the spans in which each row was keyed, and zeros over the discriminator's audio where the gate is
+    closed -- all of it the same bits for a capture fed whole or in pieces (tools/squelch_ref.c).
+
+    iq      : what fm_demod takes: CUDA tensor [nstreams, stride, 2], float32 or int16 (PCM16)
+    nsamples: None (the rows' width), an int, or a torch.int32/uint32 CUDA tensor [nstreams]
+    window  : B, samples per window, 1 .. 32768; windows lie on the grid of the samples since the state's start
+    open_db, close_db: the gate opens at a window of open_db dBFS and counts one below close_db (None:
+              open_db) as low: squelch_level(db, window) each
+    hang    : low windows in a row that leave the gate open
+    state   : None (all zero), or the "state" of a former call: taken as the start and overwritten with the
+              end, so a live capture hands one tensor from piece to piece
+    audio   : None, or fm_demod's output for the same rows, float32 [nstreams, audio_stride >= width]: zeroed
+              where the gate of that moment is closed (it opens one window late), untouched elsewhere
+    span_cap: spans stored per row (the count is the true one)
+    out     : a former call's dict to write into; None: new tensors, made on the launch stream
+    Returns {"energy": int64 [nstreams, win_stride] (the bits of uint64), "gate": uint8 [nstreams,
+    win_stride], "nwindows": int32 [nstreams], "spans": int64 [nstreams, span_cap, 2] (first window, the
+    window behind the last), "nspans": int32 [nstreams], "state": uint8 [nstreams, 32]
+    (mifsk_fm_squelch_state)}; entry j of a row is window state.seen // window + j, entries behind nwindows and
+    nspans are not written.  No synchronisation is performed."""
+    torch = _torch()
+    assert window is not None and open_db is not None, "window and open_db have no default"
+    v = _row_view(torch, iq, cx=True, one_row=False, unit="elements")
+    nstreams = v.nstreams
+    lens = _row_lengths(torch, nsamples, nstreams, v.width, allow_int=True)
+    kmax = v.stride if lens[0] is not None else min(lens[1], v.stride)
+    win_stride = kmax // int(window) + 1
+    level = [squelch_level(db, window) for db in (open_db, open_db if close_db is None else close_db)]
+    if state is None:
+        state = _new_outputs(torch, {"state": ((nstreams, 32), torch.uint8, 0)}, iq.device, stream)["state"]
+    assert state.is_cuda and state.dtype == torch.uint8 and state.shape == (nstreams, 32) and state.is_contiguous(), \
+        "state: a uint8 CUDA tensor [nstreams, 32]"
+    if out is None:
+        out = _new_outputs(torch, {"energy": ((nstreams, win_stride), torch.int64, None),
+                                   "gate": ((nstreams, win_stride), torch.uint8, None),
+                                   "nwindows": ((nstreams,), torch.int32, None),
+                                   "spans": ((nstreams, int(span_cap), 2), torch.int64, None),
+                                   "nspans": ((nstreams,), torch.int32, None)}, iq.device, stream)
+    for name, dtype, tail in (("energy", torch.int64, ()), ("gate", torch.uint8, ())):
+        _check_out_rows(torch, out[name], (dtype,), nstreams, tail)
+    assert out["energy"].shape[1] == out["gate"].shape[1], "energy and gate rows are equally far apart"
+    for name in ("nwindows", "nspans"):
+        assert out[name].is_cuda and out[name].dtype == torch.int32 and out[name].shape == (nstreams,) \
+            and out[name].is_contiguous(), "%s: an int32 CUDA tensor [nstreams]" % name
+    spans = out["spans"]
+    assert spans.is_cuda and spans.dtype == torch.int64 and spans.dim() == 3 and spans.shape[0] == nstreams \
+        and spans.shape[2] == 2 and spans.is_contiguous(), "spans: an int64 CUDA tensor [nstreams, span_cap, 2]"
+    io = _rows_io(_lib.FmSquelchIO(), v, lens)
+    io.kind, io.window, io.hang = _kind(v.s16), int(window), int(hang)
+    io.open_level, io.close_level = level
+    io.d_state = io.d_state_out = state.data_ptr()
+    io.d_energy, io.d_gate, io.win_stride = out["energy"].data_ptr(), out["gate"].data_ptr(), int(out["energy"].shape[1])
+    io.d_nwindows, io.d_nspans = out["nwindows"].data_ptr(), out["nspans"].data_ptr()
+    io.d_spans, io.span_cap = (spans.data_ptr() if spans.shape[1] else None), int(spans.shape[1])
+    if audio is not None:
+        assert audio.is_cuda and audio.dtype == torch.float32 and audio.dim() == 2 and audio.shape[0] == nstreams \
+            and audio.stride(1) == 1, "audio: fm_demod's float32 rows"
+        io.d_audio, io.audio_stride = audio.data_ptr(), int(audio.stride(0)) if nstreams > 1 else int(audio.shape[1])
+    _call("mifsk_fm_squelch_batch", ctx.handle, C.byref(io), stream=stream, errors=_EINVAL_IS_VALUE)
+    return dict(out, state=state)
 
 
 def demod_plan(ctx, cfg, nstreams, ring_exact=False, engine=None, nsamples=None):

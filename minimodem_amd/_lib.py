@@ -504,6 +504,40 @@ MUX_STREAM_SIGNATURES = {
     "mifsk_mux_stream_drain": (_u32, [_u32, _u32]),
 }
 
+# include/mifsk/squelch.h, the FM stage's power squelch: the fifth extension header, the first that brings
+# structs.  Its mirrors, their table and the binding table are names of their own: STRUCTS and the five
+# tables above stay as they are.
+SQUELCH_HEADER = "mifsk/squelch.h"
+
+
+class FmSquelchState(C.Structure):
+    _fields_ = [("seen", C.c_uint64), ("acc", C.c_uint64), ("span_first", C.c_uint64),
+                ("open", C.c_uint32), ("low", C.c_uint32)]
+
+
+class FmSquelchSpan(C.Structure):
+    _fields_ = [("first_window", C.c_uint64), ("end_window", C.c_uint64)]
+
+
+class FmSquelchIO(C.Structure):
+    _fields_ = ROWS_FIELDS + [("kind", C.c_uint32), ("flags", C.c_uint32), ("window", C.c_uint32), ("hang", C.c_uint32),
+                              ("open_level", C.c_uint64), ("close_level", C.c_uint64),
+                              ("d_state", C.c_void_p), ("d_state_out", C.c_void_p),
+                              ("d_energy", C.c_void_p), ("d_gate", C.c_void_p), ("win_stride", C.c_size_t),
+                              ("d_nwindows", C.c_void_p), ("d_spans", C.c_void_p), ("d_nspans", C.c_void_p),
+                              ("span_cap", C.c_uint32), ("reserved", C.c_uint32),
+                              ("d_audio", C.c_void_p), ("audio_stride", C.c_size_t)]
+
+
+SQUELCH_STRUCTS = {"mifsk_fm_squelch_state": FmSquelchState, "mifsk_fm_squelch_span": FmSquelchSpan,
+                   "mifsk_fm_squelch_io": FmSquelchIO}
+assert [C.sizeof(t) for t in SQUELCH_STRUCTS.values()] == [32, 16, 152]
+assert FmSquelchState.open.offset == 24 and FmSquelchIO.open_level.offset == 48 and FmSquelchIO.d_audio.offset == 136
+SQUELCH_SIGNATURES = {
+    "mifsk_fm_squelch_batch": (_int, [_vp, _P(FmSquelchIO), _vp]),
+    "mifsk_fm_squelch_level": (_u64, [_f64, _u32]),
+}
+
 _lib = None
 
 
@@ -516,7 +550,7 @@ def load():
             "%s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  minimodem_amd has no fallback path." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for table in [SIGNATURES] + list(EXTENSIONS.values()) + [STREAM_SIGNATURES, MUX_STREAM_SIGNATURES]:
+    for table in [SIGNATURES] + list(EXTENSIONS.values()) + [STREAM_SIGNATURES, MUX_STREAM_SIGNATURES, SQUELCH_SIGNATURES]:
         for name, (restype, argtypes) in table.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -5,7 +5,7 @@
 set -e
 cd "$(dirname "$0")/../minimodem_amd/csrc"
 TMP=$(mktemp -d)
-for f in ${KERNEL_FILES:-mifsk_kernels mifsk_wave mifsk_ingest mifsk_txdev mifsk_softbits mifsk_carrier mifsk_channel mifsk_channel_stream mifsk_mux mifsk_mux_stream mifsk_impair mifsk_fm}; do
+for f in ${KERNEL_FILES:-mifsk_kernels mifsk_wave mifsk_ingest mifsk_txdev mifsk_softbits mifsk_carrier mifsk_channel mifsk_channel_stream mifsk_mux mifsk_mux_stream mifsk_impair mifsk_fm mifsk_squelch}; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I../../include -I. "$@" \
         --cuda-device-only --no-gpu-bundle-output -c $f.hip -o $TMP/$f.o
     /opt/rocm/lib/llvm/bin/llvm-readelf --notes $TMP/$f.o | python3 -c '
