@@ -677,6 +677,35 @@ class _PhasePlan(_Handle):
         return p
 
 
+class _RowStream(_Handle):
+    """what ChannelStream and MuxStream share: the object that the entries named `_entry`_... make of a plan for
+    `nstreams` streams, and its counters"""
+
+    def _create(self, plan, nstreams, *flags):
+        self._lib, self._destroy = _lib.load(), self._entry + "_destroy"
+        h = C.c_void_p()
+        _call(self._entry + "_create", plan.handle, int(nstreams), *flags, C.byref(h), errors=_EINVAL_IS_VALUE)
+        self.handle = h
+        self.plan, self.nstreams = plan, int(nstreams)      # the object must not outlive its plan
+
+    def seek(self, seen=None, stream=None):
+        """..._seek: every stream has seen seen[s] elements (None: 0, the reset) and reads nothing in front of
+        them again; the class says where the outputs go on.  Waits for `stream`."""
+        arr = None
+        if seen is not None:
+            arr = np.ascontiguousarray(seen, np.uint64).reshape(-1)
+            assert arr.size == self.nstreams, "one count per stream"
+        _call(self._entry + "_seek", self.handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint64)),
+              stream=stream, errors=_EINVAL_IS_VALUE)
+
+    def seen(self, stream=None):
+        """..._seen: the elements every stream has seen, numpy uint64 [nstreams].  Waits for `stream` (None: the
+        current one)."""
+        out = np.empty(self.nstreams, np.uint64)
+        _call(self._entry + "_seen", self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), stream=stream)
+        return out
+
+
 def _row_outputs(torch, nrows, full, vec, dtype, tail, device, stream, out):
     """The outputs of channelize and multiplex, {"rows": `dtype` [nrows, out_stride, *tail], "nsamples":
     int32 [nrows]}: made on the launch stream, out_stride the whole vectors of `vec` elements that hold
@@ -760,19 +789,16 @@ def channel_stream_outputs(ntaps, decim, seen, k):
     return int(_lib.load().mifsk_channel_stream_outputs(int(ntaps), int(decim), int(seen), int(k)))
 
 
-class ChannelStream(_Handle):
+class ChannelStream(_RowStream):
     """mifsk_channel_stream (include/mifsk/channel_stream.h): `plan`'s channelizer fed in pieces.  The concatenated
     outputs of the feeds are channelize's on the concatenated capture, bit for bit; every output comes with the
     feed that brings its last element.  Counters and tails of `nstreams` streams live on the plan's device.
-    Feeds of one object are ordered by the caller: one stream, or events."""
-    _destroy = "mifsk_channel_stream_destroy"
+    Feeds of one object are ordered by the caller: one stream, or events.  Behind seek(seen) a stream holds no
+    tail: its next output is the first m with m * decim >= seen[s]."""
+    _entry = "mifsk_channel_stream"
 
     def __init__(self, plan, nstreams):
-        self._lib = _lib.load()
-        h = C.c_void_p()
-        _call("mifsk_channel_stream_create", plan.handle, int(nstreams), C.byref(h), errors=_EINVAL_IS_VALUE)
-        self.handle = h
-        self.plan, self.nstreams = plan, int(nstreams)      # the object must not outlive its plan
+        self._create(plan, nstreams)
 
     def feed(self, samples, nsamples=None, stream=None, out=None, iq=False):
         """mifsk_channel_stream_feed: the next piece of every stream, as channelize takes a batch: `samples`
@@ -784,23 +810,6 @@ class ChannelStream(_Handle):
         out, io = _channel_io(self.plan, samples, nsamples, lambda width: -(-width // self.plan.decim), None, stream, out, iq)
         _call("mifsk_channel_stream_feed", self.handle, C.byref(io), _lib.CHANNEL_STREAM_IQ if iq else 0,
               stream=stream, errors=_EINVAL_IS_VALUE)
-        return out
-
-    def seek(self, seen=None, stream=None):
-        """mifsk_channel_stream_seek: every stream has seen seen[s] elements (None: 0, the reset) and holds no
-        tail: the next output is the first m with m * decim >= seen[s].  Waits for `stream`."""
-        arr = None
-        if seen is not None:
-            arr = np.ascontiguousarray(seen, np.uint64).reshape(-1)
-            assert arr.size == self.nstreams, "one count per stream"
-        _call("mifsk_channel_stream_seek", self.handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint64)),
-              stream=stream, errors=_EINVAL_IS_VALUE)
-
-    def seen(self, stream=None):
-        """mifsk_channel_stream_seen: the elements every stream has seen, numpy uint64 [nstreams].  Waits for
-        `stream` (None: the current one)."""
-        out = np.empty(self.nstreams, np.uint64)
-        _call("mifsk_channel_stream_seen", self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), stream=stream)
         return out
 
 
@@ -845,6 +854,27 @@ class MuxPlan(_PhasePlan):
         self.interp, self.complex_output = p.interp, bool(complex_output)
 
 
+def _mux_io(plan, samples, nsamples, iq, nstreams, full, nout_cap, stream, out):
+    """What multiplex and MuxStream.feed do in front of their entry: `samples` (`iq`: rows of I, Q pairs) and
+    `nsamples` checked against the plan's channels and `nstreams` (None: as many as the rows give), the outputs
+    made (full(width): the outputs rows of that width need room for) or `out` taken over -> (the outputs' dict,
+    the mifsk_mux_io of the call)."""
+    torch = _torch()
+    if iq:
+        v = _row_view(torch, samples, cx=True, dtypes=(torch.float32, torch.complex64), one_row=False, unit="elements")
+    else:
+        v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
+    if nstreams is None:
+        nstreams = v.nstreams // plan.nchannels
+    assert v.nstreams > 0 and v.nstreams == nstreams * plan.nchannels, "samples holds nchannels rows per stream"
+    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
+    dtype = torch.int16 if plan.s16 else torch.float32
+    vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
+    out = _row_outputs(torch, nstreams, out is None and full(v.width), vec, dtype, (2,) if plan.complex_output else (),
+                       samples.device, stream, out)
+    return out, _phase_io(_lib.MuxIO(), "d_out", v, lens, nstreams, out, nout_cap)
+
+
 def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None, iq=False):
     """mifsk_multiplex_batch: the channels of every stream summed into one wideband row; with iq=True
     mifsk_multiplex_iq_batch: the same from rows of I, Q pairs, what fm_modulate writes.
@@ -860,20 +890,9 @@ def multiplex(plan, samples, nsamples=None, nout_cap=None, stream=None, out=None
     iq=True : samples is float32 [nstreams * nchannels, stride, 2] (I, Q) or complex64 [nstreams * nchannels,
               stride], stride % 2 == 0; nsamples counts such elements.  fm_modulate's float32 result goes in
               as it is, and so do "rows" and "nsamples" of channelize(..., iq=True).  The outputs are as above."""
-    torch = _torch()
-    if iq:
-        v = _row_view(torch, samples, cx=True, dtypes=(torch.float32, torch.complex64), one_row=False, unit="elements")
-    else:
-        v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
-    K = plan.nchannels
-    assert v.nstreams > 0 and v.nstreams % K == 0, "samples holds nchannels rows per stream"
-    nstreams = v.nstreams // K
-    lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
-    dtype = torch.int16 if plan.s16 else torch.float32
-    vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
-    full = out is None and ((v.width - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap))
-    out = _row_outputs(torch, nstreams, full, vec, dtype, (2,) if plan.complex_output else (), samples.device, stream, out)
-    io = _phase_io(_lib.MuxIO(), "d_out", v, lens, nstreams, out, nout_cap)
+    def full(width):
+        return (width - 1) * plan.interp + plan.ntaps if nout_cap is None else int(nout_cap)
+    out, io = _mux_io(plan, samples, nsamples, iq, None, full, nout_cap, stream, out)
     _call("mifsk_multiplex_iq_batch" if iq else "mifsk_multiplex_batch", plan.handle, C.byref(io), stream=stream)
     return out
 
@@ -884,22 +903,19 @@ def mux_stream_drain(ntaps, interp):
     return int(_lib.load().mifsk_mux_stream_drain(int(ntaps), int(interp)))
 
 
-class MuxStream(_Handle):
+class MuxStream(_RowStream):
     """mifsk_mux_stream (include/mifsk/mux_stream.h): `plan`'s multiplexer fed in pieces.  The concatenated outputs
     of the feeds are multiplex's on the concatenated rows, bit for bit, on the first N * interp elements (N: the
     rows' length); mux_stream_drain(ntaps, interp) more samples of 0.0 bring out the filter's tail.  iq=True: the
     input rows are (I, Q) pairs, as multiplex(..., iq=True) takes them; the kind is fixed at creation.  Counters
     and tails of `nstreams` streams live on the plan's device.  Feeds of one object are ordered by the caller: one
-    stream, or events."""
-    _destroy = "mifsk_mux_stream_destroy"
+    stream, or events.  Behind seek(seen) no sample in front of seen[s] exists: the next feed delivers the outputs
+    from seen[s] * interp on."""
+    _entry = "mifsk_mux_stream"
 
     def __init__(self, plan, nstreams, iq=False):
-        self._lib = _lib.load()
-        h = C.c_void_p()
-        _call("mifsk_mux_stream_create", plan.handle, int(nstreams), _lib.MUX_STREAM_IQ if iq else 0, C.byref(h),
-              errors=_EINVAL_IS_VALUE)
-        self.handle = h
-        self.plan, self.nstreams, self.iq = plan, int(nstreams), bool(iq)   # the object must not outlive its plan
+        self._create(plan, nstreams, _lib.MUX_STREAM_IQ if iq else 0)
+        self.iq = bool(iq)
 
     def feed(self, samples, nsamples=None, stream=None, out=None):
         """mifsk_mux_stream_feed: the next piece of every row, as multiplex takes a batch: `samples`
@@ -910,37 +926,9 @@ class MuxStream(_Handle):
         default out_stride is width * interp rounded up to the output kind's vector, which no piece of that
         width exceeds; `out`, a dict of a former feed, is reused when its tensors are of that kind.  No
         synchronisation is performed."""
-        torch = _torch()
-        plan = self.plan
-        if self.iq:
-            v = _row_view(torch, samples, cx=True, dtypes=(torch.float32, torch.complex64), one_row=False, unit="elements")
-        else:
-            v = _row_view(torch, samples, dtypes=(torch.float32,), one_row=False, unit="floats")
-        assert v.nstreams == self.nstreams * plan.nchannels, "samples holds nchannels rows per stream"
-        lens = _row_lengths(torch, nsamples, v.nstreams, v.width)
-        dtype = torch.int16 if plan.s16 else torch.float32
-        vec = 16 // ((2 if plan.s16 else 4) * (2 if plan.complex_output else 1))
-        out = _row_outputs(torch, self.nstreams, out is None and v.width * plan.interp, vec, dtype,
-                           (2,) if plan.complex_output else (), samples.device, stream, out)
-        io = _phase_io(_lib.MuxIO(), "d_out", v, lens, self.nstreams, out, None)
+        out, io = _mux_io(self.plan, samples, nsamples, self.iq, self.nstreams, lambda width: width * self.plan.interp,
+                          None, stream, out)
         _call("mifsk_mux_stream_feed", self.handle, C.byref(io), stream=stream, errors=_EINVAL_IS_VALUE)
-        return out
-
-    def seek(self, seen=None, stream=None):
-        """mifsk_mux_stream_seek: every stream has taken seen[s] samples (None: 0, the reset) and nothing in front
-        of them exists: the next feed delivers the outputs from seen[s] * interp on.  Waits for `stream`."""
-        arr = None
-        if seen is not None:
-            arr = np.ascontiguousarray(seen, np.uint64).reshape(-1)
-            assert arr.size == self.nstreams, "one count per stream"
-        _call("mifsk_mux_stream_seek", self.handle, None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_uint64)),
-              stream=stream, errors=_EINVAL_IS_VALUE)
-
-    def seen(self, stream=None):
-        """mifsk_mux_stream_seen: the samples every stream has taken, numpy uint64 [nstreams].  Waits for
-        `stream` (None: the current one)."""
-        out = np.empty(self.nstreams, np.uint64)
-        _call("mifsk_mux_stream_seen", self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64)), stream=stream)
         return out
 
 

@@ -93,6 +93,15 @@ inline RowsIn rows_in( const IO *io )
     return RowsIn{io->d_samples, io->stream_stride, io->d_nsamples, io->nsamples};
 }
 
+// ... and the most that one call gives a row of it, as the host knows it: a row's length is a
+// uint32_t and stops at the stride, and with per-row lengths any of them may be the stride
+template <class IO>
+inline uint64_t stream_kmax( const IO *io )
+{
+    const uint64_t stride = io->stream_stride < 0xFFFFFFFFull ? io->stream_stride : 0xFFFFFFFFull;
+    return io->d_nsamples || io->nsamples > stride ? stride : io->nsamples;
+}
+
 // An output element of the channelizer is a float, or with `iq` an (I, Q) pair: `vec` of them are 16
 // bytes, a row is `max` of them at most
 struct OutKind {

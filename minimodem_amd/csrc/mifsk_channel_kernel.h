@@ -46,10 +46,9 @@
 //   4. the workgroup of chunk 0 and channel block 0 of a stream writes the stream's new record and its
 //      new tail, virtual elements [fit D, nv), the raw elements copied.
 //   5. the arguments have five more fields (ChannelStreamArgs).
-// No launch reads what it writes: records and tails exist twice, a feed reads side `parity` and
-// writes the other (as session_append_kernel does), and the host flips the parity after a launch
-// that went out whole.  So the kernel needs no fences, and any workgroup may write the new state
-// while others still read the old.  The outputs are plain vector stores.  gfx950 only.
+// No launch reads what it writes (records and tails exist twice, mifsk_stream_check.h).  So the
+// kernel needs no fences, and any workgroup may write the new state while others still read the
+// old.  The outputs are plain vector stores.  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,14 +62,12 @@
 
 namespace mifsk {
 
-// ChannelArgs first, so a feed's rows and outputs lie where the batch kernel takes them
-struct ChannelStreamArgs : ChannelArgs {
-    const StreamRecord	*rec_in;	// [nstreams]: the side this feed reads
-    StreamRecord	*rec_out;	// ... and the one it writes
-    const char		*tail_in;	// [nstreams][tail_cap] elements
-    char		*tail_out;
-    uint32_t		tail_cap;	// elements of a tail's room
-};
+// ChannelArgs first, so a feed's rows and outputs lie where the batch kernel takes them; then the
+// stream's five fields (mifsk_stream_check.h), the tails [nstreams][tail_cap] elements
+struct ChannelStreamArgs : ChannelArgs, StreamSides<StreamRecord> {};
+
+static_assert(sizeof(ChannelArgs) == 120 && sizeof(ChannelStreamArgs) == 120 + sizeof(StreamSides<StreamRecord>),
+	      "rec_in at 120, tail_cap at 152, 160 bytes: the kernels' code reads them there");
 
 // virtual element `at` of a stream, widened: tail [0, L), then the piece from its element `skip` on
 template <bool CX, bool S16>

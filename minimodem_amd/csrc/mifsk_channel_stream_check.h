@@ -1,7 +1,8 @@
 // mifsk_channel_stream_check.h -- the host logic of a channel stream (include/mifsk/channel_stream.h,
 // mifsk_channel_stream.hip) that needs no device: the counting of outputs, a stream's record and its
-// tail, and what a feed refuses of its arguments.  It calls no HIP: tools/channel_stream_check.cpp runs
-// it on a CPU under the sanitizers (tests/test_channel_stream_args.py).
+// tail, and what a feed refuses of its arguments; what it shares with the multiplexer's stream is in
+// mifsk_stream_check.h.  It calls no HIP: tools/channel_stream_check.cpp runs it on a CPU under the
+// sanitizers (tests/test_channel_stream_args.py).
 #pragma once
 
 #include <cerrno>
@@ -10,6 +11,7 @@
 #include "mifsk.h"
 #include "mifsk/channel_stream.h"
 #include "mifsk_batch.h"
+#include "mifsk_stream_check.h"
 
 namespace mifsk {
 
@@ -40,7 +42,8 @@ inline StreamRecord stream_record_at( uint32_t D, uint64_t n0 ) { return StreamR
 constexpr uint64_t kStreamMaxSeen = 1ull << 63;
 
 // The tail, elements [next D, seen) of the stream, or none when next D >= seen.
-// It never holds more than T - 1 elements.  next >= M(seen) always (it is M(seen), or a seek's
+// It never holds more than T - 1 elements, which its room is made for (stream_tail_room of T - 1,
+// mifsk_stream_check.h).  next >= M(seen) always (it is M(seen), or a seek's
 // first output, which is no smaller), so the tail is no longer than seen - M(seen) D.  For seen < T,
 // M = 0 and that is seen <= T - 1.  For seen >= T, M = floor((seen - T) / D) + 1 > (seen - T) / D, so
 // M D > seen - T, seen - M D < T, and both sides are integers: seen - M D <= T - 1.
@@ -49,28 +52,12 @@ inline uint64_t stream_tail_len( uint32_t D, const StreamRecord &r )
     return r.seen > r.next * D ? r.seen - r.next * D : 0u;
 }
 
-// ... and its room per stream and side, in elements of `esz` bytes: T - 1 of them rounded up to
-// whole 16-byte vectors, one vector at least
-inline uint32_t stream_tail_cap( uint32_t T, uint32_t esz )
-{
-    const uint32_t bytes = ( ( T - 1u ) * esz + 15u ) / 16u * 16u;
-    return ( bytes ? bytes : 16u ) / esz;
-}
-
 // what a feed has to know of its object
 struct StreamShape {
     bool	cx, s16;	// the plan's kind
     uint32_t	D, K;		// ... its decimation and channels
     int		nstreams;
 };
-
-// the most that one feed gives a stream, as the host knows it
-template <class IO>
-inline uint64_t stream_kmax( const IO *io )
-{
-    const uint64_t stride = io->stream_stride < 0xFFFFFFFFull ? io->stream_stride : 0xFFFFFFFFull;
-    return io->d_nsamples || io->nsamples > stride ? stride : io->nsamples;
-}
 
 // What mifsk_channel_stream_feed refuses behind the NULL object and io, in the header's order:
 // everything the batch entry of the same flag refuses of the io, a number of streams that is not the

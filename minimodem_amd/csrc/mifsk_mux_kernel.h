@@ -49,8 +49,7 @@
 //      go to the other side, ahead of the tap loops (so that nothing of it is live across them); the rows
 //      of a stream are spread over all its workgroups, those that store only zeros included.  With k_s = 0 that is the record and the tails as they were.
 //   5. the arguments have five more fields (MuxStreamArgs).
-// No launch reads what it writes: records and tails exist twice, a feed reads side `parity` and writes
-// the other, and the host flips the parity after a launch that went out whole.  gfx950 only.
+// No launch reads what it writes (records and tails exist twice, mifsk_stream_check.h).  gfx950 only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -65,14 +64,12 @@
 
 namespace mifsk {
 
-// MuxArgs first, so a feed's rows and outputs lie where the batch kernel takes them
-struct MuxStreamArgs : MuxArgs {
-    const MuxStreamRecord	*rec_in;	// [nstreams]: the side this feed reads
-    MuxStreamRecord		*rec_out;	// ... and the one it writes
-    const void			*tail_in;	// [nstreams * K][tail_cap] elements
-    void			*tail_out;
-    uint32_t			tail_cap;	// elements of a tail's room
-};
+// MuxArgs first, so a feed's rows and outputs lie where the batch kernel takes them; then the stream's
+// five fields (mifsk_stream_check.h), the tails [nstreams * K][tail_cap] elements
+struct MuxStreamArgs : MuxArgs, StreamSides<MuxStreamRecord> {};
+
+static_assert(sizeof(MuxArgs) == 136 && sizeof(MuxStreamArgs) == 136 + sizeof(StreamSides<MuxStreamRecord>),
+	      "rec_in at 136, tail_cap at 168, 176 bytes: the kernel's code reads them there");
 
 // where sample e of a staged span lies: one double of padding per 8
 __device__ __forceinline__ uint32_t mux_pad( uint32_t e ) { return e + ( e >> 3 ); }

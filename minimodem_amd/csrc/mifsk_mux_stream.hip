@@ -1,8 +1,8 @@
 // mifsk_mux_stream.hip -- the multiplexer fed in pieces (include/mifsk/mux_stream.h):
 // mifsk_mux_stream_create / _destroy / _feed / _seek / _seen and the host's mifsk_mux_stream_drain.  A feed
 // launches multiplex_kernel with STREAM = true (mifsk_mux_kernel.h, which says what a stream keeps and
-// what the kernel does with it); the host logic that needs no device is in mifsk_mux_stream_check.h.
-// gfx950 only.
+// what the kernel does with it); records and tails have their owner in mifsk_stream_state.h, and the host
+// logic that needs no device is in mifsk_mux_stream_check.h.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <cerrno>
@@ -15,16 +15,12 @@
 #include "mifsk_mux_kernel.h"
 #include "mifsk_mux_plan.h"
 #include "mifsk_mux_stream_check.h"
+#include "mifsk_stream_state.h"
 
 struct mifsk_mux_stream {
     const mifsk_mux_plan			*plan;
-    int						nstreams;
-    bool					iq;		// input rows are (I, Q) pairs
-    uint32_t					tail_cap;	// elements per row and side
-    uint32_t					esz;		// bytes of an element
-    unsigned					parity;		// the side the next feed reads
-    mifsk::DevMem<mifsk::MuxStreamRecord>	rec;		// [2][nstreams]
-    mifsk::DevMem<char>				tails;		// [2][nstreams * K][tail_cap] elements
+    bool					iq;	// input rows are (I, Q) pairs
+    mifsk::StreamState<mifsk::MuxStreamRecord>	st;	// K rows per stream, H elements of tail
 };
 
 extern "C" uint32_t mifsk_mux_stream_drain( uint32_t ntaps, uint32_t interp )
@@ -41,16 +37,9 @@ extern "C" int mifsk_mux_stream_create( const mifsk_mux_plan *plan, int nstreams
     if ( !ms )
 	return -ENOMEM;
     ms->plan = plan;
-    ms->nstreams = nstreams;
     ms->iq = ( flags & MIFSK_MUX_STREAM_IQ ) != 0u;
-    ms->esz = ms->iq ? 8u : 4u;
-    ms->tail_cap = mux_stream_tail_cap(mux_stream_drain(plan->T, plan->L), ms->esz);
-    ms->parity = 0u;
-    if ( hipSetDevice(plan->device) != hipSuccess )
-	return -EIO;
-    if ( int rc = ms->rec.alloc(2u * (size_t)nstreams, 0, true) )
-	return rc;
-    if ( int rc = ms->tails.alloc(2u * (size_t)nstreams * plan->K * ms->tail_cap * ms->esz, 0, true) )
+    const uint32_t esz = ms->iq ? 8u : 4u;
+    if ( int rc = ms->st.alloc(plan->device, nstreams, plan->K, stream_tail_room(mux_stream_drain(plan->T, plan->L), esz), esz) )
 	return rc;
     *out = ms.release();
     return 0;
@@ -60,8 +49,7 @@ extern "C" void mifsk_mux_stream_destroy( mifsk_mux_stream *ms )
 {
     if ( !ms )
 	return;
-    (void)hipSetDevice(ms->plan->device);
-    (void)hipDeviceSynchronize();		// no kernel reads the tails any more
+    ms->st.quiesce();
     delete ms;
 }
 
@@ -71,22 +59,14 @@ extern "C" int mifsk_mux_stream_feed( mifsk_mux_stream *ms, const mifsk_mux_io *
     if ( !ms || !io )
 	return -EINVAL;
     const mifsk_mux_plan *plan = ms->plan;
-    if ( int rc = mux_stream_feed_check(MuxStreamShape{plan->cx, plan->s16, ms->iq, plan->L, plan->K, ms->nstreams}, io) )
+    if ( int rc = mux_stream_feed_check(MuxStreamShape{plan->cx, plan->s16, ms->iq, plan->L, plan->K, ms->st.nstreams}, io) )
 	return rc;
 
     MuxGeometry geo = {};
-    MuxStreamArgs S = {mux_args(*plan, io, geo)};
-    const size_t n = (size_t)ms->nstreams, side = n * plan->K * ms->tail_cap * ms->esz;
-    S.rec_in = ms->rec.p + ms->parity * n;
-    S.rec_out = ms->rec.p + ( ms->parity ^ 1u ) * n;
-    S.tail_in = ms->tails.p + ms->parity * side;
-    S.tail_out = ms->tails.p + ( ms->parity ^ 1u ) * side;
-    S.tail_cap = ms->tail_cap;
-
+    MuxStreamArgs S = {mux_args(*plan, io, geo), ms->st.sides()};
     const int rc = mux_launch(*plan, geo, io->nstreams, S, ms->iq, (hipStream_t)stream);
-    // (a feed that did not go out whole leaves the side it read as the current one)
     if ( rc == 0 )
-	ms->parity ^= 1u;
+	ms->st.commit();
     return rc;
 }
 
@@ -95,36 +75,12 @@ extern "C" int mifsk_mux_stream_seek( mifsk_mux_stream *ms, const uint64_t *seen
     using namespace mifsk;
     if ( !ms )
 	return -EINVAL;
-    const size_t n = (size_t)ms->nstreams;
-    const std::unique_ptr<MuxStreamRecord[]> rec(new (std::nothrow) MuxStreamRecord[n]);
-    if ( !rec )
-	return -ENOMEM;
-    for ( size_t s = 0; s < n; s++ ) {
-	if ( seen && seen[s] > kMuxStreamMaxSeen )
-	    return -EINVAL;
-	rec[s] = mux_stream_record_at(seen ? seen[s] : 0u);
-    }
-    // behind the feeds queued on `stream`; the records are there when this returns
-    if ( hipSetDevice(ms->plan->device) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess )
-	return -EIO;
-    return hipMemcpy(ms->rec.p + ms->parity * n, rec.get(), n * sizeof(MuxStreamRecord), hipMemcpyHostToDevice) == hipSuccess
-	? 0 : -EIO;
+    return ms->st.seek(seen, kMuxStreamMaxSeen, mux_stream_record_at, (hipStream_t)stream);
 }
 
 extern "C" int mifsk_mux_stream_seen( mifsk_mux_stream *ms, uint64_t *seen_out, void *stream )
 {
-    using namespace mifsk;
     if ( !ms || !seen_out )
 	return -EINVAL;
-    const size_t n = (size_t)ms->nstreams;
-    const std::unique_ptr<MuxStreamRecord[]> rec(new (std::nothrow) MuxStreamRecord[n]);
-    if ( !rec )
-	return -ENOMEM;
-    if ( hipSetDevice(ms->plan->device) != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess )
-	return -EIO;
-    if ( hipMemcpy(rec.get(), ms->rec.p + ms->parity * n, n * sizeof(MuxStreamRecord), hipMemcpyDeviceToHost) != hipSuccess )
-	return -EIO;
-    for ( size_t s = 0; s < n; s++ )
-	seen_out[s] = rec[s].seen;
-    return 0;
+    return ms->st.seen(seen_out, (hipStream_t)stream);
 }

@@ -1,7 +1,8 @@
 // mifsk_mux_stream_check.h -- the host logic of a multiplexer stream (include/mifsk/mux_stream.h,
 // mifsk_mux_stream.hip) that needs no device: the samples a later output still reads, a stream's record
-// and the room of its tails, and what a feed refuses of its arguments.  It calls no HIP:
-// tools/mux_stream_check.cpp runs it on a CPU under the sanitizers (tests/test_mux_stream_args.py).
+// (its tails have stream_tail_room of H, mifsk_stream_check.h, which holds what the two streams
+// share), and what a feed refuses of its arguments.  It calls no HIP: tools/mux_stream_check.cpp runs
+// it on a CPU under the sanitizers (tests/test_mux_stream_args.py).
 #pragma once
 
 #include <cerrno>
@@ -10,6 +11,7 @@
 #include "mifsk.h"
 #include "mifsk/mux_stream.h"
 #include "mifsk_batch.h"
+#include "mifsk_stream_check.h"
 
 namespace mifsk {
 
@@ -39,14 +41,6 @@ __host__ __device__ inline uint32_t mux_stream_back( uint32_t H, const MuxStream
     return have < H ? (uint32_t)have : H;
 }
 
-// a tail's room per row and side, in elements of `esz` bytes: H of them rounded up to whole 16-byte
-// vectors, one vector at least
-inline uint32_t mux_stream_tail_cap( uint32_t H, uint32_t esz )
-{
-    const uint32_t bytes = ( H * esz + 15u ) / 16u * 16u;
-    return ( bytes ? bytes : 16u ) / esz;
-}
-
 // what a feed has to know of its object
 struct MuxStreamShape {
     bool	cx, s16;	// the plan's kind: the output's
@@ -54,13 +48,6 @@ struct MuxStreamShape {
     uint32_t	L, K;		// ... its interpolation and channels
     int		nstreams;
 };
-
-// the most that one feed gives a stream, as the host knows it
-inline uint64_t mux_stream_kmax( const mifsk_mux_io *io )
-{
-    const uint64_t stride = io->stream_stride < 0xFFFFFFFFull ? io->stream_stride : 0xFFFFFFFFull;
-    return io->d_nsamples || io->nsamples > stride ? stride : io->nsamples;
-}
 
 // kmax * L outputs fit into `room` elements (64 bits: kmax < 2^32, L < 2^16)
 inline bool mux_stream_fits( uint64_t kmax, uint32_t L, uint64_t room ) { return kmax * (uint64_t)L <= room; }
@@ -75,7 +62,7 @@ inline int mux_stream_feed_check( const MuxStreamShape &sh, const mifsk_mux_io *
 	return rc;
     if ( io->nstreams != sh.nstreams )
 	return -EINVAL;
-    const uint64_t kmax = mux_stream_kmax(io);
+    const uint64_t kmax = stream_kmax(io);
     if ( !mux_stream_fits(kmax, sh.L, io->out_stride) )
 	return -EINVAL;
     if ( !mux_stream_fits(kmax, sh.L, io->nout_cap) )

@@ -29,7 +29,6 @@
 #include "mifsk.h"
 #include "mifsk/squelch.h"
 #include "mifsk_batch.h"
-#include "mifsk_channel_stream_check.h"
 #include "mifsk_ctx.h"
 #include "mifsk_hostmem.h"
 #include "mifsk_rows.h"

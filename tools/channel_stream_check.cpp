@@ -1,7 +1,8 @@
 // channel_stream_check.cpp -- the host logic of a channel stream without a device: the counting of
 // outputs, the records and tails, and the ladder of what a feed refuses
-// (minimodem_amd/csrc/mifsk_channel_stream_check.h), under the address and undefined-behaviour
-// sanitizers.  The checks call no HIP.
+// (minimodem_amd/csrc/mifsk_channel_stream_check.h), and what it shares with the multiplexer's stream
+// (mifsk_stream_check.h, stream_shared_check.h) for one row per stream, under the address and
+// undefined-behaviour sanitizers.  The checks call no HIP.
 //
 //   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iminimodem_amd/csrc
 //       -fsanitize=address,undefined -o channel_stream_check tools/channel_stream_check.cpp && ./channel_stream_check
@@ -13,6 +14,7 @@
 #include <cstdio>
 
 #include "mifsk_channel_stream_check.h"
+#include "stream_shared_check.h"
 
 static long g_checks = 0, g_failed = 0;
 
@@ -70,11 +72,12 @@ int main()
 	}
 	// the tail's room: T - 1 elements in whole 16-byte vectors, one at least
 	for ( uint32_t esz : { 2u, 4u, 8u } ) {
-	    const uint32_t cap = stream_tail_cap(T, esz);
+	    const uint32_t cap = stream_tail_room(T - 1u, esz);
 	    expect(cap >= T - 1u && cap * esz % 16u == 0u && cap * esz >= 16u && cap * esz < ( T - 1u ) * esz + 16u + ( T == 1u ? 16u : 0u ),
-		   1, "stream_tail_cap", T, esz);
+		   1, "stream_tail_room", T, esz);
 	}
     }
+    stream_shared_checks(expect, sizeof(StreamRecord), 1u);
     expect(stream_outputs(0u, 4u, 100u, 100u), 0, "no taps", 0, 0);
     expect(stream_outputs(4u, 0u, 100u, 100u), 0, "no decimation", 0, 0);
     expect(stream_outputs(4u, 1u, ~0ull - 5u, 100u), 5, "a sum beyond 2^64 counts to 2^64 - 1", 0, 0);

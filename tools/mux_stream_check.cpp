@@ -1,7 +1,8 @@
 // mux_stream_check.cpp -- the host logic of a multiplexer stream without a device: H, the tails' room,
 // kmax and the capacity rule in 64 bits, the seek limit and a seek's record, and the ladder of what a feed
-// refuses (minimodem_amd/csrc/mifsk_mux_stream_check.h), under the address and undefined-behaviour
-// sanitizers.  The checks call no HIP.
+// refuses (minimodem_amd/csrc/mifsk_mux_stream_check.h), and what it shares with the channelizer's stream
+// (mifsk_stream_check.h, stream_shared_check.h) for K rows per stream, under the address and
+// undefined-behaviour sanitizers.  The checks call no HIP.
 //
 //   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Iminimodem_amd/csrc
 //       -fsanitize=address,undefined -o mux_stream_check tools/mux_stream_check.cpp && ./mux_stream_check
@@ -13,6 +14,7 @@
 #include <cstdio>
 
 #include "mifsk_mux_stream_check.h"
+#include "stream_shared_check.h"
 
 static long g_checks = 0, g_failed = 0;
 
@@ -54,9 +56,9 @@ int main()
 		expect(H, 0, "no tail up to T = L", T, L);
 	    // the tails' room: H elements in whole 16-byte vectors, one at least
 	    for ( uint32_t esz : { 4u, 8u } ) {
-		const uint32_t cap = mux_stream_tail_cap(H, esz);
+		const uint32_t cap = stream_tail_room(H, esz);
 		expect(cap >= H && cap * esz % 16u == 0u && cap * esz >= 16u && cap * esz < H * esz + 16u + ( H == 0u ? 16u : 0u ),
-		       1, "mux_stream_tail_cap", H, esz);
+		       1, "stream_tail_room", H, esz);
 	    }
 	    // the tail samples that exist: min(seen - first, H)
 	    const uint64_t firsts[4] = { 0u, 1u, 1ull << 32, kMuxStreamMaxSeen };
@@ -71,6 +73,8 @@ int main()
 	    }
 	}
     }
+    for ( uint32_t K : { 3u, 65u } )
+	stream_shared_checks(expect, sizeof(MuxStreamRecord), K);
     expect(mux_stream_drain(100u, 0u), 0, "no interpolation", 0, 0);
     expect(mux_stream_drain(0u, 4u), 0, "no taps", 0, 0);
     // the seek limit: seen * L below 2^62 for the largest L
@@ -100,7 +104,7 @@ int main()
     good.nout_cap = 392u;
     good.d_nout = counts;
     expect(rc64(mux_stream_feed_check(sh, &good)), 0, "a good feed", 0, 0);
-    expect(mux_stream_kmax(&good), 98, "kmax", 0, 0);
+    expect(stream_kmax(&good), 98, "kmax", 0, 0);
     // each violation alone, then each with every later one: the earlier one's refusal is what comes
     // back (they all return -EINVAL, so the order shows in the code, and here: none passes)
     struct Bad { const char *what; void (*set)( mifsk_mux_io & ); };
@@ -130,7 +134,7 @@ int main()
     // the room a feed needs: kmax L, kmax from nsamples without d_nsamples, from the stride with it
     mifsk_mux_io io = good;
     io.nsamples = 101u;						// beyond the stride: the stride counts
-    expect(mux_stream_kmax(&io), 100, "kmax beyond the stride", 0, 0);
+    expect(stream_kmax(&io), 100, "kmax beyond the stride", 0, 0);
     expect(rc64(mux_stream_feed_check(sh, &io)), rc64(no), "400 outputs do not fit into 392", 0, 0);
     io.out_stride = io.nout_cap = 400u;
     expect(rc64(mux_stream_feed_check(sh, &io)), 0, "400 outputs fit into 400", 0, 0);
@@ -176,7 +180,7 @@ int main()
     io = good;
     io.stream_stride = 1ull << 33;
     io.d_nsamples = counts;
-    expect(mux_stream_kmax(&io), 0xFFFFFFFFull, "kmax of a huge stride", 0, 0);
+    expect(stream_kmax(&io), 0xFFFFFFFFull, "kmax of a huge stride", 0, 0);
 
     std::printf("mux_stream_check: %ld checks, %ld failed\n", g_checks, g_failed);
     return g_failed ? 1 : 0;

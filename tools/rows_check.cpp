@@ -1,5 +1,5 @@
 // rows_check.cpp -- what the batch entries refuse of a batch of rows, without a device: kind_check,
-// out_rows_check, feed_rows_check and rows_in of minimodem_amd/csrc/mifsk_batch.h with the argument
+// out_rows_check, feed_rows_check, rows_in and stream_kmax of minimodem_amd/csrc/mifsk_batch.h with the argument
 // ladders of mifsk_impair_batch, mifsk_fm_demod_batch and mifsk_fm_modulate_batch (and the output rows
 // of the channelizer and the multiplexer, phase_check_io's).  The checks call no HIP.
 //
@@ -99,6 +99,21 @@ int main()
     const mifsk_fm_mod_io none = {};
     const RowsIn zero = rows_in(&none);
     expect(!zero.x && zero.stride == 0u && !zero.nsamples_v && zero.nsamples_u == 0u ? 0 : no, 0, "rows_in {}", 0, 0);
+
+    // the most one call gives a row of it: nsamples up to the stride, the stride with per-row lengths
+    // (any of them may reach it), and never more than a uint32_t holds
+    expect(stream_kmax(&none) == 0u ? 0 : no, 0, "kmax {}", 0, 0);
+    for ( uint64_t stride : { 64ull, 0xFFFFFFFEull, 0xFFFFFFFFull, 0x100000000ull, 1ull << 33 } ) {
+	const uint64_t most = stride < 0xFFFFFFFFull ? stride : 0xFFFFFFFFull;
+	io.stream_stride = stride;
+	for ( uint32_t n : { 0u, 1u, 60u, 64u, 65u, 0xFFFFFFFFu } ) {
+	    io.nsamples = n;
+	    io.d_nsamples = nullptr;
+	    expect(stream_kmax(&io) == ( n < most ? n : most ) ? 0 : no, 0, "kmax of nsamples", stride, n);
+	    io.d_nsamples = counts;
+	    expect(stream_kmax(&io) == most ? 0 : no, 0, "kmax with per-row lengths", stride, n);
+	}
+    }
 
     std::printf("rows_check: %ld checks, %ld failed\n", g_checks, g_failed);
     return g_failed ? 1 : 0;
